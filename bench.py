@@ -66,6 +66,37 @@ class _DryScanner:
         buf[:n, 1] = self.rank | (5 << 32)
         return n
 
+    def hits_array(self):
+        """Made-up records in the layout of device.Scanner.hits_array(): line_number, id, to, start, len."""
+        import numpy as np
+
+        line = np.arange(self.n, dtype=np.uint64) * 7
+        return np.stack([line, np.full_like(line, self.rank), np.full_like(line, 5), line * 120, np.full_like(line, 119)], axis=1)
+
+
+DUMP_LIMIT = 64 * 10**6  # bytes, all --dump-outputs files together
+DUMP_SEED = 20250917   # the row sample of a larger output: the same rows in every run with the same arguments
+
+
+def dump_outputs(path: str, counts, records, columns: list[str]) -> dict:
+    """--dump-outputs: what the last timed step computed, as float64 .npy files (every value is an integer below 2**53,
+    so float64 holds it exactly).  scan_counts.npy = [lines, hits]; hits.npy = the hit records, one row each (`columns`),
+    ordered by line, then id, to, ...; all of them if they fit into DUMP_LIMIT, else a seeded sample of rows (the same rows
+    for the same number of hits); hits_index.npy = each written row's position in the whole ordered list."""
+    import numpy as np
+
+    records = np.asarray(records, dtype=np.uint64).reshape(-1, len(columns))
+    records = records[np.lexsort(records.T[::-1])]
+    n = records.shape[0]
+    room = (DUMP_LIMIT - (64 << 10)) // (8 * (len(columns) + 1))  # (64 KiB for the files' headers and the counts)
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, room, replace=False)) if n > room else np.arange(n)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "scan_counts.npy"), np.asarray(counts, dtype=np.float64))
+    np.save(os.path.join(path, "hits.npy"), records[rows].astype(np.float64))
+    np.save(os.path.join(path, "hits_index.npy"), rows.astype(np.float64))
+    return {"dir": path, "files": ["scan_counts.npy", "hits.npy", "hits_index.npy"], "hit_columns": columns, "hits": n,
+            "rows_written": int(rows.shape[0]), "sampled": bool(n > room)}
+
 
 def main() -> None:
     ap = argparse.ArgumentParser()
@@ -81,7 +112,11 @@ def main() -> None:
     ap.add_argument("--no-extra", action="store_true", help="skip the untuned / other-ids legs (experiments)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU, no scan: rehearse launch + exchange + gather + JSON with made-up counts (CPU tests)")
     ap.add_argument("--dry-hits", type=int, default=1000, help="--dry-run: hit records per rank and step")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (line and hit "
+                    "counts, hit records) as DIR/<name>.npy, float64, at most 64 MB in all (a fixed seeded sample of the records beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(_self_launch(args.gpus))
@@ -171,6 +206,7 @@ def main() -> None:
     recv_sets: list = [[], []]
     slot_free: list = [None, None]  # event: the gather that last used the slot has finished
     pending: list = []              # (slot, hits copied, counts exchange, event: the copy into the slot is done)
+    gathered: list = [None]         # (slot, own hits, totals) of the last gather: --dump-outputs reads rank 0's records from it
     step_no = [0]
 
     def prime() -> None:
@@ -186,6 +222,7 @@ def main() -> None:
     def flush_gather():
         slot, n, counts, ready = pending.pop(0)
         totals = counts.result()  # (pinned host memory: no device round trip)
+        gathered[0] = (slot, n, totals)
         hit_buf = hit_bufs[slot]
         if rank == 0 and int(totals[1:, 1].max()) > recv_sets[slot][0].shape[0]:  # (a step with more hits than prime() saw + 25 %: never on a fixed text)
             need = int(totals[1:, 1].max())
@@ -256,6 +293,18 @@ def main() -> None:
         total_hits, total_lines = int(tot[0]), int(tot[1])
     else:
         total_hits, total_lines = last.n_hits, last.n_lines
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (untimed; before the legs below scan again)
+        if world == 1:
+            dumped = dump_outputs(args.dump_outputs, [total_lines, total_hits], sc.hits_array(), ["line_number", "id", "to", "start", "len"])
+        else:  # what rank 0 holds after the gather: int64 (line, id | to << 32) records of every rank
+            import numpy as np
+
+            slot, n, totals = gathered[0]
+            parts = [hit_bufs[slot][:n]] + [buf[: int(totals[src, 1])] for src, buf in enumerate(recv_sets[slot], start=1)]
+            rec = torch.cat(parts).cpu().numpy().view("<u8")
+            rec = np.stack([rec[:, 0], rec[:, 1] & 0xFFFFFFFF, rec[:, 1] >> 32], axis=1)
+            dumped = dump_outputs(args.dump_outputs, [total_lines, total_hits], rec, ["line_number", "id", "to"])
 
     if rank == 0:
         ms_per_step = elapsed * 1e3 / args.steps
@@ -296,6 +345,8 @@ def main() -> None:
             "pipeline": {"candidates": last.n_candidates, "raw_hits": last.n_raw_hits, "reruns": last.reruns,
                          "ms_total_device": round(last.ms_total, 4)},
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         # HBM bytes per launch measured with PMC counters (tools/record_round.sh) for the same workload, if committed
         try:
             with open(os.path.join(REPO, "profiles", "hbm_traffic_latest.json"), encoding="utf-8") as f:

@@ -163,6 +163,19 @@ class Scanner:
             raise DeviceError(f"hg_copy_hits failed ({rc})")
         return [(hits[i].line_number, hits[i].id, hits[i].to, aux[i].start, aux[i].len) for i in range(n)]
 
+    def hits_array(self):
+        """Last scan's hits as a uint64 numpy array [n_hits, 5], the columns of hits(), without one Python tuple per hit."""
+        import numpy as np
+
+        n = self._last.n_hits
+        hits = np.zeros(n, dtype=[("line_number", "<u8"), ("id", "<u4"), ("to", "<u4")])
+        aux = np.zeros(n, dtype=[("start", "<u8"), ("len", "<u4"), ("pattern", "<u4")])
+        if n:
+            rc = lib().hg_copy_hits(self._h, hits.ctypes.data_as(ctypes.POINTER(HgHit)), aux.ctypes.data_as(ctypes.POINTER(HgHitAux)), n)
+            if rc != 0:
+                raise DeviceError(f"hg_copy_hits failed ({rc})")
+        return np.stack([hits["line_number"], hits["id"], hits["to"], aux["start"], aux["len"]], axis=1).astype(np.uint64)
+
     def copy_hits_to(self, d_dst: int, limit: int, stream: int = 0) -> int:
         """Async device-to-device copy of the last scan's hit records (16 B each); returns the number copied."""
         n = min(limit, self._last.n_hits)

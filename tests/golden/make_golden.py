@@ -206,6 +206,29 @@ def main() -> None:
         json.dump(vectors, out, indent=1, sort_keys=True)
     for v in vectors:
         print(f"  {v['name']}: rc={v['rc']} rows={[(r[0], r[1], base64.b64decode(r[2])) for r in v['rows']]} batches={v['batches']}")
+    shim_abi()
+
+
+def shim_abi() -> None:
+    """reference_shim_abi.json: what the reference's prebuilt shim asks of the dynamic loader (readelf -d, nm -D), the
+    contract tests/test_abi.py::test_reference_loader_accepts_the_face_a_artefact holds the Face A artefact to."""
+    import re
+
+    shim = os.path.join(REF, "hypergrep", "lib", "libhyperscanner.so")
+    dyn = subprocess.check_output(["readelf", "-d", shim], text=True)
+    undefined = subprocess.check_output(["nm", "-D", "--undefined-only", shim], text=True)
+    defined = subprocess.check_output(["nm", "-D", "--defined-only", shim], text=True)
+    out = {
+        "source": "hypergrep/lib/libhyperscanner.so of the reference (prebuilt shim): readelf -d, nm -D",
+        "needed": re.findall(r"\(NEEDED\)\s+Shared library: \[(.+?)\]", dyn),
+        "runpath": re.findall(r"\((?:RPATH|RUNPATH)\)\s+Library r(?:un)?path: \[(.+?)\]", dyn),
+        "libhs_imports": sorted(line.split()[-1] for line in undefined.splitlines() if line.split()[-1].startswith("hs_")),
+        "python_entry_points": sorted(s for s in (line.split()[-1] for line in defined.splitlines() if " T " in line)
+                                      if s in ("check_patterns", "hyperscan")),
+    }
+    with open(os.path.join(HERE, "reference_shim_abi.json"), "w", encoding="utf-8") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
 
 
 if __name__ == "__main__":

@@ -156,37 +156,62 @@ def test_face_a_artefact_has_the_soname_the_reference_shim_needs():
     assert lib.hs_free_database(db) == 0 and lib.hs_free_database(None) == 0
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/hypergrep/lib/libhyperscanner.so"), reason="build container only: needs the reference tree")
-def test_reference_loader_accepts_the_face_a_artefact():
-    """The north-star boundary, exercised with the reference's own files: its unmodified Python
-    (hypergrep/utils.py:125-144 configure_libraries, :55-83 loaders) loads hypergrep_amd/lib/libhs.so.5 as `libhs`, then its
-    unmodified prebuilt shim, whose DT_NEEDED libhs.so.5 binds to that object; check_compatibility() (utils.py:97-121 ->
-    hyperscanner.c:154-167 -> hs_compile_multi) then runs this repository's compiler.  No GPU is needed for the compile path;
-    a scan through the same stack stops at hs_alloc_scratch without one (rc 3), never on a CPU fallback.  Runs in a child
-    process: the reference caches its library handles per process."""
+def test_reference_loader_accepts_the_face_a_artefact(tmp_path):
+    """The north-star boundary: the reference's Python (hypergrep/utils.py:125-144 configure_libraries, :55-83 loaders) loads
+    the configured `libhs` by path with ctypes' default mode, then its prebuilt shim, whose DT_NEEDED libhs.so.5 (no RPATH /
+    RUNPATH) can only bind to an already-loaded object of that SONAME.  The shim's link requirements are recorded in
+    tests/golden/reference_shim_abi.json; tests/native/libhs_consumer.c stands in for the shim with the same libhs imports,
+    linked against the ORACLE's libhs.so.5 as the shim was linked against real Hyperscan, and is loaded the same way after
+    hypergrep_amd/lib/libhs.so.5.  Its compile calls then run this repository's compiler.  No GPU is needed for the compile
+    path; a scan through the same stack stops at hs_alloc_scratch without one, never on a CPU fallback.  Runs in a child
+    process: a loaded libhs stays bound for the life of the process."""
+    import json
     import sys
 
-    libhs = os.path.join(REPO, "hypergrep_amd", "lib", "libhs.so.5")
-    code = (
-        "import sys, json; sys.path.insert(0, '/root/reference'); import hypergrep; "
-        f"hypergrep.configure_libraries(libhs={libhs!r}); "
-        "ok = hypergrep.check_compatibility(['foobar', 'status=5[0-9]{2}']); bad = hypergrep.check_compatibility(['(?<!a)b']); "
-        "maps = open('/proc/self/maps').read(); "
-        "rows, rc = hypergrep.grep('/root/reference/hypergrep/test/samplefile.txt', ['bar'], no_messages=True); "
-        "print(json.dumps({'ok': ok, 'bad': bad, 'ours': 'hypergrep_amd/lib/libhs.so.5' in maps, "
-        "'shim': '/root/reference/hypergrep/lib/libhyperscanner.so' in maps, 'rc': rc, 'rows': len(rows)}))"
-    )
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    with open(os.path.join(REPO, "tests", "golden", "reference_shim_abi.json"), encoding="utf-8") as f:
+        shim = json.load(f)
+    assert "libhs.so.5" in shim["needed"] and not shim["runpath"]
+    libhs = os.path.realpath(os.path.join(REPO, "hypergrep_amd", "lib", "libhs.so.5"))
+    oracle_libhs = os.path.realpath(os.path.join(REPO, "oracle", "_build", "libhs.so.5"))
+    assert os.path.exists(oracle_libhs), "build() makes oracle/_build/libhs.so.5"
+    # every symbol the shim imports from libhs is exported, unversioned, by the artefact
+    syms = subprocess.check_output(["nm", "-D", "--defined-only", libhs], text=True)
+    for name in shim["libhs_imports"]:
+        assert re.search(rf" T {name}$", syms, flags=re.M), name
+    # the stand-in: same libhs imports, same DT_NEEDED, no search path of its own
+    consumer = str(tmp_path / "libhs_consumer.so")
+    subprocess.check_call(["gcc", "-std=c99", "-O2", "-Wall", "-Wextra", "-fPIC", "-shared", "-I", os.path.join(REPO, "include"),
+                           "-o", consumer, os.path.join(REPO, "tests", "native", "libhs_consumer.c"),
+                           "-L", os.path.dirname(oracle_libhs), "-l:libhs.so.5"])
+    dyn = subprocess.check_output(["readelf", "-d", consumer], text=True)
+    assert "Shared library: [libhs.so.5]" in dyn and "RPATH" not in dyn and "RUNPATH" not in dyn
+    imports = subprocess.check_output(["nm", "-D", "--undefined-only", consumer], text=True)
+    assert sorted(line.split()[-1] for line in imports.splitlines() if line.split()[-1].startswith("hs_")) == shim["libhs_imports"]
+    code = """
+import ctypes, json, sys
+libhs, consumer = sys.argv[1:3]
+ctypes.cdll.LoadLibrary(libhs)  # by path, ctypes' default mode: what the reference's loader does
+c = ctypes.cdll.LoadLibrary(consumer)
+def check(ps):
+    n = len(ps)
+    return c.consumer_compile((ctypes.c_char_p * n)(*[p.encode() for p in ps]), (ctypes.c_uint * n)(*[14] * n), (ctypes.c_uint * n)(*[0] * n), n)
+ok, bad = check(["foobar", "status=5[0-9]{2}"]), check(["(?<!a)b"])
+maps = open("/proc/self/maps").read()
+alloc = ctypes.c_int(0)
+reports = c.consumer_scan(b"bar", b"foo\\nbar\\nfoobar\\n", 15, ctypes.byref(alloc))
+print(json.dumps({"ok": ok, "bad": bad, "ours": libhs in maps, "oracle": sys.argv[3] in maps, "alloc": alloc.value, "reports": reports}))
+"""
+    out = subprocess.run([sys.executable, "-c", code, libhs, consumer, oracle_libhs], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
-    import json
-
     res = json.loads(out.stdout.strip().splitlines()[-1])
-    assert res["ok"] == 0 and res["bad"] == 4
-    assert res["ours"] and res["shim"], "the reference's shim did not bind to this repository's libhs.so.5"
+    assert res["ok"] == 0 and res["bad"] == -4  # HS_SUCCESS; HS_COMPILER_ERROR from this repository's compiler
+    assert res["ours"] and not res["oracle"], "the consumer's DT_NEEDED libhs.so.5 did not bind to this repository's artefact"
     import torch
 
     if not torch.cuda.is_available():
-        assert res["rc"] == 3 and res["rows"] == 0  # HYPERSCANNER_SCRATCH: no GPU, and no CPU path
+        assert res["alloc"] != 0 and res["reports"] == -1  # no GPU, and no CPU path
+    else:
+        assert res["alloc"] == 0 and res["reports"] == 1  # (SINGLEMATCH: one report per id and scan call)
 
 
 def test_compile_cache_hits_and_bound():

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Keyword lists (many short literals) through the device API: which filter the compiler picks and what it costs.
     python tools/keywords_bench.py [GiB]"""
+import os
 import random
 import sys
 import time
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from hypergrep_amd import benchspec, device

@@ -1,6 +1,6 @@
 """Throughput of patterns without a long required literal (always-on tier) next to a prefiltered one; GPU box only."""
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import os
 import torch
 import hypergrep_amd

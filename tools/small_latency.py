@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, hypergrep_amd
 from hypergrep_amd import benchspec, device
 _, needles, hpm = benchspec.c3_spec()

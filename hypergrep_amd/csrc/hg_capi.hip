@@ -19,6 +19,7 @@ struct hg_database {
 struct hg_scanner {
   HgScanner *sc;
   hg_scan_result_t last;
+  const uint32_t *d_from;  // the last scan's hit starts (SOM databases), else nullptr: every start is 0
 };
 
 static_assert(sizeof(hg_hit_t) == sizeof(HgHit) && sizeof(hg_hit_aux_t) == sizeof(HgHitAux), "ABI records mirror the device records");
@@ -83,7 +84,7 @@ int hg_scanner_create(const hg_database_t *db, int device, hg_scanner_t **scanne
     put_err(err, errlen, msg);
     return rc;
   }
-  *scanner = new hg_scanner{sc, {}};
+  *scanner = new hg_scanner{sc, {}, nullptr};
   return HG_OK;
 }
 
@@ -115,6 +116,7 @@ int hg_scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, i
   result->joiner_launches = o.joiner_launches;
   result->reserved = 0;
   scanner->last = *result;
+  scanner->d_from = o.d_from;
   return HG_OK;
 }
 
@@ -136,6 +138,29 @@ int hg_copy_hits_device(hg_scanner_t *scanner, void *d_dst, uint64_t max, void *
   if (hipMemcpyAsync(d_dst, scanner->last.d_hits, n * sizeof(hg_hit_t), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)) != hipSuccess)
     return HG_ERR_HIP;
   return HG_OK;
+}
+
+int hg_copy_hit_starts(hg_scanner_t *scanner, uint32_t *from, uint64_t max) {
+  if (!scanner || !from) return HG_ERR_ARG;
+  uint64_t n = scanner->last.n_hits < max ? scanner->last.n_hits : max;
+  if (!n) return HG_OK;
+  if (!scanner->d_from) {  // no SOM expression in the database
+    std::memset(from, 0, n * sizeof(uint32_t));
+    return HG_OK;
+  }
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  if (hipMemcpy(from, scanner->d_from, n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
+}
+
+int hg_copy_hit_starts_device(hg_scanner_t *scanner, void *d_dst, uint64_t max, void *stream) {
+  if (!scanner || !d_dst) return HG_ERR_ARG;
+  uint64_t n = scanner->last.n_hits < max ? scanner->last.n_hits : max;
+  if (!n) return HG_OK;
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  const hipError_t e = scanner->d_from ? hipMemcpyAsync(d_dst, scanner->d_from, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream))
+                                       : hipMemsetAsync(d_dst, 0, n * sizeof(uint32_t), static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? HG_OK : HG_ERR_HIP;
 }
 
 }  // extern "C"

@@ -7,7 +7,9 @@
 // look-around, back-references, atomic groups, possessive quantifiers, conditionals, recursion,
 // callouts, \G \K \X \R \C, unicode properties without UCP), rejects expressions that can match the
 // empty string (no HS_FLAG_ALLOWEMPTY), embedded start/end anchors outside multiline mode, and flag
-// bits other than CASELESS|DOTALL|MULTILINE|SINGLEMATCH.  Byte semantics throughout (no UTF-8 mode).
+// bits other than CASELESS|DOTALL|MULTILINE|SINGLEMATCH|SOM_LEFTMOST (SOM_LEFTMOST: not with SINGLEMATCH, not on automata
+// of more than HG_MAX_NODES nodes, and on all or none of the expressions that share a report id).  Byte semantics throughout
+// (no UTF-8 mode).
 #include "hg_compile.h"
 #include "hg_core.h"
 
@@ -1497,6 +1499,8 @@ int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned 
     for (cur = 0; cur < n; cur++) {
       uint32_t f = flags ? flags[cur] : 0;
       if (f & ~HG_FLAGS_SUPPORTED) throw CompileError("unsupported flag bits");
+      if ((f & HG_FLAG_SOM_LEFTMOST) && (f & HG_FLAG_SINGLEMATCH))
+        throw CompileError("HS_FLAG_SOM_LEFTMOST cannot be combined with HS_FLAG_SINGLEMATCH");
       if (!exprs[cur] || !exprs[cur][0]) throw CompileError("empty expression");
       std::string text(exprs[cur]);
       db->exprs.push_back(text);
@@ -1726,6 +1730,17 @@ int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned 
         const long ml = max_match_len(*root);
         p.max_len = ml > 0 ? static_cast<uint32_t>(ml) : 0;
       }
+      if (f & HG_FLAG_SOM_LEFTMOST) {
+        // the reverse automaton of the start-of-match pass (hg_som.h): the same nodes, with the follow table transposed
+        if (huge)
+          throw CompileError("HS_FLAG_SOM_LEFTMOST needs an automaton of at most " + std::to_string(HG_MAX_NODES) + " nodes (HG_MAX_NODES); this expression has " +
+                             std::to_string(nn));
+        p.som_follow_off = alloc(static_cast<size_t>(nn) * nw);
+        for (uint32_t v = 0; v < nn; v++)
+          for (uint32_t w = 0; w < nw; w++)
+            for (uint32_t x = db->pool[p.follow_off + v * nw + w]; x; x &= x - 1) setbit(p.som_follow_off + (w * 32 + hg_ctz(x)) * nw, v);
+        db->nsom++;
+      }
       db->patterns.push_back(p);
     }
   } catch (const CompileError &e) {
@@ -1736,6 +1751,34 @@ int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned 
     if (err) *err = "out of memory";
     if (bad_index) *bad_index = static_cast<int>(cur);
     return -2;
+  }
+  if (db->nsom) {
+    // Expressions that share a report id either all carry HS_FLAG_SOM_LEFTMOST or none does; the SOM expressions of one id
+    // form a cycle (som_next), so that the pass can give an (id, to) report the smallest start over all of them.
+    std::map<uint32_t, uint32_t> last;  // id -> the latest SOM expression seen with it
+    std::map<uint32_t, uint32_t> first_plain;  // id -> the first expression without the flag
+    for (uint32_t i = 0; i < n; i++) {
+      HgPattern &p = db->patterns[i];
+      if (!(p.flags & HG_FLAG_SOM_LEFTMOST)) {
+        first_plain.emplace(p.id, i);
+        continue;
+      }
+      auto it = last.find(p.id);
+      if (it == last.end()) {
+        p.som_next = i;
+      } else {
+        p.som_next = db->patterns[it->second].som_next;  // insert behind the latest: the cycle stays closed
+        db->patterns[it->second].som_next = i;
+      }
+      last[p.id] = i;
+    }
+    for (auto &kv : last) {
+      auto it = first_plain.find(kv.first);
+      if (it == first_plain.end()) continue;
+      if (err) *err = "expressions with report id " + std::to_string(kv.first) + " must all carry HS_FLAG_SOM_LEFTMOST, or none of them";
+      if (bad_index) *bad_index = static_cast<int>(std::max(it->second, kv.second));
+      return -4;
+    }
   }
 
   // Tiers.  A pattern whose required literals all have at least `min_factor` bytes is found through the window prefilter

@@ -47,6 +47,7 @@ struct HgDb {
                                      // need among the huge expressions that fits HG_HUGE_STAGE_MAX (an expression that needs more reads L2)
   uint32_t nslow_huge = 0;           // huge always-on expressions: the LAST nslow_huge entries of `slow`
   uint32_t max_id = 0;               // largest report id (sizes the sort key)
+  uint32_t nsom = 0;                 // expressions with HS_FLAG_SOM_LEFTMOST: the scanner runs the start-of-match pass (hg_som.h)
   uint32_t n_confirm_mode[HG_CONFIRM_MODES] = {};  // tier-0 patterns by confirm routine (hg_confirm_mode)
   std::vector<std::string> exprs;
   bool tuned = false;

@@ -14,7 +14,8 @@
 
 // Flag values (hypergrep/utils.py:10-13).
 constexpr uint32_t HG_FLAG_CASELESS = 1, HG_FLAG_DOTALL = 2, HG_FLAG_MULTILINE = 4, HG_FLAG_SINGLEMATCH = 8;
-constexpr uint32_t HG_FLAGS_SUPPORTED = 15;
+constexpr uint32_t HG_FLAG_SOM_LEFTMOST = 256;  // Hyperscan's value: report the leftmost start of each match (hg_som.h)
+constexpr uint32_t HG_FLAGS_SUPPORTED = 15 | HG_FLAG_SOM_LEFTMOST;
 
 // Boundary contexts for zero-width assertions.  Every assertion the compiler accepts (^ $ \A \z \Z \b \B)
 // is a boolean function of (context of the previous byte, context of the next byte); a 20-bit truth
@@ -109,7 +110,10 @@ struct HgPattern {
   uint32_t acc_all;     // accepting nodes when `simple`
   uint32_t init_word;   // init[0] when `simple`
   uint32_t literal_only;  // the whole expression is one literal (its factor): a verified occurrence IS the match
-  uint32_t reserved[3];
+  // HS_FLAG_SOM_LEFTMOST expressions only (0 otherwise): the reverse automaton for the start-of-match pass (hg_som.h)
+  uint32_t som_follow_off;  // followT[nnodes][nw]: the transposed follow table (the predecessors of each node)
+  uint32_t som_next;        // the next SOM expression with the same report id (a cycle; the expression itself when it is alone)
+  uint32_t reserved;
 };
 static_assert(sizeof(HgPattern) == 80, "HgPattern layout");
 

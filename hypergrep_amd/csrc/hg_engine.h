@@ -129,7 +129,13 @@ struct HgScanOutput {
   uint32_t stream_launches;  // hg_stream_kernel launches of the (last) pass: one per pipeline chunk
   uint32_t joiner_launches;  // ... and hg_stream_join_kernel launches
   uint64_t joiner_tiles;     // tiles (of 16 KiB) the joiner launches took: bytes the hg_stream_kernel launches did NOT stream
+  const uint32_t *d_from;    // databases with HS_FLAG_SOM_LEFTMOST expressions: the start of each hit (hg_som.hip), else nullptr
 };
+
+// The start-of-match pass (hg_som.hip): from[i] for the n final hits, on `stream`.  max_nw: the most state words of any SOM
+// expression (its multi-word walks keep their state in LDS).
+hipError_t hg_som_launch(const uint8_t *text, const HgHit *hits, const HgHitAux *aux, uint64_t n, const HgPattern *patterns, const uint32_t *pool, uint32_t max_nw,
+                         uint32_t *from, hipStream_t stream);
 
 // Test / experiment knobs of the engine, read from the environment ONCE, when a scanner is created (never during a scan:
 // getenv is not safe against a concurrent setenv, and a scan must not change behaviour half-way).  None is needed in normal
@@ -243,6 +249,9 @@ class HgScanner {
   uint64_t fin_expect_hits_ = 0;  // raw hits of the last pass: the next one picks its bucket count for ~24 records a bucket
   void *d_huge_claim_ = nullptr;      // huge automata: (piece start, expression) pairs already run (hg_confirm_huge_kernel), 8-byte slots
   uint64_t huge_claim_slots_ = 0;
+  uint32_t *d_from_ = nullptr;  // starts of the last scan's hits (SOM databases only, allocated by the first scan that needs them)
+  uint64_t from_cap_ = 0;
+  uint32_t som_max_nw_ = 0;
   uint32_t *d_seg_count2_ = nullptr;  // second set for double buffering
   HgCand *d_cands2_ = nullptr;
 };

@@ -170,6 +170,8 @@ int HgScanner::create(std::shared_ptr<const HgDb> db, int device, HgScanner **ou
   s->view_.nslow_huge = db->nslow_huge;
   s->view_.ngroups = static_cast<uint32_t>(db->groups.size());
   s->view_.groups = static_cast<const HgSlowGroup *>(s->d_groups_);
+  for (const HgPattern &p : db->patterns)
+    if (p.flags & HG_FLAG_SOM_LEFTMOST) s->som_max_nw_ = std::max(s->som_max_nw_, p.nw);
   s->view_.fold_mask = db->fold_mask;
   s->view_.window_mask = db->window_mask;
   static_assert(HG_CNT_CURSORS == kMaxChunks, "one tile cursor per pipeline chunk");
@@ -199,7 +201,7 @@ HgScanner::~HgScanner() {
   (void)hipSetDevice(device_);
   void *ptrs[] = {d_patterns_, d_pool_, d_factors_, d_windows_, d_bucket_, d_filter_, d_ext_, d_slow_, d_sums_, d_bases_, d_block_base_,
                   d_agg_, d_cands_, d_hits_raw_, d_hits_out_, d_aux_raw_, d_aux_out_,
-                  d_key_a_, d_key_b_, d_perm_a_, d_perm_b_, d_keep_, d_counters_, d_temp_, d_seg_count_, d_pflags_, d_deferred_, d_defer_count_, d_seg_count2_, d_cands2_, d_disc_, d_bucket2_, d_windows2_, d_groups_, d_acc_hits_, d_acc_aux_, d_huge_claim_, d_wtab_};
+                  d_key_a_, d_key_b_, d_perm_a_, d_perm_b_, d_keep_, d_counters_, d_temp_, d_seg_count_, d_pflags_, d_deferred_, d_defer_count_, d_seg_count2_, d_cands2_, d_disc_, d_bucket2_, d_windows2_, d_groups_, d_acc_hits_, d_acc_aux_, d_huge_claim_, d_wtab_, d_from_};
   for (void *p : ptrs) hgmem::dev_free(p, "scanner");
   hgmem::host_free(h_counters_, "h_counters_");
   for (auto &ev : ev_)
@@ -884,6 +886,22 @@ int HgScanner::scan_impl(const void *d_text, uint64_t nbytes, int buffer_size, u
     }
   }
   out->reruns = reruns;
+  if (db_->nsom) {
+    // start of match: one pass over the final ordered hits (those of all segments, one after the other)
+    if (out->n_hits > from_cap_) {
+      hgmem::dev_free(d_from_, "d_from_");
+      d_from_ = nullptr;
+      from_cap_ = 0;
+      const uint64_t cap = std::max<uint64_t>(out->n_hits + out->n_hits / 4, 4096);
+      if (fail(hgmem::dev_alloc(&d_from_, cap * sizeof(uint32_t), "d_from_"), "alloc (hit starts)")) return HG_ERR_HIP;
+      from_cap_ = cap;
+    }
+    if (fail(hg_som_launch(text, out->d_hits, out->d_aux, out->n_hits, static_cast<const HgPattern *>(d_patterns_), static_cast<const uint32_t *>(d_pool_),
+                           som_max_nw_, d_from_, stream), "start-of-match launch") ||
+        fail(hipStreamSynchronize(stream), "stream sync (start of match)"))
+      return HG_ERR_HIP;
+    out->d_from = d_from_;
+  }
   return HG_OK;
 }
 

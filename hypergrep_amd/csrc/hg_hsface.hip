@@ -30,6 +30,8 @@ struct hs_scratch {
   uint8_t *d_text = nullptr;
   size_t d_cap = 0;
   std::vector<HgHit> hits;
+  std::vector<uint32_t> from;  // (SOM databases) the start of each hit
+  std::vector<uint32_t> order;
   // short blocks (HgScanner::launch_block_small): pinned copies of the block and of the raw reports
   uint8_t *h_text = nullptr;
   HgHit *h_out = nullptr;
@@ -136,7 +138,8 @@ int hs_scan(const hs_database_t *db, const char *data, unsigned int length, unsi
   // Short blocks (the reference shim scans line by line, hyperscanner.c:217): one launch on a pinned copy of the block,
   // raw reports straight into pinned memory, the report rules on the host.
   static const bool small_path = !std::getenv("HG_NO_BLOCK_SMALL");
-  if (length <= HG_BLOCK_SMALL_MAX && small_path) {
+  // (databases with HS_FLAG_SOM_LEFTMOST expressions take the general path: its start-of-match pass fills `from`)
+  if (length <= HG_BLOCK_SMALL_MAX && small_path && !db->db->nsom) {
     std::memcpy(scratch->h_text, data, length);
     std::memset(scratch->h_text + length, 0, (16 - (length & 15)) & 15);
     const uint32_t seq = ++scratch->seq ? scratch->seq : ++scratch->seq;  // (never 0)
@@ -203,15 +206,21 @@ int hs_scan(const hs_database_t *db, const char *data, unsigned int length, unsi
     return HS_INVALID;
   }
   scratch->hits.resize(out.n_hits);
+  scratch->from.assign(out.n_hits, 0u);
   if (out.n_hits) {
     if (hipMemcpyAsync(scratch->hits.data(), out.d_hits, out.n_hits * sizeof(HgHit), hipMemcpyDeviceToHost, scratch->stream) != hipSuccess ||
+        (out.d_from && hipMemcpyAsync(scratch->from.data(), out.d_from, out.n_hits * sizeof(uint32_t), hipMemcpyDeviceToHost, scratch->stream) != hipSuccess) ||
         hipStreamSynchronize(scratch->stream) != hipSuccess)
       return HS_INVALID;
   }
   // device order is (id, to); Hyperscan delivers by ascending end offset (ties by id here)
-  std::sort(scratch->hits.begin(), scratch->hits.end(), [](const HgHit &a, const HgHit &b) { return a.to != b.to ? a.to < b.to : a.id < b.id; });
-  for (const HgHit &h : scratch->hits)
-    if (on_event && on_event(h.id, 0, h.to, 0, context)) return HS_SCAN_TERMINATED;
+  auto &h = scratch->hits;
+  auto &order = scratch->order;
+  order.resize(h.size());
+  for (uint32_t i = 0; i < order.size(); i++) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return h[a].to != h[b].to ? h[a].to < h[b].to : h[a].id < h[b].id; });
+  for (uint32_t i : order)
+    if (on_event && on_event(h[i].id, scratch->from[i], h[i].to, 0, context)) return HS_SCAN_TERMINATED;
   return HS_SUCCESS;
 }
 

@@ -11,6 +11,8 @@ from dataclasses import dataclass
 from hypergrep_amd import utils
 
 DEFAULT_FLAGS = utils.HS_FLAG_DOTALL | utils.HS_FLAG_MULTILINE | utils.HS_FLAG_SINGLEMATCH
+# Report where each match starts (Scanner.hit_starts); not with SINGLEMATCH.  See include/hypergrep_amd.h for the contract.
+HS_FLAG_SOM_LEFTMOST = 256
 
 
 class HgHit(ctypes.Structure):
@@ -63,6 +65,8 @@ def lib() -> ctypes.CDLL:
                                      ctypes.POINTER(HgScanResult)]
         l.hg_copy_hits.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
         l.hg_copy_hits_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        l.hg_copy_hit_starts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
+        l.hg_copy_hit_starts_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_synth_device.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(HgSynthSpec), ctypes.c_int, ctypes.c_void_p]
         l.hg_synth_host.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(HgSynthSpec)]
         l.hg_debug_alloc_guarded.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]
@@ -182,6 +186,28 @@ class Scanner:
         rc = lib().hg_copy_hits_device(self._h, ctypes.c_void_p(d_dst), n, ctypes.c_void_p(stream))
         if rc != 0:
             raise DeviceError(f"hg_copy_hits_device failed ({rc})")
+        return n
+
+    def hit_starts(self, limit: int | None = None):
+        """Start of match of the last scan's hits as a uint32 numpy array, in the order of hits(), with the origin of `to`
+        (offsets inside the scanned bytes): the leftmost start for expressions compiled with HS_FLAG_SOM_LEFTMOST, 0 for the
+        others."""
+        import numpy as np
+
+        n = self._last.n_hits if limit is None else min(limit, self._last.n_hits)
+        out = np.zeros(n, dtype=np.uint32)
+        if n:
+            rc = lib().hg_copy_hit_starts(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n)
+            if rc != 0:
+                raise DeviceError(f"hg_copy_hit_starts failed ({rc})")
+        return out
+
+    def copy_hit_starts_to(self, d_dst: int, limit: int, stream: int = 0) -> int:
+        """Async device-to-device copy of the last scan's hit starts (4 B each); returns the number copied."""
+        n = min(limit, self._last.n_hits)
+        rc = lib().hg_copy_hit_starts_device(self._h, ctypes.c_void_p(d_dst), n, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise DeviceError(f"hg_copy_hit_starts_device failed ({rc})")
         return n
 
     def __del__(self):

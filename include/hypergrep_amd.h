@@ -88,6 +88,14 @@ typedef int (*match_event_handler)(unsigned int id, unsigned long long from, uns
 #define HS_FLAG_DOTALL 2
 #define HS_FLAG_MULTILINE 4
 #define HS_FLAG_SINGLEMATCH 8
+/* Report where each match starts.  For a report (id, to) of an expression with this flag, `from` is the SMALLEST s such
+ * that the expression has a match spanning [s, to) of the scanned bytes; assertions at s (^ \b \B) see the byte before s,
+ * or the start of the scanned bytes, exactly as in the forward scan.  The flag adds `from` and nothing else: the reports
+ * (lines, ids, `to`, order) are those of the same database without it; expressions without it report from = 0.
+ * Rejected with HS_FLAG_SINGLEMATCH, on automata of more than 1024 nodes (e.g. foo.{0,3000}bar), and unless all or none of
+ * the expressions that share a report id carry it (several SOM expressions of one id that end at the same `to` give one
+ * report with the smallest of their starts). */
+#define HS_FLAG_SOM_LEFTMOST 256
 
 /* call site hyperscanner.c:136 */
 int hs_compile_multi(const char *const *expressions, const unsigned int *flags, const unsigned int *ids,
@@ -98,7 +106,8 @@ int hs_free_compile_error(hs_compile_error_t *error);
 /* call site hyperscanner.c:301 */
 int hs_alloc_scratch(const hs_database_t *db, hs_scratch_t **scratch);
 /* call site hyperscanner.c:217: block-mode scan of data[0,length) as ONE unit (no line splitting).
- * The block is copied to HBM and scanned by the same kernels; `from` is always 0 (no SOM). */
+ * The block is copied to HBM and scanned by the same kernels; `from` is the start of the match for expressions compiled
+ * with HS_FLAG_SOM_LEFTMOST (the GPU start-of-match pass), 0 for the others. */
 int hs_scan(const hs_database_t *db, const char *data, unsigned int length, unsigned int flags,
             hs_scratch_t *scratch, match_event_handler on_event, void *context);
 /* call sites hyperscanner.c:323, :165/:324 (both may receive NULL) */
@@ -123,7 +132,7 @@ typedef struct hg_scanner hg_scanner_t;   /* database + workspace resident on on
 typedef struct hg_hit {
     uint64_t line_number; /* 0-based piece index == hyperscanner_result_t.line_number */
     uint32_t id;          /* == hyperscanner_result_t.id */
-    uint32_t to;          /* match end offset inside the scanned bytes (Hyperscan's `to`) */
+    uint32_t to;          /* match end offset inside the scanned bytes (Hyperscan's `to`); its start: hg_copy_hit_starts */
 } hg_hit_t;
 
 /* Where Result.line lives in the scanned buffer. */
@@ -190,6 +199,14 @@ int hg_copy_hits(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint6
 /* Copy the last scan's first `max` hit records (16 B each) into another DEVICE buffer, asynchronously on
  * `stream` (e.g. a tensor that is then sent over RCCL). */
 int hg_copy_hits_device(hg_scanner_t *scanner, void *d_dst, uint64_t max, void *stream);
+
+/* Start of match of the last scan's first `max` hits, one uint32_t per hit in hit order, the same origin as `to`
+ * (offsets inside the scanned bytes, i.e. relative to hg_hit_aux_t.start).  Hits of expressions compiled with
+ * HS_FLAG_SOM_LEFTMOST carry the leftmost start of their match; all others 0.  The starts are computed by a pass that runs
+ * after the hits are final, only when the database has SOM expressions (hg_scan_device then includes it). */
+int hg_copy_hit_starts(hg_scanner_t *scanner, uint32_t *from, uint64_t max);
+/* The same into a DEVICE buffer, asynchronously on `stream`. */
+int hg_copy_hit_starts_device(hg_scanner_t *scanner, void *d_dst, uint64_t max, void *stream);
 
 /* Deterministic synthetic log used by bench.py and the parity tests: writes nbytes at d_text (device)
  * or text (host) from the same counter-based generator; see hypergrep_amd/csrc/hg_synth.h. */

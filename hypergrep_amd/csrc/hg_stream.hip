@@ -47,17 +47,36 @@ __device__ __forceinline__ uint32_t not_newline_bits(uint32_t w) {
   return b | w | 0x7f7f7f7fu;                                     // ... or the byte's own bit 7 is set
 }
 
+// x's popcount + acc in one v_bcnt_u32_b32.  (Written out because the compiler turns a chain of four into a tree that
+// costs a v_add3 more.)
+__device__ __forceinline__ uint32_t popc_add(uint32_t x, uint32_t acc) {
+  uint32_t r;
+  asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
+  return r;
+}
+// A wave-uniform value the compiler must take as one SGPR as it is: otherwise it pulls a constant term out of a sum and
+// adds it in a VALU op of its own.
+__device__ __forceinline__ uint32_t opaque_sgpr(uint32_t v) {
+  asm("" : "+s"(v));
+  return v;
+}
+
 // LDS is addressed through explicit address-space-3 pointers so that the out-of-line drain routine also gets ds_* instructions.
 using lds_u32 = __attribute__((address_space(3))) uint32_t;
 
 // entries per wave: an iteration adds at most 64, and the queue is drained as soon as it holds a full batch of 64
 constexpr uint32_t queue_cap(int) { return 128u; }
-// dwords per entry: {chunk | rank << 10, tile} and, while LDS has room (filters up to 16 KiB, three workgroups per CU), also
+// dwords per entry: {rank | chunk << 16, tile} and, while LDS has room (filters up to 16 KiB, three workgroups per CU), also
 // {left, right, the chunk's four dwords} so that the drain does not read the text again (measured: re-reading costs ~15 % extra
 // HBM fetches on the round-1 workload, the streamed tiles have left the L2 by then)
 // (byte-aligned probing re-reads the text: its drain wants up to 28 bytes around the chunk)
 constexpr bool queue_stash(int log2, bool dense) { return log2 <= 12 && !dense; }
 constexpr uint32_t queue_entry_dw(int log2, bool dense) { return queue_stash(log2, dense) ? 8u : 2u; }
+// An entry's first dword: the newlines of the tile before the chunk in the low half (fewer than 2^14 in a 16 KiB tile), the
+// chunk's place in the tile (iteration * 64 + lane) in the high half.  In this order the hot loop builds it with the two
+// v_mbcnt that count the newline ballot's lanes below its own, on top of (place << 16) + the tile's newlines so far.
+__device__ __forceinline__ uint32_t queue_chunk(uint32_t e0) { return e0 >> 16; }
+__device__ __forceinline__ uint32_t queue_rank(uint32_t e0) { return e0 & 0xFFFFu; }
 
 template <int LOG2, bool WIDE>
 struct Probe {
@@ -92,6 +111,24 @@ struct Probe {
     if (ANY_ONLY) return (m0 || m1 || m2 || m3) ? 1u : 0u;
     return (m0 ? 1u : 0u) | (m1 ? 2u : 0u) | (m2 ? 4u : 0u) | (m3 ? 8u : 0u);  // bit k: window k matched
   }
+  // Hot path: did any of the four windows match?  `mask` gets the wave's ballot of the answer as the OR of the four compare
+  // masks (a ballot of the OR'd bool went through a v_cndmask and a v_cmp to get there)
+  template <bool FOLD>
+  __device__ __forceinline__ static bool any4(const lds_u32 *filter, uint32_t fold, uint32_t wa, uint32_t wb, uint4 v, uint64_t &mask) {
+    if (WIDE) {
+      const bool any = probe4<true, FOLD>(filter, fold, wa, wb, v) != 0;
+      mask = __builtin_amdgcn_ballot_w64(any);
+      return any;
+    }
+    const uint32_t f0 = FOLD ? v.x | fold : v.x, f1 = FOLD ? v.y | fold : v.y, f2 = FOLD ? v.z | fold : v.z, f3 = FOLD ? v.w | fold : v.w;
+    const uint32_t a0 = hg_dot4(f0, wa), a1 = hg_dot4(f1, wa), a2 = hg_dot4(f2, wa), a3 = hg_dot4(f3, wa);
+    const uint32_t t0 = at(filter, a0 & BYTE_MASK), t1 = at(filter, a1 & BYTE_MASK), t2 = at(filter, a2 & BYTE_MASK), t3 = at(filter, a3 & BYTE_MASK);
+    const uint32_t c0 = hg_dot4(f0, HG_HASH_WEIGHTS), c1 = hg_dot4(f1, HG_HASH_WEIGHTS);
+    const uint32_t c2 = hg_dot4(f2, HG_HASH_WEIGHTS), c3 = hg_dot4(f3, HG_HASH_WEIGHTS);
+    const bool m0 = hg_slot_match(t0, c0), m1 = hg_slot_match(t1, c1), m2 = hg_slot_match(t2, c2), m3 = hg_slot_match(t3, c3);
+    mask = __builtin_amdgcn_ballot_w64(m0) | __builtin_amdgcn_ballot_w64(m1) | __builtin_amdgcn_ballot_w64(m2) | __builtin_amdgcn_ballot_w64(m3);
+    return m0 || m1 || m2 || m3;
+  }
 };
 
 // Byte-aligned probing (pattern sets with required literals shorter than HG_FAST_MIN_FACTOR, db.dense): every byte of the
@@ -124,6 +161,23 @@ struct ProbeBytes {
   }
 };
 
+// Bit b set: byte b of the 16-byte chunk is '\n'.
+__device__ __forceinline__ uint32_t newline_bits16(uint4 v) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  uint32_t bits = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t m = hg_newline_mask(w[k]);
+#pragma unroll
+    for (int b = 0; b < 4; b++) bits |= ((m >> (8 * b + 7)) & 1u) << (k * 4 + b);
+  }
+  return bits;
+}
+// Lane l's chunk, as wave-uniform values.
+__device__ __forceinline__ uint4 readlane4(uint4 v, uint32_t l) {
+  return make_uint4(__builtin_amdgcn_readlane(v.x, l), __builtin_amdgcn_readlane(v.y, l), __builtin_amdgcn_readlane(v.z, l), __builtin_amdgcn_readlane(v.w, l));
+}
+
 // Dword at byte offset `at` (a multiple of 4) of the text, bytes past the end of the text zeroed.
 __device__ __forceinline__ uint32_t load_dword_checked(const uint4 *__restrict__ text16, uint64_t nbytes, uint64_t at) {
   if (at >= nbytes) return 0u;
@@ -139,8 +193,8 @@ struct StreamCtx {
   uint64_t nbytes;
   const lds_u32 *filter;
   const HgSlotInfo *ext;       // the slots' window values and neighbour conditions (HBM, L2-resident)
-  lds_u32 *queue;              // this wave's queue, one entry per 16-byte chunk whose first level matched: {chunk inside the tile | newlines of the
-                               // tile before it << 10, tile, dword left of the chunk, dword right of it, the chunk} — the drain never re-reads the text
+  lds_u32 *queue;              // this wave's queue, one entry per 16-byte chunk whose first level matched: {newlines of the tile before the chunk |
+                               // chunk inside the tile << 16, tile, dword left of the chunk, dword right of it, the chunk} — the drain never re-reads the text
   lds_u32 *cand_count;         // the workgroup's candidate counter
   HgCand *seg;                 // the workgroup's private candidate segment
   uint32_t seg_cap, fold, wa, wb;  // wb: slot weights B in wide mode; with byte-aligned probing the hash C weights (their top byte is zero
@@ -200,8 +254,8 @@ __device__ __noinline__ void drain_batch(const StreamCtx cx, uint32_t first, uin
     if (active) {
       const lds_u32 *e = cx.queue + (first + lane) * queue_entry_dw(LOG2, DENSE);
       const uint32_t e_lo = e[0], e_hi = e[1];
-      g = static_cast<uint64_t>(e_hi) * (HG_TILE_BYTES / 16) + (e_lo & 1023u);
-      rank = e_lo >> 10;
+      g = static_cast<uint64_t>(e_hi) * (HG_TILE_BYTES / 16) + queue_chunk(e_lo);
+      rank = queue_rank(e_lo);
       cur = load_chunk_checked(cx.text16, cx.nbytes, g);
       nxt = load_dword_checked(cx.text16, cx.nbytes, (g + 1) << 4);
       uint32_t l1 = ProbeBytes<LOG2, DENSE ? DENSE : 1>::template probe16<false>(cx.filter, cx.fold, cx.wa, cx.wb, cur, nxt);
@@ -258,10 +312,10 @@ __device__ __noinline__ void drain_batch(const StreamCtx cx, uint32_t first, uin
   if (active) {
     const lds_u32 *e = cx.queue + (first + lane) * queue_entry_dw(LOG2, DENSE);
     const uint32_t e_lo = e[0], e_hi = e[1];
-    g = static_cast<uint64_t>(e_hi) * (HG_TILE_BYTES / 16) + (e_lo & 1023u);
-    rank = e_lo >> 10;
+    g = static_cast<uint64_t>(e_hi) * (HG_TILE_BYTES / 16) + queue_chunk(e_lo);
+    rank = queue_rank(e_lo);
     uint32_t left = 0, right = 0;
-    bool have_left = (e_lo & 63u) != 0, have_right = (e_lo & 63u) != 63u;  // stashed neighbours come from the adjacent lanes of the 1 KiB row
+    bool have_left = (queue_chunk(e_lo) & 63u) != 0, have_right = (queue_chunk(e_lo) & 63u) != 63u;  // stashed neighbours come from the adjacent lanes of the 1 KiB row
     if (queue_stash(LOG2, DENSE)) {
       left = e[2];
       right = e[3];
@@ -337,6 +391,10 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
   const uint64_t nbytes = cx.nbytes;
   const uint64_t chunk0 = tile * (HG_TILE_BYTES / 16) + lane;
 
+  // The full tiles' loads: a buffer resource for the tile (scalar), the row's offset as a scalar and the lane's as a 32-bit
+  // VGPR.  (Global loads from a 64-bit per-lane address cost two VALU ops per row for the address.)
+  const __amdgpu_buffer_rsrc_t tile_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(text16 + tile * (HG_TILE_BYTES / 16)), 0, HG_TILE_BYTES, 0x00020000);
+  const uint32_t lane_off = lane * 16u;
   auto load_chunk = [&](int it) -> uint4 {
     const uint64_t g = chunk0 + static_cast<uint64_t>(it) * 64u;
     if (FULL) {
@@ -345,20 +403,32 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
       // Not for wide filters: their drain reads every queued chunk AGAIN a few microseconds later (no room in LDS to carry
       // it in the queue), and with the default policy most of those reads hit the L2 (config 5: 14.98 -> 14.65 ms per 32 GiB)
       if (WIDE) return text16[g];
+      if (DENSE) {  // (byte-aligned probing: a VGPR more for the buffer offset pushed it past its spill budget)
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(text16) + g);
+        return make_uint4(v.x, v.y, v.z, v.w);
+      }
 #if defined(HG_NO_NT_LOADS)
       return text16[g];
 #else
+      // (a buffer load: the tile's resource and the row offset are scalars, the lane's byte offset a 32-bit VGPR; aux 2 = nt)
       typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-      const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(text16) + g);
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc, lane_off, it * 1024, 2);
       return make_uint4(v.x, v.y, v.z, v.w);
 #endif
     }
     return load_chunk_checked(text16, nbytes, g);
   };
 
-  uint32_t seen = 0;                           // wave-uniform: newlines of the tile in the iterations done so far
-  uint32_t first_it = HG_NONE32, last_it = 0;  // wave-uniform: iterations holding the first / last newline
-  uint32_t first_lane = 0, last_lane = 0;
+  uint32_t seen = 0;  // wave-uniform: newlines of the tile in the iterations done so far
+  // Tile-relative offsets of the first / last newline.  Dword-aligned probing finds them while their chunk is still in
+  // registers: the first when the first newline ballot comes (once per tile), the last from the tile's last row.  Otherwise
+  // (a tile whose last row holds no newline; byte-aligned probing, which has no registers to spare) the chunk is read
+  // again after the loop: first_it / last_it are the rows with the first / last newline, first_nlm / last_nlm their ballots.
+  uint32_t first_nl = HG_NONE32, last_nl = HG_NONE32;
+  uint32_t first_it = 0, last_it = 0;
+  uint64_t first_nlm = 0, last_nlm = 0;
+  const uint32_t lane_key = lane << 16;  // the lane's part of a queue entry's first dword (queue_chunk / queue_rank)
 
   // byte-aligned probing: the dword after the lane's chunk is the next lane's first; the row's last lane reads it
   auto load_after = [&](int it) -> uint32_t {
@@ -367,26 +437,31 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
   };
 
   auto body = [&](int it, uint4 cur, uint32_t after) {
-    // exact newline count of this lane's 16 bytes: 128 - popcount of the "not a newline" bits
+    // exact newline count of this lane's 16 bytes: 128 - popcount of the "not a newline" bits (one v_bcnt chain)
     uint32_t notnl = __popc(not_newline_bits(cur.x));
-    notnl += __popc(not_newline_bits(cur.y));
-    notnl += __popc(not_newline_bits(cur.z));
-    notnl += __popc(not_newline_bits(cur.w));
+    notnl = popc_add(not_newline_bits(cur.y), notnl);
+    notnl = popc_add(not_newline_bits(cur.z), notnl);
+    notnl = popc_add(not_newline_bits(cur.w), notnl);
 #if defined(HG_ABLATE) && HG_ABLATE == 2  // profiling aid: no newline counting (results are wrong)
     const uint32_t c = cur.x == 0x0a0a0a0au ? 1u : 0u;
+    const bool has_nl = c != 0, several_nl = c > 1;
 #else
     const uint32_t c = 128u - notnl;
+    const bool has_nl = notnl != 128u, several_nl = notnl < 127u;  // (on notnl itself: no v_sub for c on the common path)
 #endif
 
 #if defined(HG_ABLATE) && HG_ABLATE == 1  // profiling aid: no window filter (results are wrong)
     bool any = (cur.x ^ cur.y ^ cur.z ^ cur.w) == 0x12345678u;
+    uint64_t am = __builtin_amdgcn_ballot_w64(any);
 #else
     bool any;
+    uint64_t am;  // the wave's ballot of `any`
     if constexpr (DENSE) {
       const uint32_t nxt = __builtin_amdgcn_update_dpp(after, cur.x, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);  // lane 63 keeps `after`
       any = ProbeBytes<LOG2, DENSE ? DENSE : 1>::template probe16<true>(cx.filter, cx.fold, cx.wa, cx.wb, cur, nxt) != 0;
+      am = __builtin_amdgcn_ballot_w64(any);
     } else {
-      any = Probe<LOG2, WIDE>::template probe4<true, FOLD>(cx.filter, cx.fold, cx.wa, cx.wb, cur) != 0;
+      any = Probe<LOG2, WIDE>::template any4<FOLD>(cx.filter, cx.fold, cx.wa, cx.wb, cur, am);
     }
 #endif
 
@@ -394,38 +469,54 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
     // mask folds NUL onto ' ': a required literal of spaces, or a window value of zero).  Such a chunk holds no occurrence
     // and must not reach the drain, whose neighbour reads assume a position inside the text.  (Round 1 shipped without
     // this: the drain read up to a tile past the buffer, a GPU memory fault whenever that memory was not mapped.)
-    if constexpr (!FULL) any = any && ((chunk0 + static_cast<uint64_t>(it) * 64u) << 4) < nbytes;
-
-    const uint64_t nlm = __builtin_amdgcn_ballot_w64(c != 0);
-    const uint64_t multi = __builtin_amdgcn_ballot_w64(c > 1);  // a 16-byte chunk with several newlines: rare in logs
-    if (nlm) {
-      if (first_it == HG_NONE32) {
-        first_it = it;
-        first_lane = __builtin_ctzll(nlm);
-      }
-      last_it = it;
-      last_lane = 63u - __builtin_clzll(nlm);
+    if constexpr (!FULL) {
+      any = any && ((chunk0 + static_cast<uint64_t>(it) * 64u) << 4) < nbytes;
+      am = __builtin_amdgcn_ballot_w64(any);
     }
+
+    const uint64_t nlm = __builtin_amdgcn_ballot_w64(has_nl);
+    const uint64_t multi = __builtin_amdgcn_ballot_w64(several_nl);  // a 16-byte chunk with several newlines: rare in logs
+    // first / last newline of the tile (branch-free selects for the last row with one; the byte offsets from the chunk's
+    // dwords read out of the lane that holds it, no reload after the loop: that reload from HBM left the wave without a
+    // load in flight at every tile end)
+    if constexpr (!DENSE) {
+      if (nlm && first_nl == HG_NONE32) {
+        const uint32_t l = __builtin_ctzll(nlm);
+        first_nl = static_cast<uint32_t>(it) * 1024u + l * 16u + (__ffs(newline_bits16(readlane4(cur, l))) - 1);
+      }
+      if (it == ITERS - 1 && nlm) {
+        const uint32_t l = 63u - __builtin_clzll(nlm);
+        last_nl = static_cast<uint32_t>(it) * 1024u + l * 16u + (31 - __clz(newline_bits16(readlane4(cur, l))));
+      }
+    } else {
+      first_it = first_nlm ? first_it : static_cast<uint32_t>(it);
+      first_nlm = first_nlm ? first_nlm : nlm;
+    }
+    last_it = nlm ? static_cast<uint32_t>(it) : last_it;
+    last_nlm = nlm ? nlm : last_nlm;
     // newlines of the iteration: a popcount of the ballot while every chunk has at most one (the per-lane prefix `before`,
     // newlines of the tile before this lane's chunk, is only needed by lanes that queue their chunk)
-    uint32_t total, incl = 0;
+    // The queue entry's first dword (queue_chunk / queue_rank) is built on `key` = (iteration * 64 + lane) << 16 + seen: the
+    // lanes of the newline ballot below this one are added by the mbcnt pair's accumulator.
+    const uint32_t key = lane_key + opaque_sgpr(seen + (static_cast<uint32_t>(it) << 22));
+    uint32_t total, e0 = 0;
     if (__builtin_expect(multi == 0, 1)) {
       total = __popcll(nlm);
+      e0 = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(nlm >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(nlm), key));
     } else {
-      incl = wave_inclusive_scan(c, lane);
+      const uint32_t incl = wave_inclusive_scan(c, lane);
       total = __builtin_amdgcn_readlane(incl, 63);
+      e0 = key + incl - c;
     }
-    const uint64_t am = __builtin_amdgcn_ballot_w64(any);
     if (am) {  // remember the chunks; their windows are examined in batches of 64 (drain_batch)
-      const uint32_t before = multi == 0 ? seen + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(nlm >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(nlm), 0u))
-                                         : seen + incl - c;
-      // the dwords next to the chunk, from the adjacent lanes (DPP wave shifts; the row's edge lanes get 0 and skip that condition)
-      const uint32_t left = __builtin_amdgcn_update_dpp(0u, cur.w, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-      const uint32_t right = __builtin_amdgcn_update_dpp(0u, cur.x, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
+      // the dwords next to the chunk, from the adjacent lanes (DPP wave shifts with bound_ctrl: the row's edge lanes read
+      // 0 and skip that condition; no v_mov for an old value)
+      const uint32_t left = __builtin_amdgcn_mov_dpp(cur.w, 0x138 /* wave_shr:1 */, 0xF, 0xF, true);
+      const uint32_t right = __builtin_amdgcn_mov_dpp(cur.x, 0x130 /* wave_shl:1 */, 0xF, 0xF, true);
       if (any) {
-        const uint32_t idx = qn + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(am >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(am), 0u));
-        lds_u32 *e = cx.queue + idx * queue_entry_dw(LOG2, DENSE);
-        e[0] = (static_cast<uint32_t>(it) * 64u + lane) | (before << 10);
+        const uint32_t idx = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(am >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(am), 0u));
+        lds_u32 *e = (cx.queue + qn * queue_entry_dw(LOG2, DENSE)) + idx * queue_entry_dw(LOG2, DENSE);
+        e[0] = e0;
         e[1] = static_cast<uint32_t>(tile);
         if (queue_stash(LOG2, DENSE)) {
           e[2] = left;
@@ -464,29 +555,18 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
     for (int it = 0; it < ITERS; it++) body(it, load_chunk(it), load_after(it));
   }
 
-  // tile summary: exact offsets of the first / last newline (re-read two 16-byte chunks, L2-resident)
+  // tile summary: the newlines not found in registers come from their chunk read again (bytes past the end of the text are
+  // zero in the partial tile's rows as well as here, and zero is not a newline)
   const uint32_t nl_count = seen;
-  uint32_t first_nl = HG_NONE32, last_nl = HG_NONE32;
-  if (nl_count) {
-    auto chunk_masks = [&](uint32_t it_, uint32_t lane_) -> uint32_t {  // bit b set: byte b of the chunk is '\n'
-      const uint64_t g = tile * (HG_TILE_BYTES / 16) + it_ * 64u + lane_;
-      const uint4 v = text16[g];
-      const uint64_t byte0 = g << 4;
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-      uint32_t bitsm = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const uint32_t m = hg_newline_mask(w[k]);
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-          if ((m >> (8 * b + 7)) & 1u) bitsm |= 1u << (k * 4 + b);
-      }
-      if (!FULL && byte0 + 16 > nbytes) bitsm &= (1u << static_cast<uint32_t>(nbytes - byte0)) - 1u;
-      return bitsm;
-    };
-    const uint32_t fm = chunk_masks(first_it, first_lane), lm = chunk_masks(last_it, last_lane);
-    first_nl = first_it * 1024u + first_lane * 16u + (__ffs(fm) - 1);
-    last_nl = last_it * 1024u + last_lane * 16u + (31 - __clz(lm));
+  if (nl_count && first_nl == HG_NONE32) {
+    const uint32_t l = __builtin_ctzll(first_nlm);
+    const uint4 v = load_chunk_checked(text16, nbytes, tile * (HG_TILE_BYTES / 16) + first_it * 64u + l);
+    first_nl = first_it * 1024u + l * 16u + (__ffs(newline_bits16(v)) - 1);
+  }
+  if (nl_count && last_nl == HG_NONE32) {
+    const uint32_t l = 63u - __builtin_clzll(last_nlm);
+    const uint4 v = load_chunk_checked(text16, nbytes, tile * (HG_TILE_BYTES / 16) + last_it * 64u + l);
+    last_nl = last_it * 1024u + l * 16u + (31 - __clz(newline_bits16(v)));
   }
   if (lane == 0) sums[tile] = HgTileSum{nl_count, first_nl, last_nl, nl_count ? nl_count - 1 : 0};
 }

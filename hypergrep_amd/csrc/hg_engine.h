@@ -148,6 +148,7 @@ struct HgEngineKnobs {
   std::string chunk_weights;       // HG_CHUNK_WEIGHTS: relative chunk sizes
   long stream_wgs_per_cu = 0;      // HG_STREAM_WGS_PER_CU (0: default)
   long joiner = -1;                // HG_JOINER (-1: default)
+  bool joiner_ahead = false;       // HG_JOINER_AHEAD: the joiner goes in front of its chunk's stream launch (it takes tiles for sure)
   bool no_early_finalize = false;  // HG_NO_EARLY_FINALIZE
   uint32_t confirm_mode_mask = 0x1F;  // HG_DEBUG_CONFIRM_MODES (profiling builds only: results are incomplete)
   long confirm_blocks_per_cu = 0;  // HG_CONFIRM_BLOCKS_PER_CU (0: default)

@@ -91,6 +91,7 @@ HgEngineKnobs HgEngineKnobs::from_env() {
   if (const char *env = std::getenv("HG_CHUNK_WEIGHTS")) k.chunk_weights = env;
   k.stream_wgs_per_cu = static_cast<long>(num("HG_STREAM_WGS_PER_CU", 0));
   if (const char *env = std::getenv("HG_JOINER")) k.joiner = std::max(0l, std::min(2l, std::strtol(env, nullptr, 10)));
+  k.joiner_ahead = std::getenv("HG_JOINER_AHEAD") != nullptr;
   k.no_early_finalize = std::getenv("HG_NO_EARLY_FINALIZE") != nullptr;
 #ifdef HG_PROFILE_CONFIRM
   if (const char *env = std::getenv("HG_DEBUG_CONFIRM_MODES")) k.confirm_mode_mask = static_cast<uint32_t>(std::strtoul(env, nullptr, 0));
@@ -500,7 +501,17 @@ int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint
       const uint32_t join_seg_cap = sa.cand_seg_cap / 4;
       sa.alone = (c == 0 && wgs_c == wgs_alone && !knobs_.stream_wgs_per_cu) ? 1u : 0u;
       sa.counters = d_counters_;
+      HgStreamArgs ja = sa;  // the joiner: its own candidate segments behind the stream launch's
+      ja.cands = cands + static_cast<uint64_t>(wgs_c) * sa.cand_seg_cap;
+      ja.cand_seg_cap = join_seg_cap;
+      ja.seg_count = seg_count + wgs_c;
+      ja.alone = 0;
       HG_TRY(hipEventRecord(piped ? ev_k1_begin_[c] : ev_[1], stream), "event");
+      if (joiners_c && knobs_.joiner_ahead) {  // (tests: in front of the chunk's stream launch, it draws the chunk's tiles first)
+        if (!hg_launch_stream_join(ja, joiners_c, stream)) return HG_ERR_ARG;
+        out->joiner_launches++;
+        HG_TRY(hipGetLastError(), "hg_stream_kernel launch (joiner)");
+      }
       if (!hg_launch_stream(sa, wgs_c, stream)) {
         err_ = "no stream kernel for this database's filter size / mode";
         return HG_ERR_ARG;
@@ -520,12 +531,7 @@ int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint
           fin_done = lim;
         }
       }
-      if (joiners_c) {  // (the side stream: behind the side passes of chunk c - 1, in front of those of chunk c)
-        HgStreamArgs ja = sa;
-        ja.cands = cands + static_cast<uint64_t>(wgs_c) * sa.cand_seg_cap;
-        ja.cand_seg_cap = join_seg_cap;
-        ja.seg_count = seg_count + wgs_c;
-        ja.alone = 0;
+      if (joiners_c && !knobs_.joiner_ahead) {  // (the side stream: behind the side passes of chunk c - 1, in front of those of chunk c)
         if (!hg_launch_stream_join(ja, joiners_c, side)) return HG_ERR_ARG;
         out->joiner_launches++;
         HG_TRY(hipGetLastError(), "hg_stream_kernel launch (joiner)");

@@ -61,8 +61,9 @@ static HgDbView view_of(HgDb *db);
 // Invariants of the compiled prefilter, checked on the tables themselves (no text): every window of every literal
 //  (1) passes the first level at its own slot, (2) passes the second level when the literal's own bytes surround it,
 //  (3) is found by the verify pass's discriminated bucket lookup when the literal itself is the text.
-// Returns the number of violations; out[0] = filter log2, out[1] = wide, out[2] = slots holding more than two values.
-uint32_t hgsim_selfcheck(void *h, uint32_t *out) {  // out[6]
+// Returns the number of violations; out[0] = filter log2, out[1] = wide, out[2] = slots holding more than two values,
+// out[3] = byte-aligned probing step (0: dword windows), out[6] = window bytes (3 or 4).
+uint32_t hgsim_selfcheck(void *h, uint32_t *out) {  // out[7]
   HgDb *db = static_cast<HgDb *>(h);
   const HgDbView v = view_of(db);
   uint32_t bad = 0, many = 0;
@@ -119,7 +120,7 @@ uint32_t hgsim_selfcheck(void *h, uint32_t *out) {  // out[6]
       if (k && b.factor_off[k] != HG_WTAB_EMPTY && b.factor_off[k - 1] == HG_WTAB_EMPTY) bad++;
     }
   if (used * 2 > db->wtab.size() * HG_WTAB_WAYS || db->wtab.size() != static_cast<size_t>(db->wtab_mask) + 1) bad++;
-  if (out) { out[4] = db->shared_windows; out[5] = db->wtab_first; }
+  if (out) { out[4] = db->shared_windows; out[5] = db->wtab_first; out[6] = db->window_bytes; }
   return bad;
 }
 uint32_t hgsim_pattern_tier(void *h, uint32_t i) { return static_cast<HgDb *>(h)->patterns[i].tier; }

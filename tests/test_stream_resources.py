@@ -31,3 +31,15 @@ def test_config3_stream_variants_fit_three_workgroups_without_scratch():
         # three workgroups of 8 waves per CU = 6 waves per SIMD, and room for three in the CU's 160 KiB of LDS
         assert res["Occupancy [waves/SIMD]"] >= 6, (name, res["Occupancy [waves/SIMD]"])
         assert 3 * res["LDS Size [bytes/block]"] <= 160 * 1024, (name, res["LDS Size [bytes/block]"])
+
+
+def test_every_stream_instantiation_has_a_cell():
+    """The compiled hg_stream_kernel / hg_stream_join_kernel variants are exactly the cell table's (stream_cells.py): a new
+    instantiation without a cell, or a cell whose kernel is gone, fails here."""
+    import stream_cells
+
+    table = _table()
+    compiled = [stream_cells.instantiation_of_symbol(k) for k in table if "hg_stream_kernel" in k or "hg_stream_join_kernel" in k]
+    assert None not in compiled
+    assert len(compiled) == len(set(compiled)) == 35
+    assert set(compiled) == {c.instantiation for c in stream_cells.CELLS}

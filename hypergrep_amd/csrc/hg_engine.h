@@ -145,7 +145,7 @@ struct HgEngineKnobs {
   bool no_bucket_finalize = false; // HG_NO_BUCKET_FINALIZE
   uint64_t chunk_tiles = 0;        // HG_CHUNK_TILES: pipeline chunk size (0: default)
   uint32_t max_chunks = 0;         // HG_MAX_CHUNKS (0: default)
-  std::string chunk_weights;       // HG_CHUNK_WEIGHTS: relative chunk sizes
+  std::vector<double> chunk_weights;  // HG_CHUNK_WEIGHTS: relative chunk sizes
   long stream_wgs_per_cu = 0;      // HG_STREAM_WGS_PER_CU (0: default)
   long joiner = -1;                // HG_JOINER (-1: default)
   bool joiner_ahead = false;       // HG_JOINER_AHEAD: the joiner goes in front of its chunk's stream launch (it takes tiles for sure)
@@ -179,6 +179,7 @@ class HgScanner {
 
  private:
   HgScanner() = default;
+  int init();
   int ensure(uint64_t nbytes);
   int alloc_cands(uint64_t n);
   int alloc_hits(uint64_t n);
@@ -190,10 +191,22 @@ class HgScanner {
     uint64_t tile_lo, tile_hi, cs0, piece0, own_lo, own_hi;
     bool last;  // the range ends with the text: the pass leaves the final piece count
   };
-  int scan_segments(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, hipStream_t stream, HgScanOutput *out, uint32_t nsegments, bool *too_many);
-  int run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const PassRange &range, bool block_mode, hipStream_t stream, HgScanOutput *out,
-               bool *overflow);
+  int scan_segments(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, hipStream_t stream, HgScanOutput *out, uint32_t nsegments);
+  int run_fitting(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const PassRange &range, bool block_mode, hipStream_t stream, HgScanOutput *out);
+  int run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const PassRange &range, bool block_mode, hipStream_t stream, HgScanOutput *out);
+  // the stages of a pass (hg_engine.hip)
+  struct PassPlan;
+  PassPlan plan_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const PassRange &range, bool block_mode, hipStream_t stream) const;
+  int alloc_fin(uint32_t nb, hipStream_t stream);
+  int launch_stream(PassPlan &p, uint32_t c, HgScanOutput *out);
+  int launch_side(PassPlan &p, uint32_t c);
+  int finalize_last(PassPlan &p, uint32_t c);
+  int launch_fin(const PassPlan &p, hipStream_t s, uint32_t lo, uint32_t hi, bool beside_stream = false);
+  int regrow(const PassPlan &p, uint64_t n_raw);
+  int finalize_compact(const PassPlan &p, uint32_t n, uint64_t line_bound);
+  int huge_lds_error() { return error(HG_ERR_HIP, "the huge-automaton kernel cannot have its LDS"); }
   bool fail(hipError_t e, const char *what);
+  int error(int rc, const std::string &what) { err_ = what; return rc; }
 
   HgEngineKnobs knobs_;
   int device_ = 0;

@@ -64,7 +64,7 @@ int hg_db_info(const hg_database_t *db, hg_db_info_t *info) {
   const HgDb &d = *db->db;
   info->n_patterns = static_cast<uint32_t>(d.patterns.size());
   info->n_always_on = static_cast<uint32_t>(d.slow.size());
-  info->n_literal_anchored = info->n_patterns - info->n_always_on;
+  info->n_literal_anchored = info->n_patterns - info->n_always_on - d.ncomb;  // (combinations are neither: no automaton)
   info->n_factors = d.nreal_factors;
   info->n_windows = d.nreal_factors ? static_cast<uint32_t>(d.windows.size()) : 0;
   info->fold_mask = d.fold_mask;

@@ -7,10 +7,11 @@
 // look-around, back-references, atomic groups, possessive quantifiers, conditionals, recursion,
 // callouts, \G \K \X \R \C, unicode properties without UCP), rejects expressions that can match the
 // empty string (no HS_FLAG_ALLOWEMPTY), embedded start/end anchors outside multiline mode, and flag
-// bits other than CASELESS|DOTALL|MULTILINE|SINGLEMATCH|SOM_LEFTMOST (SOM_LEFTMOST: not with SINGLEMATCH, not on automata
-// of more than HG_MAX_NODES nodes, and on all or none of the expressions that share a report id).  Byte semantics throughout
-// (no UTF-8 mode).
+// bits other than CASELESS|DOTALL|MULTILINE|SINGLEMATCH|SOM_LEFTMOST|COMBINATION|QUIET (SOM_LEFTMOST: not with SINGLEMATCH,
+// not on automata of more than HG_MAX_NODES nodes, and on all or none of the expressions that share a report id; COMBINATION:
+// a formula over report ids, parse_combination below and hg_comb.h).  Byte semantics throughout (no UTF-8 mode).
 #include "hg_compile.h"
+#include "hg_comb.h"
 #include "hg_core.h"
 
 #include <algorithm>
@@ -1403,6 +1404,90 @@ struct CompileKnobs {
   bool no_case_expand = std::getenv("HG_NO_CASE_EXPAND") != nullptr;
 };
 
+// ---- logical combinations (HS_FLAG_COMBINATION): infix formula over report ids -> postfix program over operand slots
+// Grammar: operands are decimal report ids; `!` binds tighter than `&`, which binds tighter than `|`; parentheses group;
+// whitespace is ignored.  Shunting-yard (no recursion: a long formula cannot exhaust the stack), operands numbered into slots
+// in order of first appearance.
+struct CombProgram {
+  std::vector<uint32_t> ops;   // slot -> operand report id
+  std::vector<uint32_t> prog;  // postfix: a slot number or HG_COMB_NOT / HG_COMB_AND / HG_COMB_OR
+};
+
+CombProgram parse_combination(const std::string &text) {
+  CombProgram out;
+  std::vector<char> stack;  // operators and '(' not yet emitted
+  auto prec = [](char c) { return c == '!' ? 3 : c == '&' ? 2 : c == '|' ? 1 : 0; };
+  auto emit = [&](char c) { out.prog.push_back(c == '!' ? HG_COMB_NOT : c == '&' ? HG_COMB_AND : HG_COMB_OR); };
+  bool want_operand = true;  // the next token must be an operand, '!' or '('
+  bool any = false;
+  for (size_t i = 0; i < text.size();) {
+    const char c = text[i];
+    if (c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\f' || c == '\v') {
+      i++;
+      continue;
+    }
+    any = true;
+    if (c >= '0' && c <= '9') {
+      if (!want_operand) throw CompileError("combination: two operands without an operator between them");
+      uint64_t v = 0;
+      for (; i < text.size() && text[i] >= '0' && text[i] <= '9'; i++) {
+        v = v * 10 + static_cast<uint64_t>(text[i] - '0');
+        if (v > 0xFFFFFFFFull) throw CompileError("combination: operand id above 4294967295 (UINT32_MAX)");
+      }
+      const uint32_t id = static_cast<uint32_t>(v);
+      auto it = std::find(out.ops.begin(), out.ops.end(), id);
+      if (it == out.ops.end()) {
+        if (out.ops.size() == HG_COMB_MAX_OPERANDS)
+          throw CompileError("combination: more than " + std::to_string(HG_COMB_MAX_OPERANDS) + " distinct operands (the limit is " +
+                             std::to_string(HG_COMB_MAX_OPERANDS) + ")");
+        out.ops.push_back(id);
+        it = out.ops.end() - 1;
+      }
+      out.prog.push_back(static_cast<uint32_t>(it - out.ops.begin()));
+      want_operand = false;
+      continue;
+    }
+    i++;
+    if (c == '!' || c == '(') {
+      if (!want_operand) throw CompileError(std::string("combination: '") + c + "' after an operand (missing operator)");
+      stack.push_back(c);
+    } else if (c == '&' || c == '|') {
+      if (want_operand) throw CompileError(std::string("combination: dangling operator '") + c + "'");
+      while (!stack.empty() && stack.back() != '(' && prec(stack.back()) >= prec(c)) {
+        emit(stack.back());
+        stack.pop_back();
+      }
+      stack.push_back(c);
+      want_operand = true;
+    } else if (c == ')') {
+      if (want_operand) throw CompileError(stack.empty() || stack.back() != '(' ? "combination: dangling operator before ')'" : "combination: empty parentheses");
+      while (!stack.empty() && stack.back() != '(') {
+        emit(stack.back());
+        stack.pop_back();
+      }
+      if (stack.empty()) throw CompileError("combination: unbalanced parentheses (')' without '(')");
+      stack.pop_back();
+    } else {
+      throw CompileError(std::string("combination: unexpected character '") + c + "' (operands are decimal report ids, operators ! & | and parentheses)");
+    }
+  }
+  if (!any) throw CompileError("combination: empty formula");
+  if (want_operand) throw CompileError("combination: dangling operator at the end");
+  while (!stack.empty()) {
+    if (stack.back() == '(') throw CompileError("combination: unbalanced parentheses ('(' without ')')");
+    emit(stack.back());
+    stack.pop_back();
+  }
+  // the evaluation stack is one 64-bit mask (hg_comb_eval)
+  long depth = 0, most = 0;
+  for (uint32_t op : out.prog) {
+    depth += op < HG_COMB_NOT ? 1 : op == HG_COMB_NOT ? 0 : -1;
+    most = std::max(most, depth);
+  }
+  if (most > 64) throw CompileError("combination: more than 64 values on the evaluation stack (parentheses nested too deeply)");
+  return out;
+}
+
 void build_slow_groups(HgDb &db, const CompileKnobs &knobs) {
   db.groups.clear();
   db.nslow_grouped = 0;
@@ -1494,11 +1579,30 @@ int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned 
   auto db = std::make_unique<HgDb>();
   struct Pending { std::vector<Lit> lits; bool literal_only = false; };
   std::vector<Pending> covers(n);
+  std::map<uint32_t, CombProgram> comb_programs;  // expression index -> its program (combinations)
   unsigned cur = 0;
   try {
     for (cur = 0; cur < n; cur++) {
       uint32_t f = flags ? flags[cur] : 0;
       if (f & ~HG_FLAGS_SUPPORTED) throw CompileError("unsupported flag bits");
+      if (f & HG_FLAG_COMBINATION) {
+        // no automaton: a formula over other expressions' report ids (hg_comb.h); of its flags only SINGLEMATCH and QUIET count
+        if (!exprs[cur] || !exprs[cur][0]) throw CompileError("empty expression");
+        db->exprs.push_back(exprs[cur]);
+        CombProgram cp = parse_combination(exprs[cur]);
+        if (hg_comb_eval(cp.prog.data(), static_cast<uint32_t>(cp.prog.size()), 0))
+          throw CompileError("combination is true when none of its operands has matched: such combinations report at the end of the data, which is not supported");
+        HgPattern p{};
+        p.id = ids ? ids[cur] : 0;
+        p.flags = f & (HG_FLAG_COMBINATION | HG_FLAG_SINGLEMATCH | HG_FLAG_QUIET);
+        p.single = (f & HG_FLAG_SINGLEMATCH) ? 1 : 0;
+        p.tier = HG_TIER_COMB;
+        db->max_id = std::max(db->max_id, p.id);
+        db->ncomb++;
+        db->patterns.push_back(p);
+        comb_programs.emplace(cur, std::move(cp));
+        continue;
+      }
       if ((f & HG_FLAG_SOM_LEFTMOST) && (f & HG_FLAG_SINGLEMATCH))
         throw CompileError("HS_FLAG_SOM_LEFTMOST cannot be combined with HS_FLAG_SINGLEMATCH");
       if (!exprs[cur] || !exprs[cur][0]) throw CompileError("empty expression");
@@ -1741,6 +1845,7 @@ int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned 
             for (uint32_t x = db->pool[p.follow_off + v * nw + w]; x; x &= x - 1) setbit(p.som_follow_off + (w * 32 + hg_ctz(x)) * nw, v);
         db->nsom++;
       }
+      if (f & HG_FLAG_QUIET) db->nquiet++;
       db->patterns.push_back(p);
     }
   } catch (const CompileError &e) {
@@ -1781,6 +1886,59 @@ int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned 
     }
   }
 
+  if (db->ncomb || db->nquiet) {
+    // Combinations: their ids are unique, their operands name ids of expressions that are not combinations; expressions that
+    // share an id are all QUIET or none is (else de-duplication would decide whether the report is delivered).
+    auto reject = [&](uint32_t i, const std::string &m) {
+      if (err) *err = m;
+      if (bad_index) *bad_index = static_cast<int>(i);
+      return -4;
+    };
+    std::map<uint32_t, std::pair<uint32_t, bool>> plain;  // id -> (first expression with it that is not a combination, it is QUIET)
+    std::map<uint32_t, uint32_t> comb_of;                 // id -> the combination with it
+    for (uint32_t i = 0; i < n; i++) {
+      const HgPattern &p = db->patterns[i];
+      if (p.tier == HG_TIER_COMB) continue;
+      const bool quiet = (p.flags & HG_FLAG_QUIET) != 0;
+      auto ins = plain.emplace(p.id, std::make_pair(i, quiet));
+      if (!ins.second && ins.first->second.second != quiet)
+        return reject(i, "expressions with report id " + std::to_string(p.id) + " must all carry HS_FLAG_QUIET, or none of them");
+    }
+    for (uint32_t i = 0; i < n; i++) {
+      const HgPattern &p = db->patterns[i];
+      if (p.tier != HG_TIER_COMB) continue;
+      if (plain.count(p.id) || !comb_of.emplace(p.id, i).second)
+        return reject(i, "combination report id " + std::to_string(p.id) + " is shared with another expression (a combination's id must be unique)");
+    }
+    std::vector<std::pair<uint32_t, uint32_t>> feed;  // (operand id, combination record)
+    for (auto &kv : comb_programs) {
+      const uint32_t i = kv.first;
+      const HgPattern &p = db->patterns[i];
+      const CombProgram &cp = kv.second;
+      for (uint32_t id : cp.ops) {
+        if (id == p.id) return reject(i, "combination refers to its own report id " + std::to_string(id));
+        if (comb_of.count(id)) return reject(i, "combination refers to report id " + std::to_string(id) + " of another combination (nested combinations are not supported)");
+        if (!plain.count(id)) return reject(i, "combination refers to report id " + std::to_string(id) + ", which no expression in the set has");
+      }
+      if (p.flags & HG_FLAG_QUIET) continue;  // (evaluated for nothing: it reports nothing and nothing can refer to it)
+      HgComb c{};
+      c.id = p.id;
+      c.pattern = i;
+      c.single = p.single;
+      c.nops = static_cast<uint32_t>(cp.ops.size());
+      c.ops_off = static_cast<uint32_t>(db->comb_words.size());
+      db->comb_words.insert(db->comb_words.end(), cp.ops.begin(), cp.ops.end());
+      c.prog_off = static_cast<uint32_t>(db->comb_words.size());
+      c.prog_len = static_cast<uint32_t>(cp.prog.size());
+      db->comb_words.insert(db->comb_words.end(), cp.prog.begin(), cp.prog.end());
+      for (uint32_t id : cp.ops) feed.emplace_back(id, static_cast<uint32_t>(db->combs.size()));
+      db->combs.push_back(c);
+    }
+    std::sort(feed.begin(), feed.end());
+    for (auto &f : feed) db->comb_feed.push_back(f.first);
+    for (auto &f : feed) db->comb_feed.push_back(f.second);
+  }
+
   // Tiers.  A pattern whose required literals all have at least `min_factor` bytes is found through the window prefilter
   // (tier 0), the others run on every line (tier 1).  Dword-aligned windows need HG_FAST_MIN_FACTOR bytes (a window on
   // every residue mod 4).  When that leaves patterns with shorter literals behind, the stream pass probes a window at
@@ -1798,6 +1956,7 @@ int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned 
     for (uint32_t m = 0; m < HG_CONFIRM_MODES; m++) db->n_confirm_mode[m] = 0;
     for (unsigned i = 0; i < n; i++) {
       HgPattern &p = db->patterns[i];
+      if (p.tier == HG_TIER_COMB) continue;  // (no automaton: the combination pass evaluates it)
       const LitSet &cover = covers[i].lits;
       const bool fast = !cover.empty() && min_len(cover) >= min_factor;
       p.tier = fast ? 0 : 1;

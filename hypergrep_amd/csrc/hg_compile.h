@@ -48,6 +48,15 @@ struct HgDb {
   uint32_t nslow_huge = 0;           // huge always-on expressions: the LAST nslow_huge entries of `slow`
   uint32_t max_id = 0;               // largest report id (sizes the sort key)
   uint32_t nsom = 0;                 // expressions with HS_FLAG_SOM_LEFTMOST: the scanner runs the start-of-match pass (hg_som.h)
+  // Logical combinations (hg_comb.h).  ncomb: expressions with HS_FLAG_COMBINATION (tier HG_TIER_COMB), nquiet: expressions
+  // with HS_FLAG_QUIET; the scanner runs the combination pass when either is non-zero.  combs: the non-quiet combinations,
+  // comb_words: their operand ids and programs, comb_feed: (operand id, combination) pairs ordered by id, as nfeed ids
+  // followed by nfeed combination indices (the combinations a report can make true).
+  uint32_t ncomb = 0, nquiet = 0;
+  std::vector<HgComb> combs;
+  std::vector<uint32_t> comb_words;
+  std::vector<uint32_t> comb_feed;
+  bool comb_pass() const { return ncomb || nquiet; }
   uint32_t n_confirm_mode[HG_CONFIRM_MODES] = {};  // tier-0 patterns by confirm routine (hg_confirm_mode)
   std::vector<std::string> exprs;
   bool tuned = false;

@@ -15,7 +15,10 @@
 // Flag values (hypergrep/utils.py:10-13).
 constexpr uint32_t HG_FLAG_CASELESS = 1, HG_FLAG_DOTALL = 2, HG_FLAG_MULTILINE = 4, HG_FLAG_SINGLEMATCH = 8;
 constexpr uint32_t HG_FLAG_SOM_LEFTMOST = 256;  // Hyperscan's value: report the leftmost start of each match (hg_som.h)
-constexpr uint32_t HG_FLAGS_SUPPORTED = 15 | HG_FLAG_SOM_LEFTMOST;
+// Hyperscan's values: a logical combination of other expressions' report ids, and reports that count for combinations but
+// are never delivered (hg_comb.h)
+constexpr uint32_t HG_FLAG_COMBINATION = 512, HG_FLAG_QUIET = 1024;
+constexpr uint32_t HG_FLAGS_SUPPORTED = 15 | HG_FLAG_SOM_LEFTMOST | HG_FLAG_COMBINATION | HG_FLAG_QUIET;
 
 // Boundary contexts for zero-width assertions.  Every assertion the compiler accepts (^ $ \A \z \Z \b \B)
 // is a boolean function of (context of the previous byte, context of the next byte); a 20-bit truth
@@ -105,7 +108,8 @@ struct HgPattern {
   uint32_t init_off;    // init[nw]         nodes enterable from the (always active) start state
   uint32_t amask_off;   // amask[4][4][nw]  nodes whose entry condition holds for (prev ctx, ctx of own byte)
   uint32_t acc_off;     // acc[4][5][nw]    nodes that accept for (ctx of own byte, next ctx)
-  uint32_t tier;        // 0: anchored by a required literal (stream prefilter + confirm); 1: always-on
+  uint32_t tier;        // 0: anchored by a required literal (stream prefilter + confirm); 1: always-on; 2 (HG_TIER_COMB): a
+                        // combination, no automaton (nw = 0, no tables): no scan pass runs it, the combination pass evaluates it
   uint32_t simple;      // one state word and no boundary conditions: S' = (init | follow(S)) & reach[c], accept = S & acc_all
   uint32_t acc_all;     // accepting nodes when `simple`
   uint32_t init_word;   // init[0] when `simple`
@@ -116,6 +120,25 @@ struct HgPattern {
   uint32_t reserved;
 };
 static_assert(sizeof(HgPattern) == 80, "HgPattern layout");
+
+constexpr uint32_t HG_TIER_COMB = 2;
+
+// One logical combination (HS_FLAG_COMBINATION, hg_comb.h): a postfix program over operand slots.  Slot s stands for the
+// report id words[ops_off + s]; program word k = words[prog_off + k] is HG_COMB_NOT / HG_COMB_AND / HG_COMB_OR or a slot
+// number (push the slot's status).  QUIET combinations report nothing and have no record.
+constexpr uint32_t HG_COMB_MAX_OPERANDS = 64;  // distinct operand ids of one combination: the statuses are one 64-bit mask
+constexpr uint32_t HG_COMB_NOT = 64, HG_COMB_AND = 65, HG_COMB_OR = 66;
+struct HgComb {
+  uint32_t id;        // the combination's report id
+  uint32_t pattern;   // its expression index (HgHitAux::pattern of its reports)
+  uint32_t single;    // HS_FLAG_SINGLEMATCH
+  uint32_t nops;      // operand slots, <= HG_COMB_MAX_OPERANDS
+  uint32_t ops_off;   // words[ops_off ..]: the operand id of each slot
+  uint32_t prog_off;  // words[prog_off ..]: the postfix program
+  uint32_t prog_len;
+  uint32_t reserved;
+};
+static_assert(sizeof(HgComb) == 32, "HgComb layout");
 
 // A required literal of one pattern ("factor"): any match of the pattern contains an occurrence.  ONE 64-byte cache line
 // (round 2: 80 bytes with a mask byte per literal byte — three to five 16-byte fetches from two lines per verified candidate).

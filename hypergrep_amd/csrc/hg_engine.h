@@ -137,6 +137,24 @@ struct HgScanOutput {
 hipError_t hg_som_launch(const uint8_t *text, const HgHit *hits, const HgHitAux *aux, uint64_t n, const HgPattern *patterns, const uint32_t *pool, uint32_t max_nw,
                          uint32_t *from, hipStream_t stream);
 
+// The combination pass (hg_comb.hip) over the n final hits of a pass: count (emit == false: count[i] = records of hit i,
+// count[n] = 0), or write the records of hit i to out_*[pos[i] ..] (emit == true), on `stream`.
+struct HgCombArgs {
+  const HgHit *hits;
+  const HgHitAux *aux;
+  uint64_t n;
+  const HgPattern *patterns;
+  const HgComb *combs;
+  const uint32_t *words;
+  const uint32_t *feed;
+  uint32_t nfeed;
+  uint32_t *count;
+  const uint64_t *pos;
+  HgHit *out_hits;
+  HgHitAux *out_aux;
+};
+hipError_t hg_comb_launch(const HgCombArgs &a, bool emit, hipStream_t stream);
+
 // Test / experiment knobs of the engine, read from the environment ONCE, when a scanner is created (never during a scan:
 // getenv is not safe against a concurrent setenv, and a scan must not change behaviour half-way).  None is needed in normal
 // use.  The limit-lowering ones exist so that tests reach segmented scans / chunk halving on small texts.
@@ -203,7 +221,8 @@ class HgScanner {
   int finalize_last(PassPlan &p, uint32_t c);
   int launch_fin(const PassPlan &p, hipStream_t s, uint32_t lo, uint32_t hi, bool beside_stream = false);
   int regrow(const PassPlan &p, uint64_t n_raw);
-  int finalize_compact(const PassPlan &p, uint32_t n, uint64_t line_bound);
+  int finalize_compact(const HgHit *hits, const HgHitAux *aux, uint32_t n, uint32_t id_bits, uint32_t to_bits, uint64_t line_bound, hipStream_t stream);
+  int comb_pass(HgScanOutput *out, uint64_t bs1, uint64_t line_bound, hipStream_t stream);
   int huge_lds_error() { return error(HG_ERR_HIP, "the huge-automaton kernel cannot have its LDS"); }
   bool fail(hipError_t e, const char *what);
   int error(int rc, const std::string &what) { err_ = what; return rc; }
@@ -266,6 +285,18 @@ class HgScanner {
   uint32_t *d_from_ = nullptr;  // starts of the last scan's hits (SOM databases only, allocated by the first scan that needs them)
   uint64_t from_cap_ = 0;
   uint32_t som_max_nw_ = 0;
+  // combination pass (databases with combinations or QUIET expressions only): the tables, the per-hit counts / positions and
+  // the union of delivered and combination records it hands to the finalize
+  HgComb *d_combs_ = nullptr;
+  uint32_t *d_comb_words_ = nullptr, *d_comb_feed_ = nullptr;
+  uint32_t *d_comb_count_ = nullptr;
+  uint64_t *d_comb_pos_ = nullptr;
+  uint64_t comb_in_cap_ = 0;
+  HgHit *d_comb_hits_ = nullptr;
+  HgHitAux *d_comb_aux_ = nullptr;
+  uint64_t comb_out_cap_ = 0;
+  uint8_t *d_comb_temp_ = nullptr;
+  size_t comb_temp_bytes_ = 0;
   uint32_t *d_seg_count2_ = nullptr;  // second set for double buffering
   HgCand *d_cands2_ = nullptr;
 };

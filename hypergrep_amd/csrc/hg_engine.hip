@@ -189,6 +189,11 @@ int HgScanner::init() {
   view_.groups = static_cast<const HgSlowGroup *>(d_groups_);
   for (const HgPattern &p : db.patterns)
     if (p.flags & HG_FLAG_SOM_LEFTMOST) som_max_nw_ = std::max(som_max_nw_, p.nw);
+  if (db.comb_pass()) {
+    HG_TRY(upload(reinterpret_cast<void **>(&d_combs_), db.combs, "d_combs_"), "upload combinations");
+    HG_TRY(upload(reinterpret_cast<void **>(&d_comb_words_), db.comb_words, "d_comb_words_"), "upload combinations");
+    HG_TRY(upload(reinterpret_cast<void **>(&d_comb_feed_), db.comb_feed, "d_comb_feed_"), "upload combinations");
+  }
   view_.fold_mask = db.fold_mask;
   view_.window_mask = db.window_mask;
   static_assert(HG_CNT_CURSORS == kMaxChunks, "one tile cursor per pipeline chunk");
@@ -215,7 +220,8 @@ HgScanner::~HgScanner() {
   (void)hipSetDevice(device_);
   void *ptrs[] = {d_patterns_, d_pool_, d_factors_, d_windows_, d_bucket_, d_filter_, d_ext_, d_slow_, d_sums_, d_bases_, d_block_base_,
                   d_agg_, d_cands_, d_hits_raw_, d_hits_out_, d_aux_raw_, d_aux_out_,
-                  d_key_a_, d_key_b_, d_perm_a_, d_perm_b_, d_keep_, d_counters_, d_temp_, d_seg_count_, d_pflags_, d_deferred_, d_defer_count_, d_seg_count2_, d_cands2_, d_disc_, d_bucket2_, d_windows2_, d_groups_, d_acc_hits_, d_acc_aux_, d_huge_claim_, d_wtab_, d_from_, d_fin_fill_, d_fin_kept_, d_fin_big_};
+                  d_key_a_, d_key_b_, d_perm_a_, d_perm_b_, d_keep_, d_counters_, d_temp_, d_seg_count_, d_pflags_, d_deferred_, d_defer_count_, d_seg_count2_, d_cands2_, d_disc_, d_bucket2_, d_windows2_, d_groups_, d_acc_hits_, d_acc_aux_, d_huge_claim_, d_wtab_, d_from_, d_fin_fill_, d_fin_kept_, d_fin_big_,
+                  d_combs_, d_comb_words_, d_comb_feed_, d_comb_count_, d_comb_pos_, d_comb_hits_, d_comb_aux_, d_comb_temp_};
   for (void *p : ptrs) hgmem::dev_free(p, "scanner");
   hgmem::host_free(h_counters_, "h_counters_");
   for (auto &ev : ev_)
@@ -334,7 +340,7 @@ struct HgScanner::PassPlan {
 HgScanner::PassPlan HgScanner::plan_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const PassRange &range, bool block_mode,
                                          hipStream_t stream) const {
   const uint64_t tile_lo = range.tile_lo, tile_hi = range.tile_hi, ntiles = tile_hi - tile_lo;
-  PassPlan p{text, nbytes, bs1, ntiles, range, block_mode, db_->patterns.size() > db_->slow.size(), stream};
+  PassPlan p{text, nbytes, bs1, ntiles, range, block_mode, db_->patterns.size() - db_->ncomb > db_->slow.size(), stream};
   // the bytes whose pieces this pass reports (buckets of the finalize count from own_lo)
   const uint64_t own_end = std::min<uint64_t>(range.own_hi, nbytes), own_len = own_end > range.own_lo ? own_end - range.own_lo : 0;
   // Bucketed emission + finalize (hg_fin_*): buckets of 2^fin_shift text bytes (1 KiB at least) by line start, at most
@@ -738,35 +744,93 @@ int HgScanner::regrow(const PassPlan &p, uint64_t n_raw) {
 // Compact array + library sort of the pass's n raw hits (scanners that left bucketed emission, keys wider than 64 bits):
 // order by (line, id, to, single-after-multi), apply the report rules, and count the kept hits into d_selected_.  The line
 // numbers stay below line_bound.
-int HgScanner::finalize_compact(const PassPlan &p, uint32_t n, uint64_t line_bound) {
+int HgScanner::finalize_compact(const HgHit *hits, const HgHitAux *aux, uint32_t n, uint32_t id_bits, uint32_t to_bits, uint64_t line_bound, hipStream_t stream) {
   const HgPattern *pats = static_cast<const HgPattern *>(d_patterns_);
-  const hipStream_t stream = p.stream;
   uint32_t blocks = (n + 255) / 256;
   // one radix sort over exactly the bits in use when they fit in 64, else two
-  const uint32_t line_bits = bits_for(line_bound), id_bits = p.id_bits, to_bits = p.to_bits;
+  const uint32_t line_bits = bits_for(line_bound);
   const uint32_t *perm = nullptr;
   uint32_t *pos = nullptr;
   size_t tb = temp_bytes_;
   if (line_bits + id_bits + to_bits + 1 <= 64) {
-    hipLaunchKernelGGL(hg_key_packed_kernel, dim3(blocks), dim3(256), 0, stream, d_hits_raw_, d_aux_raw_, pats, n, id_bits, to_bits, d_key_a_, d_perm_a_);
+    hipLaunchKernelGGL(hg_key_packed_kernel, dim3(blocks), dim3(256), 0, stream, hits, aux, pats, n, id_bits, to_bits, d_key_a_, d_perm_a_);
     HG_TRY(rocprim::radix_sort_pairs(d_temp_, tb, d_key_a_, d_key_b_, d_perm_a_, d_perm_b_, n, 0, line_bits + id_bits + to_bits + 1, stream), "radix sort");
     perm = d_perm_b_;
     pos = d_perm_a_;
   } else {
-    hipLaunchKernelGGL(hg_key_kernel, dim3(blocks), dim3(256), 0, stream, d_hits_raw_, d_aux_raw_, pats, n, d_key_a_, d_perm_a_);
+    hipLaunchKernelGGL(hg_key_kernel, dim3(blocks), dim3(256), 0, stream, hits, aux, pats, n, d_key_a_, d_perm_a_);
     HG_TRY(rocprim::radix_sort_pairs(d_temp_, tb, d_key_a_, d_key_b_, d_perm_a_, d_perm_b_, n, 0, 64, stream), "radix sort (id, to)");
-    hipLaunchKernelGGL(hg_line_key_kernel, dim3(blocks), dim3(256), 0, stream, d_hits_raw_, d_perm_b_, n, d_key_a_);
+    hipLaunchKernelGGL(hg_line_key_kernel, dim3(blocks), dim3(256), 0, stream, hits, d_perm_b_, n, d_key_a_);
     tb = temp_bytes_;
     HG_TRY(rocprim::radix_sort_pairs(d_temp_, tb, d_key_a_, d_key_b_, d_perm_b_, d_perm_a_, n, 0, std::min<uint32_t>(64, line_bits), stream), "radix sort (line)");
     perm = d_perm_a_;
     pos = d_perm_b_;
   }
-  hipLaunchKernelGGL(hg_keep_kernel, dim3(blocks), dim3(256), 0, stream, d_hits_raw_, d_aux_raw_, perm, pats, n, d_keep_);
+  hipLaunchKernelGGL(hg_keep_kernel, dim3(blocks), dim3(256), 0, stream, hits, aux, perm, pats, n, d_keep_);
   tb = temp_bytes_;
   HG_TRY(rocprim::exclusive_scan(d_temp_, tb, d_keep_, pos, 0u, n, rocprim::plus<uint32_t>(), stream), "scan");
-  hipLaunchKernelGGL(hg_scatter_kernel, dim3(blocks), dim3(256), 0, stream, d_hits_raw_, d_aux_raw_, perm, d_keep_, pos, n, d_hits_out_, d_aux_out_, d_selected_);
+  hipLaunchKernelGGL(hg_scatter_kernel, dim3(blocks), dim3(256), 0, stream, hits, aux, perm, d_keep_, pos, n, d_hits_out_, d_aux_out_, d_selected_);
   HG_TRY(hipGetLastError(), "finalize launch");
   HG_TRY(hipMemcpyAsync(h_counters_ + HG_ST_SELECTED, d_selected_, 4, hipMemcpyDeviceToHost, stream), "copy count");
+  return HG_OK;
+}
+
+// The combination pass over a pass's final hits (databases with combinations or QUIET expressions): hg_comb.hip counts the
+// records each hit hands on (itself unless QUIET, the reports of the combinations it makes true), an exclusive scan sizes the
+// union, the second launch writes it, and the compact finalize orders it and applies the report rules into d_hits_out_.  *out
+// then describes the delivered hits.  (The input may be d_hits_out_ itself: it is read completely before the finalize
+// writes there.)
+int HgScanner::comb_pass(HgScanOutput *out, uint64_t bs1, uint64_t line_bound, hipStream_t stream) {
+  const uint64_t n = out->n_hits;
+  if (n == 0) return HG_OK;
+  if (n + 1 > comb_in_cap_) {
+    const uint64_t cap = std::max<uint64_t>(n + n / 4 + 1, 4096);
+    comb_in_cap_ = 0;
+    HG_TRY(realloc_dev(d_comb_count_, cap, "d_comb_count_"), "alloc (combination pass)");
+    HG_TRY(realloc_dev(d_comb_pos_, cap, "d_comb_pos_"), "alloc (combination pass)");
+    size_t tb = 0;
+    HG_TRY(rocprim::exclusive_scan(nullptr, tb, d_comb_count_, d_comb_pos_, uint64_t{0}, cap, rocprim::plus<uint64_t>(), stream), "scan (combination pass)");
+    if (tb > comb_temp_bytes_) {
+      comb_temp_bytes_ = 0;
+      HG_TRY(realloc_dev(d_comb_temp_, tb, "d_comb_temp_"), "alloc (combination pass)");
+      comb_temp_bytes_ = tb;
+    }
+    comb_in_cap_ = cap;
+  }
+  const HgDb &db = *db_;
+  HgCombArgs a{out->d_hits, out->d_aux, n, static_cast<const HgPattern *>(d_patterns_), d_combs_, d_comb_words_, d_comb_feed_,
+               static_cast<uint32_t>(db.comb_feed.size() / 2), d_comb_count_, d_comb_pos_, nullptr, nullptr};
+  HG_TRY(hg_comb_launch(a, false, stream), "combination pass launch (count)");
+  size_t tb = comb_temp_bytes_;
+  HG_TRY(rocprim::exclusive_scan(d_comb_temp_, tb, d_comb_count_, d_comb_pos_, uint64_t{0}, n + 1, rocprim::plus<uint64_t>(), stream), "scan (combination pass)");
+  uint64_t total = 0;
+  HG_TRY(hipMemcpyAsync(&total, d_comb_pos_ + n, sizeof total, hipMemcpyDeviceToHost, stream), "copy count");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (combination pass)");
+  if (total > 0x7FFFFFF0u) return error(HG_ERR_NOMEM, "more than 2^31 reports with the combination reports of one pass");
+  if (total == 0) {
+    out->n_hits = 0;
+    return HG_OK;
+  }
+  if (total > comb_out_cap_) {
+    const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(total + total / 4, 4096), 0x7FFFFFF0u);
+    comb_out_cap_ = 0;
+    HG_TRY(realloc_dev(d_comb_hits_, cap, "d_comb_hits_"), "alloc (combination pass)");
+    HG_TRY(realloc_dev(d_comb_aux_, cap, "d_comb_aux_"), "alloc (combination pass)");
+    comb_out_cap_ = cap;
+  }
+  a.out_hits = d_comb_hits_;
+  a.out_aux = d_comb_aux_;
+  HG_TRY(hg_comb_launch(a, true, stream), "combination pass launch (emit)");
+  if (total > hit_cap_) {  // the finalize's workspace (d_hits_out_ included: the input has been read by now)
+    HG_TRY(hipStreamSynchronize(stream), "stream sync (combination pass)");
+    if (int rc = alloc_hits(total)) return rc;
+  }
+  if (int rc = finalize_compact(d_comb_hits_, d_comb_aux_, static_cast<uint32_t>(total), bits_for(static_cast<uint64_t>(db.max_id) + 1), bits_for(bs1 + 1), line_bound, stream))
+    return rc;
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (combination pass)");
+  out->n_hits = h_counters_[HG_ST_SELECTED];
+  out->d_hits = d_hits_out_;
+  out->d_aux = d_aux_out_;
   return HG_OK;
 }
 
@@ -836,7 +900,7 @@ int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint
   const uint64_t n_pieces = block_mode ? 1 : !range.last ? 0 : h_final_->L - line_base + (nbytes > h_final_->cs ? hg_pieces(nbytes - h_final_->cs, bs1) : 0);
   const uint32_t n = static_cast<uint32_t>(n_raw);
   if (n && !p.bucketed)
-    if (int rc = finalize_compact(p, n, line_base + (range.last ? n_pieces : nbytes) + 1)) return rc;
+    if (int rc = finalize_compact(d_hits_raw_, d_aux_raw_, n, p.id_bits, p.to_bits, line_base + (range.last ? n_pieces : nbytes) + 1, p.stream)) return rc;
   if (!p.bucketed) {
     HG_TRY(hipEventRecord(ev_[3], stream), "event");
     HG_TRY(hipStreamSynchronize(stream), "stream sync (finalize)");
@@ -898,6 +962,7 @@ int HgScanner::scan_impl(const void *d_text, uint64_t nbytes, int buffer_size, u
   const uint64_t ntiles = (nbytes + HG_TILE_BYTES - 1) / HG_TILE_BYTES;
   const PassRange whole{0, ntiles, 0, line_base, 0, ~0ull, true};
   rc = run_fitting(text, nbytes, bs1, line_base, whole, block_mode, stream, out);
+  if (rc == HG_OK && db_->comb_pass()) rc = comb_pass(out, bs1, line_base + nbytes + 2, stream);
   if (rc == HG_SPLIT) {
     // More reports (or pipeline chunks) than one pass may have: the buffer is scanned in 2, 4, 8 ... segments.  (The scan
     // reports the repeats of its whole-buffer attempt.)
@@ -908,7 +973,7 @@ int HgScanner::scan_impl(const void *d_text, uint64_t nbytes, int buffer_size, u
   }
   if (rc) return rc;
   if (db_->nsom) {
-    // start of match: one pass over the final ordered hits (those of all segments, one after the other)
+    // start of match (behind the combination pass: only delivered hits get a start): one pass over the final ordered hits (those of all segments, one after the other)
     if (out->n_hits > from_cap_) {
       from_cap_ = 0;
       const uint64_t cap = std::max<uint64_t>(out->n_hits + out->n_hits / 4, 4096);
@@ -945,6 +1010,8 @@ int HgScanner::scan_segments(const uint8_t *text, uint64_t nbytes, uint64_t bs1,
     const bool last = lo + seg_tiles >= ntiles;
     const PassRange range{lo, last ? ntiles : std::min<uint64_t>(ntiles, lo + seg_tiles + reach), cs0, piece0, lo << HG_TILE_SHIFT, last ? ~0ull : (lo + seg_tiles) << HG_TILE_SHIFT, last};
     if (int rc = run_fitting(text, nbytes, bs1, line_base, range, false, stream, &part)) return rc;
+    if (db_->comb_pass())  // (pieces never cross segments: each pass's hits are complete pieces)
+      if (int rc = comb_pass(&part, bs1, line_base + nbytes + 2, stream)) return rc;
     // this pass's ordered hits behind those of the earlier segments
     if (acc + part.n_hits > acc_cap_) {
       // sized from the hits so far, the share of the text they came from, and a quarter on top

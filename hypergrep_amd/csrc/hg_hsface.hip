@@ -138,8 +138,9 @@ int hs_scan(const hs_database_t *db, const char *data, unsigned int length, unsi
   // Short blocks (the reference shim scans line by line, hyperscanner.c:217): one launch on a pinned copy of the block,
   // raw reports straight into pinned memory, the report rules on the host.
   static const bool small_path = !std::getenv("HG_NO_BLOCK_SMALL");
-  // (databases with HS_FLAG_SOM_LEFTMOST expressions take the general path: its start-of-match pass fills `from`)
-  if (length <= HG_BLOCK_SMALL_MAX && small_path && !db->db->nsom) {
+  // (databases with HS_FLAG_SOM_LEFTMOST expressions take the general path: its start-of-match pass fills `from`; so do databases
+  // with combinations or QUIET expressions: its combination pass applies them)
+  if (length <= HG_BLOCK_SMALL_MAX && small_path && !db->db->nsom && !db->db->comb_pass()) {
     std::memcpy(scratch->h_text, data, length);
     std::memset(scratch->h_text + length, 0, (16 - (length & 15)) & 15);
     const uint32_t seq = ++scratch->seq ? scratch->seq : ++scratch->seq;  // (never 0)

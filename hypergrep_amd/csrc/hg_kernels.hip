@@ -625,6 +625,7 @@ __global__ __launch_bounds__(256) void hg_block_scan_kernel(HgConfirmArgs a, con
   for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < a.db.npatterns; p += gridDim.x * blockDim.x) {
     const HgPattern &pat = a.db.patterns[p];
     if (pat.tier == 0 && !pattern_flags[p]) continue;
+    if (pat.tier == HG_TIER_COMB) continue;  // a combination: no automaton (the combination pass)
     if (pat.nw > HG_MAX_W) continue;  // a huge automaton: hg_block_huge_kernel
     hg_nfa_scan(a.db.pool, pat, a.text, a.nbytes,
                 [&](uint32_t to) { sink.push(a, 0, pat.id, to, 0, static_cast<uint32_t>(a.nbytes), p, pat.single != 0); });

@@ -13,6 +13,9 @@ from hypergrep_amd import utils
 DEFAULT_FLAGS = utils.HS_FLAG_DOTALL | utils.HS_FLAG_MULTILINE | utils.HS_FLAG_SINGLEMATCH
 # Report where each match starts (Scanner.hit_starts); not with SINGLEMATCH.  See include/hypergrep_amd.h for the contract.
 HS_FLAG_SOM_LEFTMOST = 256
+# Logical combinations of other expressions' report ids, and reports that only feed combinations (include/hypergrep_amd.h).
+HS_FLAG_COMBINATION = utils.HS_FLAG_COMBINATION
+HS_FLAG_QUIET = utils.HS_FLAG_QUIET
 
 
 class HgHit(ctypes.Structure):

@@ -27,6 +27,9 @@ from typing import Callable, Sequence
 
 # Hyperscan's compile flags, the values the reference passes through (utils.py:10-13).
 HS_FLAG_CASELESS, HS_FLAG_DOTALL, HS_FLAG_MULTILINE, HS_FLAG_SINGLEMATCH = 1, 2, 4, 8
+# Logical combinations: a formula over other expressions' report ids, and reports that only feed combinations
+# (include/hypergrep_amd.h has the contract).
+HS_FLAG_COMBINATION, HS_FLAG_QUIET = 512, 1024
 _GREP_FLAGS = HS_FLAG_DOTALL | HS_FLAG_MULTILINE | HS_FLAG_SINGLEMATCH  # what grep() and the default of scan() use
 
 RC_INVALID_FILE = 101  # grep(): the path is missing or a directory (utils.py:16)
@@ -113,9 +116,10 @@ def prepare_patterns(patterns: list[str], flags: list[int] = (), ids: list[int] 
     )
 
 
-def check_compatibility(patterns: list, flags: list[int] = ()) -> int:
-    """Compile the patterns without scanning anything: 0 if the engine accepts them all, else 4."""
-    c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags)
+def check_compatibility(patterns: list, flags: list[int] = (), ids: list[int] = ()) -> int:
+    """Compile the patterns without scanning anything: 0 if the engine accepts them all, else 4.  `ids` (default all 0)
+    matter for sets with HS_FLAG_COMBINATION, whose formulas name report ids."""
+    c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags, ids=ids)
     return _get_hyperscanner_lib().check_patterns(c_patterns, c_flags, c_ids, len(c_patterns))
 
 

@@ -96,6 +96,27 @@ typedef int (*match_event_handler)(unsigned int id, unsigned long long from, uns
  * the expressions that share a report id carry it (several SOM expressions of one id that end at the same `to` give one
  * report with the smallest of their starts). */
 #define HS_FLAG_SOM_LEFTMOST 256
+/* Logical combinations.  An expression with HS_FLAG_COMBINATION is not a regex but a formula over the REPORT IDS of other
+ * expressions of the set: decimal ids, `!` (not) > `&` (and) > `|` (or), parentheses, whitespace ignored.  Of its flags only
+ * HS_FLAG_SINGLEMATCH and HS_FLAG_QUIET count (its `from` is 0).  The rules are per line piece (per block for hs_scan), on
+ * the piece's reports after the report rules:
+ *  - operand id X is true at offset t iff X has a report in the piece with to <= t;
+ *  - combination C reports (C.id, t) at every distinct t where one of its operands reports, if C is true with the statuses
+ *    at t.  All reports at offsets <= t count (this project's tie rule): `101 & !102` with both ending at 10 gives nothing;
+ *  - its reports join the others under the usual rules: order by (line, id, to), an identical (id, to) once, SINGLEMATCH:
+ *    the smallest `to` only.
+ * HS_FLAG_QUIET on any expression: its reports still count for combinations but are never delivered (Results, hg_copy_hits,
+ * hs_scan callbacks); a line whose only reports are quiet is not a matching line (max_match_count).  A QUIET combination
+ * reports nothing.
+ * Rejected (HS_COMPILER_ERROR / HG_ERR_COMPILE, with the rule in the message): syntax errors (empty formula, unbalanced
+ * parentheses, dangling operator, a token that is not an operator or a decimal id, an id above 4294967295); an operand id no
+ * expression of the set has; an operand that is itself a combination (no nesting); a combination id shared with any other
+ * expression, or used as its own operand; more than 64 distinct operands, or more than 64 values on the evaluation stack; a
+ * report id shared by QUIET and non-QUIET expressions; any combination that is true when none of its operands has matched
+ * (e.g. `!101`, `101 | !102`): Hyperscan reports those at the end of the data, which this project does not.
+ * The semantics follow Hyperscan's documentation of logical combinations; they are not checked against a Hyperscan binary. */
+#define HS_FLAG_COMBINATION 512
+#define HS_FLAG_QUIET 1024
 
 /* call site hyperscanner.c:136 */
 int hs_compile_multi(const char *const *expressions, const unsigned int *flags, const unsigned int *ids,

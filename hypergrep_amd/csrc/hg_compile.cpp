@@ -29,8 +29,12 @@ namespace {
 
 using ByteSet = std::bitset<256>;
 
+// A rejection.  `index` is the expression it names: by default the one being compiled; set-wide rules name their own
+// (-1: the set as a whole).
+constexpr int kThisExpression = -2;
 struct CompileError : std::runtime_error {
-  using std::runtime_error::runtime_error;
+  int index;
+  explicit CompileError(const std::string &what, int index = kThisExpression) : std::runtime_error(what), index(index) {}
 };
 
 // ---------------------------------------------------------------- truth tables for assertions
@@ -1392,15 +1396,9 @@ int build_filter(HgDb &db, const SampleStats *stats, std::string *err) {
   return 0;
 }
 
-// Packs single-word always-on expressions into shared state words (HgSlowGroup): first fit by node count, the expressions
-// with boundary conditions first (their bins run the routine with conditions, and whatever context-free expression still
-// fits rides along), then the context-free ones (bins of their own once the others are full).
-// A/B knobs of the compiler (older code paths, for experiments and one test), read from the environment once per compile.
+// A/B knobs of the compiler (the older code paths that tests reach), read from the environment once per compile.
 struct CompileKnobs {
-  bool no_slow_groups = std::getenv("HG_NO_SLOW_GROUPS") != nullptr;
   bool no_ctx_groups = std::getenv("HG_NO_CTX_GROUPS") != nullptr;
-  bool no_confirm_window = std::getenv("HG_NO_CONFIRM_WINDOW") != nullptr;
-  bool no_byte_windows = std::getenv("HG_NO_BYTE_WINDOWS") != nullptr;
   bool no_case_expand = std::getenv("HG_NO_CASE_EXPAND") != nullptr;
 };
 
@@ -1488,10 +1486,12 @@ CombProgram parse_combination(const std::string &text) {
   return out;
 }
 
+// Packs single-word always-on expressions into shared state words (HgSlowGroup): first fit by node count, the expressions
+// with boundary conditions first (their bins run the routine with conditions, and whatever context-free expression still
+// fits rides along), then the context-free ones (bins of their own once the others are full).
 void build_slow_groups(HgDb &db, const CompileKnobs &knobs) {
   db.groups.clear();
   db.nslow_grouped = 0;
-  if (knobs.no_slow_groups) return;
   const bool mixed = !knobs.no_ctx_groups;
   struct Bin { std::vector<uint32_t> members; uint32_t nodes = 0; bool ctx = false; };
   std::vector<Bin> bins;
@@ -1561,6 +1561,460 @@ void build_slow_groups(HgDb &db, const CompileKnobs &knobs) {
   db.nslow_grouped = static_cast<uint32_t>(grouped.size());
 }
 
+// ---------------------------------------------------------------- compile stages (hgc_compile)
+uint32_t alloc(HgDb &db, size_t words) {  // `words` zeroed pool words: their offset
+  if (db.pool.size() + words > 0xFFFF0000ull) throw CompileError("pattern set too large");
+  const uint32_t off = static_cast<uint32_t>(db.pool.size());
+  db.pool.resize(db.pool.size() + words, 0);
+  return off;
+}
+void setbit(HgDb &db, uint32_t base, uint32_t node) { db.pool[base + node / 32] |= 1u << (node % 32); }
+
+// No automaton: a formula over other expressions' report ids (hg_comb.h); of its flags only SINGLEMATCH and QUIET count.
+HgPattern compile_combination(HgDb &db, const char *expr, uint32_t f, uint32_t id, CombProgram &program) {
+  if (!expr || !expr[0]) throw CompileError("empty expression");
+  db.exprs.push_back(expr);
+  program = parse_combination(expr);
+  if (hg_comb_eval(program.prog.data(), static_cast<uint32_t>(program.prog.size()), 0))
+    throw CompileError("combination is true when none of its operands has matched: such combinations report at the end of the data, which is not supported");
+  HgPattern p{};
+  p.id = id;
+  p.flags = f & (HG_FLAG_COMBINATION | HG_FLAG_SINGLEMATCH | HG_FLAG_QUIET);
+  p.single = (f & HG_FLAG_SINGLEMATCH) ? 1 : 0;
+  p.tier = HG_TIER_COMB;
+  db.ncomb++;
+  return p;
+}
+
+// The position automaton of one expression.  Nodes are the distinct (position, entry condition) pairs, numbered in
+// (position, condition) order: linear expressions get follow = next bit, and the nodes of one position are consecutive.
+struct Automaton {
+  NodeP root;
+  Glushkov g;                                        // edges: one per (p, q), ordered by (p, q)
+  std::vector<Cond> first;
+  std::vector<std::pair<uint32_t, uint32_t>> nodes;  // (position, entry condition)
+  std::vector<uint32_t> node_lo;                     // nodes of position q: [node_lo[q], node_lo[q + 1])
+  std::vector<uint32_t> last_tt;                     // per position: the contexts in which a match can end there
+  uint32_t nn = 0, nw = 1;
+  uint32_t node(uint32_t pos, uint32_t tt) const {
+    return static_cast<uint32_t>(std::lower_bound(nodes.begin(), nodes.end(), std::make_pair(pos, tt)) - nodes.begin());
+  }
+};
+
+Automaton build_automaton(const std::string &text, uint32_t flags) {
+  Automaton a;
+  a.root = Parser(text, flags).parse();
+  check_embedded_anchors(*a.root, false, false);
+  if (program_size(*a.root) > HG_HUGE_MAX_PROGRAM) throw CompileError("pattern too large");
+  Frag top = a.g.build(*a.root);
+  if (top.nullable) throw CompileError("expression can match the empty string (HS_FLAG_ALLOWEMPTY is not supported)");
+  if (a.g.pos_class.empty()) throw CompileError("expression matches nothing");
+
+  // one edge per (p, q): the ways of getting from p to q (through different assertions) merge into one condition
+  std::vector<Edge> &edges = a.g.edges;
+  std::sort(edges.begin(), edges.end(), [](const Edge &x, const Edge &y) { return x.p != y.p ? x.p < y.p : x.q < y.q; });
+  size_t ne = 0;
+  for (size_t i = 0; i < edges.size(); i++) {
+    if (ne && edges[ne - 1].p == edges[i].p && edges[ne - 1].q == edges[i].q) edges[ne - 1].tt |= edges[i].tt;
+    else edges[ne++] = edges[i];
+  }
+  edges.resize(ne);
+  a.nodes.reserve(top.first.size() + edges.size());
+  for (auto &c : top.first) a.nodes.push_back({c.pos, c.tt});
+  for (auto &e : edges) a.nodes.push_back({e.q, e.tt});
+  std::sort(a.nodes.begin(), a.nodes.end());
+  a.nodes.erase(std::unique(a.nodes.begin(), a.nodes.end()), a.nodes.end());
+  if (a.nodes.size() > HG_HUGE_MAX_NODES) throw CompileError("pattern too large");
+  const uint32_t npos = static_cast<uint32_t>(a.g.pos_class.size());
+  a.node_lo.assign(npos + 1, 0);
+  for (auto &nd : a.nodes) a.node_lo[nd.first + 1]++;
+  for (uint32_t q = 0; q < npos; q++) a.node_lo[q + 1] += a.node_lo[q];
+  a.last_tt.assign(npos, 0);
+  for (auto &l : top.last) a.last_tt[l.pos] |= l.tt;
+  a.first = std::move(top.first);
+  // (an expression whose every entry condition is contradictory, e.g. \b\Bc, has no nodes: it keeps one all-zero state
+  // word so that every routine sees well-formed tables and simply never matches)
+  a.nn = static_cast<uint32_t>(a.nodes.size());
+  a.nw = a.nn ? (a.nn + 31) / 32 : 1;
+  return a;
+}
+
+// Node v's bits in the entry condition masks (4 x 4: previous byte class, class of the byte that enters it) and the accept
+// condition masks (4 x 5: previous byte class, class of the byte after the match).
+void set_condition_masks(HgDb &db, const HgPattern &p, uint32_t v, uint32_t entry_tt, uint32_t accept_tt) {
+  for (uint32_t pc = 0; pc < 4; pc++) {
+    for (uint32_t cc = 0; cc < 4; cc++)
+      if (entry_tt >> (pc * 5 + cc) & 1) setbit(db, p.amask_off + (pc * 4 + cc) * p.nw, v);
+    for (uint32_t nc = 0; nc < 5; nc++)
+      if (accept_tt >> (pc * 5 + nc) & 1) setbit(db, p.acc_off + (pc * 5 + nc) * p.nw, v);
+  }
+}
+
+// Automata of at most HG_MAX_W state words: per-byte reach, per-node follow rows, dense condition masks.
+void emit_dense_tables(HgDb &db, const Automaton &a, HgPattern &p) {
+  const uint32_t nn = a.nn, nw = a.nw;
+  p.reach_off = alloc(db, 256 * nw);
+  p.follow_off = alloc(db, static_cast<size_t>(nn) * nw);
+  p.init_off = alloc(db, nw);
+  p.amask_off = alloc(db, 16 * nw);
+  p.acc_off = alloc(db, 20 * nw);
+  for (uint32_t v = 0; v < nn; v++) {
+    const uint32_t pos = a.nodes[v].first;
+    for (int b = 0; b < 256; b++)
+      if (a.g.pos_class[pos][b]) setbit(db, p.reach_off + b * nw, v);
+    set_condition_masks(db, p, v, a.nodes[v].second, a.last_tt[pos]);
+  }
+  for (auto &c : a.first) setbit(db, p.init_off, a.node(c.pos, c.tt));
+  for (auto &e : a.g.edges) {
+    const uint32_t to = a.node(e.q, e.tt);
+    for (uint32_t v = a.node_lo[e.p]; v < a.node_lo[e.p + 1]; v++) setbit(db, p.follow_off + v * nw, to);
+  }
+  db.max_nw = std::max(db.max_nw, nw);
+}
+
+// Huge automata (more than HG_MAX_W state words): sparse tables (HgHugeHeader, hg_db.h).
+void emit_huge_tables(HgDb &db, const Automaton &a, HgPattern &p) {
+  const uint32_t nn = a.nn, nw = a.nw, npos = static_cast<uint32_t>(a.g.pos_class.size());
+  db.nhuge++;
+  db.huge_max_nw = std::max(db.huge_max_nw, nw);
+  // byte classes: bytes that belong to the same position classes are one class
+  std::vector<ByteSet> distinct;
+  {
+    std::map<std::string, uint32_t> seen;
+    for (auto &cs : a.g.pos_class)
+      if (seen.emplace(cs.to_string(), 0).second) distinct.push_back(cs);
+  }
+  uint32_t cls_of[256], ncls = 0;
+  uint32_t rep[256];  // a representative byte of each class
+  {
+    std::map<std::vector<bool>, uint32_t> sig_cls;
+    for (int b = 0; b < 256; b++) {
+      std::vector<bool> sig(distinct.size());
+      for (size_t d = 0; d < distinct.size(); d++) sig[d] = distinct[d][b];
+      auto it = sig_cls.find(sig);
+      if (it == sig_cls.end()) {
+        rep[ncls] = static_cast<uint32_t>(b);
+        it = sig_cls.emplace(std::move(sig), ncls++).first;
+      }
+      cls_of[b] = it->second;
+    }
+  }
+  bool ctxfree = true;
+  for (uint32_t v = 0; v < nn; v++) ctxfree = ctxfree && a.nodes[v].second == HG_TT_ALL;
+  for (uint32_t q = 0; q < npos; q++) ctxfree = ctxfree && (a.last_tt[q] == 0 || a.last_tt[q] == HG_TT_ALL);
+  const uint32_t hdr_off = alloc(db, sizeof(HgHugeHeader) / 4);
+  const uint32_t cls_off = alloc(db, 64);
+  for (int b = 0; b < 256; b++) db.pool[cls_off + b / 4] |= cls_of[b] << ((b & 3) * 8);
+  p.reach_off = alloc(db, static_cast<size_t>(ncls) * nw);
+  p.follow_off = hdr_off;
+  p.init_off = alloc(db, nw);
+  const uint32_t smask_off = alloc(db, nw), xsrc_off = alloc(db, nw), xrank_off = alloc(db, nw);
+  // context-free: one accept word and no entry masks
+  p.amask_off = ctxfree ? p.init_off : alloc(db, 16 * static_cast<size_t>(nw));  // (never read when ctxfree)
+  p.acc_off = alloc(db, (ctxfree ? 1 : 20) * static_cast<size_t>(nw));
+  for (uint32_t v = 0; v < nn; v++) {
+    const uint32_t pos = a.nodes[v].first;
+    for (uint32_t c = 0; c < ncls; c++)
+      if (a.g.pos_class[pos][rep[c]]) setbit(db, p.reach_off + c * nw, v);
+    if (!ctxfree) set_condition_masks(db, p, v, a.nodes[v].second, a.last_tt[pos]);
+    else if (a.last_tt[pos]) setbit(db, p.acc_off, v);
+  }
+  for (auto &c : a.first) setbit(db, p.init_off, a.node(c.pos, c.tt));
+  uint32_t init_hi = 0;
+  for (uint32_t w = 0; w < nw; w++)
+    if (db.pool[p.init_off + w]) init_hi = w + 1;
+  // follow: per source node its sorted targets; node -> node + 1 is a bit of smask, the rest become ranges
+  std::vector<uint32_t> xlist{0}, xt;
+  std::vector<uint32_t> targets;
+  const std::vector<Edge> &edges = a.g.edges;
+  size_t ei = 0;
+  for (uint32_t q = 0; q < npos; q++) {
+    targets.clear();
+    for (; ei < edges.size() && edges[ei].p == q; ei++) targets.push_back(a.node(edges[ei].q, edges[ei].tt));
+    if (targets.empty()) continue;
+    std::sort(targets.begin(), targets.end());
+    targets.erase(std::unique(targets.begin(), targets.end()), targets.end());
+    for (uint32_t v = a.node_lo[q]; v < a.node_lo[q + 1]; v++) {  // every node of the position has the position's targets
+      bool any = false;
+      for (size_t t = 0; t < targets.size();) {
+        if (targets[t] == v + 1) { setbit(db, smask_off, v); t++; continue; }
+        size_t u = t;
+        while (u + 1 < targets.size() && targets[u + 1] == targets[u] + 1 && targets[u + 1] != v + 1) u++;
+        xt.push_back(targets[t]);
+        xt.push_back(targets[u]);
+        any = true;
+        t = u + 1;
+      }
+      if (any) {
+        setbit(db, xsrc_off, v);
+        xlist.push_back(static_cast<uint32_t>(xt.size() / 2));
+      }
+    }
+  }
+  for (uint32_t w = 0, run = 0; w < nw; w++) {
+    db.pool[xrank_off + w] = run;
+    run += static_cast<uint32_t>(__builtin_popcount(db.pool[xsrc_off + w]));
+  }
+  const uint32_t xlist_off = alloc(db, xlist.size()), xt_off = alloc(db, std::max<size_t>(xt.size(), 2));
+  std::copy(xlist.begin(), xlist.end(), db.pool.begin() + xlist_off);
+  std::copy(xt.begin(), xt.end(), db.pool.begin() + xt_off);
+  HgHugeHeader h{};
+  h.cls_off = cls_off;
+  h.ncls = ncls;
+  h.smask_off = smask_off;
+  h.xsrc_off = xsrc_off;
+  h.xrank_off = xrank_off;
+  h.xlist_off = xlist_off;
+  h.xt_off = xt_off;
+  h.ctxfree = ctxfree ? 1u : 0u;
+  h.init_hi = init_hi;
+  h.nsources = static_cast<uint32_t>(xlist.size() - 1);
+  h.nranges = static_cast<uint32_t>(xt.size() / 2);
+  std::memcpy(&db.pool[hdr_off], &h, sizeof h);
+  const uint64_t stage = 64ull + static_cast<uint64_t>(nw) * (ncls + 4u + (ctxfree ? 1u : 36u));  // (hg_huge.hip huge_stage_words)
+  if (stage <= HG_HUGE_STAGE_MAX) db.huge_stage_words = std::max<uint32_t>(db.huge_stage_words, static_cast<uint32_t>(stage));
+}
+
+// Context-free single-word automaton: the confirm kernel's fast path.
+void set_simple_flags(const HgDb &db, HgPattern &p) {
+  if (p.nw != 1) return;
+  bool simple = true;
+  const uint32_t full = p.nnodes == 32 ? 0xFFFFFFFFu : ((1u << p.nnodes) - 1u);
+  for (uint32_t i = 0; i < 16; i++) simple = simple && db.pool[p.amask_off + i] == full;
+  for (uint32_t i = 1; i < 20; i++) simple = simple && db.pool[p.acc_off + i] == db.pool[p.acc_off];
+  p.simple = simple ? 1 : 0;
+  p.acc_all = db.pool[p.acc_off];
+  p.init_word = db.pool[p.init_off];
+}
+
+// An expression's required literals (cut down to HG_FACTOR_MAX bytes) and whether a verified occurrence of its one literal
+// is a match.
+struct Cover {
+  LitSet lits;
+  bool literal_only = false;
+};
+
+Cover literal_cover(const Node &root, HgPattern &p) {
+  Info info = analyze(root);
+  Cover cover;
+  long lead = info.lead;  // (a literal cut down to HG_FACTOR_MAX bytes begins that much later)
+  if (info.has_cover)
+    for (auto &l : info.cover) {
+      size_t cut = 0;
+      cover.lits.push_back(clip(l, &cut));
+      if (cut) lead = add_len(lead, static_cast<long>(cut));
+    }
+  dedupe(cover.lits);
+  p.lit_lead = (info.has_cover && lead >= 0) ? static_cast<uint32_t>(lead) : 0xFFFFFFFFu;
+  // literal-only: the expression's language is exactly one literal that fits the factor record, has no NUL
+  // or inner newline, and no assertions -> a verified factor occurrence is a match
+  if (info.exact && info.set.size() == 1 && cover.lits.size() == 1 && info.set[0].bytes.size() <= HG_FACTOR_MAX &&
+      cover.lits[0] == info.set[0] && !has_assert(root)) {
+    const std::string &lb = info.set[0].bytes;
+    bool clean = true;
+    for (size_t j = 0; j < lb.size(); j++)
+      if (lb[j] == 0 || (lb[j] == '\n' && j + 1 < lb.size())) clean = false;
+    cover.literal_only = clean;
+  }
+  return cover;
+}
+
+// The reverse automaton of the start-of-match pass (hg_som.h): the same nodes, with the follow table transposed.
+void emit_som_follow(HgDb &db, HgPattern &p) {
+  if (p.nw > HG_MAX_W)
+    throw CompileError("HS_FLAG_SOM_LEFTMOST needs an automaton of at most " + std::to_string(HG_MAX_NODES) + " nodes (HG_MAX_NODES); this expression has " +
+                       std::to_string(p.nnodes));
+  p.som_follow_off = alloc(db, static_cast<size_t>(p.nnodes) * p.nw);
+  for (uint32_t v = 0; v < p.nnodes; v++)
+    for (uint32_t w = 0; w < p.nw; w++)
+      for (uint32_t x = db.pool[p.follow_off + v * p.nw + w]; x; x &= x - 1) setbit(db, p.som_follow_off + (w * 32 + hg_ctz(x)) * p.nw, v);
+  db.nsom++;
+}
+
+// Expressions that share a report id either all carry HS_FLAG_SOM_LEFTMOST or none does; the SOM expressions of one id
+// form a cycle (som_next), so that the pass can give an (id, to) report the smallest start over all of them.
+void link_som_ids(HgDb &db) {
+  if (!db.nsom) return;
+  std::map<uint32_t, uint32_t> last;         // id -> the latest SOM expression seen with it
+  std::map<uint32_t, uint32_t> first_plain;  // id -> the first expression without the flag
+  for (uint32_t i = 0; i < db.patterns.size(); i++) {
+    HgPattern &p = db.patterns[i];
+    if (!(p.flags & HG_FLAG_SOM_LEFTMOST)) {
+      first_plain.emplace(p.id, i);
+      continue;
+    }
+    auto it = last.find(p.id);
+    if (it == last.end()) {
+      p.som_next = i;
+    } else {
+      p.som_next = db.patterns[it->second].som_next;  // insert behind the latest: the cycle stays closed
+      db.patterns[it->second].som_next = i;
+    }
+    last[p.id] = i;
+  }
+  for (auto &kv : last) {
+    auto it = first_plain.find(kv.first);
+    if (it != first_plain.end())
+      throw CompileError("expressions with report id " + std::to_string(kv.first) + " must all carry HS_FLAG_SOM_LEFTMOST, or none of them",
+                         static_cast<int>(std::max(it->second, kv.second)));
+  }
+}
+
+// Combinations: their ids are unique, their operands name ids of expressions that are not combinations; expressions that
+// share an id are all QUIET or none is (else de-duplication would decide whether the report is delivered).  Builds the
+// combination records and the feed table.
+void link_combinations(HgDb &db, const std::map<uint32_t, CombProgram> &programs) {
+  if (!db.comb_pass()) return;
+  std::map<uint32_t, std::pair<uint32_t, bool>> plain;  // id -> (first expression with it that is not a combination, it is QUIET)
+  std::map<uint32_t, uint32_t> comb_of;                 // id -> the combination with it
+  for (uint32_t i = 0; i < db.patterns.size(); i++) {
+    const HgPattern &p = db.patterns[i];
+    if (p.tier == HG_TIER_COMB) continue;
+    const bool quiet = (p.flags & HG_FLAG_QUIET) != 0;
+    auto ins = plain.emplace(p.id, std::make_pair(i, quiet));
+    if (!ins.second && ins.first->second.second != quiet)
+      throw CompileError("expressions with report id " + std::to_string(p.id) + " must all carry HS_FLAG_QUIET, or none of them", static_cast<int>(i));
+  }
+  for (uint32_t i = 0; i < db.patterns.size(); i++) {
+    const HgPattern &p = db.patterns[i];
+    if (p.tier != HG_TIER_COMB) continue;
+    if (plain.count(p.id) || !comb_of.emplace(p.id, i).second)
+      throw CompileError("combination report id " + std::to_string(p.id) + " is shared with another expression (a combination's id must be unique)",
+                         static_cast<int>(i));
+  }
+  std::vector<std::pair<uint32_t, uint32_t>> feed;  // (operand id, combination record)
+  for (auto &kv : programs) {
+    const uint32_t i = kv.first;
+    const int at = static_cast<int>(i);
+    const HgPattern &p = db.patterns[i];
+    const CombProgram &cp = kv.second;
+    for (uint32_t id : cp.ops) {
+      if (id == p.id) throw CompileError("combination refers to its own report id " + std::to_string(id), at);
+      if (comb_of.count(id))
+        throw CompileError("combination refers to report id " + std::to_string(id) + " of another combination (nested combinations are not supported)", at);
+      if (!plain.count(id)) throw CompileError("combination refers to report id " + std::to_string(id) + ", which no expression in the set has", at);
+    }
+    if (p.flags & HG_FLAG_QUIET) continue;  // (evaluated for nothing: it reports nothing and nothing can refer to it)
+    HgComb c{};
+    c.id = p.id;
+    c.pattern = i;
+    c.single = p.single;
+    c.nops = static_cast<uint32_t>(cp.ops.size());
+    c.ops_off = static_cast<uint32_t>(db.comb_words.size());
+    db.comb_words.insert(db.comb_words.end(), cp.ops.begin(), cp.ops.end());
+    c.prog_off = static_cast<uint32_t>(db.comb_words.size());
+    c.prog_len = static_cast<uint32_t>(cp.prog.size());
+    db.comb_words.insert(db.comb_words.end(), cp.prog.begin(), cp.prog.end());
+    for (uint32_t id : cp.ops) feed.emplace_back(id, static_cast<uint32_t>(db.combs.size()));
+    db.combs.push_back(c);
+  }
+  std::sort(feed.begin(), feed.end());
+  for (auto &f : feed) db.comb_feed.push_back(f.first);
+  for (auto &f : feed) db.comb_feed.push_back(f.second);
+}
+
+// Tiers for one window layout.  A pattern whose required literals all have at least `min_factor` bytes is found through the
+// window prefilter (tier 0), the others run on every line (tier 1).  Then the always-on order and groups, the factors and
+// the filter tables: build_filter's return code (-5: the layout does not fit, the caller tries the next one).
+int assign_tiers(HgDb &db, const std::vector<Cover> &covers, const CompileKnobs &knobs, uint32_t min_factor, uint32_t dense,
+                 uint32_t window_bytes, std::string *err) {
+  db.dense = dense;
+  db.window_bytes = window_bytes;
+  db.window_mask = window_bytes == 4 ? 0xFFFFFFFFu : 0x00FFFFFFu;
+  db.weights_c = HG_HASH_WEIGHTS & db.window_mask;
+  db.slow.clear();
+  db.factors.clear();
+  db.fold_mask = 0;
+  size_t ncaseless = 0;  // required literals of the anchored expressions with case-insensitive letters
+  for (uint32_t m = 0; m < HG_CONFIRM_MODES; m++) db.n_confirm_mode[m] = 0;
+  for (uint32_t i = 0; i < db.patterns.size(); i++) {
+    HgPattern &p = db.patterns[i];
+    if (p.tier == HG_TIER_COMB) continue;  // (no automaton: the combination pass evaluates it)
+    const LitSet &lits = covers[i].lits;
+    const bool fast = !lits.empty() && min_len(lits) >= min_factor;
+    p.tier = fast ? 0 : 1;
+    p.literal_only = (fast && covers[i].literal_only) ? 1 : 0;
+    if (fast) {
+      db.n_confirm_mode[hg_confirm_mode(p)]++;
+      for (auto &l : lits) {
+        bool caseless = false;
+        for (unsigned char m : l.cmask) caseless = caseless || m != 0xFF;
+        ncaseless += caseless ? 1 : 0;
+      }
+    } else {
+      db.slow.push_back(i);
+    }
+  }
+  // Case-insensitive literals.  The general way: the stream pass folds every text dword (| 0x20202020) before it hashes it, and the
+  // windows are stored folded.  Where only a few literals of a set of dword-aligned windows are case-insensitive, their windows are
+  // stored in every case variant instead (at most 16 per window) and NOTHING is folded: the hot loop saves an instruction per
+  // dword, and folded look-alikes ('@' / '`', '[' / '{', upper-case text) no longer pass the filter.
+  if (ncaseless) {
+    const bool expand = !dense && !knobs.no_case_expand && ncaseless <= 64;  // (at most 64 x 4 windows x 16 variants more)
+    db.fold_mask = expand ? 0u : 0x20202020u;
+  }
+  // always-on patterns of at most two state words go first: the segment-parallel kernel takes those
+  auto two_words = [&](uint32_t pi) { return db.patterns[pi].nw <= 2; };  // bounded or not: an unbounded pattern's lead-in is the start of its line
+  auto not_huge = [&](uint32_t pi) { return db.patterns[pi].nw <= HG_MAX_W; };  // huge automata go last: their own kernel
+  std::stable_partition(db.slow.begin(), db.slow.end(), not_huge);
+  std::stable_partition(db.slow.begin(), db.slow.end(), two_words);
+  db.nslow_fast = static_cast<uint32_t>(std::count_if(db.slow.begin(), db.slow.end(), two_words));
+  db.nslow_huge = static_cast<uint32_t>(db.slow.size() - std::count_if(db.slow.begin(), db.slow.end(), not_huge));
+  build_slow_groups(db, knobs);
+  // factors (needs the final fold mask); windows and filter tables are built from them
+  uint32_t rank_in_mode[HG_CONFIRM_MODES] = {};
+  for (uint32_t i = 0; i < db.patterns.size(); i++) {
+    if (db.patterns[i].tier != 0) continue;
+    const uint32_t mode = hg_confirm_mode(db.patterns[i]), rank = rank_in_mode[mode]++;
+    for (auto &l : covers[i].lits) {
+      HgFactor fct{};
+      fct.pattern = i;
+      fct.len = static_cast<uint32_t>(l.bytes.size());
+      fct.mode = mode;
+      fct.mode_rank = rank;
+      std::memcpy(fct.lit, l.bytes.data(), fct.len);
+      for (uint32_t b = 0; b < fct.len; b++)
+        if (static_cast<unsigned char>(l.cmask[b]) != 0xFF) fct.casebits |= 1u << b;
+      fct.id = db.patterns[i].id;
+      db.factors.push_back(fct);
+    }
+  }
+  db.nreal_factors = static_cast<uint32_t>(db.factors.size());
+  if (db.factors.empty()) db.factors.push_back(HgFactor{});  // keep device arrays non-empty
+  return build_filter(db, nullptr, err);
+}
+
+// The window layout.  Dword-aligned windows need HG_FAST_MIN_FACTOR bytes (a window on every residue mod 4).  When that
+// leaves patterns with shorter literals behind, the stream pass probes a window at every BYTE offset instead (db.dense: four
+// times the probes, a third of the streaming rate — still several times the always-on tier), which takes literals down to
+// HG_DENSE_MIN_FACTOR bytes.  Layouts are tried from the most capable down until one fits.
+void choose_windows(HgDb &db, const std::vector<Cover> &covers, const CompileKnobs &knobs) {
+  std::string msg;
+  auto assign = [&](size_t min_factor, uint32_t dense, uint32_t window_bytes) {
+    return assign_tiers(db, covers, knobs, static_cast<uint32_t>(min_factor), dense, window_bytes, &msg);
+  };
+  size_t shortest = SIZE_MAX;  // shortest required literal among the patterns dword-aligned windows leave behind
+  for (const Cover &c : covers) {
+    const size_t m = c.lits.empty() ? 0 : min_len(c.lits);
+    if (m >= HG_DENSE_MIN_FACTOR && m < HG_FAST_MIN_FACTOR) shortest = std::min(shortest, m);
+  }
+  int rc = -5;
+  if (shortest != SIZE_MAX) {
+    // every literal of the set has at least 5 bytes: a window on both residues mod 2 fits, half the probes
+    size_t set_shortest = SIZE_MAX;
+    for (const Cover &c : covers)
+      if (!c.lits.empty() && min_len(c.lits) >= shortest) set_shortest = std::min(set_shortest, min_len(c.lits));
+    const uint32_t step = set_shortest >= HG_WINDOW_BYTES + 1 ? 2u : 1u;
+    rc = assign(shortest, step, HG_WINDOW_BYTES);
+    if (rc == -5 && step == 2) rc = assign(shortest, 1, HG_WINDOW_BYTES);  // (one window per literal instead of two)
+    // too many 3-byte literals to enumerate the byte after each: every window shrinks to 3 bytes instead
+    if (rc == -5 && shortest < HG_WINDOW_BYTES) rc = assign(shortest, 1, HG_WINDOW_BYTES - 1);
+    if (rc == -5 && shortest < HG_WINDOW_BYTES) rc = assign(HG_WINDOW_BYTES, 1, HG_WINDOW_BYTES);  // without the short literals
+  }
+  if (rc == -5) rc = assign(HG_FAST_MIN_FACTOR, 0, HG_WINDOW_BYTES);
+  if (rc != 0) throw CompileError(msg, -1);
+}
+
 }  // namespace
 
 int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned *ids, unsigned n, HgDb **out,
@@ -1571,469 +2025,55 @@ int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned 
     if (err) *err = "invalid arguments: at least one expression is required";
     return -1;
   }
-  if (n > HG_MAX_PATTERNS) {
-    if (err) *err = "too many expressions (limit 16777216)";
-    return -4;
-  }
   const CompileKnobs knobs;
   auto db = std::make_unique<HgDb>();
-  struct Pending { std::vector<Lit> lits; bool literal_only = false; };
-  std::vector<Pending> covers(n);
-  std::map<uint32_t, CombProgram> comb_programs;  // expression index -> its program (combinations)
-  unsigned cur = 0;
+  int at = -1;  // the expression being compiled (-1: a set-wide stage)
   try {
-    for (cur = 0; cur < n; cur++) {
-      uint32_t f = flags ? flags[cur] : 0;
+    if (n > HG_MAX_PATTERNS) throw CompileError("too many expressions (limit 16777216)", -1);
+    std::vector<Cover> covers(n);
+    std::map<uint32_t, CombProgram> programs;  // expression index -> its program (combinations)
+    for (at = 0; at < static_cast<int>(n); at++) {
+      const uint32_t f = flags ? flags[at] : 0, id = ids ? ids[at] : 0;
       if (f & ~HG_FLAGS_SUPPORTED) throw CompileError("unsupported flag bits");
       if (f & HG_FLAG_COMBINATION) {
-        // no automaton: a formula over other expressions' report ids (hg_comb.h); of its flags only SINGLEMATCH and QUIET count
-        if (!exprs[cur] || !exprs[cur][0]) throw CompileError("empty expression");
-        db->exprs.push_back(exprs[cur]);
-        CombProgram cp = parse_combination(exprs[cur]);
-        if (hg_comb_eval(cp.prog.data(), static_cast<uint32_t>(cp.prog.size()), 0))
-          throw CompileError("combination is true when none of its operands has matched: such combinations report at the end of the data, which is not supported");
-        HgPattern p{};
-        p.id = ids ? ids[cur] : 0;
-        p.flags = f & (HG_FLAG_COMBINATION | HG_FLAG_SINGLEMATCH | HG_FLAG_QUIET);
-        p.single = (f & HG_FLAG_SINGLEMATCH) ? 1 : 0;
-        p.tier = HG_TIER_COMB;
-        db->max_id = std::max(db->max_id, p.id);
-        db->ncomb++;
-        db->patterns.push_back(p);
-        comb_programs.emplace(cur, std::move(cp));
+        db->patterns.push_back(compile_combination(*db, exprs[at], f, id, programs[at]));
+        db->max_id = std::max(db->max_id, id);
         continue;
       }
       if ((f & HG_FLAG_SOM_LEFTMOST) && (f & HG_FLAG_SINGLEMATCH))
         throw CompileError("HS_FLAG_SOM_LEFTMOST cannot be combined with HS_FLAG_SINGLEMATCH");
-      if (!exprs[cur] || !exprs[cur][0]) throw CompileError("empty expression");
-      std::string text(exprs[cur]);
-      db->exprs.push_back(text);
-      Parser parser(text, f);
-      NodeP root = parser.parse();
-      check_embedded_anchors(*root, false, false);
-
-      if (program_size(*root) > HG_HUGE_MAX_PROGRAM) throw CompileError("pattern too large");
-      Glushkov g;
-      Frag top = g.build(*root);
-      if (top.nullable) throw CompileError("expression can match the empty string (HS_FLAG_ALLOWEMPTY is not supported)");
-      if (g.pos_class.empty()) throw CompileError("expression matches nothing");
-
-      // one edge per (p, q): the ways of getting from p to q (through different assertions) merge into one condition
-      std::sort(g.edges.begin(), g.edges.end(), [](const Edge &x, const Edge &y) { return x.p != y.p ? x.p < y.p : x.q < y.q; });
-      {
-        size_t out_n = 0;
-        for (size_t i = 0; i < g.edges.size(); i++) {
-          if (out_n && g.edges[out_n - 1].p == g.edges[i].p && g.edges[out_n - 1].q == g.edges[i].q) g.edges[out_n - 1].tt |= g.edges[i].tt;
-          else g.edges[out_n++] = g.edges[i];
-        }
-        g.edges.resize(out_n);
-      }
-      // nodes = distinct (position, entry condition), numbered in (position, condition) order: linear expressions get
-      // follow = next bit, and the nodes of one position are consecutive
-      std::vector<std::pair<uint32_t, uint32_t>> nodes;
-      nodes.reserve(top.first.size() + g.edges.size());
-      for (auto &c : top.first) nodes.push_back({c.pos, c.tt});
-      for (auto &e : g.edges) nodes.push_back({e.q, e.tt});
-      std::sort(nodes.begin(), nodes.end());
-      nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());
-      if (nodes.size() > HG_HUGE_MAX_NODES) throw CompileError("pattern too large");
-      auto intern = [&](uint32_t pos, uint32_t tt) {
-        return static_cast<uint32_t>(std::lower_bound(nodes.begin(), nodes.end(), std::make_pair(pos, tt)) - nodes.begin());
-      };
-      const uint32_t npos = static_cast<uint32_t>(g.pos_class.size());
-      std::vector<uint32_t> node_lo(npos + 1, 0);  // nodes of position q: [node_lo[q], node_lo[q + 1])
-      for (auto &nd : nodes) node_lo[nd.first + 1]++;
-      for (uint32_t q = 0; q < npos; q++) node_lo[q + 1] += node_lo[q];
-
-      // (an expression whose every entry condition is contradictory, e.g. \b\Bc, has no nodes: it keeps one all-zero state
-      // word so that every routine sees well-formed tables and simply never matches)
-      uint32_t nn = static_cast<uint32_t>(nodes.size()), nw = nn ? (nn + 31) / 32 : 1;
+      if (!exprs[at] || !exprs[at][0]) throw CompileError("empty expression");
+      db->exprs.push_back(exprs[at]);
+      const Automaton a = build_automaton(db->exprs.back(), f);
       HgPattern p{};
-      p.id = ids ? ids[cur] : 0;
+      p.id = id;
       p.flags = f;
-      p.nnodes = nn;
-      p.nw = nw;
+      p.nnodes = a.nn;
+      p.nw = a.nw;
       p.single = (f & HG_FLAG_SINGLEMATCH) ? 1 : 0;
-      auto alloc = [&](size_t words) {
-        if (db->pool.size() + words > 0xFFFF0000ull) throw CompileError("pattern set too large");
-        uint32_t off = static_cast<uint32_t>(db->pool.size());
-        db->pool.resize(db->pool.size() + words, 0);
-        return off;
-      };
-      std::vector<uint32_t> last_tt(npos, 0);
-      for (auto &l : top.last) last_tt[l.pos] |= l.tt;
-      auto setbit = [&](uint32_t base, uint32_t node) { db->pool[base + node / 32] |= 1u << (node % 32); };
-      const bool huge = nw > HG_MAX_W;
-      if (!huge) {
-        p.reach_off = alloc(256 * nw);
-        p.follow_off = alloc(static_cast<size_t>(nn) * nw);
-        p.init_off = alloc(nw);
-        p.amask_off = alloc(16 * nw);
-        p.acc_off = alloc(20 * nw);
-        for (uint32_t v = 0; v < nn; v++) {
-          uint32_t pos = nodes[v].first, tt = nodes[v].second;
-          for (int b = 0; b < 256; b++)
-            if (g.pos_class[pos][b]) setbit(p.reach_off + b * nw, v);
-          for (uint32_t pc = 0; pc < 4; pc++) {
-            for (uint32_t cc = 0; cc < 4; cc++)
-              if (tt >> (pc * 5 + cc) & 1) setbit(p.amask_off + (pc * 4 + cc) * nw, v);
-            for (uint32_t nc = 0; nc < 5; nc++)
-              if (last_tt[pos] >> (pc * 5 + nc) & 1) setbit(p.acc_off + (pc * 5 + nc) * nw, v);
-          }
-        }
-        for (auto &c : top.first) setbit(p.init_off, intern(c.pos, c.tt));
-        for (auto &e : g.edges) {
-          uint32_t to = intern(e.q, e.tt);
-          for (uint32_t v = node_lo[e.p]; v < node_lo[e.p + 1]; v++) setbit(p.follow_off + v * nw, to);
-        }
-      } else {
-        // ---- huge automaton: sparse tables (HgHugeHeader, hg_db.h)
-        db->nhuge++;
-        db->huge_max_nw = std::max(db->huge_max_nw, nw);
-        // byte classes: bytes that belong to the same position classes are one class
-        std::vector<ByteSet> distinct;
-        {
-          std::map<std::string, uint32_t> seen;
-          for (auto &cs : g.pos_class) {
-            std::string key = cs.to_string();
-            if (seen.emplace(key, 0).second) distinct.push_back(cs);
-          }
-        }
-        uint32_t cls_of[256], ncls = 0;
-        uint32_t rep[256];  // a representative byte of each class
-        {
-          std::map<std::vector<bool>, uint32_t> sig_cls;
-          for (int b = 0; b < 256; b++) {
-            std::vector<bool> sig(distinct.size());
-            for (size_t d = 0; d < distinct.size(); d++) sig[d] = distinct[d][b];
-            auto it = sig_cls.find(sig);
-            if (it == sig_cls.end()) {
-              rep[ncls] = static_cast<uint32_t>(b);
-              it = sig_cls.emplace(std::move(sig), ncls++).first;
-            }
-            cls_of[b] = it->second;
-          }
-        }
-        bool ctxfree = true;
-        for (uint32_t v = 0; v < nn; v++) ctxfree = ctxfree && nodes[v].second == HG_TT_ALL;
-        for (uint32_t q = 0; q < npos; q++) ctxfree = ctxfree && (last_tt[q] == 0 || last_tt[q] == HG_TT_ALL);
-        const uint32_t hdr_off = alloc(sizeof(HgHugeHeader) / 4);
-        const uint32_t cls_off = alloc(64);
-        for (int b = 0; b < 256; b++) db->pool[cls_off + b / 4] |= cls_of[b] << ((b & 3) * 8);
-        p.reach_off = alloc(static_cast<size_t>(ncls) * nw);
-        p.follow_off = hdr_off;
-        p.init_off = alloc(nw);
-        const uint32_t smask_off = alloc(nw), xsrc_off = alloc(nw), xrank_off = alloc(nw);
-        p.amask_off = ctxfree ? p.init_off : alloc(16 * static_cast<size_t>(nw));  // (never read when ctxfree)
-        p.acc_off = alloc((ctxfree ? 1 : 20) * static_cast<size_t>(nw));
-        for (uint32_t v = 0; v < nn; v++) {
-          const uint32_t pos = nodes[v].first, tt = nodes[v].second;
-          for (uint32_t c = 0; c < ncls; c++)
-            if (g.pos_class[pos][rep[c]]) setbit(p.reach_off + c * nw, v);
-          if (ctxfree) {
-            if (last_tt[pos]) setbit(p.acc_off, v);
-            continue;
-          }
-          for (uint32_t pc = 0; pc < 4; pc++) {
-            for (uint32_t cc = 0; cc < 4; cc++)
-              if (tt >> (pc * 5 + cc) & 1) setbit(p.amask_off + (pc * 4 + cc) * nw, v);
-            for (uint32_t nc = 0; nc < 5; nc++)
-              if (last_tt[pos] >> (pc * 5 + nc) & 1) setbit(p.acc_off + (pc * 5 + nc) * nw, v);
-          }
-        }
-        for (auto &c : top.first) setbit(p.init_off, intern(c.pos, c.tt));
-        uint32_t init_hi = 0;
-        for (uint32_t w = 0; w < nw; w++)
-          if (db->pool[p.init_off + w]) init_hi = w + 1;
-        // follow: per source node its sorted targets; node -> node + 1 is a bit of smask, the rest become ranges
-        std::vector<uint32_t> xlist{0}, xt;
-        std::vector<uint32_t> targets;
-        size_t ei = 0;
-        for (uint32_t q = 0; q < npos; q++) {
-          targets.clear();
-          for (; ei < g.edges.size() && g.edges[ei].p == q; ei++) targets.push_back(intern(g.edges[ei].q, g.edges[ei].tt));
-          if (targets.empty()) continue;
-          std::sort(targets.begin(), targets.end());
-          targets.erase(std::unique(targets.begin(), targets.end()), targets.end());
-          for (uint32_t v = node_lo[q]; v < node_lo[q + 1]; v++) {  // every node of the position has the position's targets
-            bool any = false;
-            for (size_t t = 0; t < targets.size();) {
-              if (targets[t] == v + 1) { setbit(smask_off, v); t++; continue; }
-              size_t u = t;
-              while (u + 1 < targets.size() && targets[u + 1] == targets[u] + 1 && targets[u + 1] != v + 1) u++;
-              xt.push_back(targets[t]);
-              xt.push_back(targets[u]);
-              any = true;
-              t = u + 1;
-            }
-            if (any) {
-              setbit(xsrc_off, v);
-              xlist.push_back(static_cast<uint32_t>(xt.size() / 2));
-            }
-          }
-        }
-        for (uint32_t w = 0, run = 0; w < nw; w++) {
-          db->pool[xrank_off + w] = run;
-          run += static_cast<uint32_t>(__builtin_popcount(db->pool[xsrc_off + w]));
-        }
-        const uint32_t xlist_off = alloc(xlist.size()), xt_off = alloc(std::max<size_t>(xt.size(), 2));
-        std::copy(xlist.begin(), xlist.end(), db->pool.begin() + xlist_off);
-        std::copy(xt.begin(), xt.end(), db->pool.begin() + xt_off);
-        HgHugeHeader h{};
-        h.cls_off = cls_off;
-        h.ncls = ncls;
-        h.smask_off = smask_off;
-        h.xsrc_off = xsrc_off;
-        h.xrank_off = xrank_off;
-        h.xlist_off = xlist_off;
-        h.xt_off = xt_off;
-        h.ctxfree = ctxfree ? 1u : 0u;
-        h.init_hi = init_hi;
-        h.nsources = static_cast<uint32_t>(xlist.size() - 1);
-        h.nranges = static_cast<uint32_t>(xt.size() / 2);
-        std::memcpy(&db->pool[hdr_off], &h, sizeof h);
-        const uint64_t stage = 64ull + static_cast<uint64_t>(nw) * (ncls + 4u + (ctxfree ? 1u : 36u));  // (hg_huge.hip huge_stage_words)
-        if (stage <= HG_HUGE_STAGE_MAX) db->huge_stage_words = std::max<uint32_t>(db->huge_stage_words, static_cast<uint32_t>(stage));
-      }
-      if (!huge) db->max_nw = std::max(db->max_nw, nw);
-      db->max_id = std::max(db->max_id, p.id);
-      if (nw == 1) {  // context-free single-word automaton: the confirm kernel's fast path
-        bool simple = true;
-        const uint32_t full = nn == 32 ? 0xFFFFFFFFu : ((1u << nn) - 1u);
-        for (uint32_t i = 0; i < 16; i++) simple = simple && db->pool[p.amask_off + i] == full;
-        for (uint32_t i = 1; i < 20; i++) simple = simple && db->pool[p.acc_off + i] == db->pool[p.acc_off];
-        p.simple = simple ? 1 : 0;
-        p.acc_all = db->pool[p.acc_off];
-        p.init_word = db->pool[p.init_off];
-      }
-
-      // required literals
-      Info info = analyze(*root);
-      LitSet cover;
-      long lead = info.lead;  // (a literal cut down to HG_FACTOR_MAX bytes begins that much later)
-      if (info.has_cover)
-        for (auto &l : info.cover) {
-          size_t cut = 0;
-          cover.push_back(clip(l, &cut));
-          if (cut) lead = add_len(lead, static_cast<long>(cut));
-        }
-      dedupe(cover);
-      covers[cur].lits = cover;
-      p.lit_lead = (info.has_cover && lead >= 0 && !knobs.no_confirm_window) ? static_cast<uint32_t>(lead) : 0xFFFFFFFFu;
-      // literal-only: the expression's language is exactly one literal that fits the factor record, has no NUL
-      // or inner newline, and no assertions -> a verified factor occurrence is a match
-      if (info.exact && info.set.size() == 1 && cover.size() == 1 && info.set[0].bytes.size() <= HG_FACTOR_MAX &&
-          cover[0] == info.set[0] && !has_assert(*root)) {
-        const std::string &lb = info.set[0].bytes;
-        bool clean = true;
-        for (size_t j = 0; j < lb.size(); j++)
-          if (lb[j] == 0 || (lb[j] == '\n' && j + 1 < lb.size())) clean = false;
-        covers[cur].literal_only = clean;
-      }
-      {
-        const long ml = max_match_len(*root);
-        p.max_len = ml > 0 ? static_cast<uint32_t>(ml) : 0;
-      }
-      if (f & HG_FLAG_SOM_LEFTMOST) {
-        // the reverse automaton of the start-of-match pass (hg_som.h): the same nodes, with the follow table transposed
-        if (huge)
-          throw CompileError("HS_FLAG_SOM_LEFTMOST needs an automaton of at most " + std::to_string(HG_MAX_NODES) + " nodes (HG_MAX_NODES); this expression has " +
-                             std::to_string(nn));
-        p.som_follow_off = alloc(static_cast<size_t>(nn) * nw);
-        for (uint32_t v = 0; v < nn; v++)
-          for (uint32_t w = 0; w < nw; w++)
-            for (uint32_t x = db->pool[p.follow_off + v * nw + w]; x; x &= x - 1) setbit(p.som_follow_off + (w * 32 + hg_ctz(x)) * nw, v);
-        db->nsom++;
-      }
+      if (a.nw > HG_MAX_W) emit_huge_tables(*db, a, p);
+      else emit_dense_tables(*db, a, p);
+      set_simple_flags(*db, p);
+      covers[at] = literal_cover(*a.root, p);
+      const long ml = max_match_len(*a.root);
+      p.max_len = ml > 0 ? static_cast<uint32_t>(ml) : 0;
+      if (f & HG_FLAG_SOM_LEFTMOST) emit_som_follow(*db, p);
       if (f & HG_FLAG_QUIET) db->nquiet++;
+      db->max_id = std::max(db->max_id, id);
       db->patterns.push_back(p);
     }
+    at = -1;
+    link_som_ids(*db);
+    link_combinations(*db, programs);
+    choose_windows(*db, covers, knobs);
   } catch (const CompileError &e) {
     if (err) *err = e.what();
-    if (bad_index) *bad_index = static_cast<int>(cur);
+    if (bad_index) *bad_index = e.index == kThisExpression ? at : e.index;
     return -4;
   } catch (const std::bad_alloc &) {
     if (err) *err = "out of memory";
-    if (bad_index) *bad_index = static_cast<int>(cur);
+    if (bad_index) *bad_index = at;
     return -2;
-  }
-  if (db->nsom) {
-    // Expressions that share a report id either all carry HS_FLAG_SOM_LEFTMOST or none does; the SOM expressions of one id
-    // form a cycle (som_next), so that the pass can give an (id, to) report the smallest start over all of them.
-    std::map<uint32_t, uint32_t> last;  // id -> the latest SOM expression seen with it
-    std::map<uint32_t, uint32_t> first_plain;  // id -> the first expression without the flag
-    for (uint32_t i = 0; i < n; i++) {
-      HgPattern &p = db->patterns[i];
-      if (!(p.flags & HG_FLAG_SOM_LEFTMOST)) {
-        first_plain.emplace(p.id, i);
-        continue;
-      }
-      auto it = last.find(p.id);
-      if (it == last.end()) {
-        p.som_next = i;
-      } else {
-        p.som_next = db->patterns[it->second].som_next;  // insert behind the latest: the cycle stays closed
-        db->patterns[it->second].som_next = i;
-      }
-      last[p.id] = i;
-    }
-    for (auto &kv : last) {
-      auto it = first_plain.find(kv.first);
-      if (it == first_plain.end()) continue;
-      if (err) *err = "expressions with report id " + std::to_string(kv.first) + " must all carry HS_FLAG_SOM_LEFTMOST, or none of them";
-      if (bad_index) *bad_index = static_cast<int>(std::max(it->second, kv.second));
-      return -4;
-    }
-  }
-
-  if (db->ncomb || db->nquiet) {
-    // Combinations: their ids are unique, their operands name ids of expressions that are not combinations; expressions that
-    // share an id are all QUIET or none is (else de-duplication would decide whether the report is delivered).
-    auto reject = [&](uint32_t i, const std::string &m) {
-      if (err) *err = m;
-      if (bad_index) *bad_index = static_cast<int>(i);
-      return -4;
-    };
-    std::map<uint32_t, std::pair<uint32_t, bool>> plain;  // id -> (first expression with it that is not a combination, it is QUIET)
-    std::map<uint32_t, uint32_t> comb_of;                 // id -> the combination with it
-    for (uint32_t i = 0; i < n; i++) {
-      const HgPattern &p = db->patterns[i];
-      if (p.tier == HG_TIER_COMB) continue;
-      const bool quiet = (p.flags & HG_FLAG_QUIET) != 0;
-      auto ins = plain.emplace(p.id, std::make_pair(i, quiet));
-      if (!ins.second && ins.first->second.second != quiet)
-        return reject(i, "expressions with report id " + std::to_string(p.id) + " must all carry HS_FLAG_QUIET, or none of them");
-    }
-    for (uint32_t i = 0; i < n; i++) {
-      const HgPattern &p = db->patterns[i];
-      if (p.tier != HG_TIER_COMB) continue;
-      if (plain.count(p.id) || !comb_of.emplace(p.id, i).second)
-        return reject(i, "combination report id " + std::to_string(p.id) + " is shared with another expression (a combination's id must be unique)");
-    }
-    std::vector<std::pair<uint32_t, uint32_t>> feed;  // (operand id, combination record)
-    for (auto &kv : comb_programs) {
-      const uint32_t i = kv.first;
-      const HgPattern &p = db->patterns[i];
-      const CombProgram &cp = kv.second;
-      for (uint32_t id : cp.ops) {
-        if (id == p.id) return reject(i, "combination refers to its own report id " + std::to_string(id));
-        if (comb_of.count(id)) return reject(i, "combination refers to report id " + std::to_string(id) + " of another combination (nested combinations are not supported)");
-        if (!plain.count(id)) return reject(i, "combination refers to report id " + std::to_string(id) + ", which no expression in the set has");
-      }
-      if (p.flags & HG_FLAG_QUIET) continue;  // (evaluated for nothing: it reports nothing and nothing can refer to it)
-      HgComb c{};
-      c.id = p.id;
-      c.pattern = i;
-      c.single = p.single;
-      c.nops = static_cast<uint32_t>(cp.ops.size());
-      c.ops_off = static_cast<uint32_t>(db->comb_words.size());
-      db->comb_words.insert(db->comb_words.end(), cp.ops.begin(), cp.ops.end());
-      c.prog_off = static_cast<uint32_t>(db->comb_words.size());
-      c.prog_len = static_cast<uint32_t>(cp.prog.size());
-      db->comb_words.insert(db->comb_words.end(), cp.prog.begin(), cp.prog.end());
-      for (uint32_t id : cp.ops) feed.emplace_back(id, static_cast<uint32_t>(db->combs.size()));
-      db->combs.push_back(c);
-    }
-    std::sort(feed.begin(), feed.end());
-    for (auto &f : feed) db->comb_feed.push_back(f.first);
-    for (auto &f : feed) db->comb_feed.push_back(f.second);
-  }
-
-  // Tiers.  A pattern whose required literals all have at least `min_factor` bytes is found through the window prefilter
-  // (tier 0), the others run on every line (tier 1).  Dword-aligned windows need HG_FAST_MIN_FACTOR bytes (a window on
-  // every residue mod 4).  When that leaves patterns with shorter literals behind, the stream pass probes a window at
-  // every BYTE offset instead (db.dense: four times the probes, a third of the streaming rate — still several times the
-  // always-on tier), which takes literals down to HG_DENSE_MIN_FACTOR bytes.
-  auto assign = [&](uint32_t min_factor, uint32_t dense, uint32_t window_bytes) -> int {
-    db->dense = dense;
-    db->window_bytes = window_bytes;
-    db->window_mask = window_bytes == 4 ? 0xFFFFFFFFu : 0x00FFFFFFu;
-    db->weights_c = HG_HASH_WEIGHTS & db->window_mask;
-    db->slow.clear();
-    db->factors.clear();
-    db->fold_mask = 0;
-    size_t nlits = 0, ncaseless = 0;  // required literals of the anchored expressions / those with case-insensitive letters
-    for (uint32_t m = 0; m < HG_CONFIRM_MODES; m++) db->n_confirm_mode[m] = 0;
-    for (unsigned i = 0; i < n; i++) {
-      HgPattern &p = db->patterns[i];
-      if (p.tier == HG_TIER_COMB) continue;  // (no automaton: the combination pass evaluates it)
-      const LitSet &cover = covers[i].lits;
-      const bool fast = !cover.empty() && min_len(cover) >= min_factor;
-      p.tier = fast ? 0 : 1;
-      p.literal_only = (fast && covers[i].literal_only) ? 1 : 0;
-      if (fast) {
-        db->n_confirm_mode[hg_confirm_mode(p)]++;
-        for (auto &l : cover) {
-          nlits++;
-          bool caseless = false;
-          for (unsigned char m : l.cmask) caseless = caseless || m != 0xFF;
-          ncaseless += caseless ? 1 : 0;
-        }
-      } else {
-        db->slow.push_back(i);
-      }
-    }
-    // Case-insensitive literals.  The general way: the stream pass folds every text dword (| 0x20202020) before it hashes it, and the
-    // windows are stored folded.  Where only a few literals of a set of dword-aligned windows are case-insensitive, their windows are
-    // stored in every case variant instead (at most 16 per window) and NOTHING is folded: the hot loop saves an instruction per
-    // dword, and folded look-alikes ('@' / '`', '[' / '{', upper-case text) no longer pass the filter.
-    if (ncaseless) {
-      const bool expand = !dense && !knobs.no_case_expand && ncaseless <= 64;  // (at most 64 x 4 windows x 16 variants more)
-      (void)nlits;
-      db->fold_mask = expand ? 0u : 0x20202020u;
-    }
-    // always-on patterns of at most two state words go first: the segment-parallel kernel takes those
-    auto two_words = [&](uint32_t pi) { return db->patterns[pi].nw <= 2; };  // bounded or not: an unbounded pattern's lead-in is the start of its line
-    auto not_huge = [&](uint32_t pi) { return db->patterns[pi].nw <= HG_MAX_W; };  // huge automata go last: their own kernel
-    std::stable_partition(db->slow.begin(), db->slow.end(), not_huge);
-    std::stable_partition(db->slow.begin(), db->slow.end(), two_words);
-    db->nslow_fast = static_cast<uint32_t>(std::count_if(db->slow.begin(), db->slow.end(), two_words));
-    db->nslow_huge = static_cast<uint32_t>(db->slow.size() - std::count_if(db->slow.begin(), db->slow.end(), not_huge));
-    build_slow_groups(*db, knobs);
-    // factors (needs the final fold mask); windows and filter tables are built from them
-    uint32_t rank_in_mode[HG_CONFIRM_MODES] = {};
-    for (unsigned i = 0; i < n; i++) {
-      if (db->patterns[i].tier != 0) continue;
-      const uint32_t mode = hg_confirm_mode(db->patterns[i]), rank = rank_in_mode[mode]++;
-      for (auto &l : covers[i].lits) {
-        HgFactor fct{};
-        fct.pattern = i;
-        fct.len = static_cast<uint32_t>(l.bytes.size());
-        fct.mode = mode;
-        fct.mode_rank = rank;
-        std::memcpy(fct.lit, l.bytes.data(), fct.len);
-        for (uint32_t b = 0; b < fct.len; b++)
-          if (static_cast<unsigned char>(l.cmask[b]) != 0xFF) fct.casebits |= 1u << b;
-        fct.id = db->patterns[i].id;
-        db->factors.push_back(fct);
-      }
-    }
-    db->nreal_factors = static_cast<uint32_t>(db->factors.size());
-    if (db->factors.empty()) db->factors.push_back(HgFactor{});  // keep device arrays non-empty
-    return build_filter(*db, nullptr, err);
-  };
-  size_t shortest = SIZE_MAX;  // shortest required literal among the patterns dword-aligned windows leave behind
-  for (unsigned i = 0; i < n; i++) {
-    const size_t m = covers[i].lits.empty() ? 0 : min_len(covers[i].lits);
-    if (m >= HG_DENSE_MIN_FACTOR && m < HG_FAST_MIN_FACTOR) shortest = std::min(shortest, m);
-  }
-  int rc = -5;
-  if (shortest != SIZE_MAX && !knobs.no_byte_windows) {
-    // every literal of the set has at least 5 bytes: a window on both residues mod 2 fits, half the probes
-    size_t set_shortest = SIZE_MAX;
-    for (unsigned i = 0; i < n; i++)
-      if (!covers[i].lits.empty() && min_len(covers[i].lits) >= shortest) set_shortest = std::min(set_shortest, min_len(covers[i].lits));
-    const uint32_t step = set_shortest >= HG_WINDOW_BYTES + 1 ? 2u : 1u;
-    rc = assign(static_cast<uint32_t>(shortest), step, HG_WINDOW_BYTES);
-    if (rc == -5 && step == 2) rc = assign(static_cast<uint32_t>(shortest), 1, HG_WINDOW_BYTES);  // (one window per literal instead of two)
-    // too many 3-byte literals to enumerate the byte after each: every window shrinks to 3 bytes instead
-    if (rc == -5 && shortest < HG_WINDOW_BYTES) rc = assign(static_cast<uint32_t>(shortest), 1, HG_WINDOW_BYTES - 1);
-    if (rc == -5 && shortest < HG_WINDOW_BYTES) rc = assign(HG_WINDOW_BYTES, 1, HG_WINDOW_BYTES);  // without the short literals
-  }
-  if (rc == -5) rc = assign(HG_FAST_MIN_FACTOR, 0, HG_WINDOW_BYTES);
-  if (rc != 0) {
-    if (bad_index) *bad_index = -1;
-    return -4;
   }
   *out = db.release();
   return 0;

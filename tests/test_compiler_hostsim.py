@@ -45,6 +45,34 @@ def test_flag_and_anchor_rules():
     assert hgsim_py.Db(["a^b"]).ok()
 
 
+SOM = 256
+REJECTION_RULES = [
+    # (patterns, flags, ids, index, message fragment); the combination rules are pinned in test_comb_host.py
+    (["foo", "abc"], [0, 16], None, 1, "unsupported flag bits"),
+    (["foo", "abc"], [0, 2048], None, 1, "unsupported flag bits"),
+    (["foo", ""], None, None, 1, "empty expression"),
+    (["foo", "a^b"], [0, 10], None, 1, "embedded start anchors"),
+    (["foo", "a$b"], [0, 10], None, 1, "embedded end anchors"),
+    (["foo", "a*"], None, None, 1, "HS_FLAG_ALLOWEMPTY"),
+    (["foo", r"\b\B"], None, None, 1, "matches nothing"),
+    (["foo", "(a{1000}){1000}"], None, None, 1, "pattern too large"),
+    (["foo", "abc"], [0, SOM | 8], None, 1, "cannot be combined with HS_FLAG_SINGLEMATCH"),
+    (["foo", "foo.{0,3000}bar"], [0, SOM | 6], None, 1, "at most 1024 nodes (HG_MAX_NODES)"),
+    # SOM and plain expressions sharing a report id: the error names the larger of the first plain one and the latest SOM one
+    (["foo", "bar"], [SOM, 0], [5, 5], 1, "report id 5 must all carry HS_FLAG_SOM_LEFTMOST"),
+    (["foo", "bar"], [0, SOM], [5, 5], 1, "report id 5 must all carry HS_FLAG_SOM_LEFTMOST"),
+    (["foo", "bar", "baz"], [SOM, 0, SOM], [5, 5, 5], 2, "report id 5 must all carry HS_FLAG_SOM_LEFTMOST"),
+    (["foo", "bar", "baz"], [0, SOM, 0], [5, 5, 5], 1, "report id 5 must all carry HS_FLAG_SOM_LEFTMOST"),
+]
+
+
+@pytest.mark.parametrize("patterns,flags,ids,index,fragment", REJECTION_RULES)
+def test_rejection_names_expression_and_rule(patterns, flags, ids, index, fragment):
+    db = hgsim_py.Db(patterns, flags, ids)
+    assert not db.ok()
+    assert db.error.startswith(f"{index}: ") and fragment in db.error, db.error
+
+
 def test_tiers_and_factors():
     long_ones = ["needle_in_haystack", "user=[a-z0-9_]{4,12} status=5[0-9]{2}", "[a-z]+@[a-z]+",
                  "(alpha_long_one|beta_long_two)x", "(?i)CaseLessLiteral"]

@@ -2,11 +2,17 @@
 
 from hypergrep_amd.utils import (  # the reference package re-exports exactly these names
     CALLBACK_TYPE,
+    HS_EXT_FLAG_EDIT_DISTANCE,
+    HS_EXT_FLAG_HAMMING_DISTANCE,
+    HS_EXT_FLAG_MAX_OFFSET,
+    HS_EXT_FLAG_MIN_LENGTH,
+    HS_EXT_FLAG_MIN_OFFSET,
     HS_FLAG_CASELESS,
     HS_FLAG_DOTALL,
     HS_FLAG_MULTILINE,
     HS_FLAG_SINGLEMATCH,
     RC_INVALID_FILE,
+    ExprExt,
     Result,
     check_compatibility,
     configure_libraries,
@@ -18,5 +24,8 @@ from hypergrep_amd.utils import (  # the reference package re-exports exactly th
 __all__ = [
     "CALLBACK_TYPE", "HS_FLAG_CASELESS", "HS_FLAG_DOTALL", "HS_FLAG_MULTILINE", "HS_FLAG_SINGLEMATCH", "RC_INVALID_FILE", "Result",
     "check_compatibility", "configure_libraries", "grep", "prepare_patterns", "scan",
+    # extended parameters (approximate matching), beyond the reference's names
+    "ExprExt", "HS_EXT_FLAG_MIN_OFFSET", "HS_EXT_FLAG_MAX_OFFSET", "HS_EXT_FLAG_MIN_LENGTH", "HS_EXT_FLAG_EDIT_DISTANCE",
+    "HS_EXT_FLAG_HAMMING_DISTANCE",
 ]
 __version__ = "0.1.0"

@@ -32,12 +32,17 @@ extern "C" {
 
 int hg_db_compile(const char *const *expressions, const unsigned int *flags, const unsigned int *ids, unsigned int n,
                   hg_database_t **db, char *err, size_t errlen) {
+  return hg_db_compile_ext(expressions, flags, ids, nullptr, n, db, err, errlen);
+}
+
+int hg_db_compile_ext(const char *const *expressions, const unsigned int *flags, const unsigned int *ids, const hs_expr_ext_t *const *ext,
+                      unsigned int n, hg_database_t **db, char *err, size_t errlen) {
   if (!db) return HG_ERR_ARG;
   *db = nullptr;
   HgDb *d = nullptr;
   std::string msg;
   int bad = -1;
-  int rc = hgc_compile(expressions, flags, ids, n, &d, &msg, &bad);
+  int rc = hgc_compile_ext(expressions, flags, ids, ext, n, &d, &msg, &bad);
   if (rc != 0) {
     put_err(err, errlen, std::to_string(bad) + ": " + msg);
     return rc == -2 ? HG_ERR_NOMEM : (rc == -1 ? HG_ERR_ARG : HG_ERR_COMPILE);

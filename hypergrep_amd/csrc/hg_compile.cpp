@@ -1601,15 +1601,9 @@ struct Automaton {
   }
 };
 
-Automaton build_automaton(const std::string &text, uint32_t flags) {
-  Automaton a;
-  a.root = Parser(text, flags).parse();
-  check_embedded_anchors(*a.root, false, false);
-  if (program_size(*a.root) > HG_HUGE_MAX_PROGRAM) throw CompileError("pattern too large");
-  Frag top = a.g.build(*a.root);
-  if (top.nullable) throw CompileError("expression can match the empty string (HS_FLAG_ALLOWEMPTY is not supported)");
-  if (a.g.pos_class.empty()) throw CompileError("expression matches nothing");
-
+// Nodes of a Glushkov structure (a.g) with the given first / last sets: merges the edges, numbers the nodes, and gives each
+// position its accept conditions.
+void index_nodes(Automaton &a, std::vector<Cond> first, const std::vector<Cond> &last) {
   // one edge per (p, q): the ways of getting from p to q (through different assertions) merge into one condition
   std::vector<Edge> &edges = a.g.edges;
   std::sort(edges.begin(), edges.end(), [](const Edge &x, const Edge &y) { return x.p != y.p ? x.p < y.p : x.q < y.q; });
@@ -1619,8 +1613,8 @@ Automaton build_automaton(const std::string &text, uint32_t flags) {
     else edges[ne++] = edges[i];
   }
   edges.resize(ne);
-  a.nodes.reserve(top.first.size() + edges.size());
-  for (auto &c : top.first) a.nodes.push_back({c.pos, c.tt});
+  a.nodes.reserve(first.size() + edges.size());
+  for (auto &c : first) a.nodes.push_back({c.pos, c.tt});
   for (auto &e : edges) a.nodes.push_back({e.q, e.tt});
   std::sort(a.nodes.begin(), a.nodes.end());
   a.nodes.erase(std::unique(a.nodes.begin(), a.nodes.end()), a.nodes.end());
@@ -1630,13 +1624,214 @@ Automaton build_automaton(const std::string &text, uint32_t flags) {
   for (auto &nd : a.nodes) a.node_lo[nd.first + 1]++;
   for (uint32_t q = 0; q < npos; q++) a.node_lo[q + 1] += a.node_lo[q];
   a.last_tt.assign(npos, 0);
-  for (auto &l : top.last) a.last_tt[l.pos] |= l.tt;
-  a.first = std::move(top.first);
+  for (auto &l : last) a.last_tt[l.pos] |= l.tt;
+  a.first = std::move(first);
   // (an expression whose every entry condition is contradictory, e.g. \b\Bc, has no nodes: it keeps one all-zero state
   // word so that every routine sees well-formed tables and simply never matches)
   a.nn = static_cast<uint32_t>(a.nodes.size());
   a.nw = a.nn ? (a.nn + 31) / 32 : 1;
+}
+
+Automaton build_automaton(const std::string &text, uint32_t flags) {
+  Automaton a;
+  a.root = Parser(text, flags).parse();
+  check_embedded_anchors(*a.root, false, false);
+  if (program_size(*a.root) > HG_HUGE_MAX_PROGRAM) throw CompileError("pattern too large");
+  Frag top = a.g.build(*a.root);
+  if (top.nullable) throw CompileError("expression can match the empty string (HS_FLAG_ALLOWEMPTY is not supported)");
+  if (a.g.pos_class.empty()) throw CompileError("expression matches nothing");
+  index_nodes(a, std::move(top.first), top.last);
   return a;
+}
+
+// ---- extended parameters (hs_expr_ext_t): approximate matching -------------------------------------------------------
+constexpr uint64_t HG_EXT_FLAGS_KNOWN = HS_EXT_FLAG_MIN_OFFSET | HS_EXT_FLAG_MAX_OFFSET | HS_EXT_FLAG_MIN_LENGTH | HS_EXT_FLAG_EDIT_DISTANCE |
+                                        HS_EXT_FLAG_HAMMING_DISTANCE;
+constexpr uint32_t HG_EXT_MAX_DISTANCE = 16;
+
+// Shortest string the expression can match (saturates at 2^20).
+long min_match_len(const Node &n) {
+  const long kCap = 1 << 20;
+  switch (n.kind) {
+    case Node::Empty:
+    case Node::Assert: return 0;
+    case Node::Class: return 1;
+    case Node::Cat: {
+      long t = 0;
+      for (auto &k : n.kids) t = std::min(kCap, t + min_match_len(*k));
+      return t;
+    }
+    case Node::Alt: {
+      long t = kCap;
+      for (auto &k : n.kids) t = std::min(t, min_match_len(*k));
+      return t;
+    }
+    case Node::Rep: return n.kids.empty() ? 0 : std::min<long>(kCap, static_cast<long>(n.min) * min_match_len(*n.kids[0]));
+  }
+  return 0;
+}
+
+// The rules that need no automaton.
+void check_ext_fields(const hs_expr_ext_t &x, uint32_t f) {
+  if (x.flags & ~HG_EXT_FLAGS_KNOWN) throw CompileError("unknown HS_EXT_FLAG bits in the extended parameters");
+  if (f & HG_FLAG_COMBINATION) throw CompileError("extended parameters are not allowed on an HS_FLAG_COMBINATION expression");
+  const bool edit = x.flags & HS_EXT_FLAG_EDIT_DISTANCE, ham = x.flags & HS_EXT_FLAG_HAMMING_DISTANCE;
+  if (edit && ham) throw CompileError("edit_distance and hamming_distance cannot both be set");
+  const bool lo = x.flags & HS_EXT_FLAG_MIN_OFFSET, hi = x.flags & HS_EXT_FLAG_MAX_OFFSET, ml = x.flags & HS_EXT_FLAG_MIN_LENGTH;
+  if (lo && hi && x.min_offset > x.max_offset) throw CompileError("min_offset is larger than max_offset");
+  if (ml && hi && x.min_length > x.max_offset) throw CompileError("min_length is larger than max_offset");
+  const uint32_t k = edit ? x.edit_distance : (ham ? x.hamming_distance : 0u);
+  if (k > HG_EXT_MAX_DISTANCE)
+    throw CompileError(std::string(edit ? "edit_distance" : "hamming_distance") + " above " + std::to_string(HG_EXT_MAX_DISTANCE) + " is not supported");
+}
+
+// The rules that need the expression's minimum width; `width` bounds from below the length of every match, and so `to`.
+// Returns the shortest match length.
+long check_ext_width(const hs_expr_ext_t &x, uint32_t k, bool edit, long width) {
+  if (k && static_cast<long>(k) >= width)
+    throw CompileError(std::string(edit ? "edit_distance" : "hamming_distance") + " " + std::to_string(k) +
+                       " is not smaller than the expression's minimum match width " + std::to_string(width) + " (the expression would match anything)");
+  const long least = width - (edit ? static_cast<long>(k) : 0);  // the shortest match
+  if ((x.flags & HS_EXT_FLAG_MIN_LENGTH) && x.min_length > static_cast<unsigned long long>(least))
+    throw CompileError("min_length " + std::to_string(x.min_length) + " could remove reports (it is supported up to the shortest match length, " +
+                       std::to_string(least) + " here): start-of-match filtering is not implemented");
+  return least;
+}
+
+// The offset bounds {lo, hi} of an expression whose shortest match has `least` bytes: a min_offset of at most `least`
+// removes nothing (every `to` is at least that) and is dropped.  hi = HG_BOUND_NONE: no upper bound (a raw report's `to` is
+// below 2^31, HG_HIT_SINGLE_BIT), so {0, HG_BOUND_NONE} is no bound at all.
+std::pair<uint32_t, uint32_t> ext_bounds(const hs_expr_ext_t &x, long least) {
+  uint32_t lo = 0, hi = HG_BOUND_NONE;
+  if ((x.flags & HS_EXT_FLAG_MIN_OFFSET) && x.min_offset > static_cast<unsigned long long>(least))
+    lo = static_cast<uint32_t>(std::min<unsigned long long>(x.min_offset, 0xFFFFFFFFull));
+  if (x.flags & HS_EXT_FLAG_MAX_OFFSET) hi = static_cast<uint32_t>(std::min<unsigned long long>(x.max_offset, HG_BOUND_NONE));
+  return {lo, hi};
+}
+
+// The error-level product of a position automaton: still a position automaton, so every table emitter and routine runs it
+// unchanged.  Per original position q and error level e <= k there is a match position M(q, e) (the class of q), and for
+// e >= 1 a substitute position S(q, e) (a byte `.` matches stands for q) and, with edit distance, an insert position
+// I(q, e) (an extra byte after q; I(npos, e) is one before the first position).  A deletion consumes nothing: the follow
+// sets skip up to k - e positions instead (to the level the skips cost), and so does the accept set (a position that is
+// d deletions from the end accepts at levels up to k - d).  Hamming distance has match and substitute positions only, and
+// no skips.  Positions are numbered level by level, the match positions of a level in the original order: each level's
+// exact chain stays v -> v + 1 (the sparse tables' shift edges).  A leading ^ / \A is the entry condition of whatever the
+// start enters, a trailing $ / \z / \Z the accept condition of every accepting position; other assertions are rejected.
+Automaton expand_approx(Automaton &a, uint32_t k, bool edit, uint32_t flags) {
+  const uint32_t npos = static_cast<uint32_t>(a.g.pos_class.size());
+  const char *anchors = "approximate matching supports no assertion but a leading ^ or \\A and a trailing $, \\z or \\Z";
+  uint32_t t0 = 0, tl = 0;  // the entry condition of the start's targets, the accept condition
+  for (auto &e : a.g.edges)
+    if (e.tt != HG_TT_ALL) throw CompileError(anchors);
+  for (auto &c : a.first) {
+    if (t0 && c.tt != t0) throw CompileError(anchors);
+    t0 = c.tt;
+  }
+  for (uint32_t q = 0; q < npos; q++) {
+    if (!a.last_tt[q]) continue;
+    if (tl && a.last_tt[q] != tl) throw CompileError(anchors);
+    tl = a.last_tt[q];
+  }
+  if ((t0 != HG_TT_ALL && t0 != TT_BOL && t0 != TT_BOL_ML) || (tl != HG_TT_ALL && tl != TT_EOL && tl != TT_EOL_ML && tl != TT_EOD))
+    throw CompileError(anchors);
+
+  // original follow relation (a.g.edges is sorted by (p, q)); the start is position npos
+  std::vector<uint32_t> adj_lo(npos + 2, 0), adj;
+  for (auto &e : a.g.edges) adj_lo[e.p + 1]++;
+  adj_lo[npos + 1] += static_cast<uint32_t>(a.first.size());
+  for (uint32_t p = 0; p <= npos; p++) adj_lo[p + 1] += adj_lo[p];
+  adj.resize(adj_lo[npos + 1]);
+  {
+    std::vector<uint32_t> fill(adj_lo.begin(), adj_lo.end() - 1);
+    for (auto &e : a.g.edges) adj[fill[e.p]++] = e.q;
+    for (auto &c : a.first) adj[fill[npos]++] = c.pos;
+  }
+  const uint32_t maxskip = edit ? k : 0;
+  // reach(p): (q, d) for every q that p's follow set holds after d skipped positions, with the least such d <= maxskip
+  std::vector<uint32_t> seen(npos, UINT32_MAX);
+  auto reach = [&](uint32_t p, std::vector<std::pair<uint32_t, uint32_t>> &out) {
+    out.clear();
+    std::vector<uint32_t> frontier{p}, next;
+    for (uint32_t d = 0; d <= maxskip && !frontier.empty(); d++) {
+      next.clear();
+      for (uint32_t r : frontier)
+        for (uint32_t j = adj_lo[r]; j < adj_lo[r + 1]; j++) {
+          const uint32_t q = adj[j];
+          if (seen[q] == p) continue;
+          seen[q] = p;
+          out.push_back({q, d});
+          next.push_back(q);
+        }
+      frontier.swap(next);
+    }
+  };
+  // to_last[p]: the fewest positions to skip from p to an accepting one (0: p accepts), more than maxskip: none
+  std::vector<uint32_t> to_last(npos, UINT32_MAX);
+  {
+    std::vector<std::vector<uint32_t>> pred(npos);
+    for (auto &e : a.g.edges) pred[e.q].push_back(e.p);
+    std::vector<uint32_t> frontier, next;
+    for (uint32_t q = 0; q < npos; q++)
+      if (a.last_tt[q]) to_last[q] = 0, frontier.push_back(q);
+    for (uint32_t d = 1; d <= maxskip && !frontier.empty(); d++) {
+      next.clear();
+      for (uint32_t q : frontier)
+        for (uint32_t r : pred[q])
+          if (to_last[r] == UINT32_MAX) to_last[r] = d, next.push_back(r);
+      frontier.swap(next);
+    }
+  }
+
+  const uint64_t stride = edit ? 3ull * npos + 1 : 2ull * npos;  // positions of a level above 0
+  if (npos + k * stride > HG_HUGE_MAX_NODES) throw CompileError("pattern too large");
+  auto M = [&](uint32_t q, uint32_t e) { return static_cast<uint32_t>(e ? npos + (e - 1) * stride + q : q); };
+  auto S = [&](uint32_t q, uint32_t e) { return static_cast<uint32_t>(npos + (e - 1) * stride + npos + q); };
+  auto I = [&](uint32_t q, uint32_t e) { return static_cast<uint32_t>(npos + (e - 1) * stride + 2 * npos + q); };  // q == npos: the start
+
+  Automaton b;
+  b.root = std::move(a.root);
+  ByteSet any;
+  any.set();
+  if (!(flags & HG_FLAG_DOTALL)) any.reset('\n');
+  b.g.pos_class.resize(npos + k * stride, any);
+  for (uint32_t e = 0; e <= k; e++)
+    for (uint32_t q = 0; q < npos; q++) b.g.pos_class[M(q, e)] = a.g.pos_class[q];
+  // the targets of every position that stands at original position p (or the start) with e errors
+  std::vector<Cond> first, last;
+  std::vector<std::pair<uint32_t, uint32_t>> r;
+  std::vector<uint32_t> targets;
+  for (uint32_t p = 0; p <= npos; p++) {
+    reach(p, r);
+    for (uint32_t e = 0; e <= k; e++) {
+      targets.clear();
+      for (auto &qd : r) {
+        const uint32_t level = e + qd.second;
+        if (level <= k) targets.push_back(M(qd.first, level));
+        if (level + 1 <= k) targets.push_back(S(qd.first, level + 1));
+      }
+      if (edit && e + 1 <= k) targets.push_back(I(p, e + 1));
+      std::vector<uint32_t> sources;
+      if (p == npos) {
+        if (e == 0) {
+          for (uint32_t t : targets) first.push_back({t, t0});
+          continue;
+        }
+        if (edit) sources.push_back(I(npos, e));
+      } else {
+        sources.push_back(M(p, e));
+        if (e) sources.push_back(S(p, e));
+        if (e && edit) sources.push_back(I(p, e));
+        if (to_last[p] != UINT32_MAX && e + to_last[p] <= k)
+          for (uint32_t v : sources) last.push_back({v, tl});
+      }
+      if (b.g.edges.size() + sources.size() * targets.size() > HG_HUGE_MAX_EDGES) throw CompileError("pattern too large");
+      for (uint32_t v : sources)
+        for (uint32_t t : targets) b.g.edges.push_back({v, t, HG_TT_ALL});
+    }
+  }
+  index_nodes(b, std::move(first), last);
+  return b;
 }
 
 // Node v's bits in the entry condition masks (4 x 4: previous byte class, class of the byte that enters it) and the accept
@@ -1816,6 +2011,27 @@ Cover literal_cover(const Node &root, HgPattern &p) {
       if (lb[j] == 0 || (lb[j] == '\n' && j + 1 < lb.size())) clean = false;
     cover.literal_only = clean;
   }
+  return cover;
+}
+
+// Pigeonhole cover of an approximate expression: every match with k errors contains one of the k + 1 contiguous pieces of
+// one of the exact expression's cover literals unchanged (an edit breaks at most one piece).  No cover (the expression runs
+// always-on) when a piece is shorter than HG_DENSE_MIN_FACTOR bytes or there are too many pieces.
+Cover approx_cover(const Node &root, uint32_t k, HgPattern &p) {
+  p.lit_lead = 0xFFFFFFFFu;  // (a piece can begin anywhere in the match)
+  const Info info = analyze(root);
+  Cover cover;
+  if (!info.has_cover) return cover;
+  for (auto &l : info.cover) {
+    const size_t len = l.bytes.size();
+    for (size_t j = 0; j <= k; j++) {
+      const size_t lo = len * j / (k + 1), hi = len * (j + 1) / (k + 1);
+      if (hi - lo < HG_DENSE_MIN_FACTOR) return Cover{};
+      cover.lits.push_back(clip(Lit{l.bytes.substr(lo, hi - lo), l.cmask.substr(lo, hi - lo)}));
+    }
+  }
+  dedupe(cover.lits);
+  if (cover.lits.size() > MAX_EXACT) return Cover{};
   return cover;
 }
 
@@ -2019,6 +2235,11 @@ void choose_windows(HgDb &db, const std::vector<Cover> &covers, const CompileKno
 
 int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned *ids, unsigned n, HgDb **out,
                std::string *err, int *bad_index) {
+  return hgc_compile_ext(exprs, flags, ids, nullptr, n, out, err, bad_index);
+}
+
+int hgc_compile_ext(const char *const *exprs, const unsigned *flags, const unsigned *ids, const hs_expr_ext_t *const *ext, unsigned n,
+                    HgDb **out, std::string *err, int *bad_index) {
   if (bad_index) *bad_index = -1;
   if (out) *out = nullptr;
   if (!exprs || !out || n == 0) {
@@ -2032,9 +2253,12 @@ int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned 
     if (n > HG_MAX_PATTERNS) throw CompileError("too many expressions (limit 16777216)", -1);
     std::vector<Cover> covers(n);
     std::map<uint32_t, CombProgram> programs;  // expression index -> its program (combinations)
+    std::map<uint32_t, std::pair<uint32_t, uint32_t>> bounds;  // expression index -> its offset bounds (those that have any)
     for (at = 0; at < static_cast<int>(n); at++) {
       const uint32_t f = flags ? flags[at] : 0, id = ids ? ids[at] : 0;
       if (f & ~HG_FLAGS_SUPPORTED) throw CompileError("unsupported flag bits");
+      const hs_expr_ext_t *x = (ext && ext[at] && ext[at]->flags) ? ext[at] : nullptr;
+      if (x) check_ext_fields(*x, f);
       if (f & HG_FLAG_COMBINATION) {
         db->patterns.push_back(compile_combination(*db, exprs[at], f, id, programs[at]));
         db->max_id = std::max(db->max_id, id);
@@ -2044,25 +2268,40 @@ int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned 
         throw CompileError("HS_FLAG_SOM_LEFTMOST cannot be combined with HS_FLAG_SINGLEMATCH");
       if (!exprs[at] || !exprs[at][0]) throw CompileError("empty expression");
       db->exprs.push_back(exprs[at]);
-      const Automaton a = build_automaton(db->exprs.back(), f);
+      Automaton a = build_automaton(db->exprs.back(), f);
+      const bool edit = x && (x->flags & HS_EXT_FLAG_EDIT_DISTANCE);
+      const uint32_t k = !x ? 0u : edit ? x->edit_distance : ((x->flags & HS_EXT_FLAG_HAMMING_DISTANCE) ? x->hamming_distance : 0u);
+      std::pair<uint32_t, uint32_t> bound{0u, HG_BOUND_NONE};
+      if (x) bound = ext_bounds(*x, check_ext_width(*x, k, edit, min_match_len(*a.root)));
+      if (bound.first || bound.second != HG_BOUND_NONE) bounds[at] = bound;
+      if (k) a = expand_approx(a, k, edit, f);
       HgPattern p{};
       p.id = id;
       p.flags = f;
       p.nnodes = a.nn;
       p.nw = a.nw;
-      p.single = (f & HG_FLAG_SINGLEMATCH) ? 1 : 0;
+      // (a first end below min_offset must not stop the routines: every end is emitted, the report rules keep the smallest in bounds)
+      p.single = (f & HG_FLAG_SINGLEMATCH) && !bound.first ? 1 : 0;
       if (a.nw > HG_MAX_W) emit_huge_tables(*db, a, p);
       else emit_dense_tables(*db, a, p);
       set_simple_flags(*db, p);
-      covers[at] = literal_cover(*a.root, p);
+      covers[at] = k ? approx_cover(*a.root, k, p) : literal_cover(*a.root, p);
       const long ml = max_match_len(*a.root);
-      p.max_len = ml > 0 ? static_cast<uint32_t>(ml) : 0;
+      p.max_len = ml > 0 ? static_cast<uint32_t>(ml + (edit ? k : 0u)) : 0;  // (insertions lengthen a match by up to k)
       if (f & HG_FLAG_SOM_LEFTMOST) emit_som_follow(*db, p);
       if (f & HG_FLAG_QUIET) db->nquiet++;
       db->max_id = std::max(db->max_id, id);
       db->patterns.push_back(p);
     }
     at = -1;
+    if (!bounds.empty()) {
+      db->bounds.resize(2 * static_cast<size_t>(n));
+      for (uint32_t i = 0; i < n; i++) {
+        auto it = bounds.find(i);
+        db->bounds[2 * i] = it == bounds.end() ? 0u : it->second.first;
+        db->bounds[2 * i + 1] = it == bounds.end() ? HG_BOUND_NONE : it->second.second;
+      }
+    }
     link_som_ids(*db);
     link_combinations(*db, programs);
     choose_windows(*db, covers, knobs);

@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/hypergrep_amd.h"
 #include "hg_core.h"
 #include "hg_db.h"
 
@@ -57,6 +58,9 @@ struct HgDb {
   std::vector<uint32_t> comb_words;
   std::vector<uint32_t> comb_feed;
   bool comb_pass() const { return ncomb || nquiet; }
+  // Offset bounds (hs_expr_ext_t min_offset / max_offset): {lo, hi} per expression, lo <= to <= hi; empty unless some expression
+  // has a bound that can remove a report (HgDbView::bounds)
+  std::vector<uint32_t> bounds;
   uint32_t n_confirm_mode[HG_CONFIRM_MODES] = {};  // tier-0 patterns by confirm routine (hg_confirm_mode)
   std::vector<std::string> exprs;
   bool tuned = false;
@@ -71,4 +75,8 @@ int hgc_tune(const HgDb *db, const uint8_t *sample, size_t nbytes, HgDb **out, s
 
 int hgc_compile(const char *const *exprs, const unsigned *flags, const unsigned *ids, unsigned n, HgDb **out,
                std::string *err, int *bad_index);
+// The same with extended parameters (hs_expr_ext_t, include/hypergrep_amd.h): ext == NULL or ext[i] == NULL (or flags 0)
+// means none, and a set without any compiles to exactly what hgc_compile makes of it.
+int hgc_compile_ext(const char *const *exprs, const unsigned *flags, const unsigned *ids, const hs_expr_ext_t *const *ext, unsigned n,
+                    HgDb **out, std::string *err, int *bad_index);
 void hgc_free(HgDb *db);

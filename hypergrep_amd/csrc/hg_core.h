@@ -63,7 +63,13 @@ struct HgDbView {
   uint32_t nslow_huge;     // the LAST nslow_huge entries of `slow` are huge automata (hg_always_on_huge_kernel)
   uint32_t ngroups;
   const HgSlowGroup *groups;
+  // Offset bounds (hs_expr_ext_t min_offset / max_offset): {lo, hi} per expression, a report (id, to) exists only if lo <= to
+  // and to <= hi (HG_BOUND_NONE: no upper bound; a raw report's `to` is below 2^31).  nullptr when no expression of the
+  // database has bounds.
+  const uint32_t *bounds;
 };
+
+constexpr uint32_t HG_BOUND_NONE = 0x7FFFFFFFu;
 
 // 0x80 in every byte of x that is zero, exact (no borrow between bytes).
 HG_HD uint32_t hg_zero_bytes(uint32_t x) {

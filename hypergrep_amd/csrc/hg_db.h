@@ -96,7 +96,9 @@ static_assert(sizeof(HgHugeHeader) == 64, "HgHugeHeader layout");
 struct HgPattern {
   // the four words every confirm routine reads, in one 16-byte piece (the record is 80 bytes: no such piece straddles a cache line)
   uint32_t id;          // report id given by the caller
-  uint32_t single;      // HS_FLAG_SINGLEMATCH set
+  uint32_t single;      // HS_FLAG_SINGLEMATCH set and the routines may stop at the first end (emission-time suppression).  0 for
+                        // a SINGLEMATCH expression with a min_offset bound: its first end may lie below the bound, so every end is
+                        // emitted and the report rules (hg_report_single: the flag itself) keep the smallest that passes the bounds
   uint32_t max_len;     // longest possible match in bytes, 0 = unbounded (literal_only: the literal's length)
   uint32_t lit_lead;    // tier 0: every match contains one of the pattern's required literals starting at most this many bytes
                         // after the match's start (0xFFFFFFFF: no bound) — the confirm routines' window (hg_confirm_dev.h)
@@ -120,6 +122,9 @@ struct HgPattern {
   uint32_t reserved;
 };
 static_assert(sizeof(HgPattern) == 80, "HgPattern layout");
+// The report rule: of an (id) of a line piece only the smallest `to` is delivered.  (HgPattern::single can be 0 for such an
+// expression: offset bounds.)
+HG_HD bool hg_report_single(const HgPattern &p) { return (p.flags & HG_FLAG_SINGLEMATCH) != 0; }
 
 constexpr uint32_t HG_TIER_COMB = 2;
 

@@ -187,6 +187,8 @@ int HgScanner::init() {
   view_.nslow_huge = db.nslow_huge;
   view_.ngroups = static_cast<uint32_t>(db.groups.size());
   view_.groups = static_cast<const HgSlowGroup *>(d_groups_);
+  if (!db.bounds.empty()) HG_TRY(upload(&d_bounds_, db.bounds, "d_bounds_"), "upload offset bounds");
+  view_.bounds = static_cast<const uint32_t *>(d_bounds_);  // (nullptr: the database has no offset bounds)
   for (const HgPattern &p : db.patterns)
     if (p.flags & HG_FLAG_SOM_LEFTMOST) som_max_nw_ = std::max(som_max_nw_, p.nw);
   if (db.comb_pass()) {
@@ -221,7 +223,7 @@ HgScanner::~HgScanner() {
   void *ptrs[] = {d_patterns_, d_pool_, d_factors_, d_windows_, d_bucket_, d_filter_, d_ext_, d_slow_, d_sums_, d_bases_, d_block_base_,
                   d_agg_, d_cands_, d_hits_raw_, d_hits_out_, d_aux_raw_, d_aux_out_,
                   d_key_a_, d_key_b_, d_perm_a_, d_perm_b_, d_keep_, d_counters_, d_temp_, d_seg_count_, d_pflags_, d_deferred_, d_defer_count_, d_seg_count2_, d_cands2_, d_disc_, d_bucket2_, d_windows2_, d_groups_, d_acc_hits_, d_acc_aux_, d_huge_claim_, d_wtab_, d_from_, d_fin_fill_, d_fin_kept_, d_fin_big_,
-                  d_combs_, d_comb_words_, d_comb_feed_, d_comb_count_, d_comb_pos_, d_comb_hits_, d_comb_aux_, d_comb_temp_};
+                  d_combs_, d_comb_words_, d_comb_feed_, d_comb_count_, d_comb_pos_, d_comb_hits_, d_comb_aux_, d_comb_temp_, d_bounds_};
   for (void *p : ptrs) hgmem::dev_free(p, "scanner");
   hgmem::host_free(h_counters_, "h_counters_");
   for (auto &ev : ev_)
@@ -362,7 +364,8 @@ HgScanner::PassPlan HgScanner::plan_pass(const uint8_t *text, uint64_t nbytes, u
   // (sort key of a bucket: line start inside the bucket | id | to | single; the raw records carry that start in the top
   // 24 bits of the line number, so line numbers must stay below 2^40)
   p.bucketed = ntiles && p.fin_cap && p.fin_shift <= 64 - HG_HIT_REL_SHIFT && p.fin_shift + p.id_bits + p.to_bits + 1 <= 64 &&
-               bits_for(line_base + nbytes + 1) <= HG_HIT_REL_SHIFT && !fin_fallback_ && !knobs_.no_bucket_finalize;
+               bits_for(line_base + nbytes + 1) <= HG_HIT_REL_SHIFT && !fin_fallback_ && !knobs_.no_bucket_finalize &&
+               !view_.bounds;  // (offset bounds: the compact finalize, whose report rule reads the SINGLEMATCH flag itself)
 
   // Chunked pipeline (line mode, large buffers): the text is cut into tile-aligned chunks; the stream pass of chunk c+1
   // runs on the caller's stream while tile scan + verify + confirm of chunk c run on a side stream.  The stream pass

@@ -55,13 +55,19 @@ extern "C" {
 
 int hs_compile_multi(const char *const *expressions, const unsigned int *flags, const unsigned int *ids, unsigned int elements,
                      unsigned int mode, const hs_platform_info_t *platform, hs_database_t **db, hs_compile_error_t **error) {
+  return hs_compile_ext_multi(expressions, flags, ids, nullptr, elements, mode, platform, db, error);
+}
+
+int hs_compile_ext_multi(const char *const *expressions, const unsigned int *flags, const unsigned int *ids, const hs_expr_ext_t *const *ext,
+                         unsigned int elements, unsigned int mode, const hs_platform_info_t *platform, hs_database_t **db,
+                         hs_compile_error_t **error) {
   (void)platform;
   if (error) *error = nullptr;
   std::string msg;
   int bad = -1;
   HgDb *raw = nullptr;
   if (!db || !expressions || elements == 0 || mode != HS_MODE_BLOCK) msg = "invalid arguments (block mode, at least one expression)";
-  else if (hgc_compile(expressions, flags, ids, elements, &raw, &msg, &bad) == 0) {
+  else if (hgc_compile_ext(expressions, flags, ids, ext, elements, &raw, &msg, &bad) == 0) {
     *db = new hs_database{std::shared_ptr<HgDb>(raw, [](HgDb *d) { hgc_free(d); })};
     return HS_SUCCESS;
   }
@@ -140,7 +146,7 @@ int hs_scan(const hs_database_t *db, const char *data, unsigned int length, unsi
   static const bool small_path = !std::getenv("HG_NO_BLOCK_SMALL");
   // (databases with HS_FLAG_SOM_LEFTMOST expressions take the general path: its start-of-match pass fills `from`; so do databases
   // with combinations or QUIET expressions: its combination pass applies them)
-  if (length <= HG_BLOCK_SMALL_MAX && small_path && !db->db->nsom && !db->db->comb_pass()) {
+  if (length <= HG_BLOCK_SMALL_MAX && small_path && !db->db->nsom && !db->db->comb_pass() && db->db->bounds.empty()) {
     std::memcpy(scratch->h_text, data, length);
     std::memset(scratch->h_text + length, 0, (16 - (length & 15)) & 15);
     const uint32_t seq = ++scratch->seq ? scratch->seq : ++scratch->seq;  // (never 0)

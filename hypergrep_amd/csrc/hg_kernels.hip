@@ -1017,7 +1017,7 @@ __global__ void hg_fin_gather_kernel(const HgHit *hits, const HgHitAux *aux, con
 __global__ void hg_key_kernel(const HgHit *hits, const HgHitAux *aux, const HgPattern *patterns, uint32_t n, uint64_t *key, uint32_t *idx) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  key[i] = hg_sort_key(hits[i], patterns[aux[i].pattern].single);
+  key[i] = hg_sort_key(hits[i], hg_report_single(patterns[aux[i].pattern]));
   idx[i] = i;
 }
 __global__ void hg_line_key_kernel(const HgHit *hits, const uint32_t *perm, uint32_t n, uint64_t *key) {
@@ -1033,14 +1033,14 @@ __global__ void hg_key_packed_kernel(const HgHit *hits, const HgHitAux *aux, con
                                      uint64_t *key, uint32_t *idx) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  key[i] = hg_sort_key_packed(hits[i], patterns[aux[i].pattern].single, id_bits, to_bits);
+  key[i] = hg_sort_key_packed(hits[i], hg_report_single(patterns[aux[i].pattern]), id_bits, to_bits);
   idx[i] = i;
 }
 // SINGLEMATCH / duplicate rules on the sorted order, read through the permutation (no sorted copy of the records)
 __global__ void hg_keep_kernel(const HgHit *hits, const HgHitAux *aux, const uint32_t *perm, const HgPattern *patterns, uint32_t n, uint8_t *keep) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  keep[i] = hg_keep_hit_at([&](size_t j) { return hits[perm[j]]; }, [&](size_t j) { return patterns[aux[perm[j]].pattern].single != 0; }, i) ? 1 : 0;
+  keep[i] = hg_keep_hit_at([&](size_t j) { return hits[perm[j]]; }, [&](size_t j) { return hg_report_single(patterns[aux[perm[j]].pattern]); }, i) ? 1 : 0;
 }
 // pos = exclusive prefix sum of keep: the kept records go to their final places; the last thread leaves the count
 __global__ void hg_scatter_kernel(const HgHit *hits, const HgHitAux *aux, const uint32_t *perm, const uint8_t *keep, const uint32_t *pos, uint32_t n,

@@ -78,14 +78,14 @@ HG_HD bool hg_keep_hit_at(HitAt &&hit_at, SingleAt &&single_at, size_t i) {
 }
 HG_HD bool hg_keep_hit(const HgHit *hits, const HgHitAux *aux, const HgPattern *patterns, size_t i) {
   const HgHit &h = hits[i];
-  bool single = patterns[aux[i].pattern].single != 0;
+  bool single = hg_report_single(patterns[aux[i].pattern]);
   if (i > 0) {
     const HgHit &p = hits[i - 1];
     if (p.line_no == h.line_no && p.id == h.id && p.to == h.to) {
       // same report already present; the earlier one is kept unless it is a dropped single — a dropped single at
       // this `to` means an earlier single exists, and then this one (single) is dropped too; a non-single
       // duplicate is dropped because its twin (non-single, sorted first) was kept.
-      bool psingle = patterns[aux[i - 1].pattern].single != 0;
+      bool psingle = hg_report_single(patterns[aux[i - 1].pattern]);
       if (!single) return false;        // twin non-single kept
       if (!psingle) return false;       // non-single with same `to` kept: report delivered once
     }
@@ -94,7 +94,7 @@ HG_HD bool hg_keep_hit(const HgHit *hits, const HgHitAux *aux, const HgPattern *
   for (size_t j = i; j > 0; j--) {  // first single report of this (line, id)?
     const HgHit &p = hits[j - 1];
     if (p.line_no != h.line_no || p.id != h.id) break;
-    if (patterns[aux[j - 1].pattern].single) return false;
+    if (hg_report_single(patterns[aux[j - 1].pattern])) return false;
   }
   return true;
 }

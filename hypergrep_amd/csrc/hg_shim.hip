@@ -56,8 +56,11 @@ std::map<std::string, DbEntry> g_dbs;
 uint64_t g_stamp = 0;
 std::atomic<uint64_t> g_cache_hits{0}, g_cache_misses{0}, g_tunes{0};
 
-std::string db_key(const char *const *patterns, const unsigned *flags, const unsigned *ids, unsigned n) {
+// Extended parameters (hs_expr_ext_t) follow the expressions, one record per expression, only when some expression has any:
+// a set without them keeps the key it always had, and no key of a set with them can equal one without (it is longer).
+std::string db_key(const char *const *patterns, const unsigned *flags, const unsigned *ids, const hs_expr_ext_t *const *ext, unsigned n) {
   std::string k;
+  bool any_ext = false;
   for (unsigned i = 0; i < n; i++) {
     const char *p = patterns[i] ? patterns[i] : "";
     uint32_t len = static_cast<uint32_t>(std::strlen(p)), f = flags ? flags[i] : 0, id = ids ? ids[i] : 0;
@@ -65,19 +68,27 @@ std::string db_key(const char *const *patterns, const unsigned *flags, const uns
     k.append(reinterpret_cast<const char *>(&f), 4);
     k.append(reinterpret_cast<const char *>(&id), 4);
     k.append(p, len);
+    any_ext = any_ext || (ext && ext[i] && ext[i]->flags);
   }
+  if (any_ext)
+    for (unsigned i = 0; i < n; i++) {
+      hs_expr_ext_t x{};
+      if (ext[i] && ext[i]->flags) x = *ext[i];
+      const uint64_t words[6] = {x.flags, x.min_offset, x.max_offset, x.min_length, x.edit_distance, x.hamming_distance};
+      k.append(reinterpret_cast<const char *>(words), sizeof words);
+    }
   return k;
 }
 
-std::shared_ptr<const HgDb> get_db(const char *const *patterns, const unsigned *flags, const unsigned *ids, unsigned n, std::string *err,
-                                   std::string *key_out = nullptr) {
+std::shared_ptr<const HgDb> get_db(const char *const *patterns, const unsigned *flags, const unsigned *ids, const hs_expr_ext_t *const *ext, unsigned n,
+                                   std::string *err, std::string *key_out = nullptr) {
   if (!patterns || n == 0) {
     if (err) *err = "no patterns";
     return nullptr;
   }
   for (unsigned i = 0; i < n; i++)
     if (!patterns[i]) return nullptr;
-  std::string key = db_key(patterns, flags, ids, n);
+  std::string key = db_key(patterns, flags, ids, ext, n);
   if (key_out) *key_out = key;
   {
     std::lock_guard<std::mutex> lock(g_mu);
@@ -91,7 +102,7 @@ std::shared_ptr<const HgDb> get_db(const char *const *patterns, const unsigned *
   g_cache_misses++;
   HgDb *raw = nullptr;
   int bad = -1;
-  if (hgc_compile(patterns, flags, ids, n, &raw, err, &bad) != 0) return nullptr;
+  if (hgc_compile_ext(patterns, flags, ids, ext, n, &raw, err, &bad) != 0) return nullptr;
   std::shared_ptr<const HgDb> db(raw, [](const HgDb *d) { hgc_free(const_cast<HgDb *>(d)); });
   std::lock_guard<std::mutex> lock(g_mu);
   auto it = g_dbs.find(key);
@@ -548,22 +559,33 @@ size_t chunk_bytes() {
 
 }  // namespace
 
+extern "C" int hg_check_patterns_ext(const char *const *patterns, const unsigned int *pattern_flags, const unsigned int *pattern_ids,
+                                  const hs_expr_ext_t *const *ext, const unsigned int elements) {
+  std::string err;
+  return get_db(patterns, pattern_flags, pattern_ids, ext, elements, &err) ? 0 : HYPERSCANNER_DB;
+}
+
 extern "C" int check_patterns(const char *const *patterns, const unsigned int *pattern_flags, const unsigned int *pattern_ids,
                               const unsigned int elements) {
-  std::string err;
-  return get_db(patterns, pattern_flags, pattern_ids, elements, &err) ? 0 : HYPERSCANNER_DB;
+  return hg_check_patterns_ext(patterns, pattern_flags, pattern_ids, nullptr, elements);
 }
 
 extern "C" int hyperscan(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
                          const unsigned int *pattern_ids, const unsigned int elements, hs_event on_event, const int buffer_size,
                          int buffer_count, unsigned long long max_match_count) {
+  return hg_hyperscan_ext(file_name, patterns, pattern_flags, pattern_ids, nullptr, elements, on_event, buffer_size, buffer_count, max_match_count);
+}
+
+extern "C" int hg_hyperscan_ext(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                             const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hs_event on_event,
+                             const int buffer_size, int buffer_count, unsigned long long max_match_count) {
   if (max_match_count > 0 && max_match_count < static_cast<unsigned long long>(buffer_count)) buffer_count = static_cast<int>(max_match_count);
   if (buffer_count < 1 || buffer_size < 1 || !on_event) return HYPERSCANNER_STATE_MEM;
   Ring ring;
   if (!ring.init(buffer_count, buffer_size, on_event)) return HYPERSCANNER_COMPILE_MEM;
 
   std::string err, db_key_str;
-  std::shared_ptr<const HgDb> db = get_db(patterns, pattern_flags, pattern_ids, elements, &err, &db_key_str);
+  std::shared_ptr<const HgDb> db = get_db(patterns, pattern_flags, pattern_ids, ext, elements, &err, &db_key_str);
   if (!db) {
     std::fprintf(stderr, "ERROR: Unable to create database. Exiting.\n");
     return HYPERSCANNER_DB;

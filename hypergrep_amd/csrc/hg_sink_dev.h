@@ -21,6 +21,12 @@ struct HitSink {
   __device__ __forceinline__ void push(const HgConfirmArgs &a, uint64_t line_no, uint32_t id, uint32_t to, uint64_t start, uint32_t len, uint32_t pattern,
                                        bool single) const {
     if (start < a.own_lo || start >= a.own_hi) return;  // (segmented scans: the piece is another segment's to report)
+    if (a.db.bounds) {  // (uniform: a property of the database) offset bounds, before the report rules
+      // (a min_offset expression emits every end, HgPattern::single is 0: databases with bounds use the compact finalize,
+      // whose report rule reads the flag, hg_report_single)
+      const uint32_t lo = a.db.bounds[2 * pattern], hi = a.db.bounds[2 * pattern + 1];
+      if (to < lo || (to > hi && hi != HG_BOUND_NONE)) return;
+    }
     if (a.bucket_cap) {  // straight into the bucket of the line's start; the finalize kernels order each bucket
       const uint64_t rel_start = start - a.own_lo;
       const uint32_t b = static_cast<uint32_t>(rel_start >> a.bucket_shift);

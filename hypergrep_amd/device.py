@@ -57,6 +57,10 @@ def lib() -> ctypes.CDLL:
         l.hg_db_compile.restype = ctypes.c_int
         l.hg_db_compile.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
                                     ctypes.c_uint, ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p, ctypes.c_size_t]
+        l.hg_db_compile_ext.restype = ctypes.c_int
+        l.hg_db_compile_ext.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
+                                        ctypes.POINTER(ctypes.POINTER(utils.ExprExt)), ctypes.c_uint, ctypes.POINTER(ctypes.c_void_p),
+                                        ctypes.c_char_p, ctypes.c_size_t]
         l.hg_db_release.argtypes = [ctypes.c_void_p]
         l.hg_db_tune.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         l.hg_db_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgDbInfo)]
@@ -95,11 +99,16 @@ class DeviceError(RuntimeError):
 class Database:
     """Compiled pattern set (host side)."""
 
-    def __init__(self, patterns, flags=None, ids=None):
+    def __init__(self, patterns, flags=None, ids=None, ext=None):
+        """ext: one utils.ExprExt (extended parameters: approximate matching) or None per pattern."""
         pa, fa, ia = utils.prepare_patterns(list(patterns), flags=list(flags or ()), ids=list(ids or ()))
         self._h = ctypes.c_void_p()
         err = ctypes.create_string_buffer(512)
-        rc = lib().hg_db_compile(pa, fa, ia, len(pa), ctypes.byref(self._h), err, 512)
+        if ext is None:
+            rc = lib().hg_db_compile(pa, fa, ia, len(pa), ctypes.byref(self._h), err, 512)
+        else:
+            ea = utils.ext_array(ext, len(pa))
+            rc = lib().hg_db_compile_ext(pa, fa, ia, ea, len(pa), ctypes.byref(self._h), err, 512)
         if rc != 0:
             raise CompileError(err.value.decode(errors="replace"))
 

@@ -43,6 +43,35 @@ class Result(ctypes.Structure):
     _fields_ = [("id", ctypes.c_uint), ("line_number", ctypes.c_ulonglong), ("line", ctypes.c_char_p)]
 
 
+class ExprExt(ctypes.Structure):
+    """Extended parameters of one expression: Hyperscan's hs_expr_ext_t (include/hypergrep_amd.h has the contract).  Set the
+    fields you use and their HS_EXT_FLAG_* bits in `flags`, e.g. ExprExt(flags=HS_EXT_FLAG_EDIT_DISTANCE, edit_distance=1)."""
+
+    _fields_ = [("flags", ctypes.c_ulonglong), ("min_offset", ctypes.c_ulonglong), ("max_offset", ctypes.c_ulonglong),
+                ("min_length", ctypes.c_ulonglong), ("edit_distance", ctypes.c_uint), ("hamming_distance", ctypes.c_uint)]
+
+
+HS_EXT_FLAG_MIN_OFFSET, HS_EXT_FLAG_MAX_OFFSET, HS_EXT_FLAG_MIN_LENGTH = 1, 2, 4
+HS_EXT_FLAG_EDIT_DISTANCE, HS_EXT_FLAG_HAMMING_DISTANCE = 8, 16
+
+
+def ext_array(ext, count: int):
+    """One ExprExt or None per pattern -> a C array of hs_expr_ext_t pointers (NULL for None).  ValueError if the count is
+    not one per pattern."""
+    entries = list(ext)
+    if len(entries) != count:
+        raise ValueError(f"Found {len(entries)} ext entries, expecting {count}: one ExprExt or None per pattern.")
+    for entry in entries:
+        if entry is not None and not isinstance(entry, ExprExt):
+            raise TypeError(f"ext entries must be ExprExt or None, not {type(entry).__name__}")
+    return (ctypes.POINTER(ExprExt) * count)(*[ctypes.pointer(e) if e is not None else None for e in entries])
+
+
+def _bind_ext(engine: ctypes.CDLL) -> None:
+    engine.hg_check_patterns_ext.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
+                                          ctypes.POINTER(ctypes.POINTER(ExprExt)), ctypes.c_uint]
+
+
 # void on_event(Result *batch, int count)  (hyperscanner.c:54)
 CALLBACK_TYPE = ctypes.CFUNCTYPE(None, ctypes.POINTER(Result), ctypes.c_int, use_errno=False, use_last_error=False)
 
@@ -116,11 +145,16 @@ def prepare_patterns(patterns: list[str], flags: list[int] = (), ids: list[int] 
     )
 
 
-def check_compatibility(patterns: list, flags: list[int] = (), ids: list[int] = ()) -> int:
+def check_compatibility(patterns: list, flags: list[int] = (), ids: list[int] = (), ext=None) -> int:
     """Compile the patterns without scanning anything: 0 if the engine accepts them all, else 4.  `ids` (default all 0)
-    matter for sets with HS_FLAG_COMBINATION, whose formulas name report ids."""
+    matter for sets with HS_FLAG_COMBINATION, whose formulas name report ids.  `ext`: one ExprExt or None per pattern."""
     c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags, ids=ids)
-    return _get_hyperscanner_lib().check_patterns(c_patterns, c_flags, c_ids, len(c_patterns))
+    engine = _get_hyperscanner_lib()
+    if ext is None:
+        return engine.check_patterns(c_patterns, c_flags, c_ids, len(c_patterns))
+    c_ext = ext_array(ext, len(c_patterns))
+    _bind_ext(engine)
+    return engine.hg_check_patterns_ext(c_patterns, c_flags, c_ids, c_ext, len(c_patterns))
 
 
 def scan(  # pylint: disable=too-many-arguments
@@ -132,20 +166,27 @@ def scan(  # pylint: disable=too-many-arguments
     buffer_size: int = 262140,
     buffer_count: int = 16,
     max_match_count: int = 0,
+    ext=None,
 ) -> int:
     """Scan a plain / gzip / zstd text file; `callback(matches, count)` receives the hits in batches of `buffer_count`.
+    `ext`: one ExprExt (extended parameters: approximate matching) or None per pattern.
 
     The native call runs on a daemon thread so that Ctrl-C reaches Python (return code 130); otherwise the shim's
     return code (0 = fine, 1-7 as in hyperscanner.c:25-33) comes back.
     """
     c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags, ids=ids)
+    c_ext = None if ext is None else ext_array(ext, len(c_patterns))
     c_callback = CALLBACK_TYPE(callback)  # referenced until the call is over
     engine = _get_hyperscanner_lib()
     outcome = [0]
 
     def native_call() -> None:
-        outcome[0] = engine.hyperscan(path.encode(), c_patterns, c_flags, c_ids, len(c_patterns), c_callback, buffer_size, buffer_count,
-                                      ctypes.c_ulonglong(max_match_count))
+        if c_ext is None:
+            outcome[0] = engine.hyperscan(path.encode(), c_patterns, c_flags, c_ids, len(c_patterns), c_callback, buffer_size, buffer_count,
+                                          ctypes.c_ulonglong(max_match_count))
+        else:
+            outcome[0] = engine.hg_hyperscan_ext(path.encode(), c_patterns, c_flags, c_ids, c_ext, len(c_patterns), c_callback, buffer_size,
+                                              buffer_count, ctypes.c_ulonglong(max_match_count))
 
     worker = threading.Thread(target=native_call, daemon=True)
     worker.start()

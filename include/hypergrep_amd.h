@@ -118,10 +118,60 @@ typedef int (*match_event_handler)(unsigned int id, unsigned long long from, uns
 #define HS_FLAG_COMBINATION 512
 #define HS_FLAG_QUIET 1024
 
+/* Extended parameters of one expression (Hyperscan's hs_expr_ext_t: the same layout and flag values).  `flags` says which
+ * fields are set; an expression without parameters is a NULL entry (or a NULL array, or flags 0).  Offsets have the origin
+ * of `to`: the scanned bytes of the line piece (after the leading-NUL skip) for hyperscan() and hg_scan_device, the block
+ * for hs_scan.
+ *  - edit_distance = k: an end t is reported iff data[s:t] is within Levenshtein distance k of some string the expression
+ *    matches, for some s <= t.  Edits are one-byte insertions, deletions and substitutions.  hamming_distance = k: the
+ *    same with substitutions only.  An inserted or substituting byte is any byte `.` matches under the expression's flags
+ *    (every byte with HS_FLAG_DOTALL, every byte but '\n' without it); under HS_FLAG_CASELESS a case change is no edit.
+ *    A leading ^ / \A holds at s and a trailing $ / \z / \Z at t, with the usual multiline rules.  With
+ *    HS_FLAG_SOM_LEFTMOST `from` is the smallest such s (automata of at most 1024 nodes after the expansion).
+ *  - min_offset / max_offset: a report (id, to) exists only if min_offset <= to <= max_offset.  The bounds apply before
+ *    the report rules: under HS_FLAG_SINGLEMATCH the delivered report is the smallest `to` in bounds.
+ *  - min_length: accepted where it can never remove a report: at most the expression's minimum match width (minus k with an
+ *    edit distance).  Filtering by start of match is not implemented: larger values are rejected.
+ * Rejected (HS_COMPILER_ERROR / HG_ERR_COMPILE, with the expression's index and the rule in the message): unknown
+ * HS_EXT_FLAG bits; edit and Hamming distance together; min_offset > max_offset; min_length > max_offset; any parameter on
+ * an HS_FLAG_COMBINATION expression; a distance above 16; a distance k >= the expression's minimum match width (the
+ * expression would match anything); approximate expressions with \b, \B or an anchor anywhere but the ends above, where
+ * they constrain the automaton (an assertion that only an empty alternative carries, as in (?:\b|)foo, changes nothing
+ * and is accepted);
+ * expansions over the node and edge limits ("pattern too large").
+ * These rules are this project's reading of Hyperscan's documentation; they are not checked against a Hyperscan binary. */
+typedef struct hs_expr_ext {
+    unsigned long long flags; /* HS_EXT_FLAG_*: which fields are set */
+    unsigned long long min_offset;
+    unsigned long long max_offset;
+    unsigned long long min_length;
+    unsigned edit_distance;
+    unsigned hamming_distance;
+} hs_expr_ext_t;
+#define HS_EXT_FLAG_MIN_OFFSET 1ULL
+#define HS_EXT_FLAG_MAX_OFFSET 2ULL
+#define HS_EXT_FLAG_MIN_LENGTH 4ULL
+#define HS_EXT_FLAG_EDIT_DISTANCE 8ULL
+#define HS_EXT_FLAG_HAMMING_DISTANCE 16ULL
+
+/* Face B with extended parameters: hyperscan() and check_patterns() with `ext` (one pointer or NULL per pattern, or NULL)
+ * after pattern_ids; hg_-prefixed, as every export beyond the reference's own names is.  The compiled-database cache tells
+ * sets with parameters from the same patterns without them. */
+int hg_hyperscan_ext(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                  const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements,
+                  hs_event on_event, const int buffer_size, int buffer_count, unsigned long long max_match_count);
+int hg_check_patterns_ext(const char *const *patterns, const unsigned int *pattern_flags, const unsigned int *pattern_ids,
+                       const hs_expr_ext_t *const *ext, const unsigned int elements);
+
 /* call site hyperscanner.c:136 */
 int hs_compile_multi(const char *const *expressions, const unsigned int *flags, const unsigned int *ids,
                      unsigned int elements, unsigned int mode, const hs_platform_info_t *platform,
                      hs_database_t **db, hs_compile_error_t **error);
+/* hs_compile_multi with one hs_expr_ext_t pointer (or NULL) per expression, Hyperscan's argument order.  Without
+ * parameters it compiles exactly the database hs_compile_multi compiles. */
+int hs_compile_ext_multi(const char *const *expressions, const unsigned int *flags, const unsigned int *ids,
+                         const hs_expr_ext_t *const *ext, unsigned int elements, unsigned int mode,
+                         const hs_platform_info_t *platform, hs_database_t **db, hs_compile_error_t **error);
 /* call site hyperscanner.c:140 (called with NULL when compilation succeeded) */
 int hs_free_compile_error(hs_compile_error_t *error);
 /* call site hyperscanner.c:301 */
@@ -195,6 +245,9 @@ typedef struct hg_db_info {
  * writes "<expression index>: <reason>" to err. */
 int hg_db_compile(const char *const *expressions, const unsigned int *flags, const unsigned int *ids,
                   unsigned int n, hg_database_t **db, char *err, size_t errlen);
+/* The same with extended parameters (hs_expr_ext_t above): one pointer or NULL per expression, `ext` itself may be NULL. */
+int hg_db_compile_ext(const char *const *expressions, const unsigned int *flags, const unsigned int *ids,
+                      const hs_expr_ext_t *const *ext, unsigned int n, hg_database_t **db, char *err, size_t errlen);
 /* Optional: re-select the literal windows of the prefilter using byte statistics of a host-side text sample (any
  * part of what will be scanned) and rebuild the filter tables.  Never changes results, only how often the slower
  * stages run.  The tuned tables are built aside and swapped in on success: scanners created BEFORE the call keep the

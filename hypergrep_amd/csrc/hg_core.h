@@ -426,6 +426,179 @@ HG_HD void hg_nfa_scan_slice(const uint32_t *pool, const HgPattern &p, const uin
 }
 
 
+// ---- flows (stream mode: hs_scan_stream, hg_scan_stream_batch) ---------------------------------------------------------------
+// A flow carries each expression's automaton across the writes of a stream: its state words S (the state at the CARRIED
+// position, the stream offset whose accept test comes next) and one header word, the context of the byte before that
+// position (HG_PC_*, bits 0-1) and the flags below.  The step is the one of hg_nfa_scan_slice; what a write boundary changes
+// is only which contexts are known (include/hypergrep_amd.h, stream mode rule 4):
+//  - the accept test at position i reads the context of byte i, which for a '\n' is NLFINAL only if it is the stream's last
+//    byte: a write's trailing '\n' is stepped at once by expressions that do not tell NL from NLFINAL, and HELD (not stepped)
+//    by those that do (HG_FLOW_HOLD, decided at compile time) until the next write (NL) or the close (NLFINAL);
+//  - the test at the end of a write is delivered at once when it holds for every context still possible (HG_FLOW_ACC_DONE
+//    then keeps it from being delivered again), else it is left to the next write or the close.
+enum : uint32_t {
+  HG_FLOW_PC = 3,         // bits of the previous-byte context
+  HG_FLOW_ACC_DONE = 4,   // the accept test at the carried position has been delivered
+  HG_FLOW_HELD = 8,       // the carried position is a write's trailing '\n', not stepped yet (it sits at stream offset end - 1)
+  HG_FLOW_DEAD = 16,      // an expression whose routines stop at the first end (HgPattern::single) has reported: not run again
+  HG_FLOW_HOLD = 32,      // (static) the expression holds a write's trailing '\n'
+};
+constexpr uint32_t HG_FLOW_PIECE = 4096;  // bytes of a write one workgroup of hg_flow_scan_kernel stages in LDS at a time
+constexpr uint32_t HG_FLOW_PPW = 32;      // expressions per workgroup
+
+// The context of byte c as the NEXT byte of an accept test; `final`: the byte is the stream's last.
+HG_HD uint32_t hg_flow_ctx(uint32_t c, bool final) {
+  return c == '\n' ? (final ? HG_NC_NLFINAL : HG_NC_NL) : (hg_is_word(c) ? HG_NC_WORD : HG_NC_OTHER);
+}
+// Does the accept test hold at a position with state S, previous context pc and next context cc?
+HG_HD bool hg_flow_accepts(const uint32_t *pool, const HgPattern &p, const uint32_t *S, uint32_t pc, uint32_t cc) {
+  const uint32_t *a = pool + p.acc_off + (pc * 5 + cc) * p.nw;
+  uint32_t any = 0;
+  for (uint32_t w = 0; w < p.nw; w++) any |= S[w] & a[w];
+  return any != 0;
+}
+// The step over byte c (own context cc) from state S at previous context pc, start states entering; S is updated.
+HG_HD void hg_flow_step(const uint32_t *pool, const HgPattern &p, uint32_t *S, uint32_t pc, uint32_t c, uint32_t cc) {
+  const uint32_t nw = p.nw;
+  const uint32_t *follow = pool + p.follow_off, *init = pool + p.init_off;
+  const uint32_t *r = pool + p.reach_off + c * nw, *m = pool + p.amask_off + (pc * 4 + cc) * nw;
+  uint32_t T[HG_MAX_W];
+  for (uint32_t w = 0; w < nw; w++) T[w] = init[w];
+  for (uint32_t w = 0; w < nw; w++)
+    for (uint32_t x = S[w]; x; x &= x - 1) {
+      const uint32_t *f = follow + (w * 32 + hg_ctz(x)) * nw;
+      for (uint32_t k = 0; k < nw; k++) T[k] |= f[k];
+    }
+  for (uint32_t w = 0; w < nw; w++) S[w] = T[w] & r[w] & m[w];
+}
+
+// Positions [from, stop) of one piece data[0, stop) of a write, for the matches that START in [from, upto), plus (the seeded
+// lane: S non-zero on entry) those carried in S.  pc: the context before `from`.  final_nl: the index of the stream's last
+// byte if it lies in this piece (its '\n' is NLFINAL), else HG_NONE32.  skip: the accept test at `from` was delivered already.
+// emit(i) for every position i in [from, stop) whose test holds (ascending).  On return S holds the state at `stop` (zero
+// if the lane's states died first; the OR over the lanes of a piece is the piece's state, hg_nfa_scan_slice's linearity).
+// Returns 1 if something was emitted; returns after the first emission when p.single (S is then not needed: HG_FLOW_DEAD).
+template <typename Emit>
+HG_HD uint32_t hg_flow_scan_slice(const uint32_t *pool, const HgPattern &p, const uint8_t *data, uint32_t from, uint32_t upto, uint32_t stop,
+                                  uint32_t final_nl, uint32_t *S, uint32_t pc, bool skip, Emit &&emit) {
+  const uint32_t nw = p.nw;
+  const uint32_t *reach = pool + p.reach_off, *follow = pool + p.follow_off, *init = pool + p.init_off;
+  const uint32_t *amask = pool + p.amask_off, *acc = pool + p.acc_off;
+  const bool single = p.single != 0;
+  uint32_t emitted = 0;
+  if (nw == 1) {
+    uint32_t s = S[0];
+    const uint32_t init0 = init[0];
+    for (uint32_t i = from; i < stop; i++) {
+      if (i >= upto && s == 0) break;  // no start left and nothing alive
+      const uint32_t c = data[i];
+      const uint32_t cc = hg_flow_ctx(c, i == final_nl);
+      if ((s & acc[pc * 5 + cc]) && !(skip && i == from)) {
+        emit(i);
+        emitted = 1;
+        if (single) return 1;
+      }
+      uint32_t T = i < upto ? init0 : 0u;
+      for (uint32_t x = s; x; x &= x - 1) T |= follow[hg_ctz(x)];
+      s = T & reach[c] & amask[pc * 4 + cc];
+      pc = hg_prev_ctx(c);
+    }
+    S[0] = s;
+    return emitted;
+  }
+  uint32_t T[HG_MAX_W];
+  uint32_t alive = 0;
+  for (uint32_t w = 0; w < nw; w++) alive |= S[w];
+  for (uint32_t i = from; i < stop; i++) {
+    if (i >= upto && alive == 0) break;
+    const uint32_t c = data[i];
+    const uint32_t cc = hg_flow_ctx(c, i == final_nl);
+    const uint32_t *a = acc + (pc * 5 + cc) * nw;
+    uint32_t any = 0;
+    for (uint32_t w = 0; w < nw; w++) any |= S[w] & a[w];
+    if (any && !(skip && i == from)) {
+      emit(i);
+      emitted = 1;
+      if (single) return 1;
+    }
+    for (uint32_t w = 0; w < nw; w++) T[w] = i < upto ? init[w] : 0u;
+    for (uint32_t w = 0; w < nw; w++)
+      for (uint32_t x = S[w]; x; x &= x - 1) {
+        const uint32_t *f = follow + (w * 32 + hg_ctz(x)) * nw;
+        for (uint32_t k = 0; k < nw; k++) T[k] |= f[k];
+      }
+    const uint32_t *r = reach + c * nw, *m = amask + (pc * 4 + cc) * nw;
+    alive = 0;
+    for (uint32_t w = 0; w < nw; w++) alive |= S[w] = T[w] & r[w] & m[w];
+    pc = hg_prev_ctx(c);
+  }
+  if (alive == 0)
+    for (uint32_t w = 0; w < nw; w++) S[w] = 0;
+  return emitted;
+}
+
+// A held '\n' (HG_FLOW_HELD) stepped at last: with NL when bytes follow it, NLFINAL at the close.  The accept test at its
+// position comes first (unless `skip`: delivered already); emit(-1) if it holds (the position is one before the write's
+// start).  S, *pc updated.  Returns 1 if emitted.
+template <typename Emit>
+HG_HD uint32_t hg_flow_unhold(const uint32_t *pool, const HgPattern &p, uint32_t *S, uint32_t *pc, bool final, bool skip, Emit &&emit) {
+  const uint32_t cc = final ? HG_NC_NLFINAL : HG_NC_NL;
+  uint32_t emitted = 0;
+  if (!skip && hg_flow_accepts(pool, p, S, *pc, cc)) {
+    emit(-1);
+    emitted = 1;
+  }
+  hg_flow_step(pool, p, S, *pc, '\n', cc);
+  *pc = HG_PC_NL;
+  return emitted;
+}
+
+// The end of a write for one expression.  S / pc: the state at the carried position `stop` (write-relative: the write's
+// length, one less when its trailing '\n' is held, -1 when a held '\n' of an earlier write is still held) and the context
+// before it; hdr: the header word to update (HG_FLOW_HOLD / HG_FLOW_DEAD are kept), with `held` and `acc_done` describing
+// the carried position.  close: the stream ends here (a held '\n' is the stream's last byte, then the END test).  Otherwise
+// the test at `stop` is delivered now if it holds for every context still possible ({NL, NLFINAL} at a held '\n', all five
+// else).  emit(position) per report.  Returns the new header word; *emitted |= 1 if something was emitted.
+template <typename Emit>
+HG_HD uint32_t hg_flow_finish(const uint32_t *pool, const HgPattern &p, uint32_t *S, uint32_t pc, uint32_t hdr, int32_t stop, bool held, bool acc_done,
+                              bool close, uint32_t *emitted, Emit &&emit) {
+  hdr &= HG_FLOW_HOLD | HG_FLOW_DEAD;
+  if (close) {
+    if (held) {
+      *emitted |= hg_flow_unhold(pool, p, S, &pc, true, acc_done, [&](int32_t) { emit(stop); });
+      stop++;
+      acc_done = false;
+    }
+    if (!acc_done && hg_flow_accepts(pool, p, S, pc, HG_NC_END)) {
+      emit(stop);
+      *emitted |= 1;
+    }
+    return hdr | pc;
+  }
+  if (!acc_done) {
+    bool all = true;
+    for (uint32_t cc = 0; cc < 5 && all; cc++)
+      if (!held || cc == HG_NC_NL || cc == HG_NC_NLFINAL) all = hg_flow_accepts(pool, p, S, pc, cc);
+    if (all) {
+      emit(stop);
+      *emitted |= 1;
+      acc_done = true;
+    }
+  }
+  return hdr | pc | (acc_done ? HG_FLOW_ACC_DONE : 0u) | (held ? HG_FLOW_HELD : 0u);
+}
+
+// Does the expression tell a final '\n' from any other (non-multiline $, \Z)?  Then a write's trailing '\n' is held.
+HG_HD bool hg_flow_needs_hold(const uint32_t *pool, const HgPattern &p) {
+  const uint32_t nw = p.nw;
+  for (uint32_t pc = 0; pc < 4; pc++)
+    for (uint32_t w = 0; w < nw; w++) {
+      if (pool[p.amask_off + (pc * 4 + HG_NC_NL) * nw + w] != pool[p.amask_off + (pc * 4 + HG_NC_NLFINAL) * nw + w]) return true;
+      if (pool[p.acc_off + (pc * 5 + HG_NC_NL) * nw + w] != pool[p.acc_off + (pc * 5 + HG_NC_NLFINAL) * nw + w]) return true;
+    }
+  return false;
+}
+
 // Confirm by WINDOW: what the device's confirm routines for SINGLEMATCH automata compute (hg_confirm_dev.h has the argument).
 // Every match contains an occurrence of the pattern's required literal that begins at most `lit_lead` bytes after the
 // match's start; the candidate whose verified occurrence begins at `fs` answers for the matches that start in

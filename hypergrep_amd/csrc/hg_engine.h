@@ -194,6 +194,7 @@ class HgScanner {
   uint32_t launch_block_small(const uint8_t *h_text, uint32_t nbytes, hipStream_t stream, HgHit *h_out, uint32_t *h_counts, uint32_t *h_flag, uint32_t seq);
   const std::string &last_error() const { return err_; }
   int device() const { return device_; }
+  const HgDbView &view() const { return view_; }  // the database's device tables (stream mode: hg_flows.hip)
 
  private:
   HgScanner() = default;

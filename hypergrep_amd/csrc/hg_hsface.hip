@@ -1,5 +1,5 @@
-// Face A: the six libhs symbols the reference shim links against (hypergrep/lib/c/hyperscanner.c:136,140,165,217,
-// 301,323,324), block mode only.  hs_scan copies the block to HBM and runs the same stream / filter kernels in
+// Face A: the libhs symbols the reference shim links against (hypergrep/lib/c/hyperscanner.c:136,140,165,217,
+// 301,323,324), and stream mode (hs_*_stream, hg_scan_stream_batch: hg_flows.hip, at the end).  hs_scan copies the block to HBM and runs the same stream / filter kernels in
 // block mode (the buffer is one scan unit, no line splitting), then delivers reports in ascending end offset.
 // Per-call cost is a few launches and two synchronisations, so this face is for compatibility (per-line callers such
 // as the reference shim); bulk scanning goes through hyperscan() / hg_scan_device().
@@ -18,10 +18,28 @@
 #include "../../include/hypergrep_amd.h"
 #include "hg_compile.h"
 #include "hg_engine.h"
+#include "hg_flow_rules.h"
+#include "hg_flows.h"
 #include "hg_mem.h"
 
+// Stream-mode data of a database (none in block mode): where each expression's words sit in a stream's state, and the state
+// of a freshly opened stream (header words: HG_PC_START, HG_FLOW_HOLD where the expression holds a trailing '\n').
+struct HgFlowDb {
+  std::vector<uint32_t> soff;  // npatterns
+  std::vector<uint32_t> init;  // swords
+  uint32_t swords = 0, ngroups = 0;
+};
 struct hs_database {
   std::shared_ptr<HgDb> db;
+  unsigned int mode = HS_MODE_BLOCK;
+  std::shared_ptr<const HgFlowDb> flow;  // HS_MODE_STREAM only
+};
+struct hs_stream {
+  std::shared_ptr<HgDb> db;
+  std::shared_ptr<const HgFlowDb> flow;
+  std::vector<uint32_t> state;  // flow->swords words (hg_core.h, flows)
+  bool terminated = false;
+  HgFlowRuleState rules;        // offset, SINGLEMATCH ids reported, recent reports (hg_flow_rules.h)
 };
 struct hs_scratch {
   std::shared_ptr<HgDb> db;
@@ -37,6 +55,16 @@ struct hs_scratch {
   HgHit *h_out = nullptr;
   uint32_t *h_counts = nullptr;  // [0, 64) reports per segment, [64] completion flag
   uint32_t seq = 0;
+  // stream mode (hg_flow_scan_kernel), allocated at the first stream call: pinned staging of writes, items and states, the
+  // pinned report array, the writes' HBM copy and the kernel's device counters
+  uint8_t *f_text = nullptr, *f_dtext = nullptr;
+  size_t f_text_cap = 0, f_dtext_cap = 0;
+  HgFlowItem *f_items = nullptr;
+  uint32_t *f_sin = nullptr, *f_sout = nullptr;
+  size_t f_items_cap = 0, f_state_cap = 0;
+  HgHit *f_out = nullptr;
+  uint32_t f_out_cap = 0;
+  uint32_t *f_flag = nullptr, *f_dctr = nullptr, *f_dsoff = nullptr;
 };
 
 namespace {
@@ -66,11 +94,40 @@ int hs_compile_ext_multi(const char *const *expressions, const unsigned int *fla
   std::string msg;
   int bad = -1;
   HgDb *raw = nullptr;
-  if (!db || !expressions || elements == 0 || mode != HS_MODE_BLOCK) msg = "invalid arguments (block mode, at least one expression)";
-  else if (hgc_compile_ext(expressions, flags, ids, ext, elements, &raw, &msg, &bad) == 0) {
-    *db = new hs_database{std::shared_ptr<HgDb>(raw, [](HgDb *d) { hgc_free(d); })};
+  if (!db || !expressions || elements == 0 || (mode != HS_MODE_BLOCK && mode != HS_MODE_STREAM)) {
+    msg = "invalid arguments (block or stream mode, at least one expression)";
+  } else if (mode == HS_MODE_STREAM && flags) {  // stream mode: what a flow cannot carry (include/hypergrep_amd.h, rule 7)
+    for (unsigned int i = 0; i < elements && bad < 0; i++) {
+      const char *rule = (flags[i] & HS_FLAG_SOM_LEFTMOST) ? "HS_FLAG_SOM_LEFTMOST is not supported in stream mode"
+                         : (flags[i] & HS_FLAG_COMBINATION) ? "HS_FLAG_COMBINATION is not supported in stream mode"
+                         : (flags[i] & HS_FLAG_QUIET)       ? "HS_FLAG_QUIET is not supported in stream mode"
+                                                            : nullptr;
+      if (rule) bad = static_cast<int>(i), msg = "expression " + std::to_string(i) + ": " + rule;
+    }
+  }
+  if (msg.empty() && hgc_compile_ext(expressions, flags, ids, ext, elements, &raw, &msg, &bad) == 0) {
+    std::shared_ptr<HgDb> owned(raw, [](HgDb *d) { hgc_free(d); });
+    std::shared_ptr<HgFlowDb> flow;
+    if (mode == HS_MODE_STREAM) {
+      flow = std::make_shared<HgFlowDb>();
+      const uint32_t np = static_cast<uint32_t>(owned->patterns.size());
+      for (uint32_t i = 0; i < np && bad < 0; i++)
+        if (owned->patterns[i].nw > HG_MAX_W)
+          bad = static_cast<int>(i), msg = "expression " + std::to_string(i) + ": automaton of more than 1024 positions, too large for stream mode";
+      if (bad >= 0) goto fail;
+      const std::vector<bool> hold = hg_flow_hold_flags(owned->pool.data(), owned->patterns.data(), np);
+      for (uint32_t i = 0; i < np; i++) {
+        flow->soff.push_back(flow->swords);
+        flow->init.push_back(HG_PC_START | (hold[i] ? HG_FLOW_HOLD : 0u));
+        flow->init.resize(flow->init.size() + owned->patterns[i].nw, 0u);
+        flow->swords += 1 + owned->patterns[i].nw;
+      }
+      flow->ngroups = (np + HG_FLOW_PPW - 1) / HG_FLOW_PPW;
+    }
+    *db = new hs_database{owned, mode, flow};
     return HS_SUCCESS;
   }
+fail:
   if (db) *db = nullptr;
   if (error) {
     hs_compile_error_t *e = static_cast<hs_compile_error_t *>(std::malloc(sizeof(hs_compile_error_t)));
@@ -130,6 +187,15 @@ int hs_free_scratch(hs_scratch_t *scratch) {
   hgmem::host_free(scratch->h_text, "hs h_text");
   hgmem::host_free(scratch->h_out, "hs h_out");
   hgmem::host_free(scratch->h_counts, "hs h_counts");
+  hgmem::host_free(scratch->f_text, "hs f_text");
+  hgmem::dev_free(scratch->f_dtext, "hs f_dtext");
+  hgmem::host_free(scratch->f_items, "hs f_items");
+  hgmem::host_free(scratch->f_sin, "hs f_sin");
+  hgmem::host_free(scratch->f_sout, "hs f_sout");
+  hgmem::host_free(scratch->f_out, "hs f_out");
+  hgmem::host_free(scratch->f_flag, "hs f_flag");
+  hgmem::dev_free(scratch->f_dctr, "hs f_dctr");
+  hgmem::dev_free(scratch->f_dsoff, "hs f_dsoff");
   if (scratch->stream) (void)hipStreamDestroy(scratch->stream);
   delete scratch;
   return HS_SUCCESS;
@@ -139,6 +205,7 @@ int hs_scan(const hs_database_t *db, const char *data, unsigned int length, unsi
             match_event_handler on_event, void *context) {
   (void)flags;
   if (!db || !scratch || !scratch->sc || scratch->db != db->db || (!data && length)) return HS_INVALID;
+  if (db->mode != HS_MODE_BLOCK) return HS_DB_MODE_ERROR;
   if (length == 0) return HS_SUCCESS;  // no expression can match the empty buffer (such expressions are rejected at compile time)
   if (hipSetDevice(scratch->sc->device()) != hipSuccess) return HS_INVALID;
   // Short blocks (the reference shim scans line by line, hyperscanner.c:217): one launch on a pinned copy of the block,
@@ -229,6 +296,330 @@ int hs_scan(const hs_database_t *db, const char *data, unsigned int length, unsi
   for (uint32_t i : order)
     if (on_event && on_event(h[i].id, scratch->from[i], h[i].to, 0, context)) return HS_SCAN_TERMINATED;
   return HS_SUCCESS;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ stream mode ------
+namespace {
+constexpr uint64_t FLOW_LAUNCH_BYTES = 64u << 20;  // bytes of writes one launch takes at most (a longer write: several launches)
+constexpr uint32_t FLOW_LAUNCH_ITEMS = 1u << 16;
+
+// Writes of a launch are copied to HBM once (instead of every workgroup of an item reading them over the host link) when
+// bytes x workgroups per item reach this (tools/stream_bench.py measures it; HG_FLOW_HBM_MIN overrides it)
+uint64_t flow_hbm_min() {
+  static const uint64_t v = [] {
+    const char *e = std::getenv("HG_FLOW_HBM_MIN");
+    return e ? std::strtoull(e, nullptr, 10) : static_cast<uint64_t>(HG_FLOW_HBM_MIN_DEFAULT);
+  }();
+  return v;
+}
+
+struct FlowReq {   // one write of one stream in one launch
+  hs_stream_t *s;
+  uint32_t item;   // the caller's item number (callbacks)
+  const char *data;
+  uint32_t len;
+  bool close;
+};
+
+template <typename T>
+bool grow_host(T **p, size_t *cap, size_t need, const char *name) {
+  if (*cap >= need) return true;
+  const size_t n = std::max(need, *cap * 2);
+  hgmem::host_free(*p, name);
+  *p = nullptr;
+  *cap = 0;
+  if (hgmem::host_alloc(p, n * sizeof(T) + 16, name) != hipSuccess) return false;
+  *cap = n;
+  return true;
+}
+
+int flow_setup(hs_scratch_t *sc, const HgFlowDb &f) {
+  if (!sc->f_flag) {
+    if (hgmem::host_alloc(&sc->f_flag, 4 * sizeof(uint32_t), "hs f_flag") != hipSuccess) return HS_NOMEM;
+    sc->f_flag[0] = sc->f_flag[1] = 0;
+  }
+  if (!sc->f_dctr) {
+    if (hgmem::dev_alloc(&sc->f_dctr, 4 * sizeof(uint32_t), "hs f_dctr") != hipSuccess) return HS_NOMEM;
+    if (hipMemset(sc->f_dctr, 0, 4 * sizeof(uint32_t)) != hipSuccess) return HS_NOMEM;
+  }
+  if (!sc->f_dsoff) {
+    if (hgmem::dev_alloc(&sc->f_dsoff, f.soff.size() * sizeof(uint32_t) + 16, "hs f_dsoff") != hipSuccess) return HS_NOMEM;
+    if (hipMemcpy(sc->f_dsoff, f.soff.data(), f.soff.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return HS_NOMEM;
+  }
+  return HS_SUCCESS;
+}
+
+// One launch over `reqs` (distinct streams): their writes scanned, their states advanced; the reports of each request after
+// the report rules go to on_event(item, id, to) in (to, id) order, request after request.  A non-zero return terminates
+// that stream.  Returns HS_SUCCESS, HS_SCAN_TERMINATED (some stream was terminated) or an error.
+template <typename OnEvent>
+int flow_launch(hs_scratch_t *sc, const HgFlowDb &f, const std::vector<FlowReq> &reqs, OnEvent &&on_event) {
+  const uint32_t n = static_cast<uint32_t>(reqs.size());
+  if (int rc = flow_setup(sc, f)) return rc;
+  uint64_t bytes = 0;
+  for (const FlowReq &r : reqs) bytes += (static_cast<uint64_t>(r.len) + 15u) & ~15ull;
+  const size_t sw = static_cast<size_t>(n) * f.swords;
+  if (!grow_host(&sc->f_text, &sc->f_text_cap, bytes + 16, "hs f_text") || !grow_host(&sc->f_items, &sc->f_items_cap, n, "hs f_items"))
+    return HS_NOMEM;
+  if (sc->f_state_cap < sw) {  // (f_sin and f_sout have the same capacity)
+    hgmem::host_free(sc->f_sin, "hs f_sin");
+    hgmem::host_free(sc->f_sout, "hs f_sout");
+    sc->f_sin = sc->f_sout = nullptr;
+    sc->f_state_cap = 0;
+    if (hgmem::host_alloc(&sc->f_sin, sw * sizeof(uint32_t) + 16, "hs f_sin") != hipSuccess ||
+        hgmem::host_alloc(&sc->f_sout, sw * sizeof(uint32_t) + 16, "hs f_sout") != hipSuccess)
+      return HS_NOMEM;
+    sc->f_state_cap = sw;
+  }
+  uint64_t at = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const FlowReq &r = reqs[i];
+    sc->f_items[i] = HgFlowItem{at, r.len, r.close ? HG_FLOW_ITEM_CLOSE : 0u};
+    if (r.len) std::memcpy(sc->f_text + at, r.data, r.len);
+    const uint64_t end = (at + r.len + 15u) & ~15ull;
+    std::memset(sc->f_text + at + r.len, 0, end - at - r.len);
+    at = end;
+    std::memcpy(sc->f_sin + static_cast<size_t>(i) * f.swords, r.s->state.data(), f.swords * sizeof(uint32_t));
+  }
+  const uint8_t *text = sc->f_text;
+  if (bytes && bytes * f.ngroups >= flow_hbm_min()) {
+    if (sc->f_dtext_cap < bytes) {
+      hgmem::dev_free(sc->f_dtext, "hs f_dtext");
+      sc->f_dtext = nullptr;
+      sc->f_dtext_cap = 0;
+      const size_t cap = std::max<size_t>(bytes, 1u << 20);
+      if (hgmem::dev_alloc(&sc->f_dtext, cap + 16, "hs f_dtext") != hipSuccess) return HS_NOMEM;
+      sc->f_dtext_cap = cap;
+    }
+    if (hipMemcpyAsync(sc->f_dtext, sc->f_text, bytes, hipMemcpyHostToDevice, sc->stream) != hipSuccess) return HS_INVALID;
+    text = sc->f_dtext;
+  }
+  const HgDbView &v = sc->sc->view();
+  uint32_t total = 0;
+  for (;;) {
+    if (sc->f_out_cap == 0) {
+      if (hgmem::host_alloc(&sc->f_out, 4096 * sizeof(HgHit), "hs f_out") != hipSuccess) return HS_NOMEM;
+      sc->f_out_cap = 4096;
+    }
+    const uint32_t seq = ++sc->seq ? sc->seq : ++sc->seq;
+    HgFlowArgs a{};
+    a.patterns = v.patterns;
+    a.pool = v.pool;
+    a.npatterns = v.npatterns;
+    a.text = text;
+    a.items = sc->f_items;
+    a.soff = sc->f_dsoff;
+    a.state_in = sc->f_sin;
+    a.state_out = sc->f_sout;
+    a.out = sc->f_out;
+    a.cap = sc->f_out_cap;
+    a.ngroups = f.ngroups;
+    a.swords = f.swords;
+    a.seq = seq;
+    a.d_total = sc->f_dctr;
+    a.d_done = sc->f_dctr + 1;
+    a.h_flag = sc->f_flag;
+    if (hg_flow_launch(a, n, sc->stream) != 0) return HS_INVALID;
+    volatile uint32_t *flag = sc->f_flag + 1;
+    bool done = false;
+    for (uint32_t spin = 0; spin < 400000 && !(done = *flag == seq); spin++) cpu_relax();
+    if (!done && hipStreamSynchronize(sc->stream) != hipSuccess) return HS_INVALID;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (*flag != seq) return HS_INVALID;
+    total = sc->f_flag[0];
+    if (total <= sc->f_out_cap) break;
+    // more reports than room: the states in f_sin are untouched, the launch is repeated with room for all
+    hgmem::host_free(sc->f_out, "hs f_out");
+    sc->f_out = nullptr;
+    sc->f_out_cap = 0;
+    if (hgmem::host_alloc(&sc->f_out, static_cast<size_t>(total) * 2 * sizeof(HgHit), "hs f_out") != hipSuccess) return HS_NOMEM;
+    sc->f_out_cap = total * 2;
+  }
+  // the report rules, per request (hg_flow_rules.h)
+  const HgDb &db = *sc->db;
+  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> per(n);
+  for (uint32_t i = 0; i < total; i++) {
+    const HgHit &h = sc->f_out[i];
+    per[h.line_no & 0xFFFFFFFFu].emplace_back(static_cast<uint32_t>(h.line_no >> 32), h.to);
+  }
+  int rc = HS_SUCCESS;
+  std::vector<HgFlowRep> reps;
+  for (uint32_t i = 0; i < n; i++) {
+    hs_stream_t *s = reqs[i].s;
+    std::memcpy(s->state.data(), sc->f_sout + static_cast<size_t>(i) * f.swords, f.swords * sizeof(uint32_t));
+    hg_flow_rules(db.patterns.data(), db.bounds.empty() ? nullptr : db.bounds.data(), s->rules, reqs[i].len, per[i].data(), per[i].size(), reps);
+    for (const HgFlowRep &x : reps)
+      if (!s->terminated && on_event(reqs[i].item, x.id, x.to) != 0) s->terminated = true;
+    if (s->terminated) rc = HS_SCAN_TERMINATED;
+  }
+  return rc;
+}
+
+void flow_reset(hs_stream_t *s) {
+  s->state = s->flow->init;
+  s->terminated = false;
+  s->rules = HgFlowRuleState{};
+}
+
+bool flow_usable(const hs_stream_t *s, const hs_scratch_t *sc) {
+  return s && sc && sc->sc && sc->db == s->db && hipSetDevice(sc->sc->device()) == hipSuccess;
+}
+
+// hg_scan_stream_batch, after argument checks: the items in launches of at most FLOW_LAUNCH_BYTES / FLOW_LAUNCH_ITEMS, a
+// longer write cut over consecutive launches (so every launch holds a stream once, and reports stay in item order)
+template <typename OnEvent>
+int flow_batch(hs_scratch_t *sc, hs_stream_t *const *streams, const char *const *data, const unsigned int *lengths, const unsigned int *item_flags,
+               unsigned int n, OnEvent &&on_event) {
+  const HgFlowDb &f = *streams[0]->flow;
+  std::vector<FlowReq> reqs;
+  uint64_t bytes = 0;
+  int rc = HS_SUCCESS;
+  // A write longer than one launch takes is cut over consecutive launches; its reports are held back until its last cut and
+  // delivered in (to, id) order then, so that one call's reports stay ordered (a cut is not a write boundary for the caller)
+  constexpr uint32_t NO_ITEM = 0xFFFFFFFFu;
+  uint32_t cut_item = NO_ITEM;
+  std::vector<std::pair<uint64_t, uint32_t>> held;
+  auto deliver = [&](uint32_t item, uint32_t id, uint64_t to) {
+    if (item == cut_item) {
+      held.emplace_back(to, id);
+      return 0;
+    }
+    return on_event(item, id, to);
+  };
+  auto flush = [&](bool cut_done) {
+    int r = reqs.empty() ? HS_SUCCESS : flow_launch(sc, f, reqs, deliver);
+    if (cut_done && cut_item != NO_ITEM) {
+      hs_stream_t *s = streams[cut_item];
+      std::sort(held.begin(), held.end());
+      for (const auto &x : held)
+        if (!s->terminated && on_event(cut_item, x.second, x.first) != 0) s->terminated = true;
+      if (s->terminated && r == HS_SUCCESS) r = HS_SCAN_TERMINATED;
+      held.clear();
+      cut_item = NO_ITEM;
+    }
+    for (const FlowReq &q : reqs)
+      if (q.close) flow_reset(q.s);  // (after the held reports: the reset follows the write's deliveries)
+    reqs.clear();
+    bytes = 0;
+    return r;
+  };
+  for (unsigned int i = 0; i < n; i++) {
+    hs_stream_t *s = streams[i];
+    const bool last = item_flags && (item_flags[i] & HG_STREAM_ITEM_LAST);
+    uint32_t done = 0;
+    const uint32_t len = lengths ? lengths[i] : 0u;
+    do {
+      const uint32_t room = static_cast<uint32_t>(std::min<uint64_t>(FLOW_LAUNCH_BYTES - bytes, len - done));
+      const bool all = done + room == len;
+      const bool cut = done > 0 || !all;  // this write spans launches
+      if (cut) cut_item = i;
+      if (!s->terminated) {
+        reqs.push_back(FlowReq{s, i, len ? data[i] + done : nullptr, room, last && all});
+        bytes += room;
+      } else {
+        rc = HS_SCAN_TERMINATED;  // as hs_scan_stream on a terminated stream: nothing scanned or delivered
+        if (last && all) flow_reset(s);  // (its LAST still resets it)
+      }
+      done += room;
+      if (cut || bytes >= FLOW_LAUNCH_BYTES || reqs.size() >= FLOW_LAUNCH_ITEMS) {
+        const int r = flush(all);
+        if (r != HS_SUCCESS && r != HS_SCAN_TERMINATED) return r;
+        if (r == HS_SCAN_TERMINATED) rc = r;
+      }
+    } while (done < len);
+  }
+  const int r = flush(true);
+  if (r != HS_SUCCESS && r != HS_SCAN_TERMINATED) return r;
+  return r == HS_SCAN_TERMINATED ? r : rc;
+}
+}  // namespace
+
+extern "C" {
+
+int hs_stream_size(const hs_database_t *db, size_t *stream_size) {
+  if (!db || !stream_size) return HS_INVALID;
+  if (db->mode != HS_MODE_STREAM) return HS_DB_MODE_ERROR;
+  *stream_size = sizeof(hs_stream_t) + db->flow->swords * sizeof(uint32_t);
+  return HS_SUCCESS;
+}
+
+int hs_open_stream(const hs_database_t *db, unsigned int flags, hs_stream_t **stream) {
+  (void)flags;
+  if (!db || !stream) return HS_INVALID;
+  if (db->mode != HS_MODE_STREAM) return HS_DB_MODE_ERROR;
+  hs_stream_t *s = new hs_stream_t();
+  s->db = db->db;
+  s->flow = db->flow;
+  flow_reset(s);
+  *stream = s;
+  return HS_SUCCESS;
+}
+
+int hs_scan_stream(hs_stream_t *id, const char *data, unsigned int length, unsigned int flags, hs_scratch_t *scratch, match_event_handler on_event,
+                   void *context) {
+  (void)flags;
+  if (!id || !scratch || (!data && length)) return HS_INVALID;
+  if (id->terminated) return HS_SCAN_TERMINATED;
+  if (length == 0) return HS_SUCCESS;  // (nothing changes: the state and what is pending stay as they are)
+  if (!flow_usable(id, scratch)) return HS_INVALID;
+  hs_stream_t *const streams[1] = {id};
+  const char *const datas[1] = {data};
+  const unsigned int lengths[1] = {length};
+  return flow_batch(scratch, streams, datas, lengths, nullptr, 1, [&](uint32_t, uint32_t rid, uint64_t to) {
+    return on_event ? on_event(rid, 0, to, 0, context) : 0;
+  });
+}
+
+int hs_reset_stream(hs_stream_t *id, unsigned int flags, hs_scratch_t *scratch, match_event_handler on_event, void *context) {
+  (void)flags;
+  if (!id) return HS_INVALID;
+  if (on_event && !id->terminated) {
+    if (!flow_usable(id, scratch)) return HS_INVALID;
+    hs_stream_t *const streams[1] = {id};
+    const char *const datas[1] = {nullptr};
+    const unsigned int lengths[1] = {0};
+    const unsigned int last[1] = {HG_STREAM_ITEM_LAST};
+    const int rc = flow_batch(scratch, streams, datas, lengths, last, 1, [&](uint32_t, uint32_t rid, uint64_t to) { return on_event(rid, 0, to, 0, context); });
+    if (rc != HS_SUCCESS && rc != HS_SCAN_TERMINATED) return rc;
+  }
+  flow_reset(id);
+  return HS_SUCCESS;
+}
+
+int hs_close_stream(hs_stream_t *id, hs_scratch_t *scratch, match_event_handler on_event, void *context) {
+  if (!id) return HS_INVALID;
+  int rc = HS_SUCCESS;
+  if (on_event && !id->terminated) {
+    if (!flow_usable(id, scratch)) return HS_INVALID;
+    rc = hs_reset_stream(id, 0, scratch, on_event, context);
+    if (rc == HS_SCAN_TERMINATED) rc = HS_SUCCESS;
+  }
+  delete id;
+  return rc;
+}
+
+int hs_copy_stream(hs_stream_t **to_id, const hs_stream_t *from_id) {
+  if (!to_id || !from_id) return HS_INVALID;
+  *to_id = new hs_stream_t(*from_id);
+  return HS_SUCCESS;
+}
+
+int hg_scan_stream_batch(hs_stream_t *const *streams, const char *const *data, const unsigned int *lengths, const unsigned int *item_flags, unsigned int n,
+                         hs_scratch_t *scratch, hg_stream_match_handler on_event, void *context) {
+  if (n == 0) return HS_SUCCESS;
+  if (!streams || !lengths || !scratch || !scratch->sc) return HS_INVALID;
+  std::vector<const hs_stream_t *> seen(streams, streams + n);
+  for (unsigned int i = 0; i < n; i++) {
+    if (!streams[i] || streams[i]->db != scratch->db || (lengths[i] && (!data || !data[i]))) return HS_INVALID;
+  }
+  std::sort(seen.begin(), seen.end());
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return HS_INVALID;
+  if (hipSetDevice(scratch->sc->device()) != hipSuccess) return HS_INVALID;
+  return flow_batch(scratch, streams, data, lengths, item_flags, n, [&](uint32_t item, uint32_t rid, uint64_t to) {
+    return on_event ? on_event(item, rid, 0, to, 0, context) : 0;
+  });
 }
 
 }  // extern "C"

@@ -307,3 +307,166 @@ def faceb_stats() -> dict:
 
 def faceb_next_device(ndev: int) -> int:
     return lib().hg_faceb_next_device(ndev)
+
+
+# ------------------------------------------------------------------------------------------------ stream mode ------
+HS_MODE_BLOCK, HS_MODE_STREAM = 1, 2
+HS_SUCCESS, HS_INVALID, HS_NOMEM, HS_SCAN_TERMINATED, HS_COMPILER_ERROR, HS_DB_MODE_ERROR = 0, -1, -2, -3, -4, -7
+HG_STREAM_ITEM_LAST = 1
+
+
+class HsCompileError(ctypes.Structure):
+    _fields_ = [("message", ctypes.c_char_p), ("expression", ctypes.c_int)]
+
+
+MATCH_EVENT = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_uint, ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_void_p)
+STREAM_EVENT = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_void_p)
+_face_a_configured = False
+
+
+def face_a() -> ctypes.CDLL:
+    """The library with Face A's prototypes (hs_*: block and stream mode, hg_scan_stream_batch)."""
+    global _face_a_configured
+    l = lib()
+    if not _face_a_configured:
+        vp, u = ctypes.c_void_p, ctypes.c_uint
+        l.hs_compile_ext_multi.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(u), ctypes.POINTER(u), ctypes.POINTER(ctypes.POINTER(utils.ExprExt)),
+                                           u, u, vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.POINTER(HsCompileError))]
+        l.hs_free_compile_error.argtypes = [ctypes.POINTER(HsCompileError)]
+        l.hs_free_database.argtypes = [vp]
+        l.hs_alloc_scratch.argtypes = [vp, ctypes.POINTER(vp)]
+        l.hs_free_scratch.argtypes = [vp]
+        l.hs_scan.argtypes = [vp, ctypes.c_char_p, u, u, vp, MATCH_EVENT, vp]
+        l.hs_open_stream.argtypes = [vp, u, ctypes.POINTER(vp)]
+        l.hs_scan_stream.argtypes = [vp, ctypes.c_char_p, u, u, vp, MATCH_EVENT, vp]
+        l.hs_close_stream.argtypes = [vp, vp, MATCH_EVENT, vp]
+        l.hs_reset_stream.argtypes = [vp, u, vp, MATCH_EVENT, vp]
+        l.hs_copy_stream.argtypes = [ctypes.POINTER(vp), vp]
+        l.hs_stream_size.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)]
+        l.hg_scan_stream_batch.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(u), ctypes.POINTER(u), u, vp, STREAM_EVENT, vp]
+        _face_a_configured = True
+    return l
+
+
+def hs_compile(patterns, flags=None, ids=None, ext=None, mode: int = HS_MODE_STREAM):
+    """hs_compile_ext_multi: (database handle, None) or (None, (message, expression index))."""
+    pa, fa, ia = utils.prepare_patterns(list(patterns), flags=list(flags or ()), ids=list(ids or ()))
+    ea = utils.ext_array(ext, len(pa)) if ext is not None else None
+    h = ctypes.c_void_p()
+    err = ctypes.POINTER(HsCompileError)()
+    rc = face_a().hs_compile_ext_multi(pa, fa, ia, ea, len(pa), mode, None, ctypes.byref(h), ctypes.byref(err))
+    if rc == HS_SUCCESS:
+        return h, None
+    msg = (err.contents.message.decode(errors="replace"), err.contents.expression) if err else ("", -1)
+    face_a().hs_free_compile_error(err)
+    return None, msg
+
+
+class StreamDatabase:
+    """Expressions compiled for stream mode (hs_compile_ext_multi with HS_MODE_STREAM; include/hypergrep_amd.h has the
+    contract).  It owns ONE scratch, so a StreamDatabase and its streams must not be used from several threads at once."""
+
+    def __init__(self, patterns, flags=None, ids=None, ext=None, device: int | None = None):
+        h, err = hs_compile(patterns, flags, ids, ext, HS_MODE_STREAM)
+        if err:
+            raise CompileError(err[0])
+        self._h = h
+        self._scratch = ctypes.c_void_p()
+        if face_a().hs_alloc_scratch(self._h, ctypes.byref(self._scratch)) != HS_SUCCESS:
+            raise DeviceError("hs_alloc_scratch failed")
+
+    def open(self) -> "Stream":
+        return Stream(self)
+
+    def stream_size(self) -> int:
+        n = ctypes.c_size_t()
+        if face_a().hs_stream_size(self._h, ctypes.byref(n)) != HS_SUCCESS:
+            raise DeviceError("hs_stream_size failed")
+        return n.value
+
+    def scan_streams(self, items, last=None):
+        """items: [(Stream, bytes)], each stream at most once; last: one bool per item (end of that stream's data: its
+        end-of-data reports, then a reset).  One hg_scan_stream_batch call; [[(id, to)] per item]."""
+        items = list(items)
+        n = len(items)
+        out = [[] for _ in range(n)]
+        if n == 0:
+            return out
+
+        def on_event(item, rid, _frm, to, _flags, _ctx):
+            out[item].append((rid, to))
+            return 0
+
+        cb = STREAM_EVENT(on_event)
+        streams = (ctypes.c_void_p * n)(*[s._require() for s, _ in items])
+        datas = (ctypes.c_char_p * n)(*[bytes(d) for _, d in items])
+        lengths = (ctypes.c_uint * n)(*[len(d) for _, d in items])
+        flags = (ctypes.c_uint * n)(*[HG_STREAM_ITEM_LAST if (last and last[i]) else 0 for i in range(n)])
+        rc = face_a().hg_scan_stream_batch(streams, datas, lengths, flags, n, self._scratch, cb, None)
+        if rc not in (HS_SUCCESS, HS_SCAN_TERMINATED):
+            raise DeviceError(f"hg_scan_stream_batch returned {rc}")
+        return out
+
+    def __del__(self):
+        if lib is None:
+            return
+        if getattr(self, "_scratch", None):
+            face_a().hs_free_scratch(self._scratch)
+            self._scratch = None
+        if getattr(self, "_h", None):
+            face_a().hs_free_database(self._h)
+            self._h = None
+
+
+class Stream:
+    """One open stream of a StreamDatabase: scan() takes the next write, close() ends the data."""
+
+    def __init__(self, db: StreamDatabase, handle=None):
+        self.db = db
+        self._h = handle
+        if handle is None:
+            self._h = ctypes.c_void_p()
+            if face_a().hs_open_stream(db._h, 0, ctypes.byref(self._h)) != HS_SUCCESS:
+                raise DeviceError("hs_open_stream failed")
+
+    def _require(self):
+        if not self._h:
+            raise ValueError("stream is closed")
+        return self._h
+
+    def _call(self, fn, *args):
+        out = []
+
+        def on_event(rid, _frm, to, _flags, _ctx):
+            out.append((rid, to))
+            return 0
+
+        rc = fn(*args, MATCH_EVENT(on_event), None)
+        if rc not in (HS_SUCCESS, HS_SCAN_TERMINATED):
+            raise DeviceError(f"{fn.__name__} returned {rc}")
+        return out
+
+    def scan(self, data: bytes):
+        """The next write: [(id, to)] delivered by it (to = stream offset)."""
+        return self._call(face_a().hs_scan_stream, self._require(), bytes(data), len(data), 0, self.db._scratch)
+
+    def reset(self):
+        """The end-of-data reports, then the stream is as freshly opened."""
+        return self._call(face_a().hs_reset_stream, self._require(), 0, self.db._scratch)
+
+    def copy(self) -> "Stream":
+        h = ctypes.c_void_p()
+        if face_a().hs_copy_stream(ctypes.byref(h), self._require()) != HS_SUCCESS:
+            raise DeviceError("hs_copy_stream failed")
+        return Stream(self.db, h)
+
+    def close(self):
+        """The end-of-data reports; the stream is freed."""
+        out = self._call(face_a().hs_close_stream, self._require(), self.db._scratch)
+        self._h = None
+        return out
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            face_a().hs_close_stream(self._h, None, MATCH_EVENT(), None)
+            self._h = None

@@ -84,6 +84,8 @@ typedef int (*match_event_handler)(unsigned int id, unsigned long long from, uns
 #define HS_SCAN_TERMINATED (-3)
 #define HS_COMPILER_ERROR (-4)
 #define HS_MODE_BLOCK 1
+#define HS_MODE_STREAM 2
+#define HS_DB_MODE_ERROR (-7)
 #define HS_FLAG_CASELESS 1
 #define HS_FLAG_DOTALL 2
 #define HS_FLAG_MULTILINE 4
@@ -184,6 +186,66 @@ int hs_scan(const hs_database_t *db, const char *data, unsigned int length, unsi
 /* call sites hyperscanner.c:323, :165/:324 (both may receive NULL) */
 int hs_free_scratch(hs_scratch_t *scratch);
 int hs_free_database(hs_database_t *db);
+
+/* ---- stream mode (HS_MODE_STREAM) ----
+ * A database compiled with HS_MODE_STREAM scans streams: data that arrives in writes, where a match may span writes.  Let D
+ * be the concatenation of a stream's writes.
+ *  1. Equivalence.  For any split of D into writes (empty and 1-byte writes, splits next to a '\n' included), the reports
+ *     of all the stream's hs_scan_stream calls plus its close are exactly those hs_scan(D) delivers on a block-mode database
+ *     of the same expressions, flags, ids and ext.  `to` is a stream offset (64-bit), `from` is 0.  SINGLEMATCH: one report
+ *     per id for the whole stream, the smallest `to` (in bounds).  min_offset / max_offset bound stream offsets.  An
+ *     identical (id, to) is delivered once.
+ *  2. Order.  Within one call reports come in ascending (to, id).  Across a stream's calls `to` never decreases, with one
+ *     exception: a write ending in a '\n' at stream offset end - 1 whose step was held (rule 4) may deliver, in the next
+ *     call, a report with to = end - 1 after reports with to = end came in the call before.
+ *  3. Latency.  A report (id, t) is delivered at the latest by the call whose write holds stream byte t + 1, else by the
+ *     close / reset.  Expressions without assertions (^ $ \A \z \Z \b \B, after ext expansion) deliver (id, t) by the
+ *     call whose write holds byte t - 1: `foo` at the very end of a write is reported by that call.
+ *  4. Write boundaries.  The accept test at byte i reads the context of byte i (the next byte of the match).  At the end of
+ *     a write, what holds for every possible next context (END included) is delivered at once; the rest is pending, decided
+ *     by the next write's first byte or by the end of data at the close, and never delivered twice.  A '\n' is the final
+ *     newline ($ and \Z before the end of data) only when it is the last byte of D, which is known only at the close: a
+ *     write's trailing '\n' is held (not stepped) by the expressions that tell a final '\n' from another (non-multiline $,
+ *     \Z; decided at compile time), until the next write or the close.  An expression that shares a SINGLEMATCH id with
+ *     one that holds holds too (so the smallest `to` of that id is never preceded by a larger one).
+ *  5. Termination.  A non-zero return from the callback ends the call with HS_SCAN_TERMINATED; the stream is terminated:
+ *     later hs_scan_stream calls deliver nothing and return HS_SCAN_TERMINATED, hs_close_stream delivers nothing and frees
+ *     it, hs_reset_stream clears the state.
+ *  6. Streams of one database may be interleaved in any order and scanned with any scratch of the database.  A copy
+ *     (hs_copy_stream) evolves independently of its original.  A stream lives in host memory; each call copies the pending
+ *     writes and states of its streams to the GPU and back in one launch.
+ *  7. Compile rules (HS_COMPILER_ERROR, the message names the expression's index and the rule): HS_FLAG_SOM_LEFTMOST (with
+ *     or without HS_MODE_SOM_HORIZON_* bits, which are rejected as modes anyway), HS_FLAG_COMBINATION, HS_FLAG_QUIET, and
+ *     automata of more than 1024 positions after ext expansion ("too large for stream mode").  Every other expression block
+ *     mode accepts is accepted.  Modes other than HS_MODE_BLOCK and HS_MODE_STREAM (HS_MODE_VECTORED, horizon bits,
+ *     combinations of modes) are rejected.  Block-mode databases are unchanged by stream mode.
+ * hs_open_stream on a block-mode database and hs_scan on a stream-mode one return HS_DB_MODE_ERROR; hs_alloc_scratch
+ * works for both. */
+typedef struct hs_stream hs_stream_t;
+int hs_open_stream(const hs_database_t *db, unsigned int flags, hs_stream_t **stream);
+int hs_scan_stream(hs_stream_t *id, const char *data, unsigned int length, unsigned int flags, hs_scratch_t *scratch,
+                   match_event_handler on_event, void *context);
+/* Delivers the end-of-data reports and frees the stream.  With on_event == NULL, scratch may be NULL and nothing is
+ * delivered. */
+int hs_close_stream(hs_stream_t *id, hs_scratch_t *scratch, match_event_handler on_event, void *context);
+/* Delivers what hs_close_stream would (nothing with on_event == NULL), then returns the stream to its freshly opened state. */
+int hs_reset_stream(hs_stream_t *id, unsigned int flags, hs_scratch_t *scratch, match_event_handler on_event,
+                    void *context);
+int hs_copy_stream(hs_stream_t **to_id, const hs_stream_t *from_id);
+int hs_stream_size(const hs_database_t *db, size_t *stream_size);
+
+/* Batched stream scan (one launch for the pending writes of many streams).  Equivalent to hs_scan_stream on items 0..n-1
+ * in order, then hs_reset_stream for the items flagged HG_STREAM_ITEM_LAST (their end-of-data reports are delivered).
+ * Reports come grouped by item, in item order, each item's in (to, id) order.  HS_INVALID before scanning anything if a
+ * stream appears twice, a stream belongs to another database than the scratch, or an argument is NULL where data is
+ * needed (data may be NULL when every length is 0; item_flags NULL: all 0).  A non-zero return from the callback
+ * terminates that item's stream only; the other items go on, and the call returns HS_SCAN_TERMINATED. */
+typedef int (*hg_stream_match_handler)(unsigned int item, unsigned int id, unsigned long long from,
+                                       unsigned long long to, unsigned int flags, void *context);
+#define HG_STREAM_ITEM_LAST 1u /* after this write: deliver the end-of-data reports, then reset the stream */
+int hg_scan_stream_batch(hs_stream_t *const *streams, const char *const *data, const unsigned int *lengths,
+                         const unsigned int *item_flags, unsigned int n, hs_scratch_t *scratch,
+                         hg_stream_match_handler on_event, void *context);
 
 /* ------------------------------------------------------------------ hg_*: device buffers ------ */
 

@@ -442,6 +442,7 @@ enum : uint32_t {
   HG_FLOW_HELD = 8,       // the carried position is a write's trailing '\n', not stepped yet (it sits at stream offset end - 1)
   HG_FLOW_DEAD = 16,      // an expression whose routines stop at the first end (HgPattern::single) has reported: not run again
   HG_FLOW_HOLD = 32,      // (static) the expression holds a write's trailing '\n'
+  HG_FLOW_LATE = 64,      // (static, start of match) the expression shares its report id: no test is delivered early
 };
 constexpr uint32_t HG_FLOW_PIECE = 4096;  // bytes of a write one workgroup of hg_flow_scan_kernel stages in LDS at a time
 constexpr uint32_t HG_FLOW_PPW = 32;      // expressions per workgroup
@@ -597,6 +598,228 @@ HG_HD bool hg_flow_needs_hold(const uint32_t *pool, const HgPattern &p) {
       if (pool[p.acc_off + (pc * 5 + HG_NC_NL) * nw + w] != pool[p.acc_off + (pc * 5 + HG_NC_NLFINAL) * nw + w]) return true;
     }
   return false;
+}
+
+// ---- flows with start of match (HS_MODE_SOM_HORIZON_*: hg_flow_som_kernel, hg_flows.hip) -------------------------------------
+// A SOM expression carries, beside its state words, one start per automaton node: the smallest stream offset at which a
+// path into the node began.  The step is hg_flow_step's; a node entered from `init` at byte i starts at i, a node entered
+// from active predecessors (the transposed follow table, HgPattern::som_follow_off) takes their smallest start, and an
+// accept reports the smallest start over its accepting nodes.  The future of a path does not depend on where it began, so
+// this is the smallest s of a match [s, to): the block-mode start (hg_som.h).  Inside a write the starts are write-relative
+// int64 values in buffers the caller owns (HgSomStarts; device memory in the kernel); across writes they are carried as distances from
+// the carried position, saturated at the horizon's width (HG_SOM_FAR once loaded: past the horizon, smaller than any start).
+constexpr uint32_t HG_FLOW_SOM_NODES = 256;  // automaton nodes of a SOM expression in stream mode, at most
+constexpr uint32_t HG_FLOW_SOM_W = HG_FLOW_SOM_NODES / 32;
+constexpr int64_t HG_SOM_FAR = -(static_cast<int64_t>(1) << 62);
+constexpr int64_t HG_SOM_NONE = static_cast<int64_t>(0x7FFFFFFFFFFFFFFFull);
+
+// One buffer of starts: node t at p[t * stride].  The kernel interleaves its lanes' buffers node-major (stride = lanes of the
+// expression), so the lanes of a wavefront that touch the same node touch neighbouring words; the host replays use stride 1.
+struct HgSomStarts {
+  int64_t *p;
+  uint32_t stride;
+  HG_HD int64_t &operator[](uint32_t t) const { return p[static_cast<uint64_t>(t) * stride]; }
+};
+
+// 32-bit words of the carried starts of an expression of `nnodes` nodes at `width` bytes per start (2, 4 or 8).
+HG_HD uint32_t hg_flow_som_words(uint32_t nnodes, uint32_t width) { return (nnodes * width + 3u) / 4u; }
+
+// The smallest start over the nodes of S that accept with previous context pc and next context cc (HG_SOM_NONE: none).
+HG_HD int64_t hg_flow_som_min(const uint32_t *pool, const HgPattern &p, const uint32_t *S, HgSomStarts st, uint32_t pc, uint32_t cc) {
+  const uint32_t *a = pool + p.acc_off + (pc * 5 + cc) * p.nw;
+  int64_t best = HG_SOM_NONE;
+  for (uint32_t w = 0; w < p.nw; w++)
+    for (uint32_t x = S[w] & a[w]; x; x &= x - 1) {
+      const int64_t s = st[w * 32 + hg_ctz(x)];
+      best = s < best ? s : best;
+    }
+  return best;
+}
+
+// hg_flow_step with starts: byte c at write position i; src holds the starts of S, dst receives those of the new S.
+HG_HD void hg_flow_som_step(const uint32_t *pool, const HgPattern &p, uint32_t *S, HgSomStarts src, HgSomStarts dst, uint32_t pc, uint32_t c, uint32_t cc,
+                            int64_t i) {
+  const uint32_t nw = p.nw;
+  const uint32_t *follow = pool + p.follow_off, *init = pool + p.init_off, *pred = pool + p.som_follow_off;
+  const uint32_t *r = pool + p.reach_off + c * nw, *m = pool + p.amask_off + (pc * 4 + cc) * nw;
+  uint32_t T[HG_FLOW_SOM_W];
+  for (uint32_t w = 0; w < nw; w++) T[w] = init[w];
+  for (uint32_t w = 0; w < nw; w++)
+    for (uint32_t x = S[w]; x; x &= x - 1) {
+      const uint32_t *f = follow + (w * 32 + hg_ctz(x)) * nw;
+      for (uint32_t k = 0; k < nw; k++) T[k] |= f[k];
+    }
+  for (uint32_t w = 0; w < nw; w++) T[w] &= r[w] & m[w];
+  for (uint32_t w = 0; w < nw; w++)
+    for (uint32_t x = T[w]; x; x &= x - 1) {
+      const uint32_t b = hg_ctz(x), t = w * 32 + b;
+      int64_t best = (init[w] >> b) & 1u ? i : HG_SOM_NONE;
+      const uint32_t *q = pred + t * nw;
+      for (uint32_t v = 0; v < nw; v++)
+        for (uint32_t y = S[v] & q[v]; y; y &= y - 1) {
+          const int64_t s = src[v * 32 + hg_ctz(y)];
+          best = s < best ? s : best;
+        }
+      dst[t] = best;
+    }
+  for (uint32_t w = 0; w < nw; w++) S[w] = T[w];
+}
+
+// Positions [from, stop) of a write data[0, stop...) for one SOM expression, serially (no slices: a start is not linear in
+// the state).  *st / *tmp: the starts of S and a second buffer, swapped per byte.  emit(i, start) per position whose test
+// holds; returns 1 if something was emitted.  The other arguments are hg_flow_scan_slice's.
+template <typename Emit>
+HG_HD uint32_t hg_flow_som_scan(const uint32_t *pool, const HgPattern &p, const uint8_t *data, uint32_t from, uint32_t stop, uint32_t final_nl, uint32_t *S,
+                                HgSomStarts *st, HgSomStarts *tmp, uint32_t pc, bool skip, Emit &&emit) {
+  uint32_t emitted = 0;
+  for (uint32_t i = from; i < stop; i++) {
+    const uint32_t c = data[i];
+    const uint32_t cc = hg_flow_ctx(c, i == final_nl);
+    if (!(skip && i == from)) {
+      const int64_t s = hg_flow_som_min(pool, p, S, *st, pc, cc);
+      if (s != HG_SOM_NONE) {
+        emit(static_cast<int32_t>(i), s);
+        emitted = 1;
+      }
+    }
+    hg_flow_som_step(pool, p, S, *st, *tmp, pc, c, cc, static_cast<int64_t>(i));
+    const HgSomStarts x = *st;
+    *st = *tmp;
+    *tmp = x;
+    pc = hg_prev_ctx(c);
+  }
+  return emitted;
+}
+
+// hg_flow_unhold with starts: the held '\n' sits at write position `at`.
+template <typename Emit>
+HG_HD uint32_t hg_flow_som_unhold(const uint32_t *pool, const HgPattern &p, uint32_t *S, HgSomStarts *st, HgSomStarts *tmp, uint32_t *pc, int32_t at, bool final,
+                                  bool skip, Emit &&emit) {
+  const uint32_t cc = final ? HG_NC_NLFINAL : HG_NC_NL;
+  uint32_t emitted = 0;
+  if (!skip) {
+    const int64_t s = hg_flow_som_min(pool, p, S, *st, *pc, cc);
+    if (s != HG_SOM_NONE) {
+      emit(at, s);
+      emitted = 1;
+    }
+  }
+  hg_flow_som_step(pool, p, S, *st, *tmp, *pc, '\n', cc, at);
+  const HgSomStarts x = *st;
+  *st = *tmp;
+  *tmp = x;
+  *pc = HG_PC_NL;
+  return emitted;
+}
+
+// hg_flow_finish with starts.  A test is delivered early only if every context still possible accepts with the SAME
+// smallest start (the accepting nodes may differ by context), and never for HG_FLOW_LATE expressions.
+template <typename Emit>
+HG_HD uint32_t hg_flow_som_finish(const uint32_t *pool, const HgPattern &p, uint32_t *S, HgSomStarts *st, HgSomStarts *tmp, uint32_t pc, uint32_t hdr, int32_t stop,
+                                  bool held, bool acc_done, bool close, Emit &&emit) {
+  hdr &= HG_FLOW_HOLD | HG_FLOW_LATE;
+  if (close) {
+    if (held) {
+      hg_flow_som_unhold(pool, p, S, st, tmp, &pc, stop, true, acc_done, emit);
+      stop++;
+      acc_done = false;
+    }
+    if (!acc_done) {
+      const int64_t s = hg_flow_som_min(pool, p, S, *st, pc, HG_NC_END);
+      if (s != HG_SOM_NONE) emit(stop, s);
+    }
+    return hdr | pc;
+  }
+  if (!acc_done && !(hdr & HG_FLOW_LATE)) {
+    int64_t first = HG_SOM_NONE;
+    bool all = true;
+    for (uint32_t cc = 0; cc < 5 && all; cc++)
+      if (!held || cc == HG_NC_NL || cc == HG_NC_NLFINAL) {
+        const int64_t s = hg_flow_som_min(pool, p, S, *st, pc, cc);
+        all = s != HG_SOM_NONE && (first == HG_SOM_NONE || s == first);
+        first = s;
+      }
+    if (all) {
+      emit(stop, first);
+      acc_done = true;
+    }
+  }
+  return hdr | pc | (acc_done ? HG_FLOW_ACC_DONE : 0u) | (held ? HG_FLOW_HELD : 0u);
+}
+
+// One write data[0, len) of a SOM expression (close: the stream's data ends with it): what one lane of hg_flow_som_kernel
+// runs.  hdr / S: the carried header and state words, *st their starts relative to this write; on return S and *st are
+// those of the new carried position, whose write-relative index *carried receives.  emit(i, start) per report at write
+// position i (-1: a '\n' held by the previous write).  Returns the new header word.
+template <typename Emit>
+HG_HD uint32_t hg_flow_som_write(const uint32_t *pool, const HgPattern &p, const uint8_t *data, uint32_t len, bool close, uint32_t hdr, uint32_t *S,
+                                 HgSomStarts *st, HgSomStarts *tmp, int32_t *carried, Emit &&emit) {
+  uint32_t pc = hdr & HG_FLOW_PC;
+  bool held = (hdr & HG_FLOW_HELD) != 0, acc_done = (hdr & HG_FLOW_ACC_DONE) != 0;
+  int32_t stop = held ? -1 : 0;
+  if (len > 0) {
+    if (held) {
+      hg_flow_som_unhold(pool, p, S, st, tmp, &pc, -1, false, acc_done, emit);
+      acc_done = false;
+    }
+    const bool held_now = !close && data[len - 1] == '\n' && (hdr & HG_FLOW_HOLD);
+    const uint32_t stop_w = held_now ? len - 1 : len;
+    if (stop_w > 0) {
+      hg_flow_som_scan(pool, p, data, 0, stop_w, close ? len - 1 : HG_NONE32, S, st, tmp, pc, acc_done, emit);
+      pc = hg_prev_ctx(data[stop_w - 1]);
+      acc_done = false;
+    }
+    held = held_now;
+    stop = static_cast<int32_t>(stop_w);
+  }
+  *carried = stop;
+  hdr = hg_flow_som_finish(pool, p, S, st, tmp, pc, hdr, stop, held, acc_done, close, emit);
+  if (close) *carried = 0;  // (the stream is reset after its close: nothing is carried)
+  return hdr;
+}
+
+// Carried starts <-> write-relative starts.  A live node at carried position `pos` began at most at pos - 1, so the
+// distance d = pos - start is at least 1 and d - 1 is stored, saturated at the width's largest value (2 and 4 bytes:
+// d > 2^16 - 1 resp. 2^32 - 1, a start past the horizon; 8 bytes never saturate).  Dead nodes store 0.
+HG_HD void hg_flow_som_load(const uint32_t *words, uint32_t width, const uint32_t *S, uint32_t nw, int64_t pos, HgSomStarts st) {
+  for (uint32_t w = 0; w < nw; w++)
+    for (uint32_t x = S[w]; x; x &= x - 1) {
+      const uint32_t t = w * 32 + hg_ctz(x);
+      uint64_t v;
+      bool sat;
+      if (width == 2) {
+        v = (words[t >> 1] >> ((t & 1u) * 16u)) & 0xFFFFu;
+        sat = v == 0xFFFFu;
+      } else if (width == 4) {
+        v = words[t];
+        sat = v == 0xFFFFFFFFu;
+      } else {
+        v = words[2 * t] | (static_cast<uint64_t>(words[2 * t + 1]) << 32);
+        sat = false;
+      }
+      st[t] = sat ? HG_SOM_FAR : pos - 1 - static_cast<int64_t>(v);
+    }
+}
+HG_HD uint64_t hg_flow_som_dist(const uint32_t *S, HgSomStarts st, uint32_t t, int64_t pos, uint64_t sat) {
+  if (!((S[t >> 5] >> (t & 31u)) & 1u)) return 0;
+  if (st[t] == HG_SOM_FAR) return sat;
+  const uint64_t d = static_cast<uint64_t>(pos - st[t] - 1);
+  return d < sat ? d : sat;
+}
+HG_HD void hg_flow_som_store(uint32_t *words, uint32_t width, const uint32_t *S, uint32_t nnodes, int64_t pos, HgSomStarts st) {
+  const uint32_t n = hg_flow_som_words(nnodes, width);
+  for (uint32_t k = 0; k < n; k++) {
+    uint32_t v;
+    if (width == 2) {
+      v = static_cast<uint32_t>(hg_flow_som_dist(S, st, 2 * k, pos, 0xFFFFu));
+      if (2 * k + 1 < nnodes) v |= static_cast<uint32_t>(hg_flow_som_dist(S, st, 2 * k + 1, pos, 0xFFFFu)) << 16;
+    } else if (width == 4) {
+      v = static_cast<uint32_t>(hg_flow_som_dist(S, st, k, pos, 0xFFFFFFFFu));
+    } else {
+      v = static_cast<uint32_t>(hg_flow_som_dist(S, st, k >> 1, pos, ~0ull) >> ((k & 1u) * 32u));
+    }
+    words[k] = v;
+  }
 }
 
 // Confirm by WINDOW: what the device's confirm routines for SINGLEMATCH automata compute (hg_confirm_dev.h has the argument).

@@ -32,7 +32,14 @@ struct HgFlowArgs {
   uint32_t seq;                // written to h_flag[1] when every workgroup is done
   uint32_t *d_total, *d_done;  // device counters, zero between launches (the last workgroup resets them)
   uint32_t *h_flag;            // pinned: [0] reports of the launch, [1] sequence number
+  // start of match (HS_MODE_SOM_HORIZON_*): hg_flow_som_kernel runs the SOM expressions, one lane per (item, expression),
+  // before hg_flow_scan_kernel, which leaves them alone.  nsom == 0: not launched.
+  const uint32_t *som_list;  // device: the nsom SOM expressions, then per SOM expression the nodes of those before it
+  uint32_t nsom;
+  uint32_t som_width;        // bytes per carried start: 2, 4 or 8
+  int64_t *som_work;         // device: nitems x 2 x (nodes of all SOM expressions) starts (hg_flow_som_kernel has the layout)
+  int64_t *from_out;         // pinned, beside `out`: a SOM expression's report's write-relative start
 };
 
-// Launches hg_flow_scan_kernel over nitems items; 0 or -1.
+// Launches hg_flow_som_kernel (if args.nsom) then hg_flow_scan_kernel over nitems items; 0 or -1.
 int hg_flow_launch(const HgFlowArgs &args, uint32_t nitems, hipStream_t stream);

@@ -10,6 +10,7 @@
 // twice are emitted once (a bitmap of ends per expression).  After the last piece one lane per expression applies the
 // write-end rules (hg_flow_finish) and writes the state back.  Reports go to one pinned array through a device counter;
 // the last workgroup to finish publishes the count and the call's sequence number in pinned memory.
+// Expressions with start of match (HS_MODE_SOM_HORIZON_*) run in hg_flow_som_kernel instead, launched first.
 #include <hip/hip_runtime.h>
 
 #include "hg_engine.h"
@@ -40,6 +41,7 @@ __global__ __launch_bounds__(256) void hg_flow_scan_kernel(HgFlowArgs a) {
   const uint32_t j = threadIdx.x % npat, k = threadIdx.x / npat;  // expression of the group, slice
   HgPattern pat = a.patterns[first + j];
   if (staged) pat.reach_off -= lo, pat.follow_off -= lo, pat.init_off -= lo, pat.amask_off -= lo, pat.acc_off -= lo;
+  const bool som = (pat.flags & HG_FLAG_SOM_LEFTMOST) != 0;  // (run and written back by hg_flow_som_kernel)
   const uint32_t nw = pat.nw;
   const uint32_t off = a.soff[first + j];
   const uint32_t *sin = a.state_in + static_cast<uint64_t>(item) * a.swords + off;
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(256) void hg_flow_scan_kernel(HgFlowArgs a) {
     __syncthreads();
     const uint32_t slice_len = max(8u, (plen + most - 1) / most);
     const uint32_t nslices = (plen + slice_len - 1) / slice_len;
-    if (!dead && !gone && k < nslices) {
+    if (!dead && !som && !gone && k < nslices) {
       const uint32_t from = k * slice_len, upto = min(from + slice_len, plen);
       const uint32_t pstop = min(stop_w - pbase, plen);
       for (uint32_t w = 0; w < HG_MAX_W; w++) S[w] = 0;
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(256) void hg_flow_scan_kernel(HgFlowArgs a) {
     }
     __syncthreads();
   }
-  if (k == 0) {  // the write's end: one lane per expression
+  if (k == 0 && !som) {  // the write's end: one lane per expression
     for (uint32_t w = 0; w < HG_MAX_W; w++) S[w] = 0;
     uint32_t h = hdr;
     if (!dead) {
@@ -150,10 +152,51 @@ __global__ __launch_bounds__(256) void hg_flow_scan_kernel(HgFlowArgs a) {
   }
 }
 
+// Start of match (HS_MODE_SOM_HORIZON_*): one lane per (item, SOM expression) walks the item's write serially
+// (hg_flow_som_write: a start is the minimum over predecessors, not linear in the state, so the write is not sliced).  The
+// starts of the automaton's nodes live in two buffers of device memory per lane (no per-node array in registers, where the
+// compiler would put it in scratch).  Lanes are expression-major (neighbouring lanes: one expression, consecutive items) and
+// the buffers node-major: SOM expression k owns 2 x nitems x nnodes starts from nitems x 2 x (nodes of the SOM expressions
+// before k), node t of item i at t x nitems + i, so lanes that touch the same node touch neighbouring words.  Reports go to the same array and counter as hg_flow_scan_kernel's, with the start in
+// from_out; that kernel runs next on the stream and publishes the count.
+__global__ __launch_bounds__(64) void hg_flow_som_kernel(HgFlowArgs a, uint32_t nitems) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= nitems * a.nsom) return;
+  const uint32_t k = g / nitems, item = g % nitems, e = a.som_list[k];
+  const HgFlowItem it = a.items[item];
+  const HgPattern pat = a.patterns[e];
+  const uint32_t nw = pat.nw;
+  const uint32_t *sin = a.state_in + static_cast<uint64_t>(item) * a.swords + a.soff[e];
+  uint32_t *sout = a.state_out + static_cast<uint64_t>(item) * a.swords + a.soff[e];
+  int64_t *base = a.som_work + static_cast<uint64_t>(nitems) * 2u * a.som_list[a.nsom + k] + item;
+  HgSomStarts st{base, nitems}, tmp{base + static_cast<uint64_t>(nitems) * pat.nnodes, nitems};
+  const uint32_t hdr = sin[0];
+  uint32_t S[HG_FLOW_SOM_W];
+  for (uint32_t w = 0; w < HG_FLOW_SOM_W; w++) S[w] = w < nw ? sin[1 + w] : 0u;
+  hg_flow_som_load(sin + 1 + nw, a.som_width, S, nw, (hdr & HG_FLOW_HELD) ? -1 : 0, st);
+  int32_t carried = 0;
+  const uint32_t h = hg_flow_som_write(a.pool, pat, a.text + it.text_off, it.len, (it.flags & HG_FLOW_ITEM_CLOSE) != 0, hdr, S, &st, &tmp, &carried,
+                                       [&](int32_t i, int64_t s) {
+                                         const uint32_t slot = atomicAdd(a.d_total, 1u);
+                                         if (slot < a.cap) {
+                                           a.out[slot] = HgHit{(static_cast<uint64_t>(e) << 32) | item, pat.id, static_cast<uint32_t>(i + 1)};
+                                           a.from_out[slot] = s;
+                                         }
+                                       });
+  sout[0] = h;
+  for (uint32_t w = 0; w < nw; w++) sout[1 + w] = S[w];
+  hg_flow_som_store(sout + 1 + nw, a.som_width, S, pat.nnodes, carried, st);
+}
+
 int hg_flow_launch(const HgFlowArgs &args, uint32_t nitems, hipStream_t stream) {
   if (nitems == 0 || args.ngroups == 0) return -1;
   const uint64_t grid = static_cast<uint64_t>(nitems) * args.ngroups;
   if (grid > 0x7FFFFFFFull) return -1;
+  if (args.nsom) {
+    const uint64_t lanes = static_cast<uint64_t>(nitems) * args.nsom;
+    if (lanes > 0xFFFFFFFFull) return -1;
+    hipLaunchKernelGGL(hg_flow_som_kernel, dim3(static_cast<uint32_t>((lanes + 63) / 64)), dim3(64), 0, stream, args, nitems);
+  }
   hipLaunchKernelGGL(hg_flow_scan_kernel, dim3(static_cast<uint32_t>(grid)), dim3(256), 0, stream, args);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -22,12 +22,23 @@
 #include "hg_flows.h"
 #include "hg_mem.h"
 
+namespace {
+constexpr uint32_t FLOW_LAUNCH_ITEMS = 1u << 16;      // items one stream-mode launch takes at most
+constexpr uint64_t FLOW_SOM_WORK_MAX = 256ull << 20;  // bytes of the SOM lanes' start buffers one launch may take
+}  // namespace
+
 // Stream-mode data of a database (none in block mode): where each expression's words sit in a stream's state, and the state
 // of a freshly opened stream (header words: HG_PC_START, HG_FLOW_HOLD where the expression holds a trailing '\n').
 struct HgFlowDb {
   std::vector<uint32_t> soff;  // npatterns
   std::vector<uint32_t> init;  // swords
   uint32_t swords = 0, ngroups = 0;
+  // start of match (HS_MODE_SOM_HORIZON_*; empty / 0 without): the SOM expressions (hg_flow_som_kernel's lanes), bytes per
+  // carried start (SMALL 2, MEDIUM 4, LARGE 8), the largest SOM automaton, and the horizon (to - from >= 2^horizon_bits:
+  // HS_OFFSET_PAST_HORIZON; 0: exact)
+  std::vector<uint32_t> som;
+  uint32_t som_width = 0, som_total = 0, horizon_bits = 0;
+  uint32_t launch_items = 0;  // items per launch at most (SOM databases: bounded by the SOM lanes' start buffers)
 };
 struct hs_database {
   std::shared_ptr<HgDb> db;
@@ -65,6 +76,11 @@ struct hs_scratch {
   HgHit *f_out = nullptr;
   uint32_t f_out_cap = 0;
   uint32_t *f_flag = nullptr, *f_dctr = nullptr, *f_dsoff = nullptr;
+  // start of match: the pinned starts beside f_out (f_out_cap of them), the SOM expressions on the device, the SOM lanes'
+  // start buffers
+  int64_t *f_from = nullptr, *f_dwork = nullptr;
+  size_t f_work_cap = 0;
+  uint32_t *f_dsom = nullptr;
 };
 
 namespace {
@@ -94,11 +110,20 @@ int hs_compile_ext_multi(const char *const *expressions, const unsigned int *fla
   std::string msg;
   int bad = -1;
   HgDb *raw = nullptr;
-  if (!db || !expressions || elements == 0 || (mode != HS_MODE_BLOCK && mode != HS_MODE_STREAM)) {
-    msg = "invalid arguments (block or stream mode, at least one expression)";
+  // a horizon bit: stream mode with start of match (include/hypergrep_amd.h, stream mode rule 7)
+  const unsigned int horizon = mode & (HS_MODE_SOM_HORIZON_LARGE | HS_MODE_SOM_HORIZON_MEDIUM | HS_MODE_SOM_HORIZON_SMALL);
+  mode &= ~horizon;
+  bool any_som = false;
+  for (unsigned int i = 0; flags && expressions && i < elements; i++) any_som = any_som || (flags[i] & HS_FLAG_SOM_LEFTMOST);
+  if (!db || !expressions || elements == 0 || (mode != HS_MODE_BLOCK && mode != HS_MODE_STREAM) || (horizon & (horizon - 1)) ||
+      (horizon && mode != HS_MODE_STREAM)) {
+    msg = "invalid arguments (block or stream mode, at most one HS_MODE_SOM_HORIZON_* bit with stream mode, at least one expression)";
+  } else if (horizon && !any_som) {
+    msg = "invalid mode: an HS_MODE_SOM_HORIZON_* bit needs at least one HS_FLAG_SOM_LEFTMOST expression";
   } else if (mode == HS_MODE_STREAM && flags) {  // stream mode: what a flow cannot carry (include/hypergrep_amd.h, rule 7)
     for (unsigned int i = 0; i < elements && bad < 0; i++) {
-      const char *rule = (flags[i] & HS_FLAG_SOM_LEFTMOST) ? "HS_FLAG_SOM_LEFTMOST is not supported in stream mode"
+      const char *rule = (flags[i] & HS_FLAG_SOM_LEFTMOST) && !horizon
+                             ? "HS_FLAG_SOM_LEFTMOST in stream mode needs an HS_MODE_SOM_HORIZON_* mode bit"
                          : (flags[i] & HS_FLAG_COMBINATION) ? "HS_FLAG_COMBINATION is not supported in stream mode"
                          : (flags[i] & HS_FLAG_QUIET)       ? "HS_FLAG_QUIET is not supported in stream mode"
                                                             : nullptr;
@@ -111,17 +136,26 @@ int hs_compile_ext_multi(const char *const *expressions, const unsigned int *fla
     if (mode == HS_MODE_STREAM) {
       flow = std::make_shared<HgFlowDb>();
       const uint32_t np = static_cast<uint32_t>(owned->patterns.size());
-      for (uint32_t i = 0; i < np && bad < 0; i++)
-        if (owned->patterns[i].nw > HG_MAX_W)
+      for (uint32_t i = 0; i < np && bad < 0; i++) {
+        const HgPattern &p = owned->patterns[i];
+        if (p.nw > HG_MAX_W)
           bad = static_cast<int>(i), msg = "expression " + std::to_string(i) + ": automaton of more than 1024 positions, too large for stream mode";
-      if (bad >= 0) goto fail;
-      const std::vector<bool> hold = hg_flow_hold_flags(owned->pool.data(), owned->patterns.data(), np);
-      for (uint32_t i = 0; i < np; i++) {
-        flow->soff.push_back(flow->swords);
-        flow->init.push_back(HG_PC_START | (hold[i] ? HG_FLOW_HOLD : 0u));
-        flow->init.resize(flow->init.size() + owned->patterns[i].nw, 0u);
-        flow->swords += 1 + owned->patterns[i].nw;
+        else if ((p.flags & HG_FLAG_SOM_LEFTMOST) && p.nnodes > HG_FLOW_SOM_NODES)
+          bad = static_cast<int>(i), msg = "expression " + std::to_string(i) + ": automaton of more than " + std::to_string(HG_FLOW_SOM_NODES) +
+                                           " positions, too large for start of match in stream mode";
       }
+      if (bad >= 0) goto fail;
+      flow->som_width = horizon == HS_MODE_SOM_HORIZON_SMALL ? 2u : horizon == HS_MODE_SOM_HORIZON_MEDIUM ? 4u : horizon ? 8u : 0u;
+      flow->horizon_bits = horizon == HS_MODE_SOM_HORIZON_SMALL ? 16u : horizon == HS_MODE_SOM_HORIZON_MEDIUM ? 32u : 0u;
+      HgFlowLayout l = hg_flow_layout(owned->pool.data(), owned->patterns.data(), np, flow->som_width);
+      flow->soff = std::move(l.soff);
+      flow->init = std::move(l.init);
+      flow->som = std::move(l.som);
+      flow->swords = l.swords;
+      flow->som_total = l.som_total;
+      flow->launch_items = FLOW_LAUNCH_ITEMS;
+      if (l.som_total)  // 2 x 8 bytes per node of every SOM expression and item: at most FLOW_SOM_WORK_MAX bytes per launch
+        flow->launch_items = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(FLOW_LAUNCH_ITEMS, FLOW_SOM_WORK_MAX / (16ull * l.som_total))));
       flow->ngroups = (np + HG_FLOW_PPW - 1) / HG_FLOW_PPW;
     }
     *db = new hs_database{owned, mode, flow};
@@ -196,6 +230,9 @@ int hs_free_scratch(hs_scratch_t *scratch) {
   hgmem::host_free(scratch->f_flag, "hs f_flag");
   hgmem::dev_free(scratch->f_dctr, "hs f_dctr");
   hgmem::dev_free(scratch->f_dsoff, "hs f_dsoff");
+  hgmem::host_free(scratch->f_from, "hs f_from");
+  hgmem::dev_free(scratch->f_dwork, "hs f_dwork");
+  hgmem::dev_free(scratch->f_dsom, "hs f_dsom");
   if (scratch->stream) (void)hipStreamDestroy(scratch->stream);
   delete scratch;
   return HS_SUCCESS;
@@ -303,7 +340,6 @@ int hs_scan(const hs_database_t *db, const char *data, unsigned int length, unsi
 // ------------------------------------------------------------------------------------------------ stream mode ------
 namespace {
 constexpr uint64_t FLOW_LAUNCH_BYTES = 64u << 20;  // bytes of writes one launch takes at most (a longer write: several launches)
-constexpr uint32_t FLOW_LAUNCH_ITEMS = 1u << 16;
 
 // Writes of a launch are copied to HBM once (instead of every workgroup of an item reading them over the host link) when
 // bytes x workgroups per item reach this (tools/stream_bench.py measures it; HG_FLOW_HBM_MIN overrides it)
@@ -348,7 +384,24 @@ int flow_setup(hs_scratch_t *sc, const HgFlowDb &f) {
     if (hgmem::dev_alloc(&sc->f_dsoff, f.soff.size() * sizeof(uint32_t) + 16, "hs f_dsoff") != hipSuccess) return HS_NOMEM;
     if (hipMemcpy(sc->f_dsoff, f.soff.data(), f.soff.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return HS_NOMEM;
   }
+  if (!f.som.empty() && !sc->f_dsom) {
+    if (hgmem::dev_alloc(&sc->f_dsom, f.som.size() * sizeof(uint32_t) + 16, "hs f_dsom") != hipSuccess) return HS_NOMEM;
+    if (hipMemcpy(sc->f_dsom, f.som.data(), f.som.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return HS_NOMEM;  // (and the offsets)
+  }
   return HS_SUCCESS;
+}
+
+// The pinned report array and, for SOM databases, the starts beside it: room for `cap` reports.
+bool flow_out_alloc(hs_scratch_t *sc, const HgFlowDb &f, uint32_t cap) {
+  hgmem::host_free(sc->f_out, "hs f_out");
+  hgmem::host_free(sc->f_from, "hs f_from");
+  sc->f_out = nullptr;
+  sc->f_from = nullptr;
+  sc->f_out_cap = 0;
+  if (hgmem::host_alloc(&sc->f_out, static_cast<size_t>(cap) * sizeof(HgHit), "hs f_out") != hipSuccess) return false;
+  if (!f.som.empty() && hgmem::host_alloc(&sc->f_from, static_cast<size_t>(cap) * sizeof(int64_t), "hs f_from") != hipSuccess) return false;
+  sc->f_out_cap = cap;
+  return true;
 }
 
 // One launch over `reqs` (distinct streams): their writes scanned, their states advanced; the reports of each request after
@@ -384,7 +437,8 @@ int flow_launch(hs_scratch_t *sc, const HgFlowDb &f, const std::vector<FlowReq> 
     std::memcpy(sc->f_sin + static_cast<size_t>(i) * f.swords, r.s->state.data(), f.swords * sizeof(uint32_t));
   }
   const uint8_t *text = sc->f_text;
-  if (bytes && bytes * f.ngroups >= flow_hbm_min()) {
+  // (the SOM lanes read their write byte by byte: from HBM always, not over the host link)
+  if (bytes && (bytes * f.ngroups >= flow_hbm_min() || !f.som.empty())) {
     if (sc->f_dtext_cap < bytes) {
       hgmem::dev_free(sc->f_dtext, "hs f_dtext");
       sc->f_dtext = nullptr;
@@ -396,13 +450,18 @@ int flow_launch(hs_scratch_t *sc, const HgFlowDb &f, const std::vector<FlowReq> 
     if (hipMemcpyAsync(sc->f_dtext, sc->f_text, bytes, hipMemcpyHostToDevice, sc->stream) != hipSuccess) return HS_INVALID;
     text = sc->f_dtext;
   }
+  const size_t work = static_cast<size_t>(n) * 2 * f.som_total;  // int64 starts of the SOM lanes (n <= f.launch_items)
+  if (sc->f_work_cap < work) {
+    hgmem::dev_free(sc->f_dwork, "hs f_dwork");
+    sc->f_dwork = nullptr;
+    sc->f_work_cap = 0;
+    if (hgmem::dev_alloc(&sc->f_dwork, work * sizeof(int64_t) + 16, "hs f_dwork") != hipSuccess) return HS_NOMEM;
+    sc->f_work_cap = work;
+  }
   const HgDbView &v = sc->sc->view();
   uint32_t total = 0;
   for (;;) {
-    if (sc->f_out_cap == 0) {
-      if (hgmem::host_alloc(&sc->f_out, 4096 * sizeof(HgHit), "hs f_out") != hipSuccess) return HS_NOMEM;
-      sc->f_out_cap = 4096;
-    }
+    if (sc->f_out_cap == 0 && !flow_out_alloc(sc, f, 4096)) return HS_NOMEM;
     const uint32_t seq = ++sc->seq ? sc->seq : ++sc->seq;
     HgFlowArgs a{};
     a.patterns = v.patterns;
@@ -421,6 +480,11 @@ int flow_launch(hs_scratch_t *sc, const HgFlowDb &f, const std::vector<FlowReq> 
     a.d_total = sc->f_dctr;
     a.d_done = sc->f_dctr + 1;
     a.h_flag = sc->f_flag;
+    a.som_list = sc->f_dsom;
+    a.nsom = static_cast<uint32_t>(f.som.size() / 2);
+    a.som_width = f.som_width;
+    a.som_work = sc->f_dwork;
+    a.from_out = sc->f_from;
     if (hg_flow_launch(a, n, sc->stream) != 0) return HS_INVALID;
     volatile uint32_t *flag = sc->f_flag + 1;
     bool done = false;
@@ -431,27 +495,27 @@ int flow_launch(hs_scratch_t *sc, const HgFlowDb &f, const std::vector<FlowReq> 
     total = sc->f_flag[0];
     if (total <= sc->f_out_cap) break;
     // more reports than room: the states in f_sin are untouched, the launch is repeated with room for all
-    hgmem::host_free(sc->f_out, "hs f_out");
-    sc->f_out = nullptr;
-    sc->f_out_cap = 0;
-    if (hgmem::host_alloc(&sc->f_out, static_cast<size_t>(total) * 2 * sizeof(HgHit), "hs f_out") != hipSuccess) return HS_NOMEM;
-    sc->f_out_cap = total * 2;
+    if (!flow_out_alloc(sc, f, total * 2)) return HS_NOMEM;
   }
   // the report rules, per request (hg_flow_rules.h)
   const HgDb &db = *sc->db;
+  const bool som = f.som_total != 0;
   std::vector<std::vector<std::pair<uint32_t, uint32_t>>> per(n);
+  std::vector<std::vector<int64_t>> per_from(som ? n : 0);
   for (uint32_t i = 0; i < total; i++) {
     const HgHit &h = sc->f_out[i];
     per[h.line_no & 0xFFFFFFFFu].emplace_back(static_cast<uint32_t>(h.line_no >> 32), h.to);
+    if (som) per_from[h.line_no & 0xFFFFFFFFu].push_back(sc->f_from[i]);  // (read for SOM expressions only)
   }
   int rc = HS_SUCCESS;
   std::vector<HgFlowRep> reps;
   for (uint32_t i = 0; i < n; i++) {
     hs_stream_t *s = reqs[i].s;
     std::memcpy(s->state.data(), sc->f_sout + static_cast<size_t>(i) * f.swords, f.swords * sizeof(uint32_t));
-    hg_flow_rules(db.patterns.data(), db.bounds.empty() ? nullptr : db.bounds.data(), s->rules, reqs[i].len, per[i].data(), per[i].size(), reps);
+    hg_flow_rules(db.patterns.data(), db.bounds.empty() ? nullptr : db.bounds.data(), s->rules, reqs[i].len, per[i].data(), per[i].size(), reps,
+                  som ? per_from[i].data() : nullptr, f.horizon_bits);
     for (const HgFlowRep &x : reps)
-      if (!s->terminated && on_event(reqs[i].item, x.id, x.to) != 0) s->terminated = true;
+      if (!s->terminated && on_event(reqs[i].item, x.id, x.from, x.to) != 0) s->terminated = true;
     if (s->terminated) rc = HS_SCAN_TERMINATED;
   }
   return rc;
@@ -480,21 +544,26 @@ int flow_batch(hs_scratch_t *sc, hs_stream_t *const *streams, const char *const 
   // delivered in (to, id) order then, so that one call's reports stay ordered (a cut is not a write boundary for the caller)
   constexpr uint32_t NO_ITEM = 0xFFFFFFFFu;
   uint32_t cut_item = NO_ITEM;
-  std::vector<std::pair<uint64_t, uint32_t>> held;
-  auto deliver = [&](uint32_t item, uint32_t id, uint64_t to) {
+  struct Held {
+    uint64_t to;
+    uint32_t id;
+    uint64_t from;
+  };
+  std::vector<Held> held;
+  auto deliver = [&](uint32_t item, uint32_t id, uint64_t from, uint64_t to) {
     if (item == cut_item) {
-      held.emplace_back(to, id);
+      held.push_back(Held{to, id, from});
       return 0;
     }
-    return on_event(item, id, to);
+    return on_event(item, id, from, to);
   };
   auto flush = [&](bool cut_done) {
     int r = reqs.empty() ? HS_SUCCESS : flow_launch(sc, f, reqs, deliver);
     if (cut_done && cut_item != NO_ITEM) {
       hs_stream_t *s = streams[cut_item];
-      std::sort(held.begin(), held.end());
-      for (const auto &x : held)
-        if (!s->terminated && on_event(cut_item, x.second, x.first) != 0) s->terminated = true;
+      std::stable_sort(held.begin(), held.end(), [](const Held &a, const Held &b) { return a.to != b.to ? a.to < b.to : a.id < b.id; });
+      for (const Held &x : held)
+        if (!s->terminated && on_event(cut_item, x.id, x.from, x.to) != 0) s->terminated = true;
       if (s->terminated && r == HS_SUCCESS) r = HS_SCAN_TERMINATED;
       held.clear();
       cut_item = NO_ITEM;
@@ -523,7 +592,7 @@ int flow_batch(hs_scratch_t *sc, hs_stream_t *const *streams, const char *const 
         if (last && all) flow_reset(s);  // (its LAST still resets it)
       }
       done += room;
-      if (cut || bytes >= FLOW_LAUNCH_BYTES || reqs.size() >= FLOW_LAUNCH_ITEMS) {
+      if (cut || bytes >= FLOW_LAUNCH_BYTES || reqs.size() >= f.launch_items) {
         const int r = flush(all);
         if (r != HS_SUCCESS && r != HS_SCAN_TERMINATED) return r;
         if (r == HS_SCAN_TERMINATED) rc = r;
@@ -567,8 +636,8 @@ int hs_scan_stream(hs_stream_t *id, const char *data, unsigned int length, unsig
   hs_stream_t *const streams[1] = {id};
   const char *const datas[1] = {data};
   const unsigned int lengths[1] = {length};
-  return flow_batch(scratch, streams, datas, lengths, nullptr, 1, [&](uint32_t, uint32_t rid, uint64_t to) {
-    return on_event ? on_event(rid, 0, to, 0, context) : 0;
+  return flow_batch(scratch, streams, datas, lengths, nullptr, 1, [&](uint32_t, uint32_t rid, uint64_t from, uint64_t to) {
+    return on_event ? on_event(rid, from, to, 0, context) : 0;
   });
 }
 
@@ -581,7 +650,8 @@ int hs_reset_stream(hs_stream_t *id, unsigned int flags, hs_scratch_t *scratch, 
     const char *const datas[1] = {nullptr};
     const unsigned int lengths[1] = {0};
     const unsigned int last[1] = {HG_STREAM_ITEM_LAST};
-    const int rc = flow_batch(scratch, streams, datas, lengths, last, 1, [&](uint32_t, uint32_t rid, uint64_t to) { return on_event(rid, 0, to, 0, context); });
+    const int rc = flow_batch(scratch, streams, datas, lengths, last, 1,
+                              [&](uint32_t, uint32_t rid, uint64_t from, uint64_t to) { return on_event(rid, from, to, 0, context); });
     if (rc != HS_SUCCESS && rc != HS_SCAN_TERMINATED) return rc;
   }
   flow_reset(id);
@@ -617,8 +687,8 @@ int hg_scan_stream_batch(hs_stream_t *const *streams, const char *const *data, c
   std::sort(seen.begin(), seen.end());
   if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return HS_INVALID;
   if (hipSetDevice(scratch->sc->device()) != hipSuccess) return HS_INVALID;
-  return flow_batch(scratch, streams, data, lengths, item_flags, n, [&](uint32_t item, uint32_t rid, uint64_t to) {
-    return on_event ? on_event(item, rid, 0, to, 0, context) : 0;
+  return flow_batch(scratch, streams, data, lengths, item_flags, n, [&](uint32_t item, uint32_t rid, uint64_t from, uint64_t to) {
+    return on_event ? on_event(item, rid, from, to, 0, context) : 0;
   });
 }
 

@@ -311,6 +311,9 @@ def faceb_next_device(ndev: int) -> int:
 
 # ------------------------------------------------------------------------------------------------ stream mode ------
 HS_MODE_BLOCK, HS_MODE_STREAM = 1, 2
+HS_MODE_SOM_HORIZON_LARGE, HS_MODE_SOM_HORIZON_MEDIUM, HS_MODE_SOM_HORIZON_SMALL = 1 << 24, 1 << 25, 1 << 26
+HS_OFFSET_PAST_HORIZON = (1 << 64) - 1
+SOM_HORIZONS = {"large": HS_MODE_SOM_HORIZON_LARGE, "medium": HS_MODE_SOM_HORIZON_MEDIUM, "small": HS_MODE_SOM_HORIZON_SMALL}
 HS_SUCCESS, HS_INVALID, HS_NOMEM, HS_SCAN_TERMINATED, HS_COMPILER_ERROR, HS_DB_MODE_ERROR = 0, -1, -2, -3, -4, -7
 HG_STREAM_ITEM_LAST = 1
 
@@ -364,10 +367,15 @@ def hs_compile(patterns, flags=None, ids=None, ext=None, mode: int = HS_MODE_STR
 
 class StreamDatabase:
     """Expressions compiled for stream mode (hs_compile_ext_multi with HS_MODE_STREAM; include/hypergrep_amd.h has the
-    contract).  It owns ONE scratch, so a StreamDatabase and its streams must not be used from several threads at once."""
+    contract).  It owns ONE scratch, so a StreamDatabase and its streams must not be used from several threads at once.
+    som_horizon: None, or "large" / "medium" / "small" (HS_MODE_SOM_HORIZON_*: start of match for the expressions with
+    HS_FLAG_SOM_LEFTMOST); with a horizon, reports are (id, from, to) triples, else (id, to) pairs."""
 
-    def __init__(self, patterns, flags=None, ids=None, ext=None, device: int | None = None):
-        h, err = hs_compile(patterns, flags, ids, ext, HS_MODE_STREAM)
+    def __init__(self, patterns, flags=None, ids=None, ext=None, device: int | None = None, som_horizon: str | None = None):
+        if som_horizon is not None and som_horizon not in SOM_HORIZONS:
+            raise ValueError(f"som_horizon must be None or one of {sorted(SOM_HORIZONS)}")
+        self.som = som_horizon is not None
+        h, err = hs_compile(patterns, flags, ids, ext, HS_MODE_STREAM | (SOM_HORIZONS[som_horizon] if self.som else 0))
         if err:
             raise CompileError(err[0])
         self._h = h
@@ -386,15 +394,17 @@ class StreamDatabase:
 
     def scan_streams(self, items, last=None):
         """items: [(Stream, bytes)], each stream at most once; last: one bool per item (end of that stream's data: its
-        end-of-data reports, then a reset).  One hg_scan_stream_batch call; [[(id, to)] per item]."""
+        end-of-data reports, then a reset).  One hg_scan_stream_batch call; [[(id, to)] per item] ((id, from, to) with a
+        horizon)."""
         items = list(items)
         n = len(items)
         out = [[] for _ in range(n)]
         if n == 0:
             return out
+        som = self.som
 
-        def on_event(item, rid, _frm, to, _flags, _ctx):
-            out[item].append((rid, to))
+        def on_event(item, rid, frm, to, _flags, _ctx):
+            out[item].append((rid, frm, to) if som else (rid, to))
             return 0
 
         cb = STREAM_EVENT(on_event)
@@ -436,9 +446,10 @@ class Stream:
 
     def _call(self, fn, *args):
         out = []
+        som = self.db.som
 
-        def on_event(rid, _frm, to, _flags, _ctx):
-            out.append((rid, to))
+        def on_event(rid, frm, to, _flags, _ctx):
+            out.append((rid, frm, to) if som else (rid, to))
             return 0
 
         rc = fn(*args, MATCH_EVENT(on_event), None)
@@ -447,7 +458,7 @@ class Stream:
         return out
 
     def scan(self, data: bytes):
-        """The next write: [(id, to)] delivered by it (to = stream offset)."""
+        """The next write: [(id, to)] delivered by it (to = stream offset; (id, from, to) with a horizon)."""
         return self._call(face_a().hs_scan_stream, self._require(), bytes(data), len(data), 0, self.db._scratch)
 
     def reset(self):

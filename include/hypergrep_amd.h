@@ -85,6 +85,12 @@ typedef int (*match_event_handler)(unsigned int id, unsigned long long from, uns
 #define HS_COMPILER_ERROR (-4)
 #define HS_MODE_BLOCK 1
 #define HS_MODE_STREAM 2
+/* Start of match in stream mode (with HS_MODE_STREAM, exactly one; stream mode rules 1, 3 and 7): the precision of `from`.
+ * LARGE is exact; MEDIUM gives HS_OFFSET_PAST_HORIZON when to - from >= 2^32, SMALL when to - from >= 2^16. */
+#define HS_MODE_SOM_HORIZON_LARGE (1U << 24)
+#define HS_MODE_SOM_HORIZON_MEDIUM (1U << 25)
+#define HS_MODE_SOM_HORIZON_SMALL (1U << 26)
+#define HS_OFFSET_PAST_HORIZON (~0ULL)
 #define HS_DB_MODE_ERROR (-7)
 #define HS_FLAG_CASELESS 1
 #define HS_FLAG_DOTALL 2
@@ -192,15 +198,22 @@ int hs_free_database(hs_database_t *db);
  * be the concatenation of a stream's writes.
  *  1. Equivalence.  For any split of D into writes (empty and 1-byte writes, splits next to a '\n' included), the reports
  *     of all the stream's hs_scan_stream calls plus its close are exactly those hs_scan(D) delivers on a block-mode database
- *     of the same expressions, flags, ids and ext.  `to` is a stream offset (64-bit), `from` is 0.  SINGLEMATCH: one report
- *     per id for the whole stream, the smallest `to` (in bounds).  min_offset / max_offset bound stream offsets.  An
- *     identical (id, to) is delivered once.
+ *     of the same expressions, flags, ids and ext.  `to` is a stream offset (64-bit).  `from` is 0, except for expressions
+ *     with HS_FLAG_SOM_LEFTMOST in a database compiled with an HS_MODE_SOM_HORIZON_* bit: their `from` is the block-mode
+ *     start of match (a stream offset), or HS_OFFSET_PAST_HORIZON when to - from reaches the horizon (MEDIUM 2^32, SMALL
+ *     2^16; LARGE is exact).  SINGLEMATCH: one report per id for the whole stream, the smallest `to` (in bounds).
+ *     min_offset / max_offset bound stream offsets (of `to` only).  An identical (id, to) is delivered once; of several SOM
+ *     expressions sharing the id, with the smallest of their starts.
  *  2. Order.  Within one call reports come in ascending (to, id).  Across a stream's calls `to` never decreases, with one
  *     exception: a write ending in a '\n' at stream offset end - 1 whose step was held (rule 4) may deliver, in the next
  *     call, a report with to = end - 1 after reports with to = end came in the call before.
  *  3. Latency.  A report (id, t) is delivered at the latest by the call whose write holds stream byte t + 1, else by the
  *     close / reset.  Expressions without assertions (^ $ \A \z \Z \b \B, after ext expansion) deliver (id, t) by the
- *     call whose write holds byte t - 1: `foo` at the very end of a write is reported by that call.
+ *     call whose write holds byte t - 1: `foo` at the very end of a write is reported by that call.  A SOM expression
+ *     delivers a write-end test early only when every possible next context gives the same start; a SOM expression that
+ *     shares its report id with another never delivers early (its reports wait for the next byte or the close, by the
+ *     first rule of this item), and holds a trailing '\n' whenever one expression of the id does, so that every report of
+ *     an (id, to) arrives in one call with the smallest `from`.
  *  4. Write boundaries.  The accept test at byte i reads the context of byte i (the next byte of the match).  At the end of
  *     a write, what holds for every possible next context (END included) is delivered at once; the rest is pending, decided
  *     by the next write's first byte or by the end of data at the close, and never delivered twice.  A '\n' is the final
@@ -214,11 +227,20 @@ int hs_free_database(hs_database_t *db);
  *  6. Streams of one database may be interleaved in any order and scanned with any scratch of the database.  A copy
  *     (hs_copy_stream) evolves independently of its original.  A stream lives in host memory; each call copies the pending
  *     writes and states of its streams to the GPU and back in one launch.
- *  7. Compile rules (HS_COMPILER_ERROR, the message names the expression's index and the rule): HS_FLAG_SOM_LEFTMOST (with
- *     or without HS_MODE_SOM_HORIZON_* bits, which are rejected as modes anyway), HS_FLAG_COMBINATION, HS_FLAG_QUIET, and
- *     automata of more than 1024 positions after ext expansion ("too large for stream mode").  Every other expression block
- *     mode accepts is accepted.  Modes other than HS_MODE_BLOCK and HS_MODE_STREAM (HS_MODE_VECTORED, horizon bits,
- *     combinations of modes) are rejected.  Block-mode databases are unchanged by stream mode.
+ *  7. Compile rules (HS_COMPILER_ERROR, the message names the expression's index and the rule): HS_FLAG_SOM_LEFTMOST
+ *     without an HS_MODE_SOM_HORIZON_* bit, HS_FLAG_COMBINATION, HS_FLAG_QUIET, automata of more than 1024 positions after
+ *     ext expansion ("too large for stream mode"), and SOM expressions of more than 256 positions after ext expansion
+ *     ("too large for start of match in stream mode").  Block mode's SOM rules apply (no SOM with SINGLEMATCH; the
+ *     expressions sharing a report id are all SOM or none).  Every other expression block mode accepts is accepted.  Modes:
+ *     HS_MODE_BLOCK, HS_MODE_STREAM, and HS_MODE_STREAM with exactly one horizon bit when at least one expression has
+ *     HS_FLAG_SOM_LEFTMOST; everything else (HS_MODE_VECTORED, a horizon bit with block mode or on a set without SOM
+ *     expressions, two horizon bits) is rejected.  Block-mode databases are unchanged by stream mode.
+ *  8. State.  hs_stream_size grows with the horizon: a SOM expression carries one start per automaton position, 2 (SMALL),
+ *     4 (MEDIUM) or 8 (LARGE) bytes each, a saturating distance from the carried position.  A database without SOM
+ *     expressions has the layout and size of one compiled without a horizon.  hs_copy_stream and hs_reset_stream carry and
+ *     restore the starts.
+ * The horizon and shared-id rules are this project's reading of Hyperscan's documentation, not checked against a Hyperscan
+ * binary.
  * hs_open_stream on a block-mode database and hs_scan on a stream-mode one return HS_DB_MODE_ERROR; hs_alloc_scratch
  * works for both. */
 typedef struct hs_stream hs_stream_t;

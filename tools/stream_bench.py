@@ -2,10 +2,13 @@
 """Stream mode on the GPU (hs_scan_stream / hg_scan_stream_batch): per-call latency, batch throughput and the HBM cut-off.
 
     python tools/stream_bench.py [--quick] [--hbm-child MODE]
+    python tools/stream_bench.py --som [--rounds N]
 
 Prints one line per measurement.  Reports are not delivered to Python (NULL callback), so the numbers are the library's.
 The HBM cut-off (HG_FLOW_HBM_MIN: bytes x workgroups per item from which a launch's writes are copied to HBM first) is
 measured by running the batch legs in child processes with the copy always on (0) and always off (2^62).
+--som: the 4-expression set without the SOM flag and with it (horizons LARGE and SMALL), alternated round by round in one
+process: hs_scan_stream on a 64-byte and on a 1 MiB write, batches of 1024 and 16384 streams with 256 B and 4 KiB writes.
 """
 from __future__ import annotations
 
@@ -90,9 +93,30 @@ def run_batches(quick: bool, only=None):
                       f"writes/s={n / dt:.0f}", flush=True)
 
 
+def run_som(rounds: int):
+    pats, flags = FOUR
+    ids = list(range(len(pats)))
+    dbs = {"plain": device.StreamDatabase(pats, flags, ids),
+           "som_large": device.StreamDatabase(pats, [f | 256 for f in flags], ids, som_horizon="large"),
+           "som_small": device.StreamDatabase(pats, [f | 256 for f in flags], ids, som_horizon="small")}
+    for r in range(rounds):
+        for name, sdb in dbs.items():
+            for size, reps in ((64, 200), (1 << 20, 3)):
+                dt = latency(sdb, size, reps)
+                print(f"som round={r} db={name} latency write={size} us_per_call={dt * 1e6:.1f}", flush=True)
+            for n in (1024, 16384):
+                for size in (256, 4096):
+                    reps = max(2, min(20, (8 << 20) // (n * size)))
+                    dt = batch(sdb, n, size, reps)
+                    print(f"som round={r} db={name} batch streams={n} bytes={size} ms_per_call={dt * 1e3:.3f} "
+                          f"MiB/s={n * size / dt / 2**20:.1f} writes/s={n / dt:.0f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--som", action="store_true", help="start of match: plain against SOM LARGE / SMALL, alternated")
+    ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--hbm-child", choices=["on", "off"], help="(internal) batch legs with the HBM copy forced on / off")
     args = ap.parse_args()
     if args.hbm_child:
@@ -101,6 +125,9 @@ def main():
     import torch  # noqa: F401  (one HIP runtime: torch's)
 
     print(f"device: {torch.cuda.get_device_name(0)}", flush=True)
+    if args.som:
+        run_som(args.rounds)
+        return
     pats, flags = FOUR
     sdb = device.StreamDatabase(pats, flags, list(range(len(pats))))
     for size in (64, 1024, 8192, 1 << 20):

@@ -113,6 +113,12 @@ constexpr uint32_t HG_BLOCK_SLICED_MAX = 2047;   // ... blocks up to this many b
 constexpr uint32_t HG_BLOCK_SLICED_WORDS = 64;   // ... (bitmap of emitted ends per expression: ends 0 .. HG_BLOCK_SLICED_MAX)
 constexpr uint32_t HG_BLOCK_SMALL_MAX = 8192;   // Face A: blocks up to this many bytes take the one-launch path (hg_block_small_kernel)
 constexpr uint32_t HG_BLOCK_SMALL_SEG = 1024;   // ... reports per workgroup (32 or 256 expressions) it can hold
+// The grouping of the short-block paths (hg_block_small_kernel, hg_block_batch_kernel): 32 expressions per workgroup while 64
+// groups hold the set (their tables then usually fit in LDS), else 256; returns the number of groups.
+inline uint32_t hg_block_small_grouping(uint32_t npatterns, uint32_t *ppw) {
+  *ppw = npatterns <= 32u * 64u ? 32u : 256u;
+  return (npatterns + *ppw - 1) / *ppw;
+}
 constexpr uint32_t HG_HIT_REL_SHIFT = 40;  // raw bucketed records: line_no (< 2^40) | line start inside the bucket (< 2^24) << 40
 constexpr uint32_t HG_HIT_SINGLE_BIT = 0x80000000u;  // raw bucketed records: bit 31 of `to` = the expression has HS_FLAG_SINGLEMATCH (`to` < 2^31)
 

@@ -920,9 +920,8 @@ int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint
 }
 
 uint32_t HgScanner::launch_block_small(const uint8_t *h_text, uint32_t nbytes, hipStream_t stream, HgHit *h_out, uint32_t *h_counts, uint32_t *h_flag, uint32_t seq) {
-  // 32 expressions per workgroup while 64 segments hold the set (their tables then usually fit in LDS), else 256
-  const uint32_t ppw = view_.npatterns <= 32u * 64u ? 32u : 256u;
-  const uint32_t segs = (view_.npatterns + ppw - 1) / ppw;
+  uint32_t ppw;
+  const uint32_t segs = hg_block_small_grouping(view_.npatterns, &ppw);
   if (nbytes == 0 || nbytes > HG_BLOCK_SMALL_MAX || segs == 0 || segs > 64 || db_->nhuge) return 0;  // (huge automata: the general path)
   if (hipSetDevice(device_) != hipSuccess) return 0;
   hipLaunchKernelGGL(hg_block_small_kernel, dim3(segs), dim3(256), 0, stream, view_, h_text, nbytes, h_out, static_cast<uint32_t>(HG_BLOCK_SMALL_SEG), h_counts,

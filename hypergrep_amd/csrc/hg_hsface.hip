@@ -1,5 +1,5 @@
 // Face A: the libhs symbols the reference shim links against (hypergrep/lib/c/hyperscanner.c:136,140,165,217,
-// 301,323,324), and stream mode (hs_*_stream, hg_scan_stream_batch: hg_flows.hip, at the end).  hs_scan copies the block to HBM and runs the same stream / filter kernels in
+// 301,323,324), stream mode (hs_*_stream, hg_scan_stream_batch: hg_flows.hip) and the batched block scan (hg_scan_blocks: hg_batch.hip), at the end.  hs_scan copies the block to HBM and runs the same stream / filter kernels in
 // block mode (the buffer is one scan unit, no line splitting), then delivers reports in ascending end offset.
 // Per-call cost is a few launches and two synchronisations, so this face is for compatibility (per-line callers such
 // as the reference shim); bulk scanning goes through hyperscan() / hg_scan_device().
@@ -16,6 +16,8 @@
 #include <vector>
 
 #include "../../include/hypergrep_amd.h"
+#include "hg_batch.h"
+#include "hg_batch_launch.h"
 #include "hg_compile.h"
 #include "hg_engine.h"
 #include "hg_flow_rules.h"
@@ -81,6 +83,15 @@ struct hs_scratch {
   int64_t *f_from = nullptr, *f_dwork = nullptr;
   size_t f_work_cap = 0;
   uint32_t *f_dsom = nullptr;
+  // batched block scan (hg_block_batch_kernel), allocated at the first hg_scan_blocks call: pinned staging of the items' bytes
+  // and their table, the pinned report array, the bytes' HBM copy, the pinned flag words and the kernel's device counters
+  uint8_t *b_text = nullptr, *b_dtext = nullptr;
+  size_t b_text_cap = 0, b_dtext_cap = 0;
+  HgBatchItem *b_items = nullptr, *b_ditems = nullptr;
+  size_t b_items_cap = 0, b_ditems_cap = 0;
+  HgHit *b_out = nullptr;
+  uint32_t b_out_cap = 0;
+  uint32_t *b_flag = nullptr, *b_dctr = nullptr;
 };
 
 namespace {
@@ -92,6 +103,40 @@ inline void cpu_relax() {  // a polite spin-wait hint, whatever the host is
 #else
   std::this_thread::yield();
 #endif
+}
+
+// The general path of a block scan (hs_scan's tail; hg_scan_blocks for what its kernel does not take): the block copied to
+// HBM, HgScanner::scan_block, the reports copied back into scratch->hits / from, their delivery order (to, id) in
+// scratch->order.  HS_SUCCESS or an error.
+int block_general(hs_scratch_t *scratch, const char *data, unsigned int length) {
+  if (scratch->d_cap < length) {
+    hgmem::dev_free(scratch->d_text, "hs d_text");
+    scratch->d_text = nullptr;
+    size_t cap = std::max<size_t>(length, 4096) * 2;
+    if (hgmem::dev_alloc(&scratch->d_text, cap + 16, "hs d_text") != hipSuccess) return HS_NOMEM;
+    scratch->d_cap = cap;
+  }
+  if (hipMemcpyAsync(scratch->d_text, data, length, hipMemcpyHostToDevice, scratch->stream) != hipSuccess) return HS_INVALID;
+  HgScanOutput out{};
+  if (scratch->sc->scan_block(scratch->d_text, length, scratch->stream, &out) != HG_OK) {
+    std::fprintf(stderr, "hypergrep_amd: block scan (hs_scan / hg_scan_blocks): %s\n", scratch->sc->last_error().c_str());
+    return HS_INVALID;
+  }
+  scratch->hits.resize(out.n_hits);
+  scratch->from.assign(out.n_hits, 0u);
+  if (out.n_hits) {
+    if (hipMemcpyAsync(scratch->hits.data(), out.d_hits, out.n_hits * sizeof(HgHit), hipMemcpyDeviceToHost, scratch->stream) != hipSuccess ||
+        (out.d_from && hipMemcpyAsync(scratch->from.data(), out.d_from, out.n_hits * sizeof(uint32_t), hipMemcpyDeviceToHost, scratch->stream) != hipSuccess) ||
+        hipStreamSynchronize(scratch->stream) != hipSuccess)
+      return HS_INVALID;
+  }
+  // device order is (id, to); Hyperscan delivers by ascending end offset (ties by id here)
+  auto &h = scratch->hits;
+  auto &order = scratch->order;
+  order.resize(h.size());
+  for (uint32_t i = 0; i < order.size(); i++) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return h[a].to != h[b].to ? h[a].to < h[b].to : h[a].id < h[b].id; });
+  return HS_SUCCESS;
 }
 }  // namespace
 
@@ -233,6 +278,13 @@ int hs_free_scratch(hs_scratch_t *scratch) {
   hgmem::host_free(scratch->f_from, "hs f_from");
   hgmem::dev_free(scratch->f_dwork, "hs f_dwork");
   hgmem::dev_free(scratch->f_dsom, "hs f_dsom");
+  hgmem::host_free(scratch->b_text, "hs b_text");
+  hgmem::dev_free(scratch->b_dtext, "hs b_dtext");
+  hgmem::host_free(scratch->b_items, "hs b_items");
+  hgmem::dev_free(scratch->b_ditems, "hs b_ditems");
+  hgmem::host_free(scratch->b_out, "hs b_out");
+  hgmem::host_free(scratch->b_flag, "hs b_flag");
+  hgmem::dev_free(scratch->b_dctr, "hs b_dctr");
   if (scratch->stream) (void)hipStreamDestroy(scratch->stream);
   delete scratch;
   return HS_SUCCESS;
@@ -271,66 +323,16 @@ int hs_scan(const hs_database_t *db, const char *data, unsigned int length, unsi
         if (fits) scratch->hits.insert(scratch->hits.end(), scratch->h_out + static_cast<size_t>(g) * HG_BLOCK_SMALL_SEG, scratch->h_out + static_cast<size_t>(g) * HG_BLOCK_SMALL_SEG + n);
       }
       if (fits) {
-        // report rules per id (hg_post.h, restated on the raw records): SINGLEMATCH expressions sharing an id give one
-        // report (the smallest end offset), the others every distinct end offset, identical (id, to) once
-        auto &h = scratch->hits;
-        auto to_of = [](const HgHit &x) { return x.to & ~HG_HIT_SINGLE_BIT; };
-        auto single_of = [](const HgHit &x) { return (x.to & HG_HIT_SINGLE_BIT) != 0; };
-        std::sort(h.begin(), h.end(), [&](const HgHit &a, const HgHit &b) {
-          if (a.id != b.id) return a.id < b.id;
-          if (to_of(a) != to_of(b)) return to_of(a) < to_of(b);
-          return single_of(a) < single_of(b);
-        });
-        size_t kept = 0;
-        bool seen_single = false;
-        for (size_t i = 0; i < h.size(); i++) {
-          if (i == 0 || h[i].id != h[i - 1].id) seen_single = false;
-          const bool dup = i > 0 && h[i].id == h[i - 1].id && to_of(h[i]) == to_of(h[i - 1]);
-          const bool single = single_of(h[i]);
-          const bool keep = !dup && !(single && seen_single);
-          if (single) seen_single = true;
-          if (keep) {
-            HgHit out = h[i];
-            out.to = to_of(h[i]);
-            h[kept++] = out;
-          }
-        }
-        h.resize(kept);
-        std::sort(h.begin(), h.end(), [](const HgHit &a, const HgHit &b) { return a.to != b.to ? a.to < b.to : a.id < b.id; });
-        for (const HgHit &x : h)
+        hg_block_rules(scratch->hits);  // (hg_batch.h: every item of hg_scan_blocks runs the same rules)
+        for (const HgHit &x : scratch->hits)
           if (on_event && on_event(x.id, 0, x.to, 0, context)) return HS_SCAN_TERMINATED;
         return HS_SUCCESS;
       }
     }
   }
-  if (scratch->d_cap < length) {
-    hgmem::dev_free(scratch->d_text, "hs d_text");
-    scratch->d_text = nullptr;
-    size_t cap = std::max<size_t>(length, 4096) * 2;
-    if (hgmem::dev_alloc(&scratch->d_text, cap + 16, "hs d_text") != hipSuccess) return HS_NOMEM;
-    scratch->d_cap = cap;
-  }
-  if (hipMemcpyAsync(scratch->d_text, data, length, hipMemcpyHostToDevice, scratch->stream) != hipSuccess) return HS_INVALID;
-  HgScanOutput out{};
-  if (scratch->sc->scan_block(scratch->d_text, length, scratch->stream, &out) != HG_OK) {
-    std::fprintf(stderr, "hypergrep_amd: hs_scan: %s\n", scratch->sc->last_error().c_str());
-    return HS_INVALID;
-  }
-  scratch->hits.resize(out.n_hits);
-  scratch->from.assign(out.n_hits, 0u);
-  if (out.n_hits) {
-    if (hipMemcpyAsync(scratch->hits.data(), out.d_hits, out.n_hits * sizeof(HgHit), hipMemcpyDeviceToHost, scratch->stream) != hipSuccess ||
-        (out.d_from && hipMemcpyAsync(scratch->from.data(), out.d_from, out.n_hits * sizeof(uint32_t), hipMemcpyDeviceToHost, scratch->stream) != hipSuccess) ||
-        hipStreamSynchronize(scratch->stream) != hipSuccess)
-      return HS_INVALID;
-  }
-  // device order is (id, to); Hyperscan delivers by ascending end offset (ties by id here)
-  auto &h = scratch->hits;
-  auto &order = scratch->order;
-  order.resize(h.size());
-  for (uint32_t i = 0; i < order.size(); i++) order[i] = i;
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return h[a].to != h[b].to ? h[a].to < h[b].to : h[a].id < h[b].id; });
-  for (uint32_t i : order)
+  if (int rc = block_general(scratch, data, length)) return rc;
+  const auto &h = scratch->hits;
+  for (uint32_t i : scratch->order)
     if (on_event && on_event(h[i].id, scratch->from[i], h[i].to, 0, context)) return HS_SCAN_TERMINATED;
   return HS_SUCCESS;
 }
@@ -378,7 +380,8 @@ int flow_setup(hs_scratch_t *sc, const HgFlowDb &f) {
   }
   if (!sc->f_dctr) {
     if (hgmem::dev_alloc(&sc->f_dctr, 4 * sizeof(uint32_t), "hs f_dctr") != hipSuccess) return HS_NOMEM;
-    if (hipMemset(sc->f_dctr, 0, 4 * sizeof(uint32_t)) != hipSuccess) return HS_NOMEM;
+    // (on the scratch's stream, which does not wait for the null stream: ordered before the first launch)
+    if (hipMemsetAsync(sc->f_dctr, 0, 4 * sizeof(uint32_t), sc->stream) != hipSuccess) return HS_NOMEM;
   }
   if (!sc->f_dsoff) {
     if (hgmem::dev_alloc(&sc->f_dsoff, f.soff.size() * sizeof(uint32_t) + 16, "hs f_dsoff") != hipSuccess) return HS_NOMEM;
@@ -690,6 +693,180 @@ int hg_scan_stream_batch(hs_stream_t *const *streams, const char *const *data, c
   return flow_batch(scratch, streams, data, lengths, item_flags, n, [&](uint32_t item, uint32_t rid, uint64_t from, uint64_t to) {
     return on_event ? on_event(item, rid, from, to, 0, context) : 0;
   });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------- batched block scan ------
+namespace {
+constexpr uint32_t BATCH_OUT_MAX = 1u << 24;  // records the pinned report array grows to at most (256 MiB); past it: item by item
+
+int batch_setup(hs_scratch_t *sc) {
+  if (!sc->b_flag) {
+    if (hgmem::host_alloc(&sc->b_flag, 4 * sizeof(uint32_t), "hs b_flag") != hipSuccess) return HS_NOMEM;
+    sc->b_flag[0] = sc->b_flag[1] = 0;
+  }
+  if (!sc->b_dctr) {
+    if (hgmem::dev_alloc(&sc->b_dctr, 4 * sizeof(uint32_t), "hs b_dctr") != hipSuccess) return HS_NOMEM;
+    // (on the scratch's stream, which does not wait for the null stream: ordered before the first launch)
+    if (hipMemsetAsync(sc->b_dctr, 0, 4 * sizeof(uint32_t), sc->stream) != hipSuccess) return HS_NOMEM;
+  }
+  return HS_SUCCESS;
+}
+
+bool batch_out_alloc(hs_scratch_t *sc, uint32_t cap) {
+  hgmem::host_free(sc->b_out, "hs b_out");
+  sc->b_out = nullptr;
+  sc->b_out_cap = 0;
+  if (hgmem::host_alloc(&sc->b_out, static_cast<size_t>(cap) * sizeof(HgHit), "hs b_out") != hipSuccess) return false;
+  sc->b_out_cap = cap;
+  return true;
+}
+
+// One launch of hg_block_batch_kernel over the items `pick` (indices into data / lengths, each of 1 .. HG_BLOCK_SMALL_MAX
+// bytes): per[k] receives item pick[k]'s reports after the report rules, in (to, id) order.  Returns HS_SUCCESS, an error, or
+// 1 when the launch's reports exceed what the report array may grow to (the caller then scans these items one by one).
+int batch_launch(hs_scratch_t *sc, const char *const *data, const unsigned int *lengths, const std::vector<uint32_t> &pick, std::vector<std::vector<HgHit>> &per) {
+  const uint32_t n = static_cast<uint32_t>(pick.size());
+  if (int rc = batch_setup(sc)) return rc;
+  const uint64_t bytes = hg_batch_bytes(lengths, pick.data(), n);
+  if (!grow_host(&sc->b_text, &sc->b_text_cap, bytes + 16, "hs b_text") || !grow_host(&sc->b_items, &sc->b_items_cap, n, "hs b_items")) return HS_NOMEM;
+  hg_batch_pack(data, lengths, pick.data(), n, sc->b_text, sc->b_items);
+  const HgDbView &v = sc->sc->view();
+  uint32_t ppw;
+  const uint32_t ngroups = hg_block_small_grouping(v.npatterns, &ppw);
+  const uint8_t *text = sc->b_text;
+  const HgBatchItem *items = sc->b_items;
+  // Every group's workgroups read every item once: past bytes x groups the bytes go to HBM first.  The threshold is the flow
+  // path's (HG_FLOW_HBM_MIN), which is no measured optimum there and none here.
+  if (bytes * ngroups >= flow_hbm_min()) {
+    if (sc->b_dtext_cap < bytes) {
+      hgmem::dev_free(sc->b_dtext, "hs b_dtext");
+      sc->b_dtext = nullptr;
+      sc->b_dtext_cap = 0;
+      const size_t cap = std::max<size_t>(bytes, 1u << 20);
+      if (hgmem::dev_alloc(&sc->b_dtext, cap + 16, "hs b_dtext") != hipSuccess) return HS_NOMEM;
+      sc->b_dtext_cap = cap;
+    }
+    if (hipMemcpyAsync(sc->b_dtext, sc->b_text, bytes, hipMemcpyHostToDevice, sc->stream) != hipSuccess) return HS_INVALID;
+    text = sc->b_dtext;
+    // ... and the item table with them (every group's workgroups read their shard's entries)
+    if (sc->b_ditems_cap < n) {
+      hgmem::dev_free(sc->b_ditems, "hs b_ditems");
+      sc->b_ditems = nullptr;
+      sc->b_ditems_cap = 0;
+      const size_t cap = std::max<size_t>(n, 4096);
+      if (hgmem::dev_alloc(&sc->b_ditems, cap * sizeof(HgBatchItem), "hs b_ditems") != hipSuccess) return HS_NOMEM;
+      sc->b_ditems_cap = cap;
+    }
+    if (hipMemcpyAsync(sc->b_ditems, sc->b_items, n * sizeof(HgBatchItem), hipMemcpyHostToDevice, sc->stream) != hipSuccess) return HS_INVALID;
+    items = sc->b_ditems;
+  }
+  uint32_t total = 0;
+  for (;;) {
+    if (sc->b_out_cap == 0 && !batch_out_alloc(sc, 4096)) return HS_NOMEM;
+    const uint32_t seq = ++sc->seq ? sc->seq : ++sc->seq;
+    HgBatchArgs a{};
+    a.patterns = v.patterns;
+    a.pool = v.pool;
+    a.npatterns = v.npatterns;
+    a.ppw = ppw;
+    a.ngroups = ngroups;
+    a.nshards = std::max(1u, std::min(n, HG_BATCH_MAX_WGS / ngroups));
+    a.text = text;
+    a.items = items;
+    a.nitems = n;
+    a.out = sc->b_out;
+    a.cap = sc->b_out_cap;
+    a.seq = seq;
+    a.d_total = sc->b_dctr;
+    a.d_done = sc->b_dctr + 1;
+    a.h_flag = sc->b_flag;
+    if (hg_batch_launch(a, sc->stream) != 0) return HS_INVALID;
+    volatile uint32_t *flag = sc->b_flag + 1;
+    bool done = false;
+    for (uint32_t spin = 0; spin < 400000 && !(done = *flag == seq); spin++) cpu_relax();
+    if (!done && hipStreamSynchronize(sc->stream) != hipSuccess) return HS_INVALID;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (*flag != seq) return HS_INVALID;
+    total = sc->b_flag[0];
+    if (total <= sc->b_out_cap) break;
+    // more reports than room: items keep no state, the launch is repeated with room for all
+    if (total > BATCH_OUT_MAX) return 1;
+    if (!batch_out_alloc(sc, static_cast<uint32_t>(std::min<uint64_t>(BATCH_OUT_MAX, std::max<uint64_t>(total, 2ull * sc->b_out_cap))))) return HS_NOMEM;
+  }
+  per.assign(n, {});
+  for (uint32_t i = 0; i < total; i++)
+    if (sc->b_out[i].line_no < n) per[sc->b_out[i].line_no].push_back(sc->b_out[i]);
+  for (auto &h : per) hg_block_rules(h);
+  return HS_SUCCESS;
+}
+}  // namespace
+
+extern "C" {
+
+int hg_scan_blocks(const hs_database_t *db, const char *const *data, const unsigned int *lengths, unsigned int n, hs_scratch_t *scratch,
+                   hg_stream_match_handler on_event, void *context) {
+  if (n == 0) return HS_SUCCESS;
+  if (!db || !lengths || !scratch || !scratch->sc || scratch->db != db->db) return HS_INVALID;
+  for (unsigned int i = 0; i < n; i++)
+    if (lengths[i] && (!data || !data[i])) return HS_INVALID;
+  if (db->mode != HS_MODE_BLOCK) return HS_DB_MODE_ERROR;
+  if (hipSetDevice(scratch->sc->device()) != hipSuccess) return HS_INVALID;
+  // What the kernel takes is what hs_scan's one-launch path takes; everything else goes item by item through the general path.
+  static const bool small_path = !std::getenv("HG_NO_BLOCK_SMALL");
+  const HgDb &d = *db->db;
+  uint32_t ppw;
+  const bool kernel_db = small_path && !d.nsom && !d.comb_pass() && d.bounds.empty() && !d.nhuge &&
+                         hg_block_small_grouping(static_cast<uint32_t>(d.patterns.size()), &ppw) <= 64;
+  // a launch's reports are counted in 32 bits: at most (bytes + items) x expressions of them
+  const uint64_t launch_bytes = std::max<uint64_t>(HG_BLOCK_SMALL_MAX + 16, std::min<uint64_t>(FLOW_LAUNCH_BYTES, 0xF0000000ull / d.patterns.size() / 2));
+  int rc = HS_SUCCESS;
+  std::vector<uint32_t> pick;
+  std::vector<std::vector<HgHit>> per;
+  unsigned int i = 0;
+  while (i < n) {
+    // the next launch: consecutive items [i, end), of them `pick` for the kernel
+    pick.clear();
+    uint64_t bytes = 0;
+    unsigned int end = i;
+    for (; end < n && pick.size() < FLOW_LAUNCH_ITEMS && end - i < 4 * FLOW_LAUNCH_ITEMS; end++) {
+      const uint32_t len = lengths[end];
+      if (!kernel_db || len == 0 || len > HG_BLOCK_SMALL_MAX) continue;
+      if (bytes + len + 16 > launch_bytes) break;
+      pick.push_back(end);
+      bytes += hg_batch_pad16(len);
+    }
+    bool launched = false;
+    if (!pick.empty()) {
+      const int r = batch_launch(scratch, data, lengths, pick, per);
+      if (r < 0) return r;
+      launched = r == HS_SUCCESS;
+    }
+    // delivery in item order: the launch's items from `per`, the others scanned now
+    size_t k = 0;
+    for (unsigned int j = i; j < end; j++) {
+      const bool picked = k < pick.size() && pick[k] == j;
+      if (picked && launched) {
+        for (const HgHit &x : per[k])
+          if (on_event && on_event(j, x.id, 0, x.to, 0, context)) {
+            rc = HS_SCAN_TERMINATED;
+            break;
+          }
+      } else if (lengths[j]) {
+        if (int r = block_general(scratch, data[j], lengths[j])) return r;
+        const auto &h = scratch->hits;
+        for (uint32_t o : scratch->order)
+          if (on_event && on_event(j, h[o].id, scratch->from[o], h[o].to, 0, context)) {
+            rc = HS_SCAN_TERMINATED;
+            break;
+          }
+      }
+      if (picked) k++;
+    }
+    i = end;
+  }
+  return rc;
 }
 
 }  // extern "C"

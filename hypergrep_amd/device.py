@@ -328,7 +328,7 @@ _face_a_configured = False
 
 
 def face_a() -> ctypes.CDLL:
-    """The library with Face A's prototypes (hs_*: block and stream mode, hg_scan_stream_batch)."""
+    """The library with Face A's prototypes (hs_*: block and stream mode, hg_scan_stream_batch, hg_scan_blocks)."""
     global _face_a_configured
     l = lib()
     if not _face_a_configured:
@@ -347,6 +347,8 @@ def face_a() -> ctypes.CDLL:
         l.hs_copy_stream.argtypes = [ctypes.POINTER(vp), vp]
         l.hs_stream_size.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)]
         l.hg_scan_stream_batch.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(u), ctypes.POINTER(u), u, vp, STREAM_EVENT, vp]
+        if hasattr(l, "hg_scan_blocks"):  # (absent from a build before the batched block scan: tools/block_batch_bench.py --lib)
+            l.hg_scan_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(u), u, vp, STREAM_EVENT, vp]
         _face_a_configured = True
     return l
 
@@ -415,6 +417,83 @@ class StreamDatabase:
         rc = face_a().hg_scan_stream_batch(streams, datas, lengths, flags, n, self._scratch, cb, None)
         if rc not in (HS_SUCCESS, HS_SCAN_TERMINATED):
             raise DeviceError(f"hg_scan_stream_batch returned {rc}")
+        return out
+
+    def __del__(self):
+        if lib is None:
+            return
+        if getattr(self, "_scratch", None):
+            face_a().hs_free_scratch(self._scratch)
+            self._scratch = None
+        if getattr(self, "_h", None):
+            face_a().hs_free_database(self._h)
+            self._h = None
+
+
+class BlockDatabase:
+    """Expressions compiled for block mode (hs_compile_ext_multi with HS_MODE_BLOCK) with ONE scratch, so it must not be used
+    from several threads at once.  scan(data) is hs_scan; scan_blocks(items) is hg_scan_blocks: many independent buffers in
+    one call, each scanned as a block of its own (include/hypergrep_amd.h, batched block scan).  Reports are (id, to) pairs,
+    (id, from, to) triples when the set has HS_FLAG_SOM_LEFTMOST expressions.  device: None or the GPU's index; hs_alloc_scratch
+    reads it from HYPERGREP_DEVICE, so an index is put there for the allocation (and the variable restored)."""
+
+    def __init__(self, patterns, flags=None, ids=None, ext=None, device: int | None = None):
+        pats = list(patterns)
+        fl = list(flags or ())
+        self.som = any(f & HS_FLAG_SOM_LEFTMOST for f in fl)
+        h, err = hs_compile(pats, fl, ids, ext, HS_MODE_BLOCK)
+        if err:
+            raise CompileError(err[0])
+        self._h = h
+        self._scratch = ctypes.c_void_p()
+        import os
+
+        before = os.environ.get("HYPERGREP_DEVICE")
+        if device is not None:
+            os.environ["HYPERGREP_DEVICE"] = str(int(device))
+        try:
+            rc = face_a().hs_alloc_scratch(self._h, ctypes.byref(self._scratch))
+        finally:
+            if device is not None:
+                if before is None:
+                    del os.environ["HYPERGREP_DEVICE"]
+                else:
+                    os.environ["HYPERGREP_DEVICE"] = before
+        if rc != HS_SUCCESS:
+            raise DeviceError("hs_alloc_scratch failed")
+
+    def scan(self, data: bytes):
+        """hs_scan of one buffer: its reports in (to, id) order."""
+        out = []
+        som = self.som
+
+        def on_event(rid, frm, to, _flags, _ctx):
+            out.append((rid, frm, to) if som else (rid, to))
+            return 0
+
+        rc = face_a().hs_scan(self._h, bytes(data), len(data), 0, self._scratch, MATCH_EVENT(on_event), None)
+        if rc not in (HS_SUCCESS, HS_SCAN_TERMINATED):
+            raise DeviceError(f"hs_scan returned {rc}")
+        return out
+
+    def scan_blocks(self, items):
+        """One hg_scan_blocks call over items (bytes each): [reports of item i, as scan(items[i]) gives them]."""
+        items = [bytes(d) for d in items]
+        n = len(items)
+        out = [[] for _ in range(n)]
+        if n == 0:
+            return out
+        som = self.som
+
+        def on_event(item, rid, frm, to, _flags, _ctx):
+            out[item].append((rid, frm, to) if som else (rid, to))
+            return 0
+
+        datas = (ctypes.c_char_p * n)(*items)
+        lengths = (ctypes.c_uint * n)(*[len(d) for d in items])
+        rc = face_a().hg_scan_blocks(self._h, datas, lengths, n, self._scratch, STREAM_EVENT(on_event), None)
+        if rc not in (HS_SUCCESS, HS_SCAN_TERMINATED):
+            raise DeviceError(f"hg_scan_blocks returned {rc}")
         return out
 
     def __del__(self):

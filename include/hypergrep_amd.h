@@ -269,6 +269,31 @@ int hg_scan_stream_batch(hs_stream_t *const *streams, const char *const *data, c
                          const unsigned int *item_flags, unsigned int n, hs_scratch_t *scratch,
                          hg_stream_match_handler on_event, void *context);
 
+/* Batched block scan: many independent buffers scanned as blocks in one call (a few launches instead of one hs_scan per
+ * buffer, measured at 16.5-19 us each on a short buffer: launch and host-link latency).  `db` is a BLOCK-mode database; item i is data[i][0, lengths[i]).
+ *  1. Equivalence.  For every item i the reports delivered with item == i are exactly those of
+ *     hs_scan(db, data[i], lengths[i], 0, scratch, ...): the same (id, from, to) in the same (to, id) order, for every
+ *     block-mode database hs_compile_ext_multi accepts.  `from` is the start of match for HS_FLAG_SOM_LEFTMOST expressions
+ *     and 0 otherwise, as in hs_scan.  An item is a block, not a line: '\n' and NUL are ordinary bytes, and `$`, `\Z`, `.`
+ *     see the item's real bytes and its real end.
+ *  2. Order.  Reports come grouped by item, in item order (the shape of hg_scan_stream_batch).  The call collects a
+ *     launch's reports before it delivers them.
+ *  3. Empty items (lengths[i] == 0; data[i] may be NULL) deliver nothing.  n == 0 returns HS_SUCCESS without touching the
+ *     GPU.
+ *  4. Termination.  A non-zero return from the callback ends that item's delivery; the other items are still delivered,
+ *     and the call returns HS_SCAN_TERMINATED.  Items keep no state, so nothing else changes.
+ *  5. Errors.  HS_INVALID before anything is scanned for NULL arguments, a scratch of another database, or a NULL data[i]
+ *     with lengths[i] > 0; HS_DB_MODE_ERROR for a stream-mode database.  on_event == NULL scans and delivers nothing (as
+ *     hs_scan does).  An error met later in the call (HS_NOMEM, or HS_INVALID for a failed GPU operation) ends the call
+ *     there: the items before the failing launch have been delivered, the others are not.
+ *  6. Speed.  One kernel takes what hs_scan's one-launch path takes: databases without HS_FLAG_SOM_LEFTMOST expressions,
+ *     without combinations or QUIET expressions, without offset bounds, without automata over 1024 positions, of at most
+ *     2048 expressions in groups of 32 (or 16384 in groups of 256), and items of at most 8192 bytes.  Everything else (a whole
+ *     batch on another database, single longer items, a launch with more than 2^24 reports) is scanned item by item as
+ *     hs_scan's general path scans it, inside the same call: correct by rule 1, with no speed-up. */
+int hg_scan_blocks(const hs_database_t *db, const char *const *data, const unsigned int *lengths, unsigned int n,
+                   hs_scratch_t *scratch, hg_stream_match_handler on_event, void *context);
+
 /* ------------------------------------------------------------------ hg_*: device buffers ------ */
 
 enum {

@@ -1,8 +1,12 @@
 // Face A: the libhs symbols the reference shim links against (hypergrep/lib/c/hyperscanner.c:136,140,165,217,
-// 301,323,324), stream mode (hs_*_stream, hg_scan_stream_batch: hg_flows.hip) and the batched block scan (hg_scan_blocks: hg_batch.hip), at the end.  hs_scan copies the block to HBM and runs the same stream / filter kernels in
+// 301,323,324), then stream mode (hs_*_stream, hg_scan_stream_batch: hg_flows.hip) and the batched block scan
+// (hg_scan_blocks: hg_batch.hip).  hs_scan copies the block to HBM and runs the same stream / filter kernels in
 // block mode (the buffer is one scan unit, no line splitting), then delivers reports in ascending end offset.
 // Per-call cost is a few launches and two synchronisations, so this face is for compatibility (per-line callers such
 // as the reference shim); bulk scanning goes through hyperscan() / hg_scan_device().
+// A scratch owns its buffers (hgmem::Buf: freed with the scratch, whatever is added to it).  The three routes that report
+// through pinned memory share the wait (wait_done); stream mode and the batched block scan also share one staging set
+// (HgStage) and the launch-wait-grow-repeat loop over it (launch_until_fits).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,8 +29,16 @@
 #include "hg_mem.h"
 
 namespace {
-constexpr uint32_t FLOW_LAUNCH_ITEMS = 1u << 16;      // items one stream-mode launch takes at most
-constexpr uint64_t FLOW_SOM_WORK_MAX = 256ull << 20;  // bytes of the SOM lanes' start buffers one launch may take
+// What one launch takes at most (stream mode and the batched block scan cut their calls into launches by these)
+constexpr uint64_t FLOW_LAUNCH_BYTES = 64u << 20;     // bytes of writes / items (a longer write: several launches)
+constexpr uint32_t FLOW_LAUNCH_ITEMS = 1u << 16;      // items
+constexpr uint64_t FLOW_SOM_WORK_MAX = 256ull << 20;  // bytes of the SOM lanes' start buffers
+constexpr uint32_t BATCH_OUT_MAX = 1u << 24;  // records the batched block scan's pinned report array grows to at most (256 MiB); past it: item by item
+
+template <typename T>
+using HostBuf = hgmem::Buf<T, hgmem::Space::Host>;
+template <typename T>
+using DevBuf = hgmem::Buf<T, hgmem::Space::Dev>;
 }  // namespace
 
 // Stream-mode data of a database (none in block mode): where each expression's words sit in a stream's state, and the state
@@ -54,44 +66,51 @@ struct hs_stream {
   bool terminated = false;
   HgFlowRuleState rules;        // offset, SINGLEMATCH ids reported, recent reports (hg_flow_rules.h)
 };
+// What a launch with pinned reports needs (launch_until_fits).  A scratch serves one database, whose mode never changes, so
+// there is one set per scratch: stream mode or the batched block scan uses it, whichever the database allows.
+struct HgStage {
+  HostBuf<uint8_t> text{"hs st_text"};  // the launch's writes / items, packed; their copy in HBM
+  DevBuf<uint8_t> dtext{"hs st_dtext"};
+  HostBuf<uint32_t> flag{"hs st_flag", 0};  // 4 words: [0] reports of the launch, [1] completion word (the launch's seq)
+  DevBuf<uint32_t> dctr{"hs st_dctr", 0};   // 4 words: the kernel's counters, cleared once (the last workgroup resets them)
+  HostBuf<HgHit> out{"hs st_out", 0};       // the report array; out.cap() is its capacity in records
+  HostBuf<int64_t> from{"hs st_from", 0};   // (with_from: stream mode with start of match) the starts beside it, as many
+  bool with_from = false;
+};
 struct hs_scratch {
   std::shared_ptr<HgDb> db;
   HgScanner *sc = nullptr;
-  hipStream_t stream = nullptr;
-  uint8_t *d_text = nullptr;
-  size_t d_cap = 0;
+  // (destroyed after the buffers below: members go in reverse order, after ~hs_scratch has deleted the scanner)
+  struct Stream {
+    hipStream_t h = nullptr;
+    ~Stream() { if (h) (void)hipStreamDestroy(h); }
+    operator hipStream_t() const { return h; }
+  } stream;
+  DevBuf<uint8_t> d_text{"hs d_text"};
   std::vector<HgHit> hits;
   std::vector<uint32_t> from;  // (SOM databases) the start of each hit
   std::vector<uint32_t> order;
   // short blocks (HgScanner::launch_block_small): pinned copies of the block and of the raw reports
-  uint8_t *h_text = nullptr;
-  HgHit *h_out = nullptr;
-  uint32_t *h_counts = nullptr;  // [0, 64) reports per segment, [64] completion flag
-  uint32_t seq = 0;
-  // stream mode (hg_flow_scan_kernel), allocated at the first stream call: pinned staging of writes, items and states, the
-  // pinned report array, the writes' HBM copy and the kernel's device counters
-  uint8_t *f_text = nullptr, *f_dtext = nullptr;
-  size_t f_text_cap = 0, f_dtext_cap = 0;
-  HgFlowItem *f_items = nullptr;
-  uint32_t *f_sin = nullptr, *f_sout = nullptr;
-  size_t f_items_cap = 0, f_state_cap = 0;
-  HgHit *f_out = nullptr;
-  uint32_t f_out_cap = 0;
-  uint32_t *f_flag = nullptr, *f_dctr = nullptr, *f_dsoff = nullptr;
-  // start of match: the pinned starts beside f_out (f_out_cap of them), the SOM expressions on the device, the SOM lanes'
-  // start buffers
-  int64_t *f_from = nullptr, *f_dwork = nullptr;
-  size_t f_work_cap = 0;
-  uint32_t *f_dsom = nullptr;
-  // batched block scan (hg_block_batch_kernel), allocated at the first hg_scan_blocks call: pinned staging of the items' bytes
-  // and their table, the pinned report array, the bytes' HBM copy, the pinned flag words and the kernel's device counters
-  uint8_t *b_text = nullptr, *b_dtext = nullptr;
-  size_t b_text_cap = 0, b_dtext_cap = 0;
-  HgBatchItem *b_items = nullptr, *b_ditems = nullptr;
-  size_t b_items_cap = 0, b_ditems_cap = 0;
-  HgHit *b_out = nullptr;
-  uint32_t b_out_cap = 0;
-  uint32_t *b_flag = nullptr, *b_dctr = nullptr;
+  HostBuf<uint8_t> h_text{"hs h_text"};
+  HostBuf<HgHit> h_out{"hs h_out", 0};
+  HostBuf<uint32_t> h_counts{"hs h_counts", 0};  // [0, 64) reports per segment, [64] completion flag
+  uint32_t seq = 0;  // of the last launch that reports through a pinned completion word (next_seq)
+  HgStage stage;  // allocated at the first stream call / hg_scan_blocks call, as everything below
+  // stream mode (hg_flow_scan_kernel): pinned items and states, the expressions' state offsets on the device
+  HostBuf<HgFlowItem> f_items{"hs f_items"};
+  HostBuf<uint32_t> f_sin{"hs f_sin"}, f_sout{"hs f_sout"};
+  DevBuf<uint32_t> f_dsoff{"hs f_dsoff"};
+  // ... with start of match: the SOM expressions on the device, the SOM lanes' start buffers
+  DevBuf<uint32_t> f_dsom{"hs f_dsom"};
+  DevBuf<int64_t> f_dwork{"hs f_dwork"};
+  // batched block scan (hg_block_batch_kernel): the pinned item table and its copy in HBM
+  HostBuf<HgBatchItem> b_items{"hs b_items"};
+  DevBuf<HgBatchItem> b_ditems{"hs b_ditems", 0};
+
+  ~hs_scratch() {  // the scanner, the buffers, the stream: in this order, on the scanner's device
+    if (sc) (void)hipSetDevice(sc->device());
+    delete sc;
+  }
 };
 
 namespace {
@@ -105,20 +124,74 @@ inline void cpu_relax() {  // a polite spin-wait hint, whatever the host is
 #endif
 }
 
+uint32_t next_seq(hs_scratch_t *sc) { return ++sc->seq ? sc->seq : ++sc->seq; }  // (never 0)
+
+// Waits for a kernel's completion word in pinned memory to become `seq` (a few microseconds of polling; a stream
+// synchronisation sleeps until an interrupt); after ~2 ms of polling falls back to the synchronisation, which also reports
+// errors.  false: the stream failed, or ended without the word.
+bool wait_done(hipStream_t stream, const uint32_t *word, uint32_t seq) {
+  const volatile uint32_t *flag = word;
+  bool done = false;
+  for (uint32_t spin = 0; spin < 400000 && !(done = *flag == seq); spin++) cpu_relax();
+  if (!done && hipStreamSynchronize(stream) != hipSuccess) return false;
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return *flag == seq;
+}
+
+constexpr int LAUNCH_TOO_MANY = 1;  // launch_until_fits: more reports than the report array may grow to (a result, not an error)
+
+// One launch that reports into the scratch's pinned report array (after stage_setup), repeated with a larger array while its reports do not fit
+// (so a launch must leave its input untouched).  launch(seq, out, from, cap) -> 0 or an error: starts the kernels on
+// sc->stream with room for `cap` reports; they publish the count in stage.flag[0], then `seq` in stage.flag[1].
+// grow(total, cap) -> the capacity to repeat with after `total` reports did not fit `cap`, 0 (anything below `total`) if the array may not grow so far.
+// Returns HS_SUCCESS with the count in *total, LAUNCH_TOO_MANY, HS_NOMEM, HS_INVALID or launch's error.
+// The stage's flag words and device counters, at a scratch's first launch.  flow_launch and batch_launch call it before they
+// allocate anything else: the pinned flag words are then the scratch's first staging allocation, as they have always been (with
+// them after the text and state buffers, report-heavy batches measured 2-4 % slower: profiles/hsface_refactor_bench.txt).
+int stage_setup(hs_scratch_t *sc) {
+  HgStage &st = sc->stage;
+  if (!st.flag.get()) {
+    if (!st.flag.reserve(4, 4)) return HS_NOMEM;
+    st.flag.get()[0] = st.flag.get()[1] = 0;
+  }
+  if (!st.dctr.get()) {
+    if (!st.dctr.reserve(4, 4)) return HS_NOMEM;
+    // (on the scratch's stream, which does not wait for the null stream: ordered before the first launch)
+    if (hipMemsetAsync(st.dctr.get(), 0, 4 * sizeof(uint32_t), sc->stream) != hipSuccess) return HS_NOMEM;
+  }
+  return HS_SUCCESS;
+}
+template <typename Grow, typename Launch>
+int launch_until_fits(hs_scratch_t *sc, Grow &&grow, Launch &&launch, uint32_t *total) {
+  HgStage &st = sc->stage;
+  for (uint32_t cap = static_cast<uint32_t>(std::max<size_t>(st.out.cap(), 4096));;) {
+    if (!st.out.reserve(cap, cap) || (st.with_from && !st.from.reserve(cap, cap))) return HS_NOMEM;
+    const uint32_t seq = next_seq(sc);
+    if (int rc = launch(seq, st.out.get(), st.from.get(), cap)) return rc;
+    if (!wait_done(sc->stream, st.flag.get() + 1, seq)) return HS_INVALID;
+    *total = st.flag.get()[0];
+    if (*total <= cap) return HS_SUCCESS;
+    if ((cap = grow(*total, cap)) < *total) return LAUNCH_TOO_MANY;
+  }
+}
+
+// The one-launch block path (HgScanner::launch_block_small, hg_block_batch_kernel) takes this database.  Databases with
+// HS_FLAG_SOM_LEFTMOST expressions take the general path: its start-of-match pass fills `from`; so do databases with
+// combinations or QUIET expressions (its combination pass applies them) and with offset bounds.
+bool block_small_db(const HgDb &d) {
+  static const bool enabled = !std::getenv("HG_NO_BLOCK_SMALL");
+  return enabled && !d.nsom && !d.comb_pass() && d.bounds.empty();
+}
+
 // The general path of a block scan (hs_scan's tail; hg_scan_blocks for what its kernel does not take): the block copied to
 // HBM, HgScanner::scan_block, the reports copied back into scratch->hits / from, their delivery order (to, id) in
 // scratch->order.  HS_SUCCESS or an error.
 int block_general(hs_scratch_t *scratch, const char *data, unsigned int length) {
-  if (scratch->d_cap < length) {
-    hgmem::dev_free(scratch->d_text, "hs d_text");
-    scratch->d_text = nullptr;
-    size_t cap = std::max<size_t>(length, 4096) * 2;
-    if (hgmem::dev_alloc(&scratch->d_text, cap + 16, "hs d_text") != hipSuccess) return HS_NOMEM;
-    scratch->d_cap = cap;
-  }
-  if (hipMemcpyAsync(scratch->d_text, data, length, hipMemcpyHostToDevice, scratch->stream) != hipSuccess) return HS_INVALID;
+  if (!scratch->d_text.reserve(length, std::max<size_t>(length, 4096) * 2)) return HS_NOMEM;
+  uint8_t *d_text = scratch->d_text.get();
+  if (hipMemcpyAsync(d_text, data, length, hipMemcpyHostToDevice, scratch->stream) != hipSuccess) return HS_INVALID;
   HgScanOutput out{};
-  if (scratch->sc->scan_block(scratch->d_text, length, scratch->stream, &out) != HG_OK) {
+  if (scratch->sc->scan_block(d_text, length, scratch->stream, &out) != HG_OK) {
     std::fprintf(stderr, "hypergrep_amd: block scan (hs_scan / hg_scan_blocks): %s\n", scratch->sc->last_error().c_str());
     return HS_INVALID;
   }
@@ -137,6 +210,47 @@ int block_general(hs_scratch_t *scratch, const char *data, unsigned int length) 
   for (uint32_t i = 0; i < order.size(); i++) order[i] = i;
   std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return h[a].to != h[b].to ? h[a].to < h[b].to : h[a].id < h[b].id; });
   return HS_SUCCESS;
+}
+
+// block_general, then the reports to emit(id, from, to) in delivery order up to the first non-zero return.  HS_SUCCESS,
+// HS_SCAN_TERMINATED (emit returned non-zero) or an error.
+template <typename Emit>
+int block_general_deliver(hs_scratch_t *scratch, const char *data, unsigned int length, Emit &&emit) {
+  if (int rc = block_general(scratch, data, length)) return rc;
+  const auto &h = scratch->hits;
+  for (uint32_t i : scratch->order)
+    if (emit(h[i].id, scratch->from[i], h[i].to)) return HS_SCAN_TERMINATED;
+  return HS_SUCCESS;
+}
+
+// The stream-mode data of a compiled database.  Null, with the expression's index in *bad and the reason in *msg, when a flow
+// cannot carry one of its expressions.
+std::shared_ptr<HgFlowDb> flow_db(const HgDb &db, unsigned int horizon, int *bad, std::string *msg) {
+  const uint32_t np = static_cast<uint32_t>(db.patterns.size());
+  for (uint32_t i = 0; i < np; i++) {
+    const HgPattern &p = db.patterns[i];
+    const bool wide = p.nw > HG_MAX_W, som_wide = (p.flags & HG_FLAG_SOM_LEFTMOST) && p.nnodes > HG_FLOW_SOM_NODES;
+    if (!wide && !som_wide) continue;
+    *bad = static_cast<int>(i);
+    *msg = "expression " + std::to_string(i) + ": automaton of more than " +
+           (wide ? std::string("1024 positions, too large for stream mode")
+                 : std::to_string(HG_FLOW_SOM_NODES) + " positions, too large for start of match in stream mode");
+    return nullptr;
+  }
+  auto flow = std::make_shared<HgFlowDb>();
+  flow->som_width = horizon == HS_MODE_SOM_HORIZON_SMALL ? 2u : horizon == HS_MODE_SOM_HORIZON_MEDIUM ? 4u : horizon ? 8u : 0u;
+  flow->horizon_bits = horizon == HS_MODE_SOM_HORIZON_SMALL ? 16u : horizon == HS_MODE_SOM_HORIZON_MEDIUM ? 32u : 0u;
+  HgFlowLayout l = hg_flow_layout(db.pool.data(), db.patterns.data(), np, flow->som_width);
+  flow->soff = std::move(l.soff);
+  flow->init = std::move(l.init);
+  flow->som = std::move(l.som);
+  flow->swords = l.swords;
+  flow->som_total = l.som_total;
+  flow->launch_items = FLOW_LAUNCH_ITEMS;
+  if (l.som_total)  // 2 x 8 bytes per node of every SOM expression and item: at most FLOW_SOM_WORK_MAX bytes per launch
+    flow->launch_items = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(FLOW_LAUNCH_ITEMS, FLOW_SOM_WORK_MAX / (16ull * l.som_total))));
+  flow->ngroups = (np + HG_FLOW_PPW - 1) / HG_FLOW_PPW;
+  return flow;
 }
 }  // namespace
 
@@ -177,36 +291,12 @@ int hs_compile_ext_multi(const char *const *expressions, const unsigned int *fla
   }
   if (msg.empty() && hgc_compile_ext(expressions, flags, ids, ext, elements, &raw, &msg, &bad) == 0) {
     std::shared_ptr<HgDb> owned(raw, [](HgDb *d) { hgc_free(d); });
-    std::shared_ptr<HgFlowDb> flow;
-    if (mode == HS_MODE_STREAM) {
-      flow = std::make_shared<HgFlowDb>();
-      const uint32_t np = static_cast<uint32_t>(owned->patterns.size());
-      for (uint32_t i = 0; i < np && bad < 0; i++) {
-        const HgPattern &p = owned->patterns[i];
-        if (p.nw > HG_MAX_W)
-          bad = static_cast<int>(i), msg = "expression " + std::to_string(i) + ": automaton of more than 1024 positions, too large for stream mode";
-        else if ((p.flags & HG_FLAG_SOM_LEFTMOST) && p.nnodes > HG_FLOW_SOM_NODES)
-          bad = static_cast<int>(i), msg = "expression " + std::to_string(i) + ": automaton of more than " + std::to_string(HG_FLOW_SOM_NODES) +
-                                           " positions, too large for start of match in stream mode";
-      }
-      if (bad >= 0) goto fail;
-      flow->som_width = horizon == HS_MODE_SOM_HORIZON_SMALL ? 2u : horizon == HS_MODE_SOM_HORIZON_MEDIUM ? 4u : horizon ? 8u : 0u;
-      flow->horizon_bits = horizon == HS_MODE_SOM_HORIZON_SMALL ? 16u : horizon == HS_MODE_SOM_HORIZON_MEDIUM ? 32u : 0u;
-      HgFlowLayout l = hg_flow_layout(owned->pool.data(), owned->patterns.data(), np, flow->som_width);
-      flow->soff = std::move(l.soff);
-      flow->init = std::move(l.init);
-      flow->som = std::move(l.som);
-      flow->swords = l.swords;
-      flow->som_total = l.som_total;
-      flow->launch_items = FLOW_LAUNCH_ITEMS;
-      if (l.som_total)  // 2 x 8 bytes per node of every SOM expression and item: at most FLOW_SOM_WORK_MAX bytes per launch
-        flow->launch_items = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(FLOW_LAUNCH_ITEMS, FLOW_SOM_WORK_MAX / (16ull * l.som_total))));
-      flow->ngroups = (np + HG_FLOW_PPW - 1) / HG_FLOW_PPW;
+    const std::shared_ptr<HgFlowDb> flow = mode == HS_MODE_STREAM ? flow_db(*owned, horizon, &bad, &msg) : nullptr;
+    if (flow || mode != HS_MODE_STREAM) {
+      *db = new hs_database{owned, mode, flow};
+      return HS_SUCCESS;
     }
-    *db = new hs_database{owned, mode, flow};
-    return HS_SUCCESS;
   }
-fail:
   if (db) *db = nullptr;
   if (error) {
     hs_compile_error_t *e = static_cast<hs_compile_error_t *>(std::malloc(sizeof(hs_compile_error_t)));
@@ -234,59 +324,26 @@ int hs_alloc_scratch(const hs_database_t *db, hs_scratch_t **scratch) {
   if (*scratch && (*scratch)->db == db->db) return HS_SUCCESS;
   if (*scratch) hs_free_scratch(*scratch);
   *scratch = nullptr;
-  // (a half-built scratch is handed to hs_free_scratch on every failure path: scanner, stream and pinned buffers are released)
-  struct Guard {
-    hs_scratch_t *p;
-    ~Guard() { if (p) hs_free_scratch(p); }
-  } s{new hs_scratch()};
-  s.p->db = db->db;
+  std::unique_ptr<hs_scratch_t> s(new hs_scratch_t());  // (a half-built scratch releases what it has on every failure path)
+  s->db = db->db;
   std::string err;
   int device = 0;
   if (const char *env = std::getenv("HYPERGREP_DEVICE")) device = std::atoi(env);
-  if (HgScanner::create(s.p->db, device, &s.p->sc, &err) != HG_OK) {
+  if (HgScanner::create(s->db, device, &s->sc, &err) != HG_OK) {
     std::fprintf(stderr, "hypergrep_amd: hs_alloc_scratch: %s\n", err.c_str());
     return HS_NOMEM;
   }
-  if (hipStreamCreateWithFlags(&s.p->stream, hipStreamNonBlocking) != hipSuccess) return HS_NOMEM;
-  if (hgmem::host_alloc(&s.p->h_text, HG_BLOCK_SMALL_MAX + 16, "hs h_text") != hipSuccess ||
-      hgmem::host_alloc(&s.p->h_out, 64 * HG_BLOCK_SMALL_SEG * sizeof(HgHit), "hs h_out") != hipSuccess ||
-      hgmem::host_alloc(&s.p->h_counts, 80 * sizeof(uint32_t), "hs h_counts") != hipSuccess)
+  if (hipStreamCreateWithFlags(&s->stream.h, hipStreamNonBlocking) != hipSuccess) return HS_NOMEM;
+  if (!s->h_text.reserve(HG_BLOCK_SMALL_MAX, HG_BLOCK_SMALL_MAX) || !s->h_out.reserve(64 * HG_BLOCK_SMALL_SEG, 64 * HG_BLOCK_SMALL_SEG) ||
+      !s->h_counts.reserve(80, 80))
     return HS_NOMEM;
-  s.p->h_counts[64] = 0;
-  *scratch = s.p;
-  s.p = nullptr;
+  s->h_counts.get()[64] = 0;
+  *scratch = s.release();
   return HS_SUCCESS;
 }
 
 int hs_free_scratch(hs_scratch_t *scratch) {
-  if (!scratch) return HS_SUCCESS;
-  if (scratch->sc) (void)hipSetDevice(scratch->sc->device());
-  delete scratch->sc;
-  hgmem::dev_free(scratch->d_text, "hs d_text");
-  hgmem::host_free(scratch->h_text, "hs h_text");
-  hgmem::host_free(scratch->h_out, "hs h_out");
-  hgmem::host_free(scratch->h_counts, "hs h_counts");
-  hgmem::host_free(scratch->f_text, "hs f_text");
-  hgmem::dev_free(scratch->f_dtext, "hs f_dtext");
-  hgmem::host_free(scratch->f_items, "hs f_items");
-  hgmem::host_free(scratch->f_sin, "hs f_sin");
-  hgmem::host_free(scratch->f_sout, "hs f_sout");
-  hgmem::host_free(scratch->f_out, "hs f_out");
-  hgmem::host_free(scratch->f_flag, "hs f_flag");
-  hgmem::dev_free(scratch->f_dctr, "hs f_dctr");
-  hgmem::dev_free(scratch->f_dsoff, "hs f_dsoff");
-  hgmem::host_free(scratch->f_from, "hs f_from");
-  hgmem::dev_free(scratch->f_dwork, "hs f_dwork");
-  hgmem::dev_free(scratch->f_dsom, "hs f_dsom");
-  hgmem::host_free(scratch->b_text, "hs b_text");
-  hgmem::dev_free(scratch->b_dtext, "hs b_dtext");
-  hgmem::host_free(scratch->b_items, "hs b_items");
-  hgmem::dev_free(scratch->b_ditems, "hs b_ditems");
-  hgmem::host_free(scratch->b_out, "hs b_out");
-  hgmem::host_free(scratch->b_flag, "hs b_flag");
-  hgmem::dev_free(scratch->b_dctr, "hs b_dctr");
-  if (scratch->stream) (void)hipStreamDestroy(scratch->stream);
-  delete scratch;
+  delete scratch;  // (~hs_scratch)
   return HS_SUCCESS;
 }
 
@@ -299,28 +356,22 @@ int hs_scan(const hs_database_t *db, const char *data, unsigned int length, unsi
   if (hipSetDevice(scratch->sc->device()) != hipSuccess) return HS_INVALID;
   // Short blocks (the reference shim scans line by line, hyperscanner.c:217): one launch on a pinned copy of the block,
   // raw reports straight into pinned memory, the report rules on the host.
-  static const bool small_path = !std::getenv("HG_NO_BLOCK_SMALL");
-  // (databases with HS_FLAG_SOM_LEFTMOST expressions take the general path: its start-of-match pass fills `from`; so do databases
-  // with combinations or QUIET expressions: its combination pass applies them)
-  if (length <= HG_BLOCK_SMALL_MAX && small_path && !db->db->nsom && !db->db->comb_pass() && db->db->bounds.empty()) {
-    std::memcpy(scratch->h_text, data, length);
-    std::memset(scratch->h_text + length, 0, (16 - (length & 15)) & 15);
-    const uint32_t seq = ++scratch->seq ? scratch->seq : ++scratch->seq;  // (never 0)
-    const uint32_t segs = scratch->sc->launch_block_small(scratch->h_text, length, scratch->stream, scratch->h_out, scratch->h_counts, scratch->h_counts + 64, seq);
+  if (length <= HG_BLOCK_SMALL_MAX && block_small_db(*db->db)) {
+    uint8_t *h_text = scratch->h_text.get();
+    HgHit *h_out = scratch->h_out.get();
+    uint32_t *h_counts = scratch->h_counts.get();
+    std::memcpy(h_text, data, length);
+    std::memset(h_text + length, 0, (16 - (length & 15)) & 15);
+    const uint32_t seq = next_seq(scratch);
+    const uint32_t segs = scratch->sc->launch_block_small(h_text, length, scratch->stream, h_out, h_counts, h_counts + 64, seq);
     if (segs) {
-      // wait for the kernel's completion word in pinned memory (a few microseconds of polling; a stream synchronisation
-      // sleeps until an interrupt); after ~2 ms of polling fall back to the synchronisation, which also reports errors
-      volatile uint32_t *flag = scratch->h_counts + 64;
-      bool done = false;
-      for (uint32_t spin = 0; spin < 400000 && !(done = *flag == seq); spin++) cpu_relax();
-      if (!done && hipStreamSynchronize(scratch->stream) != hipSuccess) return HS_INVALID;
-      std::atomic_thread_fence(std::memory_order_acquire);
+      if (!wait_done(scratch->stream, h_counts + 64, seq)) return HS_INVALID;
       bool fits = true;
       scratch->hits.clear();
       for (uint32_t g = 0; g < segs && fits; g++) {
-        const uint32_t n = scratch->h_counts[g];
+        const uint32_t n = h_counts[g];
         fits = n <= HG_BLOCK_SMALL_SEG;
-        if (fits) scratch->hits.insert(scratch->hits.end(), scratch->h_out + static_cast<size_t>(g) * HG_BLOCK_SMALL_SEG, scratch->h_out + static_cast<size_t>(g) * HG_BLOCK_SMALL_SEG + n);
+        if (fits) scratch->hits.insert(scratch->hits.end(), h_out + static_cast<size_t>(g) * HG_BLOCK_SMALL_SEG, h_out + static_cast<size_t>(g) * HG_BLOCK_SMALL_SEG + n);
       }
       if (fits) {
         hg_block_rules(scratch->hits);  // (hg_batch.h: every item of hg_scan_blocks runs the same rules)
@@ -330,19 +381,14 @@ int hs_scan(const hs_database_t *db, const char *data, unsigned int length, unsi
       }
     }
   }
-  if (int rc = block_general(scratch, data, length)) return rc;
-  const auto &h = scratch->hits;
-  for (uint32_t i : scratch->order)
-    if (on_event && on_event(h[i].id, scratch->from[i], h[i].to, 0, context)) return HS_SCAN_TERMINATED;
-  return HS_SUCCESS;
+  return block_general_deliver(scratch, data, length,
+                               [&](uint32_t id, uint32_t from, uint32_t to) { return on_event ? on_event(id, from, to, 0, context) : 0; });
 }
 
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ stream mode ------
 namespace {
-constexpr uint64_t FLOW_LAUNCH_BYTES = 64u << 20;  // bytes of writes one launch takes at most (a longer write: several launches)
-
 // Writes of a launch are copied to HBM once (instead of every workgroup of an item reading them over the host link) when
 // bytes x workgroups per item reach this (tools/stream_bench.py measures it; HG_FLOW_HBM_MIN overrides it)
 uint64_t flow_hbm_min() {
@@ -361,50 +407,18 @@ struct FlowReq {   // one write of one stream in one launch
   bool close;
 };
 
-template <typename T>
-bool grow_host(T **p, size_t *cap, size_t need, const char *name) {
-  if (*cap >= need) return true;
-  const size_t n = std::max(need, *cap * 2);
-  hgmem::host_free(*p, name);
-  *p = nullptr;
-  *cap = 0;
-  if (hgmem::host_alloc(p, n * sizeof(T) + 16, name) != hipSuccess) return false;
-  *cap = n;
-  return true;
-}
-
+// The database's tables a stream-mode launch needs on the device: uploaded at the scratch's first stream call.
 int flow_setup(hs_scratch_t *sc, const HgFlowDb &f) {
-  if (!sc->f_flag) {
-    if (hgmem::host_alloc(&sc->f_flag, 4 * sizeof(uint32_t), "hs f_flag") != hipSuccess) return HS_NOMEM;
-    sc->f_flag[0] = sc->f_flag[1] = 0;
+  if (!sc->f_dsoff.get()) {
+    if (!sc->f_dsoff.reserve(f.soff.size(), f.soff.size())) return HS_NOMEM;
+    if (hipMemcpy(sc->f_dsoff.get(), f.soff.data(), f.soff.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return HS_NOMEM;
   }
-  if (!sc->f_dctr) {
-    if (hgmem::dev_alloc(&sc->f_dctr, 4 * sizeof(uint32_t), "hs f_dctr") != hipSuccess) return HS_NOMEM;
-    // (on the scratch's stream, which does not wait for the null stream: ordered before the first launch)
-    if (hipMemsetAsync(sc->f_dctr, 0, 4 * sizeof(uint32_t), sc->stream) != hipSuccess) return HS_NOMEM;
+  if (!f.som.empty() && !sc->f_dsom.get()) {
+    if (!sc->f_dsom.reserve(f.som.size(), f.som.size())) return HS_NOMEM;
+    if (hipMemcpy(sc->f_dsom.get(), f.som.data(), f.som.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return HS_NOMEM;  // (and the offsets)
   }
-  if (!sc->f_dsoff) {
-    if (hgmem::dev_alloc(&sc->f_dsoff, f.soff.size() * sizeof(uint32_t) + 16, "hs f_dsoff") != hipSuccess) return HS_NOMEM;
-    if (hipMemcpy(sc->f_dsoff, f.soff.data(), f.soff.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return HS_NOMEM;
-  }
-  if (!f.som.empty() && !sc->f_dsom) {
-    if (hgmem::dev_alloc(&sc->f_dsom, f.som.size() * sizeof(uint32_t) + 16, "hs f_dsom") != hipSuccess) return HS_NOMEM;
-    if (hipMemcpy(sc->f_dsom, f.som.data(), f.som.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return HS_NOMEM;  // (and the offsets)
-  }
+  sc->stage.with_from = !f.som.empty();
   return HS_SUCCESS;
-}
-
-// The pinned report array and, for SOM databases, the starts beside it: room for `cap` reports.
-bool flow_out_alloc(hs_scratch_t *sc, const HgFlowDb &f, uint32_t cap) {
-  hgmem::host_free(sc->f_out, "hs f_out");
-  hgmem::host_free(sc->f_from, "hs f_from");
-  sc->f_out = nullptr;
-  sc->f_from = nullptr;
-  sc->f_out_cap = 0;
-  if (hgmem::host_alloc(&sc->f_out, static_cast<size_t>(cap) * sizeof(HgHit), "hs f_out") != hipSuccess) return false;
-  if (!f.som.empty() && hgmem::host_alloc(&sc->f_from, static_cast<size_t>(cap) * sizeof(int64_t), "hs f_from") != hipSuccess) return false;
-  sc->f_out_cap = cap;
-  return true;
 }
 
 // One launch over `reqs` (distinct streams): their writes scanned, their states advanced; the reports of each request after
@@ -413,108 +427,84 @@ bool flow_out_alloc(hs_scratch_t *sc, const HgFlowDb &f, uint32_t cap) {
 template <typename OnEvent>
 int flow_launch(hs_scratch_t *sc, const HgFlowDb &f, const std::vector<FlowReq> &reqs, OnEvent &&on_event) {
   const uint32_t n = static_cast<uint32_t>(reqs.size());
+  if (int rc = stage_setup(sc)) return rc;
   if (int rc = flow_setup(sc, f)) return rc;
   uint64_t bytes = 0;
   for (const FlowReq &r : reqs) bytes += (static_cast<uint64_t>(r.len) + 15u) & ~15ull;
   const size_t sw = static_cast<size_t>(n) * f.swords;
-  if (!grow_host(&sc->f_text, &sc->f_text_cap, bytes + 16, "hs f_text") || !grow_host(&sc->f_items, &sc->f_items_cap, n, "hs f_items"))
+  HgStage &st = sc->stage;
+  if (!st.text.reserve(bytes + 16, std::max<size_t>(bytes + 16, 2 * st.text.cap())) || !sc->f_items.reserve(n, std::max<size_t>(n, 2 * sc->f_items.cap())) ||
+      !sc->f_sin.reserve(sw, sw) || !sc->f_sout.reserve(sw, sw))
     return HS_NOMEM;
-  if (sc->f_state_cap < sw) {  // (f_sin and f_sout have the same capacity)
-    hgmem::host_free(sc->f_sin, "hs f_sin");
-    hgmem::host_free(sc->f_sout, "hs f_sout");
-    sc->f_sin = sc->f_sout = nullptr;
-    sc->f_state_cap = 0;
-    if (hgmem::host_alloc(&sc->f_sin, sw * sizeof(uint32_t) + 16, "hs f_sin") != hipSuccess ||
-        hgmem::host_alloc(&sc->f_sout, sw * sizeof(uint32_t) + 16, "hs f_sout") != hipSuccess)
-      return HS_NOMEM;
-    sc->f_state_cap = sw;
-  }
+  uint8_t *h_text = st.text.get();
   uint64_t at = 0;
   for (uint32_t i = 0; i < n; i++) {
     const FlowReq &r = reqs[i];
-    sc->f_items[i] = HgFlowItem{at, r.len, r.close ? HG_FLOW_ITEM_CLOSE : 0u};
-    if (r.len) std::memcpy(sc->f_text + at, r.data, r.len);
+    sc->f_items.get()[i] = HgFlowItem{at, r.len, r.close ? HG_FLOW_ITEM_CLOSE : 0u};
+    if (r.len) std::memcpy(h_text + at, r.data, r.len);
     const uint64_t end = (at + r.len + 15u) & ~15ull;
-    std::memset(sc->f_text + at + r.len, 0, end - at - r.len);
+    std::memset(h_text + at + r.len, 0, end - at - r.len);
     at = end;
-    std::memcpy(sc->f_sin + static_cast<size_t>(i) * f.swords, r.s->state.data(), f.swords * sizeof(uint32_t));
+    std::memcpy(sc->f_sin.get() + static_cast<size_t>(i) * f.swords, r.s->state.data(), f.swords * sizeof(uint32_t));
   }
-  const uint8_t *text = sc->f_text;
+  const uint8_t *text = h_text;
   // (the SOM lanes read their write byte by byte: from HBM always, not over the host link)
   if (bytes && (bytes * f.ngroups >= flow_hbm_min() || !f.som.empty())) {
-    if (sc->f_dtext_cap < bytes) {
-      hgmem::dev_free(sc->f_dtext, "hs f_dtext");
-      sc->f_dtext = nullptr;
-      sc->f_dtext_cap = 0;
-      const size_t cap = std::max<size_t>(bytes, 1u << 20);
-      if (hgmem::dev_alloc(&sc->f_dtext, cap + 16, "hs f_dtext") != hipSuccess) return HS_NOMEM;
-      sc->f_dtext_cap = cap;
-    }
-    if (hipMemcpyAsync(sc->f_dtext, sc->f_text, bytes, hipMemcpyHostToDevice, sc->stream) != hipSuccess) return HS_INVALID;
-    text = sc->f_dtext;
+    if (!st.dtext.reserve(bytes, std::max<size_t>(bytes, 1u << 20))) return HS_NOMEM;
+    if (hipMemcpyAsync(st.dtext.get(), h_text, bytes, hipMemcpyHostToDevice, sc->stream) != hipSuccess) return HS_INVALID;
+    text = st.dtext.get();
   }
   const size_t work = static_cast<size_t>(n) * 2 * f.som_total;  // int64 starts of the SOM lanes (n <= f.launch_items)
-  if (sc->f_work_cap < work) {
-    hgmem::dev_free(sc->f_dwork, "hs f_dwork");
-    sc->f_dwork = nullptr;
-    sc->f_work_cap = 0;
-    if (hgmem::dev_alloc(&sc->f_dwork, work * sizeof(int64_t) + 16, "hs f_dwork") != hipSuccess) return HS_NOMEM;
-    sc->f_work_cap = work;
-  }
+  if (!sc->f_dwork.reserve(work, work)) return HS_NOMEM;
   const HgDbView &v = sc->sc->view();
   uint32_t total = 0;
-  for (;;) {
-    if (sc->f_out_cap == 0 && !flow_out_alloc(sc, f, 4096)) return HS_NOMEM;
-    const uint32_t seq = ++sc->seq ? sc->seq : ++sc->seq;
-    HgFlowArgs a{};
-    a.patterns = v.patterns;
-    a.pool = v.pool;
-    a.npatterns = v.npatterns;
-    a.text = text;
-    a.items = sc->f_items;
-    a.soff = sc->f_dsoff;
-    a.state_in = sc->f_sin;
-    a.state_out = sc->f_sout;
-    a.out = sc->f_out;
-    a.cap = sc->f_out_cap;
-    a.ngroups = f.ngroups;
-    a.swords = f.swords;
-    a.seq = seq;
-    a.d_total = sc->f_dctr;
-    a.d_done = sc->f_dctr + 1;
-    a.h_flag = sc->f_flag;
-    a.som_list = sc->f_dsom;
-    a.nsom = static_cast<uint32_t>(f.som.size() / 2);
-    a.som_width = f.som_width;
-    a.som_work = sc->f_dwork;
-    a.from_out = sc->f_from;
-    if (hg_flow_launch(a, n, sc->stream) != 0) return HS_INVALID;
-    volatile uint32_t *flag = sc->f_flag + 1;
-    bool done = false;
-    for (uint32_t spin = 0; spin < 400000 && !(done = *flag == seq); spin++) cpu_relax();
-    if (!done && hipStreamSynchronize(sc->stream) != hipSuccess) return HS_INVALID;
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (*flag != seq) return HS_INVALID;
-    total = sc->f_flag[0];
-    if (total <= sc->f_out_cap) break;
-    // more reports than room: the states in f_sin are untouched, the launch is repeated with room for all
-    if (!flow_out_alloc(sc, f, total * 2)) return HS_NOMEM;
-  }
+  // (more reports than room: the states in f_sin are untouched, the launch is repeated with room for twice the reports)
+  const int launched = launch_until_fits(
+      sc, [](uint32_t reports, uint32_t) { return reports > 0x7FFFFFFFu ? 0u : reports * 2; },
+      [&](uint32_t seq, HgHit *out, int64_t *from, uint32_t cap) {
+        HgFlowArgs a{};
+        a.patterns = v.patterns;
+        a.pool = v.pool;
+        a.npatterns = v.npatterns;
+        a.text = text;
+        a.items = sc->f_items.get();
+        a.soff = sc->f_dsoff.get();
+        a.state_in = sc->f_sin.get();
+        a.state_out = sc->f_sout.get();
+        a.out = out;
+        a.cap = cap;
+        a.ngroups = f.ngroups;
+        a.swords = f.swords;
+        a.seq = seq;
+        a.d_total = st.dctr.get();
+        a.d_done = st.dctr.get() + 1;
+        a.h_flag = st.flag.get();
+        a.som_list = sc->f_dsom.get();
+        a.nsom = static_cast<uint32_t>(f.som.size() / 2);
+        a.som_width = f.som_width;
+        a.som_work = sc->f_dwork.get();
+        a.from_out = from;
+        return hg_flow_launch(a, n, sc->stream) != 0 ? HS_INVALID : HS_SUCCESS;
+      },
+      &total);
+  if (launched != HS_SUCCESS) return launched == LAUNCH_TOO_MANY ? HS_NOMEM : launched;  // (2^31 reports and more: the doubled array has no 32-bit capacity)
   // the report rules, per request (hg_flow_rules.h)
   const HgDb &db = *sc->db;
   const bool som = f.som_total != 0;
   std::vector<std::vector<std::pair<uint32_t, uint32_t>>> per(n);
   std::vector<std::vector<int64_t>> per_from(som ? n : 0);
+  const HgHit *out = st.out.get();
+  const int64_t *from = st.from.get();
   for (uint32_t i = 0; i < total; i++) {
-    const HgHit &h = sc->f_out[i];
+    const HgHit &h = out[i];
     per[h.line_no & 0xFFFFFFFFu].emplace_back(static_cast<uint32_t>(h.line_no >> 32), h.to);
-    if (som) per_from[h.line_no & 0xFFFFFFFFu].push_back(sc->f_from[i]);  // (read for SOM expressions only)
+    if (som) per_from[h.line_no & 0xFFFFFFFFu].push_back(from[i]);  // (read for SOM expressions only)
   }
   int rc = HS_SUCCESS;
   std::vector<HgFlowRep> reps;
   for (uint32_t i = 0; i < n; i++) {
     hs_stream_t *s = reqs[i].s;
-    std::memcpy(s->state.data(), sc->f_sout + static_cast<size_t>(i) * f.swords, f.swords * sizeof(uint32_t));
+    std::memcpy(s->state.data(), sc->f_sout.get() + static_cast<size_t>(i) * f.swords, f.swords * sizeof(uint32_t));
     hg_flow_rules(db.patterns.data(), db.bounds.empty() ? nullptr : db.bounds.data(), s->rules, reqs[i].len, per[i].data(), per[i].size(), reps,
                   som ? per_from[i].data() : nullptr, f.horizon_bits);
     for (const HgFlowRep &x : reps)
@@ -699,105 +689,65 @@ int hg_scan_stream_batch(hs_stream_t *const *streams, const char *const *data, c
 
 // ------------------------------------------------------------------------------------------- batched block scan ------
 namespace {
-constexpr uint32_t BATCH_OUT_MAX = 1u << 24;  // records the pinned report array grows to at most (256 MiB); past it: item by item
-
-int batch_setup(hs_scratch_t *sc) {
-  if (!sc->b_flag) {
-    if (hgmem::host_alloc(&sc->b_flag, 4 * sizeof(uint32_t), "hs b_flag") != hipSuccess) return HS_NOMEM;
-    sc->b_flag[0] = sc->b_flag[1] = 0;
-  }
-  if (!sc->b_dctr) {
-    if (hgmem::dev_alloc(&sc->b_dctr, 4 * sizeof(uint32_t), "hs b_dctr") != hipSuccess) return HS_NOMEM;
-    // (on the scratch's stream, which does not wait for the null stream: ordered before the first launch)
-    if (hipMemsetAsync(sc->b_dctr, 0, 4 * sizeof(uint32_t), sc->stream) != hipSuccess) return HS_NOMEM;
-  }
-  return HS_SUCCESS;
-}
-
-bool batch_out_alloc(hs_scratch_t *sc, uint32_t cap) {
-  hgmem::host_free(sc->b_out, "hs b_out");
-  sc->b_out = nullptr;
-  sc->b_out_cap = 0;
-  if (hgmem::host_alloc(&sc->b_out, static_cast<size_t>(cap) * sizeof(HgHit), "hs b_out") != hipSuccess) return false;
-  sc->b_out_cap = cap;
-  return true;
-}
-
 // One launch of hg_block_batch_kernel over the items `pick` (indices into data / lengths, each of 1 .. HG_BLOCK_SMALL_MAX
 // bytes): per[k] receives item pick[k]'s reports after the report rules, in (to, id) order.  Returns HS_SUCCESS, an error, or
-// 1 when the launch's reports exceed what the report array may grow to (the caller then scans these items one by one).
+// LAUNCH_TOO_MANY when the launch's reports exceed what the report array may grow to (the caller then scans these items one by one).
 int batch_launch(hs_scratch_t *sc, const char *const *data, const unsigned int *lengths, const std::vector<uint32_t> &pick, std::vector<std::vector<HgHit>> &per) {
   const uint32_t n = static_cast<uint32_t>(pick.size());
-  if (int rc = batch_setup(sc)) return rc;
+  HgStage &st = sc->stage;
+  if (int rc = stage_setup(sc)) return rc;
   const uint64_t bytes = hg_batch_bytes(lengths, pick.data(), n);
-  if (!grow_host(&sc->b_text, &sc->b_text_cap, bytes + 16, "hs b_text") || !grow_host(&sc->b_items, &sc->b_items_cap, n, "hs b_items")) return HS_NOMEM;
-  hg_batch_pack(data, lengths, pick.data(), n, sc->b_text, sc->b_items);
+  if (!st.text.reserve(bytes + 16, std::max<size_t>(bytes + 16, 2 * st.text.cap())) || !sc->b_items.reserve(n, std::max<size_t>(n, 2 * sc->b_items.cap())))
+    return HS_NOMEM;
+  hg_batch_pack(data, lengths, pick.data(), n, st.text.get(), sc->b_items.get());
   const HgDbView &v = sc->sc->view();
   uint32_t ppw;
   const uint32_t ngroups = hg_block_small_grouping(v.npatterns, &ppw);
-  const uint8_t *text = sc->b_text;
-  const HgBatchItem *items = sc->b_items;
+  const uint8_t *text = st.text.get();
+  const HgBatchItem *items = sc->b_items.get();
   // Every group's workgroups read every item once: past bytes x groups the bytes go to HBM first.  The threshold is the flow
   // path's (HG_FLOW_HBM_MIN), which is no measured optimum there and none here.
   if (bytes * ngroups >= flow_hbm_min()) {
-    if (sc->b_dtext_cap < bytes) {
-      hgmem::dev_free(sc->b_dtext, "hs b_dtext");
-      sc->b_dtext = nullptr;
-      sc->b_dtext_cap = 0;
-      const size_t cap = std::max<size_t>(bytes, 1u << 20);
-      if (hgmem::dev_alloc(&sc->b_dtext, cap + 16, "hs b_dtext") != hipSuccess) return HS_NOMEM;
-      sc->b_dtext_cap = cap;
-    }
-    if (hipMemcpyAsync(sc->b_dtext, sc->b_text, bytes, hipMemcpyHostToDevice, sc->stream) != hipSuccess) return HS_INVALID;
-    text = sc->b_dtext;
     // ... and the item table with them (every group's workgroups read their shard's entries)
-    if (sc->b_ditems_cap < n) {
-      hgmem::dev_free(sc->b_ditems, "hs b_ditems");
-      sc->b_ditems = nullptr;
-      sc->b_ditems_cap = 0;
-      const size_t cap = std::max<size_t>(n, 4096);
-      if (hgmem::dev_alloc(&sc->b_ditems, cap * sizeof(HgBatchItem), "hs b_ditems") != hipSuccess) return HS_NOMEM;
-      sc->b_ditems_cap = cap;
-    }
-    if (hipMemcpyAsync(sc->b_ditems, sc->b_items, n * sizeof(HgBatchItem), hipMemcpyHostToDevice, sc->stream) != hipSuccess) return HS_INVALID;
-    items = sc->b_ditems;
+    if (!st.dtext.reserve(bytes, std::max<size_t>(bytes, 1u << 20)) || !sc->b_ditems.reserve(n, std::max<size_t>(n, 4096))) return HS_NOMEM;
+    if (hipMemcpyAsync(st.dtext.get(), text, bytes, hipMemcpyHostToDevice, sc->stream) != hipSuccess ||
+        hipMemcpyAsync(sc->b_ditems.get(), items, n * sizeof(HgBatchItem), hipMemcpyHostToDevice, sc->stream) != hipSuccess)
+      return HS_INVALID;
+    text = st.dtext.get();
+    items = sc->b_ditems.get();
   }
   uint32_t total = 0;
-  for (;;) {
-    if (sc->b_out_cap == 0 && !batch_out_alloc(sc, 4096)) return HS_NOMEM;
-    const uint32_t seq = ++sc->seq ? sc->seq : ++sc->seq;
-    HgBatchArgs a{};
-    a.patterns = v.patterns;
-    a.pool = v.pool;
-    a.npatterns = v.npatterns;
-    a.ppw = ppw;
-    a.ngroups = ngroups;
-    a.nshards = std::max(1u, std::min(n, HG_BATCH_MAX_WGS / ngroups));
-    a.text = text;
-    a.items = items;
-    a.nitems = n;
-    a.out = sc->b_out;
-    a.cap = sc->b_out_cap;
-    a.seq = seq;
-    a.d_total = sc->b_dctr;
-    a.d_done = sc->b_dctr + 1;
-    a.h_flag = sc->b_flag;
-    if (hg_batch_launch(a, sc->stream) != 0) return HS_INVALID;
-    volatile uint32_t *flag = sc->b_flag + 1;
-    bool done = false;
-    for (uint32_t spin = 0; spin < 400000 && !(done = *flag == seq); spin++) cpu_relax();
-    if (!done && hipStreamSynchronize(sc->stream) != hipSuccess) return HS_INVALID;
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (*flag != seq) return HS_INVALID;
-    total = sc->b_flag[0];
-    if (total <= sc->b_out_cap) break;
-    // more reports than room: items keep no state, the launch is repeated with room for all
-    if (total > BATCH_OUT_MAX) return 1;
-    if (!batch_out_alloc(sc, static_cast<uint32_t>(std::min<uint64_t>(BATCH_OUT_MAX, std::max<uint64_t>(total, 2ull * sc->b_out_cap))))) return HS_NOMEM;
-  }
+  // (more reports than room: items keep no state, the launch is repeated with room for all, up to BATCH_OUT_MAX records)
+  const int launched = launch_until_fits(
+      sc,
+      [](uint32_t reports, uint32_t cap) {
+        return reports > BATCH_OUT_MAX ? 0u : static_cast<uint32_t>(std::min<uint64_t>(BATCH_OUT_MAX, std::max<uint64_t>(reports, 2ull * cap)));
+      },
+      [&](uint32_t seq, HgHit *out, int64_t *, uint32_t cap) {
+        HgBatchArgs a{};
+        a.patterns = v.patterns;
+        a.pool = v.pool;
+        a.npatterns = v.npatterns;
+        a.ppw = ppw;
+        a.ngroups = ngroups;
+        a.nshards = std::max(1u, std::min(n, HG_BATCH_MAX_WGS / ngroups));
+        a.text = text;
+        a.items = items;
+        a.nitems = n;
+        a.out = out;
+        a.cap = cap;
+        a.seq = seq;
+        a.d_total = st.dctr.get();
+        a.d_done = st.dctr.get() + 1;
+        a.h_flag = st.flag.get();
+        return hg_batch_launch(a, sc->stream) != 0 ? HS_INVALID : HS_SUCCESS;
+      },
+      &total);
+  if (launched != HS_SUCCESS) return launched;
+  const HgHit *out = st.out.get();
   per.assign(n, {});
   for (uint32_t i = 0; i < total; i++)
-    if (sc->b_out[i].line_no < n) per[sc->b_out[i].line_no].push_back(sc->b_out[i]);
+    if (out[i].line_no < n) per[out[i].line_no].push_back(out[i]);
   for (auto &h : per) hg_block_rules(h);
   return HS_SUCCESS;
 }
@@ -814,11 +764,9 @@ int hg_scan_blocks(const hs_database_t *db, const char *const *data, const unsig
   if (db->mode != HS_MODE_BLOCK) return HS_DB_MODE_ERROR;
   if (hipSetDevice(scratch->sc->device()) != hipSuccess) return HS_INVALID;
   // What the kernel takes is what hs_scan's one-launch path takes; everything else goes item by item through the general path.
-  static const bool small_path = !std::getenv("HG_NO_BLOCK_SMALL");
   const HgDb &d = *db->db;
   uint32_t ppw;
-  const bool kernel_db = small_path && !d.nsom && !d.comb_pass() && d.bounds.empty() && !d.nhuge &&
-                         hg_block_small_grouping(static_cast<uint32_t>(d.patterns.size()), &ppw) <= 64;
+  const bool kernel_db = block_small_db(d) && !d.nhuge && hg_block_small_grouping(static_cast<uint32_t>(d.patterns.size()), &ppw) <= 64;
   // a launch's reports are counted in 32 bits: at most (bytes + items) x expressions of them
   const uint64_t launch_bytes = std::max<uint64_t>(HG_BLOCK_SMALL_MAX + 16, std::min<uint64_t>(FLOW_LAUNCH_BYTES, 0xF0000000ull / d.patterns.size() / 2));
   int rc = HS_SUCCESS;
@@ -854,13 +802,11 @@ int hg_scan_blocks(const hs_database_t *db, const char *const *data, const unsig
             break;
           }
       } else if (lengths[j]) {
-        if (int r = block_general(scratch, data[j], lengths[j])) return r;
-        const auto &h = scratch->hits;
-        for (uint32_t o : scratch->order)
-          if (on_event && on_event(j, h[o].id, scratch->from[o], h[o].to, 0, context)) {
-            rc = HS_SCAN_TERMINATED;
-            break;
-          }
+        const int r = block_general_deliver(scratch, data[j], lengths[j], [&](uint32_t id, uint32_t from, uint32_t to) {
+          return on_event ? on_event(j, id, from, to, 0, context) : 0;
+        });
+        if (r != HS_SUCCESS && r != HS_SCAN_TERMINATED) return r;
+        if (r == HS_SCAN_TERMINATED) rc = r;  // (the rest of this item is dropped, the next items are still scanned)
       }
       if (picked) k++;
     }

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cassert>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -56,5 +57,45 @@ inline void host_free(void *p, const char *name) {
   if (log_file()) note("free  host %-14s %p\n", name, p);
   (void)hipHostFree(p);
 }
+
+enum class Space { Host, Dev };  // pinned host memory, device memory
+
+// The owner of one allocation: pointer, capacity in elements, log name, bytes of slack behind the elements (16 where kernels
+// read whole 16-byte words up to the end; 0 for arrays that are written by index).  Not copyable.  The destructor frees, so
+// every `alloc` line of the log gets its `free` line; reserve() is the only way to allocate.
+template <typename T, Space S>
+class Buf {
+ public:
+  explicit Buf(const char *name, size_t slack = 16) : name_(name), slack_(slack) {}
+  Buf(const Buf &) = delete;
+  Buf &operator=(const Buf &) = delete;
+  ~Buf() { release(); }
+  T *get() const { return p_; }
+  size_t cap() const { return cap_; }
+  // Room for `need` elements: nothing to do if there is.  Else the buffer is freed and one of new_cap (>= need) elements plus
+  // the slack allocated; contents are not kept.  false, with {nullptr, 0} left behind, if that fails.
+  bool reserve(size_t need, size_t new_cap) {
+    if (cap_ >= need) return true;
+    assert(new_cap >= need);
+    release();
+    const size_t bytes = new_cap * sizeof(T) + slack_;
+    if ((S == Space::Dev ? dev_alloc(&p_, bytes, name_) : host_alloc(&p_, bytes, name_)) != hipSuccess) {
+      p_ = nullptr;
+      return false;
+    }
+    cap_ = new_cap;
+    return true;
+  }
+
+ private:
+  void release() {
+    S == Space::Dev ? dev_free(p_, name_) : host_free(p_, name_);
+    p_ = nullptr, cap_ = 0;
+  }
+  T *p_ = nullptr;
+  size_t cap_ = 0;
+  const char *name_;
+  size_t slack_;
+};
 
 }  // namespace hgmem

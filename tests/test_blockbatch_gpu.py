@@ -203,7 +203,7 @@ def test_report_array_grows_and_second_call_on_the_same_scratch():
     rng = random.Random(3)
     items = [text(rng, 8192) for _ in range(6)]
     got = check(bdb, twin, items)
-    # 6 x 8192 = 49152 reports and more against the 4096 records batch_launch (hg_hsface.hip) allocates first and the 512 a
+    # 6 x 8192 = 49152 reports and more against the 4096 records launch_until_fits (hg_hsface.hip) allocates first and the 512 a
     # workgroup stages per round: the array grew and the launch was repeated.  (Should that first size ever exceed 49152,
     # this batch must grow with it.)
     assert all(len(g) >= 8192 for g in got)

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Stream mode on the GPU (hs_scan_stream / hg_scan_stream_batch): per-call latency, batch throughput and the HBM cut-off.
 
-    python tools/stream_bench.py [--quick] [--hbm-child MODE]
+    python tools/stream_bench.py [--quick] [--lib PATH] [--hbm-child MODE]
     python tools/stream_bench.py --som [--rounds N]
 
 Prints one line per measurement.  Reports are not delivered to Python (NULL callback), so the numbers are the library's.
+--lib: another build of the library (e.g. one of the parent commit), as tools/block_batch_bench.py's.
 The HBM cut-off (HG_FLOW_HBM_MIN: bytes x workgroups per item from which a launch's writes are copied to HBM first) is
 measured by running the batch legs in child processes with the copy always on (0) and always off (2^62).
 --som: the 4-expression set without the SOM flag and with it (horizons LARGE and SMALL), alternated round by round in one
@@ -118,7 +119,12 @@ def main():
     ap.add_argument("--som", action="store_true", help="start of match: plain against SOM LARGE / SMALL, alternated")
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--hbm-child", choices=["on", "off"], help="(internal) batch legs with the HBM copy forced on / off")
+    ap.add_argument("--lib", help="another build of libhyperscanner.so")
     args = ap.parse_args()
+    if args.lib:
+        import hypergrep_amd
+
+        hypergrep_amd.configure_libraries(libhs=os.path.abspath(args.lib))
     if args.hbm_child:
         run_batches(True)
         return
@@ -137,7 +143,7 @@ def main():
     for mode, value in (("on", "0"), ("off", str(1 << 62))):
         env = dict(os.environ, HG_FLOW_HBM_MIN=value)
         print(f"-- HBM copy forced {mode} (HG_FLOW_HBM_MIN={value})", flush=True)
-        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--hbm-child", mode], env=env, capture_output=True, text=True, timeout=900)
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--hbm-child", mode] + (["--lib", args.lib] if args.lib else []), env=env, capture_output=True, text=True, timeout=900)
         sys.stdout.write(out.stdout)
         if out.returncode:
             sys.stdout.write(out.stderr[-3000:])

@@ -99,6 +99,8 @@ def _merge_resources() -> None:
             raise RuntimeError(f"{kernel} uses {res['ScratchSize [bytes/lane]']} bytes of scratch per lane: the streaming hot path must stay in registers")
         if "hg_som_kernel" in kernel and res.get("ScratchSize [bytes/lane]", 0) > 0:
             raise RuntimeError(f"{kernel} uses {res['ScratchSize [bytes/lane]']} bytes of scratch per lane: the start-of-match walks keep their state in registers / LDS")
+        if "hg_minlen_kernel" in kernel and res.get("ScratchSize [bytes/lane]", 0) > 0:
+            raise RuntimeError(f"{kernel} uses {res['ScratchSize [bytes/lane]']} bytes of scratch per lane: the match-length walks keep their state in registers / LDS")
         if "hg_flow_som_kernel" in kernel and res.get("ScratchSize [bytes/lane]", 0) > 0:
             raise RuntimeError(f"{kernel} uses {res['ScratchSize [bytes/lane]']} bytes of scratch per lane: the stream-mode start-of-match lanes keep their starts in device memory")
         if "hg_block_batch_kernel" in kernel and (res.get("ScratchSize [bytes/lane]", 0) > 0 or res.get("VGPRs Spill", 0) > 0):

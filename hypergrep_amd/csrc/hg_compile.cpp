@@ -1686,15 +1686,28 @@ void check_ext_fields(const hs_expr_ext_t &x, uint32_t f) {
 }
 
 // The rules that need the expression's minimum width; `width` bounds from below the length of every match, and so `to`.
-// Returns the shortest match length.
-long check_ext_width(const hs_expr_ext_t &x, uint32_t k, bool edit, long width) {
+// Returns the shortest match length.  *min_length: the min_length the match-length pass (hg_som.hip) filters the expression's
+// reports by, 0 when it has none or one that removes nothing (at most the shortest match: dropped).  `longest`: the longest
+// match (max_match_len: negative when unbounded), `a`: the automaton before any expansion.
+long check_ext_width(const hs_expr_ext_t &x, uint32_t k, bool edit, long width, long longest, const Automaton &a, uint32_t *min_length) {
+  *min_length = 0;
   if (k && static_cast<long>(k) >= width)
     throw CompileError(std::string(edit ? "edit_distance" : "hamming_distance") + " " + std::to_string(k) +
                        " is not smaller than the expression's minimum match width " + std::to_string(width) + " (the expression would match anything)");
   const long least = width - (edit ? static_cast<long>(k) : 0);  // the shortest match
-  if ((x.flags & HS_EXT_FLAG_MIN_LENGTH) && x.min_length > static_cast<unsigned long long>(least))
-    throw CompileError("min_length " + std::to_string(x.min_length) + " could remove reports (it is supported up to the shortest match length, " +
-                       std::to_string(least) + " here): start-of-match filtering is not implemented");
+  if (!(x.flags & HS_EXT_FLAG_MIN_LENGTH) || x.min_length <= static_cast<unsigned long long>(least)) return least;
+  const std::string could = "min_length " + std::to_string(x.min_length) + " could remove reports";
+  if (k)
+    throw CompileError(could + " (it is supported up to the shortest match length, " + std::to_string(least) +
+                       " here): start-of-match filtering is not implemented");  // (not for approximate expressions)
+  // (a raw report's `to` is below 2^31: no match of an unbounded expression is longer either)
+  if (longest >= 0 ? x.min_length > static_cast<unsigned long long>(longest) : x.min_length >= (1ull << 31))
+    throw CompileError(could + ": no match of the expression can be that long" +
+                       (longest >= 0 ? " (its longest match has " + std::to_string(longest) + " bytes)" : std::string(" (a scanned piece has less than 2^31 bytes)")));
+  if (a.nw > HG_MAX_W)
+    throw CompileError(could + ": that needs an automaton of at most " + std::to_string(HG_MAX_NODES) + " nodes (HG_MAX_NODES); this expression has " +
+                       std::to_string(a.nn));
+  *min_length = static_cast<uint32_t>(x.min_length);
   return least;
 }
 
@@ -2035,8 +2048,10 @@ Cover approx_cover(const Node &root, uint32_t k, HgPattern &p) {
   return cover;
 }
 
-// The reverse automaton of the start-of-match pass (hg_som.h): the same nodes, with the follow table transposed.
-void emit_som_follow(HgDb &db, HgPattern &p) {
+// The reverse automaton of the start-of-match pass and the match-length pass (hg_som.h): the same nodes, with the follow
+// table transposed.  som: the expression has HS_FLAG_SOM_LEFTMOST (else a filtering min_length, whose node limit
+// check_ext_width has applied).
+void emit_som_follow(HgDb &db, HgPattern &p, bool som) {
   if (p.nw > HG_MAX_W)
     throw CompileError("HS_FLAG_SOM_LEFTMOST needs an automaton of at most " + std::to_string(HG_MAX_NODES) + " nodes (HG_MAX_NODES); this expression has " +
                        std::to_string(p.nnodes));
@@ -2044,7 +2059,7 @@ void emit_som_follow(HgDb &db, HgPattern &p) {
   for (uint32_t v = 0; v < p.nnodes; v++)
     for (uint32_t w = 0; w < p.nw; w++)
       for (uint32_t x = db.pool[p.follow_off + v * p.nw + w]; x; x &= x - 1) setbit(db, p.som_follow_off + (w * 32 + hg_ctz(x)) * p.nw, v);
-  db.nsom++;
+  if (som) db.nsom++;
 }
 
 // Expressions that share a report id either all carry HS_FLAG_SOM_LEFTMOST or none does; the SOM expressions of one id
@@ -2254,6 +2269,7 @@ int hgc_compile_ext(const char *const *exprs, const unsigned *flags, const unsig
     std::vector<Cover> covers(n);
     std::map<uint32_t, CombProgram> programs;  // expression index -> its program (combinations)
     std::map<uint32_t, std::pair<uint32_t, uint32_t>> bounds;  // expression index -> its offset bounds (those that have any)
+    std::map<uint32_t, uint32_t> min_lengths;                  // expression index -> its filtering min_length (those that have one)
     for (at = 0; at < static_cast<int>(n); at++) {
       const uint32_t f = flags ? flags[at] : 0, id = ids ? ids[at] : 0;
       if (f & ~HG_FLAGS_SUPPORTED) throw CompileError("unsupported flag bits");
@@ -2272,23 +2288,26 @@ int hgc_compile_ext(const char *const *exprs, const unsigned *flags, const unsig
       const bool edit = x && (x->flags & HS_EXT_FLAG_EDIT_DISTANCE);
       const uint32_t k = !x ? 0u : edit ? x->edit_distance : ((x->flags & HS_EXT_FLAG_HAMMING_DISTANCE) ? x->hamming_distance : 0u);
       std::pair<uint32_t, uint32_t> bound{0u, HG_BOUND_NONE};
-      if (x) bound = ext_bounds(*x, check_ext_width(*x, k, edit, min_match_len(*a.root)));
+      uint32_t min_length = 0;
+      if (x) bound = ext_bounds(*x, check_ext_width(*x, k, edit, min_match_len(*a.root), max_match_len(*a.root), a, &min_length));
       if (bound.first || bound.second != HG_BOUND_NONE) bounds[at] = bound;
+      if (min_length) min_lengths[at] = min_length;
       if (k) a = expand_approx(a, k, edit, f);
       HgPattern p{};
       p.id = id;
       p.flags = f;
       p.nnodes = a.nn;
       p.nw = a.nw;
-      // (a first end below min_offset must not stop the routines: every end is emitted, the report rules keep the smallest in bounds)
-      p.single = (f & HG_FLAG_SINGLEMATCH) && !bound.first ? 1 : 0;
+      // (a first end below min_offset, or of a match shorter than min_length, must not stop the routines: every end is emitted,
+      // the report rules keep the smallest that passes the parameters)
+      p.single = (f & HG_FLAG_SINGLEMATCH) && !bound.first && !min_length ? 1 : 0;
       if (a.nw > HG_MAX_W) emit_huge_tables(*db, a, p);
       else emit_dense_tables(*db, a, p);
       set_simple_flags(*db, p);
       covers[at] = k ? approx_cover(*a.root, k, p) : literal_cover(*a.root, p);
       const long ml = max_match_len(*a.root);
       p.max_len = ml > 0 ? static_cast<uint32_t>(ml + (edit ? k : 0u)) : 0;  // (insertions lengthen a match by up to k)
-      if (f & HG_FLAG_SOM_LEFTMOST) emit_som_follow(*db, p);
+      if ((f & HG_FLAG_SOM_LEFTMOST) || min_length) emit_som_follow(*db, p, (f & HG_FLAG_SOM_LEFTMOST) != 0);
       if (f & HG_FLAG_QUIET) db->nquiet++;
       db->max_id = std::max(db->max_id, id);
       db->patterns.push_back(p);
@@ -2301,6 +2320,10 @@ int hgc_compile_ext(const char *const *exprs, const unsigned *flags, const unsig
         db->bounds[2 * i] = it == bounds.end() ? 0u : it->second.first;
         db->bounds[2 * i + 1] = it == bounds.end() ? HG_BOUND_NONE : it->second.second;
       }
+    }
+    if (!min_lengths.empty()) {
+      db->min_lengths.assign(n, 0u);
+      for (auto &kv : min_lengths) db->min_lengths[kv.first] = kv.second;
     }
     link_som_ids(*db);
     link_combinations(*db, programs);

@@ -61,6 +61,10 @@ struct HgDb {
   // Offset bounds (hs_expr_ext_t min_offset / max_offset): {lo, hi} per expression, lo <= to <= hi; empty unless some expression
   // has a bound that can remove a report (HgDbView::bounds)
   std::vector<uint32_t> bounds;
+  // min_length (hs_expr_ext_t): one word per expression, the least length of a match whose report exists, 0 for expressions
+  // without one; empty unless some expression has a min_length that can remove a report.  The scanner then runs the
+  // match-length pass over each pass's raw reports (hg_som.h, hg_minlen_kernel)
+  std::vector<uint32_t> min_lengths;
   uint32_t n_confirm_mode[HG_CONFIRM_MODES] = {};  // tier-0 patterns by confirm routine (hg_confirm_mode)
   std::vector<std::string> exprs;
   bool tuned = false;

@@ -27,11 +27,11 @@ struct HgDeferred {
   uint32_t rank;      // newlines between the tile start and pos
 };
 // The scanner's small device state is ONE block of words (reset by one launch, read back by one copy):
-//   [0, 8) counters, [24, 28) finalize totals {kept, raw, large buckets, -}, [28, 30) {count, overflow flag}
+//   [0, 8) counters, [16] reports the match-length pass kept, [24, 28) finalize totals {kept, raw, large buckets, -}, [28, 30) {count, overflow flag}
 //   of the finalize, [32, 36) tile-scan state (HgTileBase), [64, 128) tile cursors: one per pipeline chunk (a cursor of its own
 //   for each of the 64 chunks a pass may have, all zeroed by hg_reset_kernel: no chunk ever waits for, or races with, the
 //   reset of a cursor an earlier chunk has used)
-enum { HG_ST_FIN_TOTAL = 24, HG_ST_SELECTED = 28, HG_ST_FINAL = 32, HG_ST_WORDS = 36, HG_ST_ZERO_WORDS = 32,
+enum { HG_ST_MINLEN_KEPT = 16, HG_ST_FIN_TOTAL = 24, HG_ST_SELECTED = 28, HG_ST_FINAL = 32, HG_ST_WORDS = 36, HG_ST_ZERO_WORDS = 32,
        HG_ST_BLOCK_DONE = 40 };  // (outside the words a pass resets: workgroups of hg_block_small_kernel that have finished)
 enum { HG_CNT_CANDS = 0, HG_CNT_HITS = 1, HG_CNT_CAND_NEED = 2, HG_CNT_HIT_NEED = 3, HG_CNT_DEFER_NEED = 4,
        HG_CNT_HITS_WRAPPED = 5,  // the 32-bit hit counter went round (direct appends): the buffer is scanned in segments instead
@@ -126,7 +126,7 @@ struct HgScanOutput {
   uint64_t n_hits;       // final (ordered, de-duplicated) hits
   uint64_t n_pieces;     // line pieces in the buffer (the reference's final line_number)
   uint64_t n_cands;      // verified required-literal occurrences
-  uint64_t n_raw_hits;   // reports before de-duplication
+  uint64_t n_raw_hits;   // reports before de-duplication (and before the min_length filter)
   const HgHit *d_hits;   // device arrays, valid until the next scan on this scanner
   const HgHitAux *d_aux;
   float ms_stream;       // hg_stream_kernel alone (HIP events on the launch stream)
@@ -140,8 +140,14 @@ struct HgScanOutput {
 
 // The start-of-match pass (hg_som.hip): from[i] for the n final hits, on `stream`.  max_nw: the most state words of any SOM
 // expression (its multi-word walks keep their state in LDS).
+// min_lengths: HgDb::min_lengths on the device or nullptr (expressions sharing a SOM id count only where their own report survives).
 hipError_t hg_som_launch(const uint8_t *text, const HgHit *hits, const HgHitAux *aux, uint64_t n, const HgPattern *patterns, const uint32_t *pool, uint32_t max_nw,
-                         uint32_t *from, hipStream_t stream);
+                         const uint32_t *min_lengths, uint32_t *from, hipStream_t stream);
+// The match-length pass (hg_som.hip, hs_expr_ext_t min_length): of the n raw reports of a pass, those whose expression has no
+// filtering min_length or a match of at least that length ending at `to` are appended to out_* (room for n), *count (zero
+// before the launch) receives their number.  max_nw: the most state words of any filtering expression.
+hipError_t hg_minlen_launch(const uint8_t *text, const HgHit *hits, const HgHitAux *aux, uint32_t n, const HgPattern *patterns, const uint32_t *pool, uint32_t max_nw,
+                            const uint32_t *min_lengths, HgHit *out_hits, HgHitAux *out_aux, uint32_t *count, hipStream_t stream);
 
 // The combination pass (hg_comb.hip) over the n final hits of a pass: count (emit == false: count[i] = records of hit i,
 // count[n] = 0), or write the records of hit i to out_*[pos[i] ..] (emit == true), on `stream`.
@@ -230,6 +236,7 @@ class HgScanner {
   int regrow(const PassPlan &p, uint64_t n_raw);
   int finalize_compact(const HgHit *hits, const HgHitAux *aux, uint32_t n, uint32_t id_bits, uint32_t to_bits, uint64_t line_bound, hipStream_t stream);
   int comb_pass(HgScanOutput *out, uint64_t bs1, uint64_t line_bound, hipStream_t stream);
+  int minlen_pass(const uint8_t *text, uint32_t *n, hipStream_t stream);
   int huge_lds_error() { return error(HG_ERR_HIP, "the huge-automaton kernel cannot have its LDS"); }
   bool fail(hipError_t e, const char *what);
   int error(int rc, const std::string &what) { err_ = what; return rc; }
@@ -292,6 +299,13 @@ class HgScanner {
   uint32_t *d_from_ = nullptr;  // starts of the last scan's hits (SOM databases only, allocated by the first scan that needs them)
   uint64_t from_cap_ = 0;
   uint32_t som_max_nw_ = 0;
+  // match-length pass (databases with a filtering min_length only): the per-expression lengths, and the second raw array the
+  // survivors of a pass's raw reports go to (allocated by the first pass that needs it)
+  uint32_t *d_min_lengths_ = nullptr;
+  HgHit *d_minlen_hits_ = nullptr;
+  HgHitAux *d_minlen_aux_ = nullptr;
+  uint64_t minlen_cap_ = 0;
+  uint32_t minlen_max_nw_ = 0;
   // combination pass (databases with combinations or QUIET expressions only): the tables, the per-hit counts / positions and
   // the union of delivered and combination records it hands to the finalize
   HgComb *d_combs_ = nullptr;

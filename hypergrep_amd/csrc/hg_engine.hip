@@ -189,8 +189,12 @@ int HgScanner::init() {
   view_.groups = static_cast<const HgSlowGroup *>(d_groups_);
   if (!db.bounds.empty()) HG_TRY(upload(&d_bounds_, db.bounds, "d_bounds_"), "upload offset bounds");
   view_.bounds = static_cast<const uint32_t *>(d_bounds_);  // (nullptr: the database has no offset bounds)
-  for (const HgPattern &p : db.patterns)
+  if (!db.min_lengths.empty()) HG_TRY(upload(reinterpret_cast<void **>(&d_min_lengths_), db.min_lengths, "d_min_lengths_"), "upload min_length");
+  for (uint32_t i = 0; i < db.patterns.size(); i++) {
+    const HgPattern &p = db.patterns[i];
     if (p.flags & HG_FLAG_SOM_LEFTMOST) som_max_nw_ = std::max(som_max_nw_, p.nw);
+    if (!db.min_lengths.empty() && db.min_lengths[i]) minlen_max_nw_ = std::max(minlen_max_nw_, p.nw);
+  }
   if (db.comb_pass()) {
     HG_TRY(upload(reinterpret_cast<void **>(&d_combs_), db.combs, "d_combs_"), "upload combinations");
     HG_TRY(upload(reinterpret_cast<void **>(&d_comb_words_), db.comb_words, "d_comb_words_"), "upload combinations");
@@ -223,7 +227,8 @@ HgScanner::~HgScanner() {
   void *ptrs[] = {d_patterns_, d_pool_, d_factors_, d_windows_, d_bucket_, d_filter_, d_ext_, d_slow_, d_sums_, d_bases_, d_block_base_,
                   d_agg_, d_cands_, d_hits_raw_, d_hits_out_, d_aux_raw_, d_aux_out_,
                   d_key_a_, d_key_b_, d_perm_a_, d_perm_b_, d_keep_, d_counters_, d_temp_, d_seg_count_, d_pflags_, d_deferred_, d_defer_count_, d_seg_count2_, d_cands2_, d_disc_, d_bucket2_, d_windows2_, d_groups_, d_acc_hits_, d_acc_aux_, d_huge_claim_, d_wtab_, d_from_, d_fin_fill_, d_fin_kept_, d_fin_big_,
-                  d_combs_, d_comb_words_, d_comb_feed_, d_comb_count_, d_comb_pos_, d_comb_hits_, d_comb_aux_, d_comb_temp_, d_bounds_};
+                  d_combs_, d_comb_words_, d_comb_feed_, d_comb_count_, d_comb_pos_, d_comb_hits_, d_comb_aux_, d_comb_temp_, d_bounds_,
+                  d_min_lengths_, d_minlen_hits_, d_minlen_aux_};
   for (void *p : ptrs) hgmem::dev_free(p, "scanner");
   hgmem::host_free(h_counters_, "h_counters_");
   for (auto &ev : ev_)
@@ -365,7 +370,8 @@ HgScanner::PassPlan HgScanner::plan_pass(const uint8_t *text, uint64_t nbytes, u
   // 24 bits of the line number, so line numbers must stay below 2^40)
   p.bucketed = ntiles && p.fin_cap && p.fin_shift <= 64 - HG_HIT_REL_SHIFT && p.fin_shift + p.id_bits + p.to_bits + 1 <= 64 &&
                bits_for(line_base + nbytes + 1) <= HG_HIT_REL_SHIFT && !fin_fallback_ && !knobs_.no_bucket_finalize &&
-               !view_.bounds;  // (offset bounds: the compact finalize, whose report rule reads the SINGLEMATCH flag itself)
+               !view_.bounds &&     // (offset bounds: the compact finalize, whose report rule reads the SINGLEMATCH flag itself)
+               !d_min_lengths_;     // (min_length: the same, and the match-length pass runs over the compact raw array)
 
   // Chunked pipeline (line mode, large buffers): the text is cut into tile-aligned chunks; the stream pass of chunk c+1
   // runs on the caller's stream while tile scan + verify + confirm of chunk c run on a side stream.  The stream pass
@@ -837,6 +843,26 @@ int HgScanner::comb_pass(HgScanOutput *out, uint64_t bs1, uint64_t line_bound, h
   return HG_OK;
 }
 
+// The match-length pass (hs_expr_ext_t min_length, hg_som.hip) over the *n raw reports of a pass in the compact array: the
+// survivors go to a second raw array (allocated by the first pass that needs it) and *n becomes their number.  The count
+// word was zeroed by the pass's reset launch.
+int HgScanner::minlen_pass(const uint8_t *text, uint32_t *n, hipStream_t stream) {
+  if (*n > minlen_cap_) {
+    minlen_cap_ = 0;
+    const uint64_t cap = std::max<uint64_t>(static_cast<uint64_t>(*n) + *n / 4, 4096);
+    HG_TRY(realloc_dev(d_minlen_hits_, cap, "d_minlen_hits_"), "alloc (match-length pass)");
+    HG_TRY(realloc_dev(d_minlen_aux_, cap, "d_minlen_aux_"), "alloc (match-length pass)");
+    minlen_cap_ = cap;
+  }
+  HG_TRY(hg_minlen_launch(text, d_hits_raw_, d_aux_raw_, *n, static_cast<const HgPattern *>(d_patterns_), static_cast<const uint32_t *>(d_pool_), minlen_max_nw_,
+                          d_min_lengths_, d_minlen_hits_, d_minlen_aux_, d_counters_ + HG_ST_MINLEN_KEPT, stream),
+         "match-length launch");
+  HG_TRY(hipMemcpyAsync(h_counters_ + HG_ST_MINLEN_KEPT, d_counters_ + HG_ST_MINLEN_KEPT, 4, hipMemcpyDeviceToHost, stream), "copy count");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (match-length pass)");
+  *n = h_counters_[HG_ST_MINLEN_KEPT];
+  return HG_OK;
+}
+
 int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const PassRange &range, bool block_mode, hipStream_t stream,
                         HgScanOutput *out) {
   // (the first pass that streams asks how many stream workgroups a CU holds)
@@ -901,9 +927,16 @@ int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint
   fin_expect_hits_ = n_raw;
   // (a pass that stops short of the text's end leaves no piece count: scan_segments takes it from its last pass)
   const uint64_t n_pieces = block_mode ? 1 : !range.last ? 0 : h_final_->L - line_base + (nbytes > h_final_->cs ? hg_pieces(nbytes - h_final_->cs, bs1) : 0);
-  const uint32_t n = static_cast<uint32_t>(n_raw);
+  uint32_t n = static_cast<uint32_t>(n_raw);
+  const HgHit *fin_hits = d_hits_raw_;
+  const HgHitAux *fin_aux = d_aux_raw_;
+  if (n && d_min_lengths_) {  // min_length applies before the report rules: the finalize sees the surviving raw reports only
+    if (int rc = minlen_pass(text, &n, p.stream)) return rc;
+    fin_hits = d_minlen_hits_;
+    fin_aux = d_minlen_aux_;
+  }
   if (n && !p.bucketed)
-    if (int rc = finalize_compact(d_hits_raw_, d_aux_raw_, n, p.id_bits, p.to_bits, line_base + (range.last ? n_pieces : nbytes) + 1, p.stream)) return rc;
+    if (int rc = finalize_compact(fin_hits, fin_aux, n, p.id_bits, p.to_bits, line_base + (range.last ? n_pieces : nbytes) + 1, p.stream)) return rc;
   if (!p.bucketed) {
     HG_TRY(hipEventRecord(ev_[3], stream), "event");
     HG_TRY(hipStreamSynchronize(stream), "stream sync (finalize)");
@@ -983,7 +1016,7 @@ int HgScanner::scan_impl(const void *d_text, uint64_t nbytes, int buffer_size, u
       from_cap_ = cap;
     }
     HG_TRY(hg_som_launch(text, out->d_hits, out->d_aux, out->n_hits, static_cast<const HgPattern *>(d_patterns_), static_cast<const uint32_t *>(d_pool_), som_max_nw_,
-                         d_from_, stream),
+                         d_min_lengths_, d_from_, stream),
            "start-of-match launch");
     HG_TRY(hipStreamSynchronize(stream), "stream sync (start of match)");
     out->d_from = d_from_;

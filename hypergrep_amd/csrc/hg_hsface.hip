@@ -177,10 +177,11 @@ int launch_until_fits(hs_scratch_t *sc, Grow &&grow, Launch &&launch, uint32_t *
 
 // The one-launch block path (HgScanner::launch_block_small, hg_block_batch_kernel) takes this database.  Databases with
 // HS_FLAG_SOM_LEFTMOST expressions take the general path: its start-of-match pass fills `from`; so do databases with
-// combinations or QUIET expressions (its combination pass applies them) and with offset bounds.
+// combinations or QUIET expressions (its combination pass applies them), with offset bounds and with a min_length that can
+// remove reports (its match-length pass applies it).
 bool block_small_db(const HgDb &d) {
   static const bool enabled = !std::getenv("HG_NO_BLOCK_SMALL");
-  return enabled && !d.nsom && !d.comb_pass() && d.bounds.empty();
+  return enabled && !d.nsom && !d.comb_pass() && d.bounds.empty() && d.min_lengths.empty();
 }
 
 // The general path of a block scan (hs_scan's tail; hg_scan_blocks for what its kernel does not take): the block copied to
@@ -227,6 +228,12 @@ int block_general_deliver(hs_scratch_t *scratch, const char *data, unsigned int 
 // cannot carry one of its expressions.
 std::shared_ptr<HgFlowDb> flow_db(const HgDb &db, unsigned int horizon, int *bad, std::string *msg) {
   const uint32_t np = static_cast<uint32_t>(db.patterns.size());
+  for (uint32_t i = 0; i < db.min_lengths.size(); i++) {  // (a flow carries no starts for expressions without HS_FLAG_SOM_LEFTMOST)
+    if (!db.min_lengths[i]) continue;
+    *bad = static_cast<int>(i);
+    *msg = "expression " + std::to_string(i) + ": min_length that can remove reports is not supported in stream mode";
+    return nullptr;
+  }
   for (uint32_t i = 0; i < np; i++) {
     const HgPattern &p = db.patterns[i];
     const bool wide = p.nw > HG_MAX_W, som_wide = (p.flags & HG_FLAG_SOM_LEFTMOST) && p.nnodes > HG_FLOW_SOM_NODES;

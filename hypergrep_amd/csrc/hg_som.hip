@@ -5,6 +5,7 @@
 // flight (walk_back4, hg_confirm_dev.h); the walk of an expression is bounded by its longest match (max_len) when it has
 // one, and literal-only expressions alone on their id need no walk at all.  Hits of expressions without the flag get 0.
 // The engine launches this kernel only for databases with SOM expressions (HgDb::nsom), so every other scan is unchanged.
+// The match-length pass (hg_minlen_kernel, below) is the same walk with an early exit, over a pass's raw reports.
 #include <hip/hip_runtime.h>
 
 #include "hg_confirm_dev.h"
@@ -34,8 +35,11 @@ struct LdsState {
 
 // hg_nfa_som on the device.  The byte before a position decides that position's entry condition, so the walk keeps ONE
 // position pending: visiting byte j finalises position j + 1 (entry condition, start test) and steps the state onto j.
-template <typename St>
-__device__ __forceinline__ uint32_t som_walk(const uint8_t *text, uint64_t a, uint32_t len, uint32_t to, const HgPattern &p, const uint32_t *pool, St &st) {
+// EARLY (the match-length pass, hg_nfa_minlen): the walk ends at the first start at or below `limit` and returns it;
+// starts above `limit` do not count, HG_NONE32 when there is none at or below it.
+template <bool EARLY, typename St>
+__device__ __forceinline__ uint32_t som_walk(const uint8_t *text, uint64_t a, uint32_t len, uint32_t to, const HgPattern &p, const uint32_t *pool, St &st,
+                                             uint32_t limit = 0) {
   const uint32_t nw = st.nw();
   const uint32_t *reach = pool + p.reach_off, *rfollow = pool + p.som_follow_off, *init = pool + p.init_off;
   const uint32_t *amask = pool + p.amask_off, *acc = pool + p.acc_off;
@@ -56,7 +60,14 @@ __device__ __forceinline__ uint32_t som_walk(const uint8_t *text, uint64_t a, ui
       any |= x;
       start |= x & init[w];
     }
-    if (start) best = q;
+    if (EARLY) {
+      if (start && q <= limit) {
+        best = q;
+        return false;
+      }
+    } else if (start) {
+      best = q;
+    }
     return any != 0 && q != lo;
   };
   // The text backwards in aligned 16-byte chunks, the (up to) four chunks of a 64-byte line in flight at once, as walk_back4
@@ -129,7 +140,7 @@ __device__ __forceinline__ uint32_t som_walk(const uint8_t *text, uint64_t a, ui
 }  // namespace
 
 __global__ __launch_bounds__(kSomThreads) void hg_som_kernel(const uint8_t *text, const HgHit *hits, const HgHitAux *aux, uint64_t n,
-                                                           const HgPattern *patterns, const uint32_t *pool, uint32_t *from) {
+                                                           const HgPattern *patterns, const uint32_t *pool, const uint32_t *min_lengths, uint32_t *from) {
   extern __shared__ uint32_t som_lds[];
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kSomThreads + threadIdx.x;
   if (i >= n) return;
@@ -150,25 +161,80 @@ __global__ __launch_bounds__(kSomThreads) void hg_som_kernel(const uint8_t *text
     uint32_t s;
     if (p.nw == 1) {
       RegState<1> st;
-      s = som_walk(text, x.start, x.len, to, p, pool, st);
+      s = som_walk<false>(text, x.start, x.len, to, p, pool, st);
     } else if (p.nw == 2) {
       RegState<2> st;
-      s = som_walk(text, x.start, x.len, to, p, pool, st);
+      s = som_walk<false>(text, x.start, x.len, to, p, pool, st);
     } else {
       LdsState st{som_lds + threadIdx.x, p.nw};
-      s = som_walk(text, x.start, x.len, to, p, pool, st);
+      s = som_walk<false>(text, x.start, x.len, to, p, pool, st);
     }
-    best = s < best ? s : best;
+    // (an expression of a shared id counts only if its own report at `to` survives its min_length: hg_hit_som)
+    if (s != HG_NONE32 && to - s >= (min_lengths ? min_lengths[j] : 0u)) best = s < best ? s : best;
     j = p.som_next;
   } while (j != x.pattern);
   from[i] = best;
 }
 
+// The match-length pass (hs_expr_ext_t min_length): one launch over the RAW compact reports of a pass, before the finalize
+// (the filter applies before the report rules).  Lane i takes raw record i.  Records of expressions without a filtering
+// min_length are kept without touching the text; the others are kept iff hg_nfa_minlen holds: the walk above with its
+// early exit.  The kept records are compacted into out_*: a wave ballot, ONE global atomic per wave (= workgroup) and the
+// lane's rank among the kept lanes below it.  Their order does not matter: the finalize sorts.
+__global__ __launch_bounds__(kSomThreads) void hg_minlen_kernel(const uint8_t *text, const HgHit *hits, const HgHitAux *aux, uint32_t n, const HgPattern *patterns,
+                                                              const uint32_t *pool, const uint32_t *min_lengths, HgHit *out_hits, HgHitAux *out_aux,
+                                                              uint32_t *count) {
+  extern __shared__ uint32_t som_lds[];
+  const uint32_t i = blockIdx.x * kSomThreads + threadIdx.x;
+  bool keep = false;
+  if (i < n) {
+    const HgHitAux x = aux[i];
+    const uint32_t to = hits[i].to, need = min_lengths[x.pattern];
+    if (!need) {
+      keep = true;
+    } else if (to >= need && to <= x.len) {
+      const HgPattern &p = patterns[x.pattern];
+      const uint32_t limit = to - need;
+      uint32_t s;
+      if (p.nw == 1) {
+        RegState<1> st;
+        s = som_walk<true>(text, x.start, x.len, to, p, pool, st, limit);
+      } else if (p.nw == 2) {
+        RegState<2> st;
+        s = som_walk<true>(text, x.start, x.len, to, p, pool, st, limit);
+      } else {
+        LdsState st{som_lds + threadIdx.x, p.nw};
+        s = som_walk<true>(text, x.start, x.len, to, p, pool, st, limit);
+      }
+      keep = s != HG_NONE32;
+    }
+  }
+  const uint64_t km = __builtin_amdgcn_ballot_w64(keep);
+  if (!km) return;
+  uint32_t base = 0;
+  if (threadIdx.x == 0) base = atomicAdd(count, static_cast<uint32_t>(__popcll(km)));
+  base = __builtin_amdgcn_readfirstlane(base);
+  if (keep) {
+    const uint32_t at = base + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(km >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(km), 0u));
+    out_hits[at] = hits[i];  // (read again: a record held across the walk went through scratch)
+    out_aux[at] = aux[i];
+  }
+}
+
 hipError_t hg_som_launch(const uint8_t *text, const HgHit *hits, const HgHitAux *aux, uint64_t n, const HgPattern *patterns, const uint32_t *pool, uint32_t max_nw,
-                         uint32_t *from, hipStream_t stream) {
+                         const uint32_t *min_lengths, uint32_t *from, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   const uint64_t blocks = (n + kSomThreads - 1) / kSomThreads;
   const size_t lds = max_nw > 2 ? 2u * max_nw * kSomThreads * sizeof(uint32_t) : 0u;  // (single- and two-word walks keep their state in registers)
-  hipLaunchKernelGGL(hg_som_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(kSomThreads), lds, stream, text, hits, aux, n, patterns, pool, from);
+  hipLaunchKernelGGL(hg_som_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(kSomThreads), lds, stream, text, hits, aux, n, patterns, pool, min_lengths, from);
+  return hipGetLastError();
+}
+
+hipError_t hg_minlen_launch(const uint8_t *text, const HgHit *hits, const HgHitAux *aux, uint32_t n, const HgPattern *patterns, const uint32_t *pool, uint32_t max_nw,
+                            const uint32_t *min_lengths, HgHit *out_hits, HgHitAux *out_aux, uint32_t *count, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const uint32_t blocks = (n + kSomThreads - 1) / kSomThreads;
+  const size_t lds = max_nw > 2 ? 2u * max_nw * kSomThreads * sizeof(uint32_t) : 0u;  // (as hg_som_launch)
+  hipLaunchKernelGGL(hg_minlen_kernel, dim3(blocks), dim3(kSomThreads), lds, stream, text, hits, aux, n, patterns, pool, min_lengths, out_hits, out_aux, count);
   return hipGetLastError();
 }

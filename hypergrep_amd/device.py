@@ -100,7 +100,7 @@ class Database:
     """Compiled pattern set (host side)."""
 
     def __init__(self, patterns, flags=None, ids=None, ext=None):
-        """ext: one utils.ExprExt (extended parameters: approximate matching) or None per pattern."""
+        """ext: one utils.ExprExt (extended parameters: approximate matching, offset bounds, min_length) or None per pattern."""
         pa, fa, ia = utils.prepare_patterns(list(patterns), flags=list(flags or ()), ids=list(ids or ()))
         self._h = ctypes.c_void_p()
         err = ctypes.create_string_buffer(512)

@@ -45,7 +45,8 @@ class Result(ctypes.Structure):
 
 class ExprExt(ctypes.Structure):
     """Extended parameters of one expression: Hyperscan's hs_expr_ext_t (include/hypergrep_amd.h has the contract).  Set the
-    fields you use and their HS_EXT_FLAG_* bits in `flags`, e.g. ExprExt(flags=HS_EXT_FLAG_EDIT_DISTANCE, edit_distance=1)."""
+    fields you use and their HS_EXT_FLAG_* bits in `flags`, e.g. ExprExt(flags=HS_EXT_FLAG_EDIT_DISTANCE, edit_distance=1) or
+    ExprExt(flags=HS_EXT_FLAG_MIN_LENGTH, min_length=12): only reports of matches of at least 12 bytes."""
 
     _fields_ = [("flags", ctypes.c_ulonglong), ("min_offset", ctypes.c_ulonglong), ("max_offset", ctypes.c_ulonglong),
                 ("min_length", ctypes.c_ulonglong), ("edit_distance", ctypes.c_uint), ("hamming_distance", ctypes.c_uint)]
@@ -169,7 +170,7 @@ def scan(  # pylint: disable=too-many-arguments
     ext=None,
 ) -> int:
     """Scan a plain / gzip / zstd text file; `callback(matches, count)` receives the hits in batches of `buffer_count`.
-    `ext`: one ExprExt (extended parameters: approximate matching) or None per pattern.
+    `ext`: one ExprExt (extended parameters: approximate matching, offset bounds, min_length) or None per pattern.
 
     The native call runs on a daemon thread so that Ctrl-C reaches Python (return code 130); otherwise the shim's
     return code (0 = fine, 1-7 as in hyperscanner.c:25-33) comes back.

@@ -138,8 +138,21 @@ typedef int (*match_event_handler)(unsigned int id, unsigned long long from, uns
  *    HS_FLAG_SOM_LEFTMOST `from` is the smallest such s (automata of at most 1024 nodes after the expansion).
  *  - min_offset / max_offset: a report (id, to) exists only if min_offset <= to <= max_offset.  The bounds apply before
  *    the report rules: under HS_FLAG_SINGLEMATCH the delivered report is the smallest `to` in bounds.
- *  - min_length: accepted where it can never remove a report: at most the expression's minimum match width (minus k with an
- *    edit distance).  Filtering by start of match is not implemented: larger values are rejected.
+ *  - min_length = L: a report (id, to) of the expression exists iff it has a match spanning [s, to) of the scanned bytes
+ *    with to - s >= L; equivalently, the leftmost start at `to` (what HS_FLAG_SOM_LEFTMOST reports) is at most to - L.
+ *    The scanned bytes are the piece after the leading-NUL skip, or the block for hs_scan (the origin of `to`);
+ *    assertions are evaluated in the real context, as for start of match.  The filter applies before the report rules,
+ *    as the offset bounds do: under HS_FLAG_SINGLEMATCH the delivered report is the smallest `to` that passes all of the
+ *    expression's parameters; an identical (id, to) of several expressions sharing an id is delivered once if at least
+ *    one of them produces it and passes its own min_length; combination operands see only surviving reports; a line
+ *    whose reports are all removed is not a matching line (Face B rows, max_match_count).  HS_FLAG_SOM_LEFTMOST is not
+ *    required.  With the flag `from` is unchanged, except for several SOM expressions sharing an id: there it is the
+ *    smallest start over those expressions whose own report at `to` survives.  A value that can remove nothing (at most
+ *    the shortest match length: the minimum match width, minus k with an edit distance) is accepted in every mode and
+ *    dropped: the database is the one compiled without it.  A value that can remove a report is rejected with
+ *    edit_distance or hamming_distance; when it is above the expression's longest match, or at least 2^31 on an unbounded
+ *    expression (no report could survive); on automata of more than 1024 positions (they have no reverse tables: the rule
+ *    of HS_FLAG_SOM_LEFTMOST); and in stream mode ("min_length that can remove reports is not supported in stream mode").
  * Rejected (HS_COMPILER_ERROR / HG_ERR_COMPILE, with the expression's index and the rule in the message): unknown
  * HS_EXT_FLAG bits; edit and Hamming distance together; min_offset > max_offset; min_length > max_offset; any parameter on
  * an HS_FLAG_COMBINATION expression; a distance above 16; a distance k >= the expression's minimum match width (the
@@ -287,7 +300,8 @@ int hg_scan_stream_batch(hs_stream_t *const *streams, const char *const *data, c
  *     hs_scan does).  An error met later in the call (HS_NOMEM, or HS_INVALID for a failed GPU operation) ends the call
  *     there: the items before the failing launch have been delivered, the others are not.
  *  6. Speed.  One kernel takes what hs_scan's one-launch path takes: databases without HS_FLAG_SOM_LEFTMOST expressions,
- *     without combinations or QUIET expressions, without offset bounds, without automata over 1024 positions, of at most
+ *     without combinations or QUIET expressions, without offset bounds or a min_length that can remove reports, without
+ *     automata over 1024 positions, of at most
  *     2048 expressions in groups of 32 (or 16384 in groups of 256), and items of at most 8192 bytes.  Everything else (a whole
  *     batch on another database, single longer items, a launch with more than 2^24 reports) is scanned item by item as
  *     hs_scan's general path scans it, inside the same call: correct by rule 1, with no speed-up. */

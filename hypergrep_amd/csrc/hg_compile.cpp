@@ -662,6 +662,24 @@ uint32_t nullable_tt(const Node &n) {
   return 0;
 }
 
+// Whether the expression can match the empty string when every assertion is taken to hold: the rule the ALLOWEMPTY rejection
+// goes by (the oracle's, orx.c nullable()).  `\b\B|a` and `(a|\b)\B` are empty-matchable by it although no context satisfies
+// their assertions; nullable_tt above is the exact answer, and only the automaton is built from it.
+bool nullable_syntactic(const Node &n) {
+  switch (n.kind) {
+    case Node::Empty: case Node::Assert: return true;
+    case Node::Class: return false;
+    case Node::Cat:
+      for (auto &k : n.kids) if (!nullable_syntactic(*k)) return false;
+      return true;
+    case Node::Alt:
+      for (auto &k : n.kids) if (nullable_syntactic(*k)) return true;
+      return false;
+    case Node::Rep: return n.min == 0 || n.kids.empty() || nullable_syntactic(*n.kids[0]);
+  }
+  return true;
+}
+
 // Size of the expression as a Thompson program (one instruction per class / assertion, two per alternation branch point,
 // a split per optional copy, split + jump per loop): the measure Hyperscan's graph limits and the oracle (orx.c gen())
 // bound an expression by.  Saturates.
@@ -1638,8 +1656,10 @@ Automaton build_automaton(const std::string &text, uint32_t flags) {
   check_embedded_anchors(*a.root, false, false);
   if (program_size(*a.root) > HG_HUGE_MAX_PROGRAM) throw CompileError("pattern too large");
   Frag top = a.g.build(*a.root);
-  if (top.nullable) throw CompileError("expression can match the empty string (HS_FLAG_ALLOWEMPTY is not supported)");
-  if (a.g.pos_class.empty()) throw CompileError("expression matches nothing");
+  // an expression of assertions alone that no context satisfies (\b\B) is named for what it is; every other expression that is
+  // empty-matchable by syntax is refused, satisfiable or not (top.nullable != 0 implies nullable_syntactic)
+  if (a.g.pos_class.empty() && !top.nullable) throw CompileError("expression matches nothing");
+  if (nullable_syntactic(*a.root)) throw CompileError("expression can match the empty string (HS_FLAG_ALLOWEMPTY is not supported)");
   index_nodes(a, std::move(top.first), top.last);
   return a;
 }

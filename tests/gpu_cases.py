@@ -99,6 +99,9 @@ def run_many_sets() -> dict:
         for i in range(nsets):
             pairs = [regex_gen.anchored_pattern(rng) for _ in range(rng.randint(1, 6))]
             pats = [p for p, _ in pairs] + [regex_gen.random_pattern(rng) for _ in range(rng.randint(0, 2))]
+            for p in pats:  # the product's decision on each expression is the oracle's, before any is dropped
+                if (hypergrep_amd.check_compatibility([p]) == 0) != (oracle_py.check_patterns([p]) == 0):
+                    return {"ok": False, "set": i, "accept/reject differs from the oracle": p}
             pats = [p for p in pats if oracle_py.check_patterns([p]) == 0] or ["needle_in_haystack"]
             ids = list(range(len(pats)))
             data = regex_gen.anchored_text(rng, [s for _, s in pairs], rng.choice([200, 2000])) + regex_gen.random_text(rng, 200, maxlen=100)

@@ -69,6 +69,56 @@ def random_pattern(rng: random.Random) -> str:
     return p
 
 
+# ---- expressions dense in zero-width assertions, for the accept/reject differential (test_accept_parity.py).  The assertions
+# sit where they decide whether the expression can match the empty string: alone in an alternation branch, inside an optional
+# group, next to a contradicting one, between starred atoms.  A compiler that asks "is there a context in which this matches
+# the empty string" and one that asks "does it match the empty string if every assertion holds" part ways on these.
+_ASSERTIONS = ["\\b", "\\B", "\\b", "\\B", "\\b", "\\B", "^", "$"]
+
+
+def _short_literal(rng: random.Random) -> str:
+    return "".join(rng.choice("abcxyz019_ ") for _ in range(rng.randint(1, 3)))
+
+
+def _assertion_part(rng: random.Random) -> str:
+    a, b = rng.choice(_ASSERTIONS), rng.choice(_ASSERTIONS)
+    x, y = _short_literal(rng), _short_literal(rng)
+    r = rng.random()
+    if r < 0.14:
+        return "(" + x + "|" + a + ")"
+    if r < 0.26:
+        return "(?:" + a + "|" + x + ")"
+    if r < 0.34:
+        return "(" + a + ")?"
+    if r < 0.44:
+        return x[0] + "*" + a + b + y[0] + "*"
+    if r < 0.54:
+        return a + b
+    if r < 0.64:
+        return "(" + x + "|" + a + ")" + b
+    if r < 0.74:
+        return a + "(" + b + "|" + x + ")"
+    if r < 0.82:
+        return "(" + a + b + "|" + _atom(rng, 2) + ")"
+    if r < 0.90:
+        return "(?:" + x + "|" + y + "|" + a + ")" + rng.choice(["", "?", "+", "{1,2}"])
+    return a
+
+
+def assertion_heavy_pattern(rng: random.Random) -> str:
+    """Like random_pattern, with a far larger share of \\b \\B ^ $ placed in optional groups and alternation branches.  Most
+    expressions keep one part that must consume a byte, so that most stay legal; repeats stay small (no capacity limits)."""
+    parts = []
+    for _ in range(rng.randint(1, 4)):
+        if rng.random() < 0.5:
+            parts.append(_assertion_part(rng))
+        else:
+            parts.append(_atom(rng, 1) + rng.choice(["", "", "", "*", "+", "?", "{1,2}", "{0,2}"]))
+    if rng.random() < 0.78:
+        parts.insert(rng.randint(0, len(parts)), _short_literal(rng) if rng.random() < 0.6 else rng.choice(["[a-c]", "\\d", "\\w+", "[^a]", ".{1,2}"]))
+    return "".join(parts)
+
+
 def random_line(rng: random.Random, maxlen: int = 24) -> bytes:
     n = rng.randint(0, maxlen)
     return "".join(rng.choice(ALPHABET) for _ in range(n)).encode()

@@ -11,6 +11,7 @@ import re
 
 import pytest
 
+import accept_rules
 import batchsim_py
 import regex_gen
 from hypergrep_amd import device
@@ -128,7 +129,8 @@ def _compiled_random_set(rng, k):
     pats, flags = [], []
     while len(pats) < k:
         p, f = regex_gen.random_pattern(rng), rng.choice([0, 2, 4, 6, 1, 5]) | (8 if rng.random() < 0.3 else 0)
-        if batchsim_py.Db([p], [f]).h:
+        one = batchsim_py.Db([p], [f])
+        if accept_rules.Tally().decide([p], [f], bool(one.h), one.error, features=True):
             pats.append(p)
             flags.append(f)
     return pats, flags
@@ -182,6 +184,7 @@ def test_replay_groups_of_256_expressions():
 
 def test_replay_matches_python_re_on_assertion_free_expressions():
     rng = random.Random(77)
+    tally = accept_rules.Tally()
     cases, ran = 60, 0
     while ran < cases:
         pat = regex_gen.random_pattern(rng)
@@ -189,8 +192,8 @@ def test_replay_matches_python_re_on_assertion_free_expressions():
         if any(a in pat for a in ASSERTION_CHARS):
             continue  # (not a case: the subset is the assertion-free expressions; replaced by the next one)
         db = batchsim_py.Db([pat], [flags])
-        if not db.h:
-            continue  # (rejected by the compiler: replaced by the next generated expression)
+        if not tally.decide([pat], [flags], bool(db.h), db.error, features=True):
+            continue  # (rejected by both compilers, or by a documented limit: replaced by the next generated expression)
         items = [regex_gen.random_text(rng, rng.randint(1, 3), maxlen=8, final_newline=rng.random() < 0.5) for _ in range(rng.randint(1, 3))]
         items.insert(rng.randint(0, len(items)), b"")
         got = db.run(items, lanes=rng.choice([16, 64, 256]), ppw=32, nshards=rng.randint(1, 5))

@@ -8,6 +8,7 @@ import random
 
 import pytest
 
+import accept_rules
 import approx_ref
 import extsim_py
 import regex_gen
@@ -178,7 +179,11 @@ def _approx_case(rng):
     x = ext(edit=k) if edit else ext(hamming=k)
     db = extsim_py.Db([pat], [flags], exts=[x])
     if not db.h:
+        # refused by the oracle too (as an exact expression), or by a documented rule of approximate matching / a capacity limit
+        assert (not accept_rules.oracle_accepts([pat], [flags]) or "_distance " in db.error
+                or "approximate matching supports no assertion" in db.error or accept_rules.explained_rejection(db.error)), (pat, flags, k, db.error)
         return None
+    assert accept_rules.oracle_accepts([pat], [flags]), (pat, flags)
     try:
         ref = approx_ref.Approx(pat, flags, edit=k if edit else 0, hamming=0 if edit else k)
     except approx_ref.Unsupported:

@@ -13,6 +13,7 @@ import random
 
 import pytest
 
+import accept_rules
 import oracle_py
 import regex_gen
 
@@ -265,22 +266,32 @@ def test_not_singlematch_and_mixed_ids(torch_cuda):
 
 @pytest.mark.parametrize("seed", range(6))
 def test_random_patterns_match_oracle(torch_cuda, seed):
+    from hypergrep_amd import device
+
     rng = random.Random(9000 + seed)
+    tally = accept_rules.Tally()
     done = 0
     for _ in range(12):
         k = rng.randint(1, 4)
         pats = [regex_gen.random_pattern(rng) for _ in range(k)]
         flags = [rng.choice([14, 14, 15, 10, 6, 12]) for _ in range(k)]
         ids = [rng.randint(0, 2) for _ in range(k)]
-        if oracle_py.check_patterns(pats, flags=flags) != 0:
-            continue
+        try:
+            device.Database(pats, flags=flags, ids=ids)
+            error = None
+        except device.CompileError as e:
+            error = str(e)
+        if not tally.decide(pats, flags, error is None, error):
+            continue  # both compilers refuse the set (asserted)
         data = regex_gen.random_text(rng, 400, final_newline=rng.random() < 0.8)
         want, nlines = oracle_hits(data, pats, flags, ids)
         got, stats = gpu_scan_buffer(torch_cuda, data, pats, flags, ids)
         assert got == want, (pats, flags, ids)
         assert stats.n_lines == nlines
         done += 1
-    assert done >= 4
+    tally.done = done
+    assert tally.generated == 12 and tally.product_only_rejected == 0, tally.report()
+    assert done >= 4, tally.report()
 
 
 def test_many_literals_dense_hits_and_workspace_growth(torch_cuda):
@@ -358,6 +369,48 @@ def test_large_file_chunked_face_b(torch_cuda, tmp_path, monkeypatch):
     assert rc == 0
     orc, want, _ = oracle_py.scan_file(str(path), patterns, ids=ids, buffer_count=64)
     assert orc == 0 and rows == want and len(rows) > 500
+
+
+def test_compressed_files_chunked_face_b(torch_cuda, tmp_path, monkeypatch):
+    """hyperscan() on compressed input that spans several 1 MiB ingest chunks, against the oracle's zlib (gzgets) path: one
+    gzip member, three members cut inside lines that also cross an ingest chunk cut, trailing non-gzip bytes, streams
+    truncated inside the deflate data and inside the 8-byte trailer (expected: whatever the oracle's zlib delivers), an empty
+    member, a plain file that starts with the gzip magic, and many concatenated zstd frames.  (rc, rows, batches) must be
+    equal for scan buffers of 262140 and 1000 bytes and batches of 1, 16 and 64 rows.  No zstd compressor is available to
+    the tests, so there is no zstd case of several ingest chunks."""
+    import concurrent.futures
+    import multiprocessing
+
+    import gz_cases
+    import hypergrep_amd
+
+    text, patterns = gz_cases.large_text()
+    patterns = patterns + [gz_cases.EXTRA_PATTERN]
+    ids = list(range(len(patterns) - 1)) + [gz_cases.EXTRA_ID]
+    cases = gz_cases.build(tmp_path, text)
+    jobs = [(name, path, bs, count) for name, path, _, large in cases for bs, count in gz_cases.runs(large)]
+    # the oracle needs seconds per large file: its scans run in worker processes (started fresh: this one holds the GPU)
+    with concurrent.futures.ProcessPoolExecutor(max_workers=12, mp_context=multiprocessing.get_context("spawn")) as pool:
+        wants = list(pool.map(gz_cases.oracle_job, [(path, patterns, ids, bs, count) for _, path, bs, count in jobs]))
+    monkeypatch.setenv("HYPERGREP_CHUNK_MB", "1")
+    delivered = {}
+    for (name, path, bs, count), (want_rc, want_rows, want_batches) in zip(jobs, wants):
+        rows, batches = [], []
+
+        def cb(matches, n, rows=rows, batches=batches):
+            batches.append(n)
+            for i in range(n):
+                rows.append((matches[i].line_number, matches[i].id, matches[i].line))
+
+        rc = hypergrep_amd.scan(path, patterns, cb, ids=ids, buffer_size=bs, buffer_count=count)
+        first = next((i for i, (x, y) in enumerate(zip(rows, want_rows)) if x != y), min(len(rows), len(want_rows)))
+        print(f"{name} bs={bs} count={count}: rc {rc}/{want_rc} rows {len(rows)}/{len(want_rows)} batches {len(batches)}/{len(want_batches)}")
+        assert rc == want_rc, (name, bs, count, rc, want_rc)
+        assert rows == want_rows, (name, bs, count, len(rows), len(want_rows), first, rows[first:first + 2], want_rows[first:first + 2])
+        assert batches == want_batches, (name, bs, count)
+        delivered[name] = max(delivered.get(name, 0), len(rows))
+    assert delivered["one_member"] > 500 and delivered["three_members_cut_mid_line"] == delivered["one_member"] == delivered["trailing_garbage"]
+    assert 0 < delivered["truncated_in_deflate"] < delivered["one_member"] and delivered["zstd_frames"] > 1000
 
 
 # ------------------------------------------------------------------ Face A: the six libhs symbols, block mode

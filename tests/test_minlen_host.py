@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import pytest
 
+import accept_rules
 import extsim_py
 import minlensim_py
 import regex_gen
@@ -208,7 +209,11 @@ def test_the_scalar_routine_early_exits():
 # ---- random expressions against Python `re`
 
 def _cases():
-    accepts = lambda p, f: somsim_py.Db([p], [f | SOM]).ok()  # noqa: E731  (the cases of the start-of-match tests)
+    def compile_one(p, f):
+        db = somsim_py.Db([p], [f | SOM])
+        return db.ok(), db.error
+
+    accepts = accept_rules.Tally().accepts(compile_one, features=True)  # (the cases of the start-of-match tests)
     for seed in range(12):
         for pat, flags, data, _ in regex_gen.end_offset_cases(seed, accepts=accepts):
             yield seed, pat, flags, data

@@ -49,6 +49,33 @@ def test_plumbing_vectors_file_and_buffer(v, tmp_path):
     assert [(h[0], h[1], data[h[3]:h[3] + h[4]]) for h in hits] == want
 
 
+def test_compressed_files_file_path_and_buffer_splitter_agree(tmp_path):
+    """The files of the GPU test of compressed input (gz_cases.py): wherever the format alone defines the decoded bytes, the
+    oracle's file path (zlib's gzgets; libzstd) and its restated memory splitter over those bytes deliver the same rows, so
+    the expectation the product is held to is itself checked.  Damaged streams have no decoded text of their own: there the
+    file path must deliver a prefix of the undamaged file's rows.  (A subset of the expressions: the splitter is the subject,
+    and the oracle needs seconds per file with all 256.)"""
+    import gz_cases
+    from hypergrep_amd import benchspec
+
+    text, _ = gz_cases.large_text()
+    patterns = benchspec.c3_spec(n_literals=12, n_classes=8, n_anchored=8)[0] + [gz_cases.EXTRA_PATTERN]
+    ids = list(range(len(patterns) - 1)) + [gz_cases.EXTRA_ID]
+    whole = {}
+    for name, path, decoded, large in gz_cases.build(tmp_path, text):
+        for bs in (262140, 1000):
+            rc, rows, _ = oracle_py.scan_file(path, patterns, ids=ids, buffer_size=bs, buffer_count=16)
+            if name == "one_member":
+                whole[bs] = rows
+            if decoded is not None:
+                rc2, hits, _ = oracle_py.scan_buffer(decoded, patterns, ids=ids, buffer_size=bs)
+                assert (rc, rows) == (rc2, [(h[0], h[1], decoded[h[3]:h[3] + h[4]]) for h in hits]), (name, bs)
+            elif large:
+                assert rc == 0 and rows == whole[bs][:len(rows)], (name, bs)
+            if name in ("one_member", "zstd_frames"):
+                assert len(rows) > 50, (name, bs, len(rows))
+
+
 def test_missing_file_rc6():
     v = next(v for v in VECTORS if v["name"] == "K_missing_file")
     rc, rows, batches = oracle_py.scan_file("/nonexistent/definitely/missing", ["x"])

@@ -6,6 +6,7 @@ import random
 
 import pytest
 
+import accept_rules
 import regex_gen
 import somsim_py
 from somsim_py import SOM, start_by_brute_force
@@ -78,10 +79,15 @@ def test_databases_without_som_are_unchanged():
 
 # ---- random expressions against Python `re`
 
+def _compile_one_som(pat, flags):
+    db = somsim_py.Db([pat], [flags | SOM])
+    return db.ok(), db.error
+
+
 @pytest.mark.parametrize("seed", range(20))
 def test_starts_against_python_re(seed):
     total = 0
-    for pat, flags, data, _ in regex_gen.end_offset_cases(seed, accepts=lambda p, f: somsim_py.Db([p], [f | SOM]).ok()):
+    for pat, flags, data, _ in regex_gen.end_offset_cases(seed, accepts=accept_rules.Tally().accepts(_compile_one_som, features=True)):
         total += check_text([pat], [flags | SOM], data, want_reports=False)
     assert total > 0
 
@@ -141,12 +147,14 @@ def test_literal_only_needs_no_walk():
 
 def test_random_multi_expression_sets():
     rng = random.Random(11)
+    tally = accept_rules.Tally()
     for _ in range(30):
         pats, flags = [], []
         while len(pats) < 4:
             p = regex_gen.random_pattern(rng)
             f = rng.choice([6, 7, 2, 4]) | SOM
-            if somsim_py.Db([p], [f]).ok():
+            one = somsim_py.Db([p], [f])
+            if tally.decide([p], [f], one.ok(), one.error, features=True):
                 pats.append(p)
                 flags.append(f)
         ids = [rng.randrange(3) for _ in pats]

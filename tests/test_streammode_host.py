@@ -12,6 +12,7 @@ import random
 
 import pytest
 
+import accept_rules
 import extsim_py
 import flowsim_py
 import regex_gen
@@ -114,37 +115,39 @@ def _random_cuts(rng, n):
 
 def test_flow_replay_matches_block_scan_random():
     rng = random.Random(2024)
+    tally = accept_rules.Tally()
     done = 0
     for _ in range(600):
         pats = [regex_gen.random_pattern(rng) for _ in range(3)]
         flags = [rng.choice([0, 2, 4, 6, 1, 5]) for _ in pats]
         db = flowsim_py.Db(pats, flags)
-        if not db.h:
-            continue
+        if not tally.decide(pats, flags, bool(db.h), db.error, features=True):
+            continue  # both compilers refuse the set, or a documented limit / rule of the feature does (asserted)
         text = regex_gen.random_text(rng, rng.randint(1, 6), maxlen=12, final_newline=rng.random() < 0.5)
         for _ in range(4):
             _check(db, pats, text, _random_cuts(rng, len(text)), piece=rng.choice([1, 3, 7, 4096]), lanes=rng.choice([1, 2, 5, 32]))
         # every cut position once, 1-byte writes
         _check(db, pats, text, list(range(1, len(text))), piece=4096, lanes=4)
         done += 1
-    assert done >= 300
+    assert done >= 300, tally.report()
 
 
 def test_flow_replay_matches_python_re_small():
     rng = random.Random(99)
+    tally = accept_rules.Tally()
     done = 0
     for _ in range(300):
         pat = regex_gen.random_pattern(rng)
         flags = rng.choice([0, 2, 4, 6])
         db = flowsim_py.Db([pat], [flags])
-        if not db.h:
-            continue
+        if not tally.decide([pat], [flags], bool(db.h), db.error, features=True):
+            continue  # both compilers refuse the set, or a documented limit / rule of the feature does (asserted)
         text = regex_gen.random_text(rng, rng.randint(1, 3), maxlen=8, final_newline=rng.random() < 0.5)
         want = regex_gen.ends_by_brute_force(pat, flags, text)
         got = sorted(t for _, _, t in db.run(text, _random_cuts(rng, len(text)), lanes=3))
         assert got == want, (pat, flags, text, got, want)
         done += 1
-    assert done >= 100
+    assert done >= 100, tally.report()
 
 
 @pytest.mark.parametrize("pat, flags", [("foo$", 0), (r"foo\Z", 0), ("foo$", 4), ("^x$", 0), ("^x$", 4), (r"\bab\b", 0), (r"ab\B", 0),
@@ -212,6 +215,7 @@ def test_singlematch_and_offset_bounds_across_writes():
     """Face A's report rules (hg_flow_rules.h) over the replayed raw ends equal hs_scan's rules over the block scan:
     SINGLEMATCH once per stream, min_offset / max_offset on stream offsets, ids shared between expressions."""
     rng = random.Random(5)
+    tally = accept_rules.Tally()
     done = 0
     for _ in range(400):
         pats = [regex_gen.random_pattern(rng) for _ in range(3)]
@@ -226,15 +230,15 @@ def test_singlematch_and_offset_bounds_across_writes():
             exts.append(extsim_py.ext(min_offset=lo, max_offset=hi) if (lo is not None or hi is not None) else None)
             bounds.append((lo or 0, hi if hi is not None else 1 << 62))
         db = flowsim_py.Db(pats, flags, ids=ids, exts=exts)
-        if not db.h:
-            continue
+        if not tally.decide(pats, flags, bool(db.h), db.error, features=True):
+            continue  # both compilers refuse the set, or a documented limit / rule of the feature does (asserted)
         single = [bool(f & 8) for f in flags]
         text = regex_gen.random_text(rng, rng.randint(2, 6), maxlen=12, final_newline=rng.random() < 0.5)
         for _ in range(3):
             _check_delivered(db, text, _random_cuts(rng, len(text)), ids, single, bounds, lanes=rng.choice([1, 3]))
         _check_delivered(db, text, list(range(1, len(text))), ids, single, bounds)
         done += 1
-    assert done >= 150
+    assert done >= 150, tally.report()
 
 
 def test_shared_singlematch_id_holds_together():

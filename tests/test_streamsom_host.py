@@ -9,6 +9,7 @@ import random
 
 import pytest
 
+import accept_rules
 import extsim_py
 import flowsomsim_py
 import regex_gen
@@ -157,6 +158,7 @@ def _around_newlines(data):
 
 def test_replay_random_sets_against_block_and_re():
     rng = random.Random(7)
+    tally = accept_rules.Tally()
     done = reports = 0
     for _ in range(400):
         n = rng.randint(1, 3)
@@ -164,19 +166,20 @@ def test_replay_random_sets_against_block_and_re():
         flags = [rng.choice([0, 2, 4, 6, 1, 5]) | SOM for _ in pats]
         ids = list(range(n))
         db = flowsomsim_py.Db(pats, flags, ids)
-        if not db.h:
-            continue
+        if not tally.decide(pats, flags, bool(db.h), db.error, features=True):
+            continue  # both compilers refuse the set, or a documented limit / rule of the feature does (asserted)
         text = regex_gen.random_text(rng, rng.randint(1, 5), maxlen=12, final_newline=rng.random() < 0.5)
         for _ in range(3):
             reports += _check(db, pats, flags, ids, text, _random_cuts(rng, len(text)))
         reports += _check(db, pats, flags, ids, text, list(range(1, len(text))))  # 1-byte writes
         reports += _check(db, pats, flags, ids, text, _around_newlines(text))
         done += 1
-    assert done >= 200 and reports > 500
+    assert done >= 200 and reports > 500, tally.report()
 
 
 def test_replay_shared_ids_take_the_smallest_start():
     rng = random.Random(8)
+    tally = accept_rules.Tally()
     checked = 0
     for _ in range(250):
         n = rng.randint(2, 4)
@@ -184,15 +187,15 @@ def test_replay_shared_ids_take_the_smallest_start():
         flags = [rng.choice([0, 2, 4, 6]) | SOM for _ in pats]
         ids = [rng.choice([1, 2]) for _ in pats]
         db = flowsomsim_py.Db(pats, flags, ids)
-        if not db.h:
-            continue
+        if not tally.decide(pats, flags, bool(db.h), db.error, features=True):
+            continue  # both compilers refuse the set, or a documented limit / rule of the feature does (asserted)
         for k in range(n):
             shared = ids.count(ids[k]) > 1
             assert bool(db.header(k) & LATE) == shared
         text = regex_gen.random_text(rng, rng.randint(1, 5), maxlen=12, final_newline=rng.random() < 0.5)
         for cuts in (_random_cuts(rng, len(text)), list(range(1, len(text))), _around_newlines(text)):
             checked += _check(db, pats, flags, ids, text, cuts)
-    assert checked > 200
+    assert checked > 200, tally.report()
     # fixed: both expressions end at the same `to`, the longer one wins, whatever the split
     pats, flags, ids = ["ab+c", "b+c", "xa"], [SOM, SOM, SOM], [1, 1, 2]
     db = flowsomsim_py.Db(pats, flags, ids)

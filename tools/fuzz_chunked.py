@@ -8,9 +8,11 @@ import sys
 import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "tests"))
 sys.path.insert(0, REPO)
 import torch  # noqa: E402
 
+import oracle_py  # noqa: E402
 from hypergrep_amd import benchspec, device  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
@@ -47,7 +49,12 @@ while time.time() - t0 < budget:
     try:
         db = device.Database(pats, flags=flags, ids=ids)
     except Exception as e:
-        print(f"seed {seed - 1}: compile: {e}", flush=True)
+        fails += 1  # (every expression of this tool's pools is legal: a refusal is a failure, whatever the oracle says)
+        print(f"seed {seed - 1}: compile: {e} (the oracle's check_patterns: {oracle_py.check_patterns(pats, flags=flags)})", flush=True)
+        continue
+    if oracle_py.check_patterns(pats, flags=flags) != 0:
+        fails += 1
+        print(f"ACCEPT/REJECT seed {seed - 1}: the oracle rejects what the product accepts: {pats} flags {flags}", flush=True)
         continue
     ntiles = (nbytes + 16383) // 16384
     chunk_tiles = max(1024, ntiles // rng.choice([2, 3, 5, 9]) // 1024 * 1024)  # (the engine takes multiples of 1024 tiles)

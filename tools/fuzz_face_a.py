@@ -13,9 +13,10 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 sys.path.insert(0, REPO)
 import torch  # noqa: E402,F401
 
+import accept_rules  # noqa: E402
 import oracle_py  # noqa: E402
 import regex_gen  # noqa: E402
-from hypergrep_amd import utils  # noqa: E402
+from hypergrep_amd import device, utils  # noqa: E402
 from test_gpu_parity import _hs_events  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
@@ -25,6 +26,24 @@ product = utils._get_hyperscanner_lib()
 oracle = ctypes.CDLL(os.path.join(oracle_py.ORACLE_DIR, "_build", "libhs.so.5"))
 t0 = time.time()
 cases = fails = 0
+
+
+def same_decision(pats, flags, ids):
+    """True when both compilers take the set; a disagreement on accept/reject is a reported failure, not a skipped case."""
+    global fails
+    try:
+        device.Database(pats, flags=flags, ids=ids)
+        error = None
+    except device.CompileError as e:
+        error = str(e)
+    try:
+        return accept_rules.Tally().decide(pats, flags, error is None, error)
+    except AssertionError as e:
+        fails += 1
+        print(f"ACCEPT/REJECT seed {seed - 1}: {e}", flush=True)
+        return False
+
+
 while time.time() - t0 < budget:
     rng = random.Random(seed)
     seed += 1
@@ -37,7 +56,7 @@ while time.time() - t0 < budget:
         samplers = [s for _, s in pairs]
     flags = [rng.choice([14, 14, 15, 10, 6, 12, 7, 2]) for _ in pats]
     ids = [rng.randint(0, 3) for _ in pats]
-    if oracle_py.check_patterns(pats, flags=flags) != 0:
+    if not same_decision(pats, flags, ids):
         continue
     blocks = []
     for _ in range(rng.randint(1, 4)):

@@ -11,8 +11,10 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 sys.path.insert(0, REPO)
 import torch  # noqa: E402
 
+import accept_rules  # noqa: E402
 import oracle_py  # noqa: E402
 import regex_gen  # noqa: E402
+from hypergrep_amd import device  # noqa: E402
 from test_gpu_parity import gpu_scan_buffer, oracle_hits  # noqa: E402
 
 def rich_pattern(rng):
@@ -57,6 +59,22 @@ def regex_gen_escape(word):
     return "".join("\\" + c if c in ".-=" else c for c in word)
 
 
+def same_decision(pats, flags, ids):
+    """True when both compilers take the set; a disagreement on accept/reject is a reported failure, not a skipped case."""
+    global fails
+    try:
+        device.Database(pats, flags=flags, ids=ids)
+        error = None
+    except device.CompileError as e:
+        error = str(e)
+    try:
+        return accept_rules.Tally().decide(pats, flags, error is None, error)
+    except AssertionError as e:
+        fails += 1
+        print(f"ACCEPT/REJECT seed {seed - 1}: {e}", flush=True)
+        return False
+
+
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 100000
 t0 = time.time()
@@ -96,7 +114,7 @@ while time.time() - t0 < budget:
         samplers = samplers[:4]
     flags = [rng.choice([14, 14, 15, 10, 6, 12, 7, 2]) for _ in pats]
     ids = [rng.randint(0, 3) for _ in pats] if rng.random() < 0.7 else list(range(len(pats)))
-    if oracle_py.check_patterns(pats, flags=flags) != 0:
+    if not same_decision(pats, flags, ids):
         continue
     if samplers:
         data = regex_gen.anchored_text(rng, samplers, rng.choice([300, 3000]))

@@ -101,11 +101,11 @@ void hg_scanner_destroy(hg_scanner_t *scanner) {
 
 const char *hg_scanner_error(const hg_scanner_t *scanner) { return scanner ? scanner->sc->last_error().c_str() : "null scanner"; }
 
-int hg_scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, void *stream,
-                   hg_scan_result_t *result) {
+static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, void *stream,
+                       hg_scan_result_t *result, bool invert) {
   if (!scanner || !result) return HG_ERR_ARG;
   HgScanOutput o{};
-  int rc = scanner->sc->scan(d_text, nbytes, buffer_size, line_base, static_cast<hipStream_t>(stream), &o);
+  int rc = scanner->sc->scan(d_text, nbytes, buffer_size, line_base, static_cast<hipStream_t>(stream), &o, invert);
   if (rc != HG_OK) return rc;
   result->n_hits = o.n_hits;
   result->n_lines = o.n_pieces;
@@ -119,10 +119,20 @@ int hg_scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, i
   result->stream_launches = o.stream_launches;
   result->joiner_tiles = o.joiner_tiles;
   result->joiner_launches = o.joiner_launches;
-  result->reserved = 0;
+  result->invert_us = static_cast<uint32_t>(o.ms_invert * 1000.0f + 0.5f);
   scanner->last = *result;
   scanner->d_from = o.d_from;
   return HG_OK;
+}
+
+int hg_scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, void *stream,
+                   hg_scan_result_t *result) {
+  return scan_device(scanner, d_text, nbytes, buffer_size, line_base, stream, result, false);
+}
+
+int hg_scan_device_invert(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, void *stream,
+                          hg_scan_result_t *result) {
+  return scan_device(scanner, d_text, nbytes, buffer_size, line_base, stream, result, true);
 }
 
 int hg_copy_hits(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max) {

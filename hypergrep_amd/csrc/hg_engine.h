@@ -8,6 +8,7 @@
 #include "../../include/hypergrep_amd.h"
 #include "hg_compile.h"
 #include "hg_core.h"
+#include "hg_invert.h"
 #include "hg_post.h"
 
 // Waves per stream workgroup (one 16 KiB tile per wave at a time); shared by the kernel and the grid sizing.
@@ -136,6 +137,7 @@ struct HgScanOutput {
   uint32_t joiner_launches;  // ... and hg_stream_join_kernel launches
   uint64_t joiner_tiles;     // tiles (of 16 KiB) the joiner launches took: bytes the hg_stream_kernel launches did NOT stream
   const uint32_t *d_from;    // databases with HS_FLAG_SOM_LEFTMOST expressions: the start of each hit (hg_som.hip), else nullptr
+  float ms_invert;           // inverted scans: the invert stage (count, scan, the host sync that sizes the output, write); the fields above stay the underlying scan's
 };
 
 // The start-of-match pass (hg_som.hip): from[i] for the n final hits, on `stream`.  max_nw: the most state words of any SOM
@@ -167,6 +169,10 @@ struct HgCombArgs {
 };
 hipError_t hg_comb_launch(const HgCombArgs &a, bool emit, hipStream_t stream);
 
+// The invert stage (hg_invert.hip) over the ntiles tiles of a scanned buffer: the count pass (write == false) or the write
+// pass, on `stream`, in a grid sized for num_cus compute units.
+hipError_t hg_invert_launch(const HgInvertArgs &a, bool write, uint32_t num_cus, hipStream_t stream);
+
 // Test / experiment knobs of the engine, read from the environment ONCE, when a scanner is created (never during a scan:
 // getenv is not safe against a concurrent setenv, and a scan must not change behaviour half-way).  None is needed in normal
 // use.  The limit-lowering ones exist so that tests reach segmented scans / chunk halving on small texts.
@@ -195,7 +201,8 @@ class HgScanner {
   const std::shared_ptr<const HgDb> &database() const { return db_; }
   ~HgScanner();
   // d_text: device pointer, 16-byte aligned, readable up to nbytes rounded up to 16.
-  int scan(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, hipStream_t stream, HgScanOutput *out);
+  // invert: the result is the pieces WITHOUT a delivered report (hg_scan_device_invert), one record each.
+  int scan(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, hipStream_t stream, HgScanOutput *out, bool invert = false);
   // Block mode (hs_scan): the whole buffer is one scan unit; hits carry line_no 0 and `to` relative to the buffer start.
   int scan_block(const void *d_text, uint64_t nbytes, hipStream_t stream, HgScanOutput *out);
   // Block mode for short blocks held in PINNED host memory (readable up to nbytes rounded up to 16): one launch, raw
@@ -214,7 +221,7 @@ class HgScanner {
   int ensure(uint64_t nbytes);
   int alloc_cands(uint64_t n);
   int alloc_hits(uint64_t n);
-  int scan_impl(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, bool block_mode, hipStream_t stream, HgScanOutput *out);
+  int scan_impl(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, bool block_mode, bool invert, hipStream_t stream, HgScanOutput *out);
   // One pass over the tiles [tile_lo, tile_hi) of the text: the whole buffer, or a segment of it (scan_segments).  The tile
   // scan starts from (cs0, piece0): the start of the line that contains the range's first byte and that line's piece index;
   // only pieces whose first scanned byte lies in [own_lo, own_hi) are reported.
@@ -237,6 +244,7 @@ class HgScanner {
   int finalize_compact(const HgHit *hits, const HgHitAux *aux, uint32_t n, uint32_t id_bits, uint32_t to_bits, uint64_t line_bound, hipStream_t stream);
   int comb_pass(HgScanOutput *out, uint64_t bs1, uint64_t line_bound, hipStream_t stream);
   int minlen_pass(const uint8_t *text, uint32_t *n, hipStream_t stream);
+  int invert_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, hipStream_t stream, HgScanOutput *out);
   int huge_lds_error() { return error(HG_ERR_HIP, "the huge-automaton kernel cannot have its LDS"); }
   bool fail(hipError_t e, const char *what);
   int error(int rc, const std::string &what) { err_ = what; return rc; }
@@ -318,6 +326,16 @@ class HgScanner {
   uint64_t comb_out_cap_ = 0;
   uint8_t *d_comb_temp_ = nullptr;
   size_t comb_temp_bytes_ = 0;
+  // invert stage (inverted scans only, allocated by the first one): selected pieces per tile and their exclusive scan, the
+  // scan's scratch, and the records of the selected pieces (they grow with the text and with the count the stage computes
+  // before it writes: nothing is repeated to grow them)
+  uint64_t *d_inv_count_ = nullptr, *d_inv_pos_ = nullptr;
+  uint64_t inv_tiles_cap_ = 0;
+  uint8_t *d_inv_temp_ = nullptr;
+  size_t inv_temp_bytes_ = 0;
+  HgHit *d_inv_hits_ = nullptr;
+  HgHitAux *d_inv_aux_ = nullptr;
+  uint64_t inv_cap_ = 0;
   uint32_t *d_seg_count2_ = nullptr;  // second set for double buffering
   HgCand *d_cands2_ = nullptr;
 };

@@ -228,7 +228,7 @@ HgScanner::~HgScanner() {
                   d_agg_, d_cands_, d_hits_raw_, d_hits_out_, d_aux_raw_, d_aux_out_,
                   d_key_a_, d_key_b_, d_perm_a_, d_perm_b_, d_keep_, d_counters_, d_temp_, d_seg_count_, d_pflags_, d_deferred_, d_defer_count_, d_seg_count2_, d_cands2_, d_disc_, d_bucket2_, d_windows2_, d_groups_, d_acc_hits_, d_acc_aux_, d_huge_claim_, d_wtab_, d_from_, d_fin_fill_, d_fin_kept_, d_fin_big_,
                   d_combs_, d_comb_words_, d_comb_feed_, d_comb_count_, d_comb_pos_, d_comb_hits_, d_comb_aux_, d_comb_temp_, d_bounds_,
-                  d_min_lengths_, d_minlen_hits_, d_minlen_aux_};
+                  d_min_lengths_, d_minlen_hits_, d_minlen_aux_, d_inv_count_, d_inv_pos_, d_inv_temp_, d_inv_hits_, d_inv_aux_};
   for (void *p : ptrs) hgmem::dev_free(p, "scanner");
   hgmem::host_free(h_counters_, "h_counters_");
   for (auto &ev : ev_)
@@ -863,6 +863,61 @@ int HgScanner::minlen_pass(const uint8_t *text, uint32_t *n, hipStream_t stream)
   return HG_OK;
 }
 
+// The invert stage over a finished scan (*out: its final hits, ordered by line, and its piece count): the count pass over
+// the scan's tile states and hits, an exclusive scan of the per-tile counts, and the write pass (hg_invert.hip).  *out then
+// describes the selected pieces; its counters and timings stay the scan's.  A buffer that was scanned in segments is
+// inverted here in one go: the segments leave the tile states of the whole buffer and their hits one after the other, so
+// the result is the one of inverting segment by segment.
+int HgScanner::invert_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, hipStream_t stream, HgScanOutput *out) {
+  const uint64_t ntiles = (nbytes + HG_TILE_BYTES - 1) / HG_TILE_BYTES;
+  out->d_from = nullptr;  // (a selected piece has no match: its start reads 0)
+  if (ntiles == 0) {
+    out->n_hits = 0;
+    return HG_OK;
+  }
+  if (ntiles + 1 > inv_tiles_cap_) {
+    const uint64_t cap = std::max<uint64_t>(ntiles + ntiles / 4 + 1, 4096);
+    inv_tiles_cap_ = 0;
+    HG_TRY(realloc_dev(d_inv_count_, cap, "d_inv_count_"), "alloc (invert stage)");
+    HG_TRY(realloc_dev(d_inv_pos_, cap, "d_inv_pos_"), "alloc (invert stage)");
+    inv_tiles_cap_ = cap;
+  }
+  size_t tb = 0;  // the scan's scratch, asked for the size that is scanned
+  HG_TRY(rocprim::exclusive_scan(nullptr, tb, d_inv_count_, d_inv_pos_, uint64_t{0}, ntiles + 1, rocprim::plus<uint64_t>(), stream), "scan (invert stage)");
+  if (tb > inv_temp_bytes_ || !d_inv_temp_) {
+    inv_temp_bytes_ = 0;
+    HG_TRY(realloc_dev(d_inv_temp_, tb + tb / 4, "d_inv_temp_"), "alloc (invert stage)");
+    inv_temp_bytes_ = tb + tb / 4;
+  }
+  HgInvertArgs a{text, nbytes, bs1, ntiles, line_base + out->n_pieces, d_sums_, d_bases_, out->d_hits, out->n_hits, d_inv_count_, d_inv_pos_, nullptr, nullptr};
+  HG_TRY(hipEventRecord(ev_[0], stream), "event");
+  HG_TRY(hg_invert_launch(a, false, static_cast<uint32_t>(num_cus_), stream), "invert stage launch (count)");
+  HG_TRY(rocprim::exclusive_scan(d_inv_temp_, tb, d_inv_count_, d_inv_pos_, uint64_t{0}, ntiles + 1, rocprim::plus<uint64_t>(), stream), "scan (invert stage)");
+  uint64_t total = 0;
+  HG_TRY(hipMemcpyAsync(&total, d_inv_pos_ + ntiles, sizeof total, hipMemcpyDeviceToHost, stream), "copy count");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (invert stage)");
+  if (total > out->n_pieces) return error(HG_ERR_HIP, "the invert stage counted more pieces than the buffer has");
+  if (total > inv_cap_) {
+    const uint64_t cap = std::max<uint64_t>(total + total / 4, 4096);
+    inv_cap_ = 0;
+    HG_TRY(realloc_dev(d_inv_hits_, cap, "d_inv_hits_"), "alloc (invert stage records)");
+    HG_TRY(realloc_dev(d_inv_aux_, cap, "d_inv_aux_"), "alloc (invert stage records)");
+    inv_cap_ = cap;
+  }
+  if (total) {
+    a.out_hits = d_inv_hits_;
+    a.out_aux = d_inv_aux_;
+    HG_TRY(hg_invert_launch(a, true, static_cast<uint32_t>(num_cus_), stream), "invert stage launch (write)");
+  }
+  HG_TRY(hipEventRecord(ev_[3], stream), "event");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (invert stage)");
+  (void)hipEventElapsedTime(&out->ms_invert, ev_[0], ev_[3]);
+  out->n_hits = total;
+  out->d_hits = d_inv_hits_;
+  out->d_aux = d_inv_aux_;
+  return HG_OK;
+}
+
 int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const PassRange &range, bool block_mode, hipStream_t stream,
                         HgScanOutput *out) {
   // (the first pass that streams asks how many stream workgroups a CU holds)
@@ -963,11 +1018,11 @@ uint32_t HgScanner::launch_block_small(const uint8_t *h_text, uint32_t nbytes, h
 }
 
 int HgScanner::scan_block(const void *d_text, uint64_t nbytes, hipStream_t stream, HgScanOutput *out) {
-  return scan_impl(d_text, nbytes, 0x7FFFFFFF, 0, true, stream, out);
+  return scan_impl(d_text, nbytes, 0x7FFFFFFF, 0, true, false, stream, out);
 }
 
-int HgScanner::scan(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, hipStream_t stream, HgScanOutput *out) {
-  return scan_impl(d_text, nbytes, buffer_size, line_base, false, stream, out);
+int HgScanner::scan(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, hipStream_t stream, HgScanOutput *out, bool invert) {
+  return scan_impl(d_text, nbytes, buffer_size, line_base, false, invert, stream, out);
 }
 
 // One pass over `range` (run_once), repeated while the workspace grows, 16 times at most: out->reruns.
@@ -983,7 +1038,7 @@ int HgScanner::run_fitting(const uint8_t *text, uint64_t nbytes, uint64_t bs1, u
   }
 }
 
-int HgScanner::scan_impl(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, bool block_mode, hipStream_t stream,
+int HgScanner::scan_impl(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, bool block_mode, bool invert, hipStream_t stream,
                          HgScanOutput *out) {
   if (!out || (!d_text && nbytes) || buffer_size < 2) return error(HG_ERR_ARG, "invalid arguments");
   if ((reinterpret_cast<uintptr_t>(d_text) & 15u) != 0) return error(HG_ERR_ARG, "text pointer must be 16-byte aligned");
@@ -1007,6 +1062,9 @@ int HgScanner::scan_impl(const void *d_text, uint64_t nbytes, int buffer_size, u
     out->reruns = reruns;
   }
   if (rc) return rc;
+  // the invert stage: behind the finalize, the match-length and the combination stages, on the delivered hits of the whole
+  // buffer (no start-of-match pass: the selected pieces have no match)
+  if (invert && !block_mode) return invert_pass(text, nbytes, bs1, line_base, stream, out);
   if (db_->nsom) {
     // start of match (behind the combination pass: only delivered hits get a start): one pass over the final ordered hits (those of all segments, one after the other)
     if (out->n_hits > from_cap_) {
@@ -1030,6 +1088,9 @@ int HgScanner::scan_impl(const void *d_text, uint64_t nbytes, int buffer_size, u
 // and filtered (SINGLEMATCH / duplicate rules) in exactly one pass.  The tile-scan state (carry-in line start, piece index)
 // at a segment's first tile is read from the previous pass, which has scanned past it.  The passes' ordered hits are put one
 // after the other: segments are in text order, so is their concatenation.  HG_SPLIT: some segment still overflowed a pass.
+// The tile summaries and prefix states (d_sums_, d_bases_) are indexed by ABSOLUTE tile, and a pass that rewrites the tiles a
+// neighbour has written (the `reach` overlap) writes the same values, since it starts from that neighbour's state: after the
+// last segment they describe the whole buffer.  The invert stage (invert_pass) relies on this.
 int HgScanner::scan_segments(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, hipStream_t stream, HgScanOutput *out, uint32_t nsegments) {
   const uint64_t ntiles = (nbytes + HG_TILE_BYTES - 1) / HG_TILE_BYTES;
   const uint64_t reach = (bs1 >> HG_TILE_SHIFT) + 2;  // tiles a piece that starts inside a stretch can extend past its end

@@ -576,9 +576,10 @@ extern "C" int hyperscan(char *file_name, const char *const *patterns, const uns
   return hg_hyperscan_ext(file_name, patterns, pattern_flags, pattern_ids, nullptr, elements, on_event, buffer_size, buffer_count, max_match_count);
 }
 
-extern "C" int hg_hyperscan_ext(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
-                             const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hs_event on_event,
-                             const int buffer_size, int buffer_count, unsigned long long max_match_count) {
+// Face B's file scan: the reports of the file's pieces, or (invert) one HG_ID_INVERT result per piece without a report.
+static int scan_file(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                     const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hs_event on_event,
+                     const int buffer_size, int buffer_count, unsigned long long max_match_count, const bool invert) {
   if (max_match_count > 0 && max_match_count < static_cast<unsigned long long>(buffer_count)) buffer_count = static_cast<int>(max_match_count);
   if (buffer_count < 1 || buffer_size < 1 || !on_event) return HYPERSCANNER_STATE_MEM;
   Ring ring;
@@ -737,7 +738,7 @@ extern "C" int hg_hyperscan_ext(char *file_name, const char *const *patterns, co
         break;
       }
       HgScanOutput out{};
-      int src = ctx->sc->scan(d_text, cut, buffer_size, line_base, ctx->stream, &out);
+      int src = ctx->sc->scan(d_text, cut, buffer_size, line_base, ctx->stream, &out, invert);
       if (src != HG_OK) {
         std::fprintf(stderr, "ERROR: Unable to scan buffer. Exiting. (%s)\n", ctx->sc->last_error().c_str());
         rc = HYPERSCANNER_SCAN;
@@ -796,4 +797,16 @@ extern "C" int hg_hyperscan_ext(char *file_name, const char *const *patterns, co
                  file_name, bytes_in / 1048576.0, now() - t_call, t_read, t_wait_slot, t_setup, db->tuned ? "tuned windows" : "static windows", t_scan,
                  static_cast<unsigned long long>(ring.delivered), t_deliver);
   return rc;
+}
+
+extern "C" int hg_hyperscan_ext(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                             const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hs_event on_event,
+                             const int buffer_size, int buffer_count, unsigned long long max_match_count) {
+  return scan_file(file_name, patterns, pattern_flags, pattern_ids, ext, elements, on_event, buffer_size, buffer_count, max_match_count, false);
+}
+
+extern "C" int hg_hyperscan_invert(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                                   const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hs_event on_event,
+                                   const int buffer_size, int buffer_count, unsigned long long max_match_count) {
+  return scan_file(file_name, patterns, pattern_flags, pattern_ids, ext, elements, on_event, buffer_size, buffer_count, max_match_count, true);
 }

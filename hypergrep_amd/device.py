@@ -16,6 +16,7 @@ HS_FLAG_SOM_LEFTMOST = 256
 # Logical combinations of other expressions' report ids, and reports that only feed combinations (include/hypergrep_amd.h).
 HS_FLAG_COMBINATION = utils.HS_FLAG_COMBINATION
 HS_FLAG_QUIET = utils.HS_FLAG_QUIET
+HG_ID_INVERT = utils.HG_ID_INVERT  # the id of an inverted scan's records (Scanner.scan(invert=True)): no expression
 
 
 class HgHit(ctypes.Structure):
@@ -31,7 +32,7 @@ class HgScanResult(ctypes.Structure):
         ("n_hits", ctypes.c_uint64), ("n_lines", ctypes.c_uint64), ("n_candidates", ctypes.c_uint64),
         ("n_raw_hits", ctypes.c_uint64), ("d_hits", ctypes.c_void_p), ("d_aux", ctypes.c_void_p),
         ("ms_stream", ctypes.c_float), ("ms_total", ctypes.c_float), ("reruns", ctypes.c_uint32), ("stream_launches", ctypes.c_uint32),
-        ("joiner_tiles", ctypes.c_uint64), ("joiner_launches", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("joiner_tiles", ctypes.c_uint64), ("joiner_launches", ctypes.c_uint32), ("invert_us", ctypes.c_uint32),
     ]
 
 
@@ -70,6 +71,8 @@ def lib() -> ctypes.CDLL:
         l.hg_scanner_error.argtypes = [ctypes.c_void_p]
         l.hg_scan_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p,
                                      ctypes.POINTER(HgScanResult)]
+        if hasattr(l, "hg_scan_device_invert"):  # (absent from a build before the inverted match: HG_LIB comparisons with an older library)
+            l.hg_scan_device_invert.argtypes = l.hg_scan_device.argtypes
         l.hg_copy_hits.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
         l.hg_copy_hits_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hit_starts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
@@ -140,6 +143,7 @@ class ScanStats:
     stream_launches: int = 1
     joiner_launches: int = 0
     joiner_tiles: int = 0
+    invert_us: int = 0  # inverted scans: the invert stage alone, microseconds
 
 
 class Scanner:
@@ -154,13 +158,17 @@ class Scanner:
             raise DeviceError(f"hg_scanner_create failed ({rc}): {err.value.decode(errors='replace')}")
         self._last = HgScanResult()
 
-    def scan(self, d_text: int, nbytes: int, buffer_size: int = 262140, line_base: int = 0, stream: int = 0) -> ScanStats:
+    def scan(self, d_text: int, nbytes: int, buffer_size: int = 262140, line_base: int = 0, stream: int = 0, invert: bool = False) -> ScanStats:
+        """invert: the result is the line pieces without any report (grep -v; hg_scan_device_invert): n_hits of them, and
+        hits() gives (line_number, HG_ID_INVERT, 0, start, len) per piece in line order."""
         res = HgScanResult()
-        rc = lib().hg_scan_device(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, line_base, ctypes.c_void_p(stream), ctypes.byref(res))
+        name = "hg_scan_device_invert" if invert else "hg_scan_device"
+        rc = getattr(lib(), name)(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, line_base, ctypes.c_void_p(stream), ctypes.byref(res))
         if rc != 0:
-            raise DeviceError(f"hg_scan_device failed ({rc}): {lib().hg_scanner_error(self._h).decode(errors='replace')}")
+            raise DeviceError(f"{name} failed ({rc}): {lib().hg_scanner_error(self._h).decode(errors='replace')}")
         self._last = res
-        return ScanStats(res.n_hits, res.n_lines, res.n_candidates, res.n_raw_hits, res.ms_stream, res.ms_total, res.reruns, res.stream_launches, res.joiner_launches, res.joiner_tiles)
+        return ScanStats(res.n_hits, res.n_lines, res.n_candidates, res.n_raw_hits, res.ms_stream, res.ms_total, res.reruns, res.stream_launches, res.joiner_launches, res.joiner_tiles,
+                         res.invert_us)
 
     @property
     def d_hits(self) -> int:

@@ -112,7 +112,7 @@ class _Replay:
             self.total += found
         elif opt["count_results"]:
             print(f"{name}:{found}" if opt["with_file_name"] else f"{found}")
-        else:
+        elif not opt["rows_unprinted"]:  # (-o -v: the selected lines decide the exit code, and none has a matched part to print)
             try:
                 print_results(found, name, with_file_name=opt["with_file_name"], with_line_number=opt["with_line_number"])
             except BrokenPipeError:
@@ -136,6 +136,7 @@ def parallel_grep(  # pylint: disable=too-many-arguments,too-many-locals
     files_without_match: bool = False,
     files_with_matches: bool = False,
     quiet: bool = False,
+    invert_match: bool = False,
 ) -> int:
     """Search files for the patterns and print what grep would print.
 
@@ -153,6 +154,8 @@ def parallel_grep(  # pylint: disable=too-many-arguments,too-many-locals
         max_match_count: stop reading a file after that many matching lines (0: no limit).
         files_without_match / files_with_matches: print file names only; reading stops at the first match.
         quiet: print nothing and stop everything at the first match.
+        invert_match: select the lines NO pattern matches (grep -v).  Counts, totals, -l / -L / -q and max_match_count then
+            go by the selected lines; with only_matching nothing is printed, and the exit code still goes by the selected lines.
 
     Returns:
         grep's exit code: 2 after any error, else 1 without a match, else 0.
@@ -162,14 +165,16 @@ def parallel_grep(  # pylint: disable=too-many-arguments,too-many-locals
     replay = _Replay(
         files,
         {"ordered_results": ordered_results, "count_results": count_results, "total_results": total_results, "with_file_name": with_file_name,
-         "with_line_number": with_line_number, "files_without_match": files_without_match, "files_with_matches": files_with_matches, "quiet": quiet},
+         "with_line_number": with_line_number, "files_without_match": files_without_match, "files_with_matches": files_with_matches, "quiet": quiet,
+         "rows_unprinted": only_matching and invert_match},
     )
     job_kwargs = {
         "ignore_case": ignore_case,
         "count_only": count_results or total_results,
-        "only_matching": only_matching,
+        "only_matching": only_matching and not invert_match,  # (-o -v: the jobs still report the selected lines, GNU grep's exit code)
         "no_messages": no_messages,
         "max_match_count": max_match_count,
+        "invert": invert_match,
     }
     # the reference runs one job per core; here a job is a GPU scan with its own reader threads and pinned buffers, so a
     # handful in flight already keeps every GPU of the node busy
@@ -290,6 +295,8 @@ def parse_args(args: list = None) -> argparse.Namespace:
     matching.add_argument("-e", "--regexp", action="append", dest="patterns", metavar="pattern", help="A pattern; may be repeated and combined with -f.")
     matching.add_argument("-f", "--file", action="append", dest="pattern_files", metavar="file", help="Read patterns from FILE, one per line; may be repeated.")
     matching.add_argument("-i", "--ignore-case", action="store_true", help="Case-insensitive matching.")
+    # (no attribute unless given: tests/test_multiscanner.py compares the whole namespace of the reference's command lines)
+    matching.add_argument("-v", "--invert-match", action="store_true", default=argparse.SUPPRESS, help="Select the lines that match NO pattern.")
 
     output = parser.add_argument_group("General Output Control")
     output.add_argument("-c", "--count", action="store_true", help="Print the number of matching lines per file.")
@@ -364,6 +371,7 @@ def main() -> None:
             quiet=args.quiet,
             files_without_match=args.files_without_match,
             files_with_matches=args.files_with_matches,
+            invert_match=getattr(args, "invert_match", False),
         )
     )
 

@@ -30,6 +30,7 @@ HS_FLAG_CASELESS, HS_FLAG_DOTALL, HS_FLAG_MULTILINE, HS_FLAG_SINGLEMATCH = 1, 2,
 # Logical combinations: a formula over other expressions' report ids, and reports that only feed combinations
 # (include/hypergrep_amd.h has the contract).
 HS_FLAG_COMBINATION, HS_FLAG_QUIET = 512, 1024
+HG_ID_INVERT = 0xFFFFFFFF  # Result.id of an inverted scan (scan(invert=True)): no expression
 _GREP_FLAGS = HS_FLAG_DOTALL | HS_FLAG_MULTILINE | HS_FLAG_SINGLEMATCH  # what grep() and the default of scan() use
 
 RC_INVALID_FILE = 101  # grep(): the path is missing or a directory (utils.py:16)
@@ -168,9 +169,12 @@ def scan(  # pylint: disable=too-many-arguments
     buffer_count: int = 16,
     max_match_count: int = 0,
     ext=None,
+    invert: bool = False,
 ) -> int:
     """Scan a plain / gzip / zstd text file; `callback(matches, count)` receives the hits in batches of `buffer_count`.
     `ext`: one ExprExt (extended parameters: approximate matching, offset bounds, min_length) or None per pattern.
+    `invert` (grep -v): the callback receives the lines NO pattern matches instead, one Result with id HG_ID_INVERT each, in
+    line order; `max_match_count` then bounds those lines.
 
     The native call runs on a daemon thread so that Ctrl-C reaches Python (return code 130); otherwise the shim's
     return code (0 = fine, 1-7 as in hyperscanner.c:25-33) comes back.
@@ -182,7 +186,13 @@ def scan(  # pylint: disable=too-many-arguments
     outcome = [0]
 
     def native_call() -> None:
-        if c_ext is None:
+        if invert:
+            engine.hg_hyperscan_invert.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
+                                                   ctypes.POINTER(ctypes.POINTER(ExprExt)), ctypes.c_uint, CALLBACK_TYPE, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_ulonglong]
+            outcome[0] = engine.hg_hyperscan_invert(path.encode(), c_patterns, c_flags, c_ids, c_ext, len(c_patterns), c_callback, buffer_size,
+                                                    buffer_count, max_match_count)
+        elif c_ext is None:
             outcome[0] = engine.hyperscan(path.encode(), c_patterns, c_flags, c_ids, len(c_patterns), c_callback, buffer_size, buffer_count,
                                           ctypes.c_ulonglong(max_match_count))
         else:
@@ -202,7 +212,8 @@ class _GrepSink:
     """on_match for grep(): counts, keeps whole lines, or keeps the matched parts (`re.finditer` of the pattern whose
     id the hit carries — with grep()'s all-zero ids that is the first pattern, as in the reference)."""
 
-    def __init__(self, patterns: list[str], count_only: bool, only_matching: bool, errors: str):
+    def __init__(self, patterns: list[str], count_only: bool, only_matching: bool, errors: str, invert: bool = False):
+        self.invert = invert  # the hits are the lines without a match: no matched parts to show
         self.count = 0
         self.rows: list[tuple[int, str]] = []
         self.count_only = count_only
@@ -217,7 +228,7 @@ class _GrepSink:
             text = hit.line.decode(errors=self.errors)
             if self.finders is None:
                 self.rows.append((hit.line_number + 1, text))
-            else:
+            elif not self.invert:
                 self.rows.extend((hit.line_number + 1, f"{part.group()}\n") for part in self.finders[hit.id].finditer(text))
 
     def result(self):
@@ -233,13 +244,18 @@ def grep(  # pylint: disable=too-many-arguments
     no_messages: bool = False,
     errors: str = "ignore",
     max_match_count: int = 0,
+    invert: bool = False,
 ) -> tuple[int | list[tuple[int, str]], int]:
     """grep for Python: (number of matching lines | [(1-based line number, line)], return code).
+
+    `invert` (grep -v): the lines no pattern matches are selected instead: counted, listed, and bounded by `max_match_count`;
+    with `only_matching` nothing is listed (a line without a match has no matched part): the result is [] even where lines
+    were selected, so a caller that needs to know whether any were asks without `only_matching`, as multiscanner does.
 
     A missing path raises FileNotFoundError and a directory ValueError — or, with `no_messages`, comes back as
     (nothing found, 101).  Invalid regexes raise `re.error` before anything is scanned.
     """
-    sink = _GrepSink(patterns, count_only, only_matching, errors)
+    sink = _GrepSink(patterns, count_only, only_matching, errors, invert)
     if not only_matching:
         for pattern in patterns:  # the reference compiles them for -o in every mode: same early failure for bad syntax
             re.compile(pattern)
@@ -253,5 +269,5 @@ def grep(  # pylint: disable=too-many-arguments
             raise problem
         return sink.result(), RC_INVALID_FILE
     flags = _GREP_FLAGS | (HS_FLAG_CASELESS if ignore_case else 0)
-    return_code = scan(file, patterns, sink, flags=[flags] * len(patterns), max_match_count=max_match_count)
+    return_code = scan(file, patterns, sink, flags=[flags] * len(patterns), max_match_count=max_match_count, invert=invert)
     return sink.result(), return_code

@@ -183,6 +183,13 @@ int hg_hyperscan_ext(char *file_name, const char *const *patterns, const unsigne
                   hs_event on_event, const int buffer_size, int buffer_count, unsigned long long max_match_count);
 int hg_check_patterns_ext(const char *const *patterns, const unsigned int *pattern_flags, const unsigned int *pattern_ids,
                        const hs_expr_ext_t *const *ext, const unsigned int elements);
+/* Inverted match (grep -v) for files: hg_hyperscan_ext's arguments, reader, chunking and database cache, but `on_event`
+ * receives one Result{id = HG_ID_INVERT, line_number, line} per SELECTED line piece, in ascending line order: the pieces
+ * for which hg_hyperscan_ext would deliver nothing (hg_scan_device_invert below has the rules; `line` is the piece's scanned
+ * bytes, empty for a piece of NULs only).  max_match_count: stop after that many selected pieces (0 = no limit). */
+int hg_hyperscan_invert(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                        const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements,
+                        hs_event on_event, const int buffer_size, int buffer_count, unsigned long long max_match_count);
 
 /* call site hyperscanner.c:136 */
 int hs_compile_multi(const char *const *expressions, const unsigned int *flags, const unsigned int *ids,
@@ -349,7 +356,8 @@ typedef struct hg_scan_result {
     uint32_t stream_launches; /* launches of the streaming kernel in this scan (one per pipeline chunk) */
     uint64_t joiner_tiles;    /* 16 KiB tiles streamed by the joiner launches (hg_stream_join_kernel), not by those */
     uint32_t joiner_launches; /* launches of the joiner kernel in this scan */
-    uint32_t reserved;
+    uint32_t invert_us;       /* hg_scan_device_invert: the added stage in microseconds (HIP events around its count launch, scan and write
+                                 launch, the host synchronisation that sizes the output included: more than its kernels' time); else 0 */
 } hg_scan_result_t;
 
 typedef struct hg_db_info {
@@ -389,6 +397,26 @@ const char *hg_scanner_error(const hg_scanner_t *scanner);
  * pipeline chunks than one pass has) is scanned in segments whose ordered hits are put one after the other. */
 int hg_scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size,
                    uint64_t line_base, void *stream, hg_scan_result_t *result);
+
+/* Inverted match (grep -v): the contract of hg_scan_device, but the result holds the line pieces NO expression matches.
+ * A line piece is what hg_scan_device numbers: lines end at '\n'; a line longer than buffer_size - 1 bytes is cut into pieces
+ * of buffer_size - 1 bytes, each numbered on its own; a piece's scanned bytes are those after its leading NULs up to its
+ * first NUL, the '\n' included; a zero-length tail after the buffer's last '\n' is not a piece.  A piece is SELECTED iff
+ * hg_scan_device delivers no report for it: the SINGLEMATCH, duplicate, offset-bound, min_length, combination and QUIET
+ * rules apply first, so a piece whose only reports are QUIET or were all removed is selected, and so is a piece whose
+ * scanned length is 0 (nothing but NULs up to its end), with len == 0.
+ * The result has one record per selected piece, in ascending line_number: hg_hit_t{line_number, id = HG_ID_INVERT, to = 0}
+ * and hg_hit_aux_t{start, len, pattern = 0xFFFFFFFF}, `start` and `len` as for hits.  n_hits is the number of selected
+ * pieces; n_lines, n_candidates, n_raw_hits, the timings and the counters are those of the underlying scan (invert_us: the
+ * added stage).  hg_copy_hits and hg_copy_hits_device work unchanged; hg_copy_hit_starts yields zeros.
+ * Complement identity, for every database and buffer: (the distinct line_number values among hg_scan_device's hits) +
+ * (hg_scan_device_invert's n_hits) == n_lines.
+ * The stage runs on the GPU behind the scan (hypergrep_amd/csrc/hg_invert.hip): per-tile counts from the scan's line geometry
+ * and hits, their exclusive scan, one pass over the text that writes the records in order.  A piece of gigabytes (a buffer
+ * without newlines under a huge buffer_size) is trimmed by a single wavefront. */
+#define HG_ID_INVERT 0xFFFFFFFFu /* the id of an inverted result's records: no expression */
+int hg_scan_device_invert(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base,
+                          void *stream, hg_scan_result_t *result);
 
 /* Copy the last scan's first `max` hits (and aux records, if aux != NULL) to host memory. */
 int hg_copy_hits(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max);

@@ -59,6 +59,11 @@ def guarded_cases():
                 if bs == 64 and len(pats) > 100:
                     continue
                 yield (f"{name}-{len(text)}-{bs}", text, pats, flags, ids, bs)
+    # the text-edge class of three confirm cells (tests/confirm_cells.py): a match, a near miss and a cut literal at the last
+    # byte of texts whose lengths are no multiple of 16, texts of one chunk
+    import confirm_cells
+
+    yield from confirm_cells.guarded_edge_cases()
 
 
 def regex_gen_escape(word: str) -> str:

@@ -1021,6 +1021,8 @@ struct SampleStats {
 // (Re)build windows, bucket index, LDS filter slots and neighbour conditions from db.factors.
 int build_filter(HgDb &db, const SampleStats *stats, std::string *err) {
   db.windows.clear();
+  db.filter_ctx.clear();  // (only the single-probe layout of dword-aligned windows fills it)
+  db.filter_use_ctx = 0;
   std::vector<std::pair<uint32_t, HgWindow>> keyed;
   std::vector<uint32_t> next16_of;  // per keyed entry: hg_next16 of the two bytes after the window, 0 if unknown
   const uint32_t fold = db.fold_mask;
@@ -1239,6 +1241,11 @@ int build_filter(HgDb &db, const SampleStats *stats, std::string *err) {
   // Single-probe slots.  Per table size and candidate weight vector the cost is the expected false-positive rate per
   // text dword (slot shared by windows whose fingerprints agree on b bits admits 2^-b of all dwords); the smallest
   // table that stays under the target wins: up to 16 KiB three stream workgroups fit on a CU, beyond that two or one.
+  // That rate holds for text whose dwords are uniform, which prices hash collisions only.  On log text the matches are
+  // true windows in the wrong place: config 3 with tuned windows measures 1.26 % of the dwords (target here: 0.05 %), 85 %
+  // of them the two values "tus=" and " sta", forced windows of "status=5Nd" and "_NN stale" that the text's own
+  // status=200 tokens and words in " sta" hold as well.  The context byte (filter_ctx below) brings that to 0.18 %;
+  // DESIGN.md 6a has the table.
   bool placed = false;
   {
     std::vector<uint32_t> cand_weights;
@@ -1345,6 +1352,33 @@ int build_filter(HgDb &db, const SampleStats *stats, std::string *err) {
           merge(x->pv, x->pm, pv, pm);
           merge(x->nv, x->nm, nv, nm);
         }
+      }
+      // First level with one byte of context (hg_db.h hg_slot_match_ctx), from the conditions just built, so that it never
+      // rejects a dword that `filter` and hg_slot_pass together let through.  The low bits of the test value are hash C's
+      // own: they keep the care bits of `filter`.  The bits above them also depend on the byte after the window.  A slot
+      // cares about those of them on which all its values agree, each taken with the byte its condition demands — and about
+      // none if a value has no such byte (a window that ends its literal, windows of one value that disagree, a caseless
+      // letter where nothing is folded), or if the slot is crowded: `rest` then passes dwords that are no window at all,
+      // whose hash C is anything.
+      if (!db.dense && wbytes == 4) {
+        db.filter_ctx.assign(size_t(1) << k, HG_FILTER_EMPTY);
+        const uint32_t high = 0xFFFFu & ~HG_CTX_LOW;
+        for (size_t sl = 0; sl < db.ext.size(); sl++) {
+          const HgSlotInfo &info = db.ext[sl];
+          if (!info.nvalues) continue;
+          uint32_t care = (db.filter[sl] >> 16) & HG_CTX_LOW, fp = db.filter[sl] & HG_CTX_LOW;
+          uint32_t agree = info.many ? 0u : high, first = 0;
+          for (uint32_t i = 0; i < info.nvalues && agree; i++) {
+            if ((info.cond[i].nm & 0xFFu) != 0xFFu) { agree = 0; break; }
+            const uint32_t t = hg_ctx_value(hg_hash_window(info.value[i]), info.cond[i].nv & 0xFFu);
+            if (i == 0) first = t;
+            agree &= ~(first ^ t);
+          }
+          care |= agree;
+          fp |= first & agree;
+          db.filter_ctx[sl] = (care << 16) | fp;
+        }
+        db.filter_use_ctx = 1;  // (hgc_tune decides again on its sample)
       }
     }
   }
@@ -2385,6 +2419,32 @@ int hgc_tune(const HgDb *db, const uint8_t *sample, size_t nbytes, HgDb **out, s
   }
   int rc = build_filter(*copy, &st, err);  // a failure leaves the caller's database as it was
   if (rc != 0) return rc;
+  // The context byte costs every 1 KiB wave-iteration of the stream pass about 7 vector instructions of ~55 (one per dword,
+  // the neighbour's byte, the edge lane); an iteration that no longer queues a chunk saves its queue block (~7, and as many
+  // scalar and LDS instructions) and its share of a drain (~9 and a dependent L2 fetch).  On config 3 it takes the
+  // iterations with a match from 85 % to 36 % and the pass gains 5 %; a set whose first level lets little through (one rare
+  // literal: a fraction of a percent of the iterations) only pays, 0.6 % measured.  By the instruction counts the two meet
+  // where the byte spares about 4 iterations in 10; the drains' stalls, which the counts leave out, put the measured
+  // break-even lower, so the kernels with the byte run when it spares at least 1 iteration in 4 of the sample.
+  if (copy->filter_use_ctx) {
+    const uint32_t byte_mask = ((1u << copy->filter_log2) - 1u) << 2;
+    size_t rows = 0, rows_plain = 0, rows_ctx = 0;
+    for (size_t r = 0; r + 1024 <= nbytes; r += 1024, rows++) {
+      bool any_plain = false, any_ctx = false;
+      for (size_t p = r; p < r + 1024 && !(any_plain && any_ctx); p += 4) {
+        uint32_t w, nx = 0;
+        std::memcpy(&w, sample + p, 4);
+        if (p + 8 <= nbytes) std::memcpy(&nx, sample + p + 4, 4);
+        w |= fold;
+        const uint32_t sl = hg_slot(w, copy->weights_a, byte_mask) >> 2, key = hg_hash_window(w);
+        any_plain = any_plain || hg_slot_match(copy->filter[sl], key);
+        any_ctx = any_ctx || hg_slot_match_ctx(copy->filter_ctx[sl], key, nx | fold, p + 4 < r + 1024);
+      }
+      rows_plain += any_plain;
+      rows_ctx += any_ctx;
+    }
+    if (rows && (rows_plain < rows_ctx || (rows_plain - rows_ctx) * 4 < rows)) copy->filter_use_ctx = 0;
+  }
   copy->tuned = true;
   *out = copy.release();
   return 0;

@@ -27,6 +27,11 @@ struct HgDb {
                                       // it did before the table existed: for a shared window the table is one more fetch in front of that
                                       // chain (config 3, 150 of 1400 values, the class expressions' stems: 315 against 225 us per 8 GiB)
   std::vector<uint32_t> filter;      // 1 << filter_log2 slots holding hash C of the owning window (staged in LDS by the stream kernel)
+  std::vector<uint32_t> filter_ctx;  // single-probe, dword-aligned 4-byte windows only (else empty): the same slots with one byte of context
+                                     // (hg_db.h hg_slot_match_ctx).  With filter_use_ctx THIS is what the stream kernel stages in LDS; `filter`
+                                     // goes to HBM behind `ext`, for the dwords a crowded slot judges by `rest`
+  uint32_t filter_use_ctx = 0;       // the stream pass runs the kernels that test the context byte (1 whenever filter_ctx is there, until a
+                                     // text sample says that it buys nothing: hgc_tune).  0: `filter` in LDS, the kernels without it
   uint32_t filter_log2 = HG_FILTER_MIN_LOG2;
   uint32_t filter_wide = 0;          // 1: two 16-bit fingerprints per slot, no neighbour conditions (large pattern sets)
   uint32_t window_bytes = HG_WINDOW_BYTES;  // bytes of a window: 4, or 3 with byte-aligned probing when 3-byte literals are too many to enumerate

@@ -232,6 +232,28 @@ HG_HD uint32_t hg_slot(uint32_t folded, uint32_t weights, uint32_t byte_mask) { 
 // Single-probe slot test: every fingerprint bit the slot cares about agrees with hash C (the mask has 16 bits, so the
 // upper bits of hash C drop out by themselves).  The empty slot 0xFFFFFFFF only admits fingerprint 0xFFFF.
 HG_HD bool hg_slot_match(uint32_t slot_word, uint32_t hash_c) { return (hash_c & (slot_word >> 16)) == (slot_word & 0xFFFFu); }
+// Single-probe slot test with one byte of context (HgDb::filter_ctx: dword-aligned 4-byte windows only).  Most first-level
+// matches on real text are true windows in the wrong place ("tus=" of status=200 where the literal wants status=5): the
+// byte after the window tells them apart.  The 16-bit test value is hash C + (the folded dword after the window <<
+// HG_CTX_SHIFT), one v_lshl_add_u32: its low HG_CTX_SHIFT bits are hash C's own, the 16 - HG_CTX_SHIFT bits above them are
+// hash C's next bits plus the low bits of the byte after the window (no carry reaches them from below; the rest of the next
+// dword lands beyond bit 15, where the slot's 16-bit care mask drops it).  A slot word is care << 16 | value as in
+// HgDb::filter; a slot that knows nothing about the byte after its windows cares about the low bits alone.
+// The split, 12 bits of hash C alone + 4 mixed with the byte, from config 3's text (16 MiB, tuned windows; first-level matches
+// per dword / 1 KiB rows with a match; hash C alone: 1.26 % / 85 %): 8 + 8: 0.73 % / 85 %, 10 + 6: 0.42 % / 66 %, 12 + 4:
+// 0.18 % / 36 %, 13 + 3: 0.71 % / 84 %.  Slots without a context byte (a third of them) are left with the low bits only, and
+// log text is no uniform stream of dwords: below 12 bits its common dwords start to collide with them; 3 bits of the byte no
+// longer tell 'l' from 't'.
+#ifndef HG_CTX_SHIFT
+#define HG_CTX_SHIFT 12
+#endif
+constexpr uint32_t HG_CTX_LOW = (1u << HG_CTX_SHIFT) - 1u;   // test value bits that are hash C alone
+constexpr uint32_t HG_CTX_EDGE_KEEP = HG_CTX_LOW * 0x10001u;  // a slot word ANDed with this tests those bits only
+HG_HD uint32_t hg_ctx_value(uint32_t hash_c, uint32_t next_folded) { return hash_c + (next_folded << HG_CTX_SHIFT); }
+// have_next false: the caller cannot see the dword after the window (the last dword of a 1 KiB row in the stream pass).
+HG_HD bool hg_slot_match_ctx(uint32_t ctx_word, uint32_t hash_c, uint32_t next_folded, bool have_next) {
+  return hg_slot_match(have_next ? ctx_word : (ctx_word & HG_CTX_EDGE_KEEP), hg_ctx_value(hash_c, next_folded));
+}
 // Wide-mode slots (large pattern sets): one byte-weighted sum spans too few values for text over a small alphabet
 // (hex digits: ~9000 distinct sums), so each slot mixes the low bits of both sums, sum_x + (sum_y << 8).
 HG_HD uint32_t hg_slot_wide(uint32_t sum_x, uint32_t sum_y, uint32_t byte_mask) { return (sum_x + (sum_y << 8)) & byte_mask; }

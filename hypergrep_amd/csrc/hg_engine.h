@@ -60,8 +60,8 @@ struct HgStreamArgs {
   const uint8_t *text;
   uint64_t nbytes, tile_begin, tile_end;  // the launch covers tiles [tile_begin, tile_end) of the text
   HgDbView db;
-  const uint32_t *filter;  // 1 << filter_log2 window-hash slots
-  const HgSlotInfo *ext;   // per slot: window values + neighbour-dword conditions
+  const uint32_t *filter;  // 1 << filter_log2 window-hash slots (single probe, dword-aligned windows: HgDb::filter_ctx)
+  const HgSlotInfo *ext;   // per slot: window values + neighbour-dword conditions (with filter_ctx: HgDb::filter's words behind them)
   HgTileSum *sums;
   HgCand *cands;         // nsegs x cand_seg_cap: one private segment per stream workgroup
   uint32_t *seg_count;   // candidates in each segment
@@ -69,6 +69,8 @@ struct HgStreamArgs {
   uint32_t weights_a, weights_b;
   uint32_t filter_wide;
   uint32_t dense;  // byte-aligned probing (HgDb::dense)
+  uint32_t ctx;    // the filter holds HgDb::filter_ctx and `ext` has HgDb::filter's 1 << filter_log2 words behind its 1 << filter_log2
+                   // conditions (HgDb::filter_use_ctx): the kernels that test the byte after a window
   uint32_t weights_c;  // hash C weights (HgDb::weights_c)
   uint32_t alone;  // no other kernel runs next to this launch (every workgroup slot is its own)
   uint32_t cursor_slot;  // counters[cursor_slot] = tiles of the chunk handed out so far (hg_stream_kernel draws runs of HG_STREAM_GRAB tiles)

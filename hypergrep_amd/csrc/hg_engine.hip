@@ -164,8 +164,21 @@ int HgScanner::init() {
   HG_TRY(upload(&d_bucket2_, db.bucket_off2, "d_bucket2_"), "upload buckets");
   HG_TRY(upload(&d_windows2_, db.windows2, "d_windows2_"), "upload windows");
   HG_TRY(upload(&d_wtab_, db.wtab, "d_wtab_"), "upload window table");
-  HG_TRY(upload(&d_filter_, db.filter, "d_filter_"), "upload filter");
-  HG_TRY(upload(&d_ext_, db.ext, "d_ext_"), "upload filter conditions");
+  if (db.filter_use_ctx) {
+    // single probe: the stream kernel stages the slots with the context byte in LDS; the slot words of hash C alone follow
+    // the slots' conditions in HBM (drain_batch asks them about the dwords a crowded slot judges by `rest`)
+    // (drain_batch finds HgDb::filter's word of slot s at ext + (1 << filter_log2), word s: both arrays have 1 << filter_log2 entries)
+    if (db.filter_wide || db.dense || db.filter_ctx.size() != (size_t(1) << db.filter_log2) || db.ext.size() != db.filter_ctx.size() || db.filter.size() != db.filter_ctx.size())
+      return error(HG_ERR_ARG, "the database's single-probe filter has no context slots");
+    HG_TRY(upload(&d_filter_, db.filter_ctx, "d_filter_"), "upload filter");
+    std::vector<uint32_t> ext_words(db.ext.size() * (sizeof(HgSlotInfo) / 4) + db.filter.size());
+    std::memcpy(ext_words.data(), db.ext.data(), db.ext.size() * sizeof(HgSlotInfo));
+    std::memcpy(ext_words.data() + db.ext.size() * (sizeof(HgSlotInfo) / 4), db.filter.data(), db.filter.size() * 4);
+    HG_TRY(upload(&d_ext_, ext_words, "d_ext_"), "upload filter conditions");
+  } else {
+    HG_TRY(upload(&d_filter_, db.filter, "d_filter_"), "upload filter");
+    HG_TRY(upload(&d_ext_, db.ext, "d_ext_"), "upload filter conditions");
+  }
   HG_TRY(upload(&d_slow_, db.slow, "d_slow_"), "upload always-on list");
   HG_TRY(upload(&d_groups_, db.groups, "d_groups_"), "upload always-on groups");
   view_.patterns = static_cast<const HgPattern *>(d_patterns_);
@@ -451,6 +464,7 @@ HgScanner::PassPlan HgScanner::plan_pass(const uint8_t *text, uint64_t nbytes, u
   sa.weights_a = db_->weights_a;
   sa.weights_b = db_->weights_b;
   sa.filter_wide = db_->filter_wide;
+  sa.ctx = db_->filter_use_ctx;
   sa.dense = db_->dense;
   sa.weights_c = db_->weights_c;
   sa.ext = static_cast<const HgSlotInfo *>(d_ext_);

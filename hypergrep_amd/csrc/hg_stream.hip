@@ -21,13 +21,26 @@ constexpr int WG_WAVES = HG_STREAM_WG_WAVES;
 constexpr int WG_THREADS = WG_WAVES * 64;
 constexpr int ITERS = HG_TILE_BYTES / 1024;  // 1 KiB per wave-iteration
 
+// Inclusive prefix sum over the wave; `lane` = the caller's lane number.  OWN_LANE: the shuffle is addressed with that number
+// too (a caller that has just worked it out, lane_here below); else __shfl_up, which keeps a lane number of its own.
+template <bool OWN_LANE = false>
 __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lane) {
 #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    uint32_t u = __shfl_up(v, o, 64);
-    if (lane >= static_cast<uint32_t>(o)) v += u;
+  for (uint32_t o = 1; o < 64; o <<= 1) {
+    // (OWN_LANE: lanes below o read some lane's value and drop it)
+    const uint32_t u = OWN_LANE ? static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(static_cast<int>((lane - o) << 2), static_cast<int>(v))) : __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
   }
   return v;
+}
+
+// The lane's number, computed where it is asked for (volatile: not hoisted out of a loop).  The single-probe hot loop has no
+// VGPR to spare for a lane number that only its rare paths want: kept across the loop, it went to scratch
+// (tests/test_stream_resources.py checks the compiled kernels' table for that).
+__device__ __forceinline__ uint32_t lane_here() {
+  uint32_t l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
 }
 
 }  // namespace
@@ -36,7 +49,8 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lan
 // Stream pass.  One wave owns one 16 KiB tile at a time; every workgroup streams its own consecutive range of tiles.
 //
 // Per 16 bytes of text a lane spends: 1 coalesced 16 B load (non-temporal), 4 x (4 ops: exact newline count) and
-// 4 x (fold, 2 x v_dot4_u32_u8, 1 LDS read, 2 SDWA ops) for the window filter — 16 x with byte-aligned probing.  A chunk
+// 4 x (fold, 2 x v_dot4_u32_u8, 1 LDS read, 2 SDWA ops) for the window filter — 16 x with byte-aligned probing; the single-probe
+// filter of dword-aligned windows adds the byte after the window to the test (one v_lshl_add_u32 per dword, hg_db.h).  A chunk
 // whose filter matched is queued in LDS; ranks, second level and the append to the candidate segment run out of line
 // for 64 queued chunks at a time, so the steady state is pure streaming.
 namespace {
@@ -78,8 +92,13 @@ constexpr uint32_t queue_entry_dw(int log2, bool dense) { return queue_stash(log
 __device__ __forceinline__ uint32_t queue_chunk(uint32_t e0) { return e0 >> 16; }
 __device__ __forceinline__ uint32_t queue_rank(uint32_t e0) { return e0 & 0xFFFFu; }
 
-template <int LOG2, bool WIDE>
+static_assert(HG_WINDOW_BYTES == 4, "the single-probe filter's context byte is the low byte of the dword after a 4-byte window");
+// CTX: single probe with the context byte (HgDb::filter_ctx in LDS); false: the test on hash C alone (HgDb::filter), as wide
+// filters and byte-aligned probing always have it
+template <int LOG2, bool WIDE, bool CTX>
 struct Probe {
+  static_assert(!(WIDE && CTX), "wide filters have no context byte");
+  __device__ __forceinline__ static uint32_t value(uint32_t c, uint32_t next) { return CTX ? hg_ctx_value(c, next) : c; }
   static constexpr uint32_t BYTE_MASK = ((1u << LOG2) - 1u) << 2;
   __device__ __forceinline__ static uint32_t at(const lds_u32 *filter, uint32_t byte_off) {
     return *reinterpret_cast<const lds_u32 *>(reinterpret_cast<const __attribute__((address_space(3))) uint8_t *>(filter) + byte_off);
@@ -88,8 +107,11 @@ struct Probe {
   // ANY_ONLY: non-zero iff any of the four windows matched (hot path); else per-window, per-slot match bits.
   // FOLD: the set folds the text before hashing it (case-insensitive literals stored folded); false: nothing is folded (no such
   // literal, or their windows are stored in every case variant): one instruction per dword less in the hot loop
+  // Single probe: the slots are HgDb::filter_ctx, the test value of a window takes in the byte after it (hg_ctx_value) — the
+  // low byte of the lane's next dword, for the lane's last dword that of `right`, the first dword of the chunk to the right.
+  // keep3: HG_CTX_EDGE_KEEP where there is no such chunk in sight (the last lane of a row), else all ones.
   template <bool ANY_ONLY, bool FOLD = true>
-  __device__ __forceinline__ static uint32_t probe4(const lds_u32 *filter, uint32_t fold, uint32_t wa, uint32_t wb, uint4 v) {
+  __device__ __forceinline__ static uint32_t probe4(const lds_u32 *filter, uint32_t fold, uint32_t wa, uint32_t wb, uint4 v, uint32_t right, uint32_t keep3) {
     const uint32_t f0 = FOLD ? v.x | fold : v.x, f1 = FOLD ? v.y | fold : v.y, f2 = FOLD ? v.z | fold : v.z, f3 = FOLD ? v.w | fold : v.w;
     // the hashes of the four windows first (independent v_dot4), then the eight LDS reads
     const uint32_t a0 = hg_dot4(f0, wa), a1 = hg_dot4(f1, wa), a2 = hg_dot4(f2, wa), a3 = hg_dot4(f3, wa);
@@ -105,26 +127,30 @@ struct Probe {
       if (ANY_ONLY) return (m0 || m1 || m2 || m3) ? 1u : 0u;
       return (m0 ? 1u : 0u) | (m1 ? 2u : 0u) | (m2 ? 4u : 0u) | (m3 ? 8u : 0u);
     }
-    // single probe: the window's one slot must agree with hash C on every fingerprint bit the slot cares about
-    const uint32_t t0 = at(filter, a0 & BYTE_MASK), t1 = at(filter, a1 & BYTE_MASK), t2 = at(filter, a2 & BYTE_MASK), t3 = at(filter, a3 & BYTE_MASK);
-    const bool m0 = hg_slot_match(t0, c0), m1 = hg_slot_match(t1, c1), m2 = hg_slot_match(t2, c2), m3 = hg_slot_match(t3, c3);
+    // single probe: the window's one slot must agree with the test value on every bit the slot cares about
+    const uint32_t fr = FOLD ? right | fold : right;
+    const uint32_t t0 = at(filter, a0 & BYTE_MASK), t1 = at(filter, a1 & BYTE_MASK), t2 = at(filter, a2 & BYTE_MASK), t3 = CTX ? at(filter, a3 & BYTE_MASK) & keep3 : at(filter, a3 & BYTE_MASK);
+    const bool m0 = hg_slot_match(t0, value(c0, f1)), m1 = hg_slot_match(t1, value(c1, f2));
+    const bool m2 = hg_slot_match(t2, value(c2, f3)), m3 = hg_slot_match(t3, value(c3, fr));
     if (ANY_ONLY) return (m0 || m1 || m2 || m3) ? 1u : 0u;
     return (m0 ? 1u : 0u) | (m1 ? 2u : 0u) | (m2 ? 4u : 0u) | (m3 ? 8u : 0u);  // bit k: window k matched
   }
   // Hot path: did any of the four windows match?  `mask` gets the wave's ballot of the answer as the OR of the four compare
   // masks (a ballot of the OR'd bool went through a v_cndmask and a v_cmp to get there)
+  // Single probe: `fr` = the folded first dword of the chunk to the right (zero in the row's last lane), keep3 as in probe4.
+  // Per dword one v_lshl_add_u32 more than the test on hash C alone; per iteration the AND of the last slot word with keep3.
   template <bool FOLD>
-  __device__ __forceinline__ static bool any4(const lds_u32 *filter, uint32_t fold, uint32_t wa, uint32_t wb, uint4 v, uint64_t &mask) {
+  __device__ __forceinline__ static bool any4(const lds_u32 *filter, uint32_t fold, uint32_t wa, uint32_t wb, uint4 v, uint32_t fr, uint32_t keep3, uint64_t &mask) {
     if (WIDE) {
-      const bool any = probe4<true, FOLD>(filter, fold, wa, wb, v) != 0;
+      const bool any = probe4<true, FOLD>(filter, fold, wa, wb, v, 0u, 0xFFFFFFFFu) != 0;
       mask = __builtin_amdgcn_ballot_w64(any);
       return any;
     }
     const uint32_t f0 = FOLD ? v.x | fold : v.x, f1 = FOLD ? v.y | fold : v.y, f2 = FOLD ? v.z | fold : v.z, f3 = FOLD ? v.w | fold : v.w;
     const uint32_t a0 = hg_dot4(f0, wa), a1 = hg_dot4(f1, wa), a2 = hg_dot4(f2, wa), a3 = hg_dot4(f3, wa);
-    const uint32_t t0 = at(filter, a0 & BYTE_MASK), t1 = at(filter, a1 & BYTE_MASK), t2 = at(filter, a2 & BYTE_MASK), t3 = at(filter, a3 & BYTE_MASK);
-    const uint32_t c0 = hg_dot4(f0, HG_HASH_WEIGHTS), c1 = hg_dot4(f1, HG_HASH_WEIGHTS);
-    const uint32_t c2 = hg_dot4(f2, HG_HASH_WEIGHTS), c3 = hg_dot4(f3, HG_HASH_WEIGHTS);
+    const uint32_t t0 = at(filter, a0 & BYTE_MASK), t1 = at(filter, a1 & BYTE_MASK), t2 = at(filter, a2 & BYTE_MASK), t3 = CTX ? at(filter, a3 & BYTE_MASK) & keep3 : at(filter, a3 & BYTE_MASK);
+    const uint32_t c0 = value(hg_dot4(f0, HG_HASH_WEIGHTS), f1), c1 = value(hg_dot4(f1, HG_HASH_WEIGHTS), f2);
+    const uint32_t c2 = value(hg_dot4(f2, HG_HASH_WEIGHTS), f3), c3 = value(hg_dot4(f3, HG_HASH_WEIGHTS), fr);
     const bool m0 = hg_slot_match(t0, c0), m1 = hg_slot_match(t1, c1), m2 = hg_slot_match(t2, c2), m3 = hg_slot_match(t3, c3);
     mask = __builtin_amdgcn_ballot_w64(m0) | __builtin_amdgcn_ballot_w64(m1) | __builtin_amdgcn_ballot_w64(m2) | __builtin_amdgcn_ballot_w64(m3);
     return m0 || m1 || m2 || m3;
@@ -149,7 +175,7 @@ struct ProbeBytes {
 #pragma unroll
       for (int k = STEP; k < 4; k += STEP) w[k] = __builtin_amdgcn_alignbyte(d[j + 1], d[j], k);
 #pragma unroll
-      for (int k = 0; k < 4; k += STEP) t[k] = Probe<LOG2, false>::at(filter, hg_dot4(w[k], wa) & BYTE_MASK);
+      for (int k = 0; k < 4; k += STEP) t[k] = Probe<LOG2, false, false>::at(filter, hg_dot4(w[k], wa) & BYTE_MASK);
 #pragma unroll
       for (int k = 0; k < 4; k += STEP) {
         const bool m = hg_slot_match(t[k], hg_dot4(w[k], wc));  // (3-byte windows: both weight vectors end in zero)
@@ -192,7 +218,8 @@ struct StreamCtx {
   const uint4 *text16;
   uint64_t nbytes;
   const lds_u32 *filter;
-  const HgSlotInfo *ext;       // the slots' window values and neighbour conditions (HBM, L2-resident)
+  const HgSlotInfo *ext;       // the slots' window values and neighbour conditions (HBM, L2-resident); single probe: behind them
+                               // the slot words of HgDb::filter (the LDS filter is HgDb::filter_ctx there)
   lds_u32 *queue;              // this wave's queue, one entry per 16-byte chunk whose first level matched: {newlines of the tile before the chunk |
                                // chunk inside the tile << 16, tile, dword left of the chunk, dword right of it, the chunk} — the drain never re-reads the text
   lds_u32 *cand_count;         // the workgroup's candidate counter
@@ -241,8 +268,9 @@ __device__ __forceinline__ uint32_t dense_window(uint4 cur, uint32_t nxt, uint32
 // ago), repeats the first level per window, applies the second level (the slot's neighbour conditions) and appends the
 // survivors to the workgroup's candidate segment.  The queue outlives tiles, so batches are full (64 entries) except the
 // last one of the kernel.
-template <int LOG2, bool WIDE, int DENSE>  // DENSE: 0 dword-aligned windows, else the byte step of byte-aligned probing
-__device__ __noinline__ void drain_batch(const StreamCtx cx, uint32_t first, uint32_t n, uint32_t lane) {
+template <int LOG2, bool WIDE, int DENSE, bool CTX>  // DENSE: 0 dword-aligned windows, else the byte step of byte-aligned probing
+__device__ __noinline__ void drain_batch(const StreamCtx cx, uint32_t first, uint32_t n) {
+  const uint32_t lane = lane_here();
   const bool active = lane < n;
   uint32_t hits = 0, rank = 0;
   uint64_t g = 0;
@@ -333,7 +361,8 @@ __device__ __noinline__ void drain_batch(const StreamCtx cx, uint32_t first, uin
         have_left = have_right = true;
       }
     }
-    uint32_t l1 = Probe<LOG2, WIDE>::template probe4<false>(cx.filter, cx.fold, cx.wa, cx.wb, cur);
+    // (the context byte of the chunk's last window: skipped where the second level below skips its condition on that side)
+    uint32_t l1 = Probe<LOG2, WIDE, CTX>::template probe4<false>(cx.filter, cx.fold, cx.wa, cx.wb, cur, right, have_right ? 0xFFFFFFFFu : HG_CTX_EDGE_KEEP);
     // only windows that start inside the text (see stream_tile: chunks past the end are not queued at all)
     if ((g << 4) + 16 > cx.nbytes) l1 &= (g << 4) < cx.nbytes ? (1u << static_cast<uint32_t>((cx.nbytes - (g << 4) + 3) >> 2)) - 1u : 0u;
     if (WIDE) {
@@ -350,7 +379,16 @@ __device__ __noinline__ void drain_batch(const StreamCtx cx, uint32_t first, uin
         const uint32_t wn = k == 0 ? cur.y : (k == 1 ? cur.z : (k == 2 ? cur.w : right));
         const uint32_t f = wk | cx.fold;
         // read from HBM / L2: rare, and keeping the table out of LDS leaves room for more resident waves
-        const HgSlotInfo info = cx.ext[(hg_dot4(f, cx.wa) & BYTE_MASK) >> 2];
+        const uint32_t sl = (hg_dot4(f, cx.wa) & BYTE_MASK) >> 2;
+        const HgSlotInfo info = cx.ext[sl];
+        // A crowded slot judges a dword that is none of its two exact values by `rest`, whatever the dword is: such a dword
+        // must also agree with the slot's fingerprint of hash C alone (HgDb::filter, in HBM behind the conditions), of
+        // which the context filter keeps only the low bits.  (An exact value agrees with it by construction.)
+        if (CTX && info.many && !(info.nvalues > 0 && info.value[0] == f) && !(info.nvalues > 1 && info.value[1] == f)) {
+          // (hg_engine.hip init(): with the context slots in LDS the 1 << LOG2 conditions and the 1 << LOG2 words of HgDb::filter are ONE array)
+          const uint32_t *plain = reinterpret_cast<const uint32_t *>(cx.ext + (1u << LOG2));
+          if (!hg_slot_match(plain[sl], hg_hash_window(f))) continue;
+        }
         const uint32_t pm_keep = (k == 0 && !have_left) ? 0u : 0xFFFFFFFFu;
         const uint32_t nm_keep = (k == 3 && !have_right) ? (HG_WINDOW_BYTES == 4 ? 0u : 0xFFu) : 0xFFFFFFFFu;
         const uint32_t prev = wp | cx.fold;
@@ -385,31 +423,39 @@ __device__ __noinline__ void drain_batch(const StreamCtx cx, uint32_t first, uin
 
 // One tile.  FULL: the tile lies entirely inside the text (no bounds checks on the hot path).
 // qn: entries in the wave's queue (wave-uniform, carried from tile to tile).
-template <int LOG2, bool WIDE, int DENSE, bool FULL, int DEPTH, bool FOLD>
+template <int LOG2, bool WIDE, int DENSE, bool FULL, int DEPTH, bool FOLD, bool CTX>
 __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, HgTileSum *__restrict__ sums, uint32_t lane, uint32_t &qn) {
   const uint4 *__restrict__ text16 = cx.text16;
   const uint64_t nbytes = cx.nbytes;
-  const uint64_t chunk0 = tile * (HG_TILE_BYTES / 16) + lane;
+  // Single probe: the hot loop keeps ONE VGPR of the lane's place, lane_off; what its rare paths want of the lane (a chunk
+  // number for a checked load, the prefix scan of a row with several newlines per chunk) they work out where they stand.
+  constexpr bool LANE_KEPT = WIDE || DENSE != 0;
+  const uint32_t lane_tile = (!LANE_KEPT && !FULL) ? lane_here() : 0u;
+  auto lane_cold = [&]() -> uint32_t {
+    if constexpr (LANE_KEPT) return lane;
+    else if constexpr (!FULL) return lane_tile;  // (the partial tile's loop is rolled: a VGPR to spare, one lane number per tile)
+    else return lane_here();
+  };
+  auto chunk_at = [&](int it) -> uint64_t { return tile * (HG_TILE_BYTES / 16) + static_cast<uint64_t>(it) * 64u + lane_cold(); };
 
   // The full tiles' loads: a buffer resource for the tile (scalar), the row's offset as a scalar and the lane's as a 32-bit
   // VGPR.  (Global loads from a 64-bit per-lane address cost two VALU ops per row for the address.)
   const __amdgpu_buffer_rsrc_t tile_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(text16 + tile * (HG_TILE_BYTES / 16)), 0, HG_TILE_BYTES, 0x00020000);
   const uint32_t lane_off = lane * 16u;
   auto load_chunk = [&](int it) -> uint4 {
-    const uint64_t g = chunk0 + static_cast<uint64_t>(it) * 64u;
     if (FULL) {
       // streaming (non-temporal) cache policy: the text is read once and must not push the filter's second level, the
       // tile summaries and the side passes' working set out of the L2 (measured: 5.0 -> 5.4 TB/s in the pipeline).
       // Not for wide filters: their drain reads every queued chunk AGAIN a few microseconds later (no room in LDS to carry
       // it in the queue), and with the default policy most of those reads hit the L2 (config 5: 14.98 -> 14.65 ms per 32 GiB)
-      if (WIDE) return text16[g];
+      if (WIDE) return text16[chunk_at(it)];
       if (DENSE) {  // (byte-aligned probing: a VGPR more for the buffer offset pushed it past its spill budget)
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(text16) + g);
+        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(text16) + chunk_at(it));
         return make_uint4(v.x, v.y, v.z, v.w);
       }
 #if defined(HG_NO_NT_LOADS)
-      return text16[g];
+      return text16[chunk_at(it)];
 #else
       // (a buffer load: the tile's resource and the row offset are scalars, the lane's byte offset a 32-bit VGPR; aux 2 = nt)
       typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -417,7 +463,7 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
       return make_uint4(v.x, v.y, v.z, v.w);
 #endif
     }
-    return load_chunk_checked(text16, nbytes, g);
+    return load_chunk_checked(text16, nbytes, chunk_at(it));
   };
 
   uint32_t seen = 0;  // wave-uniform: newlines of the tile in the iterations done so far
@@ -428,12 +474,13 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
   uint32_t first_nl = HG_NONE32, last_nl = HG_NONE32;
   uint32_t first_it = 0, last_it = 0;
   uint64_t first_nlm = 0, last_nlm = 0;
-  const uint32_t lane_key = lane << 16;  // the lane's part of a queue entry's first dword (queue_chunk / queue_rank)
+  // single probe: the row's last lane has no chunk to its right, its last window passes on hash C's own bits (hg_db.h)
+  const uint32_t keep3 = lane_off == 63u * 16u ? HG_CTX_EDGE_KEEP : 0xFFFFFFFFu;
 
   // byte-aligned probing: the dword after the lane's chunk is the next lane's first; the row's last lane reads it
   auto load_after = [&](int it) -> uint32_t {
     if (!DENSE || lane != 63u) return 0u;
-    return load_dword_checked(text16, nbytes, (chunk0 + static_cast<uint64_t>(it) * 64u + 1u) << 4);
+    return load_dword_checked(text16, nbytes, (chunk_at(it) + 1u) << 4);
   };
 
   auto body = [&](int it, uint4 cur, uint32_t after) {
@@ -450,6 +497,12 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
     const bool has_nl = notnl != 128u, several_nl = notnl < 127u;  // (on notnl itself: no v_sub for c on the common path)
 #endif
 
+    uint32_t right = 0;  // the first dword of the chunk to the right, zero in the row's last lane
+#if defined(HG_ABLATE) && HG_ABLATE == 1
+    constexpr bool HAVE_RIGHT = false;
+#else
+    constexpr bool HAVE_RIGHT = CTX;  // the context test has fetched it before the queue block
+#endif
 #if defined(HG_ABLATE) && HG_ABLATE == 1  // profiling aid: no window filter (results are wrong)
     bool any = (cur.x ^ cur.y ^ cur.z ^ cur.w) == 0x12345678u;
     uint64_t am = __builtin_amdgcn_ballot_w64(any);
@@ -461,7 +514,12 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
       any = ProbeBytes<LOG2, DENSE ? DENSE : 1>::template probe16<true>(cx.filter, cx.fold, cx.wa, cx.wb, cur, nxt) != 0;
       am = __builtin_amdgcn_ballot_w64(any);
     } else {
-      any = Probe<LOG2, WIDE>::template any4<FOLD>(cx.filter, cx.fold, cx.wa, cx.wb, cur, am);
+      // single probe: the byte after the lane's last window is the first of the chunk to the right (a DPP wave shift with
+      // bound_ctrl: the row's last lane reads 0, and keep3 takes the context bits out of its test).  The partial last tile
+      // needs nothing of its own: bytes past the text are zero here as in the second level, and a window whose literal
+      // goes on past the end of the text holds no occurrence.
+      if constexpr (CTX) right = __builtin_amdgcn_mov_dpp(FOLD ? cur.x | cx.fold : cur.x, 0x130 /* wave_shl:1 */, 0xF, 0xF, true);
+      any = Probe<LOG2, WIDE, CTX>::template any4<FOLD>(cx.filter, cx.fold, cx.wa, cx.wb, cur, right, keep3, am);
     }
 #endif
 
@@ -470,7 +528,7 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
     // and must not reach the drain, whose neighbour reads assume a position inside the text.  (Round 1 shipped without
     // this: the drain read up to a tile past the buffer, a GPU memory fault whenever that memory was not mapped.)
     if constexpr (!FULL) {
-      any = any && ((chunk0 + static_cast<uint64_t>(it) * 64u) << 4) < nbytes;
+      any = any && (chunk_at(it) << 4) < nbytes;
       am = __builtin_amdgcn_ballot_w64(any);
     }
 
@@ -498,21 +556,23 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
     // newlines of the tile before this lane's chunk, is only needed by lanes that queue their chunk)
     // The queue entry's first dword (queue_chunk / queue_rank) is built on `key` = (iteration * 64 + lane) << 16 + seen: the
     // lanes of the newline ballot below this one are added by the mbcnt pair's accumulator.
-    const uint32_t key = lane_key + opaque_sgpr(seen + (static_cast<uint32_t>(it) << 22));
+    // (the lane's part, lane << 16, from lane_off: one v_lshl_add_u32 as the v_add_u32 was)
+    const uint32_t key = (lane_off << 12) + opaque_sgpr(seen + (static_cast<uint32_t>(it) << 22));
     uint32_t total, e0 = 0;
     if (__builtin_expect(multi == 0, 1)) {
       total = __popcll(nlm);
       e0 = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(nlm >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(nlm), key));
     } else {
-      const uint32_t incl = wave_inclusive_scan(c, lane);
+      const uint32_t incl = wave_inclusive_scan<!LANE_KEPT>(c, lane_cold());
       total = __builtin_amdgcn_readlane(incl, 63);
       e0 = key + incl - c;
     }
     if (am) {  // remember the chunks; their windows are examined in batches of 64 (drain_batch)
       // the dwords next to the chunk, from the adjacent lanes (DPP wave shifts with bound_ctrl: the row's edge lanes read
       // 0 and skip that condition; no v_mov for an old value)
+      // (with the context byte `right` is there already, folded; the drain folds what it compares anyway)
       const uint32_t left = __builtin_amdgcn_mov_dpp(cur.w, 0x138 /* wave_shr:1 */, 0xF, 0xF, true);
-      const uint32_t right = __builtin_amdgcn_mov_dpp(cur.x, 0x130 /* wave_shl:1 */, 0xF, 0xF, true);
+      if constexpr (!HAVE_RIGHT) right = __builtin_amdgcn_mov_dpp(cur.x, 0x130 /* wave_shl:1 */, 0xF, 0xF, true);
       if (any) {
         const uint32_t idx = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(am >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(am), 0u));
         lds_u32 *e = (cx.queue + qn * queue_entry_dw(LOG2, DENSE)) + idx * queue_entry_dw(LOG2, DENSE);
@@ -531,7 +591,7 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
       if (qn >= queue_cap(LOG2) - 64u) {
         const uint32_t n = qn < 64u ? qn : 64u;
         qn -= n;
-        drain_batch<LOG2, WIDE, DENSE>(cx, qn, n, lane);
+        drain_batch<LOG2, WIDE, DENSE, CTX>(cx, qn, n);
       }
     }
     seen += total;
@@ -568,7 +628,7 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
     const uint4 v = load_chunk_checked(text16, nbytes, tile * (HG_TILE_BYTES / 16) + last_it * 64u + l);
     last_nl = last_it * 1024u + l * 16u + (31 - __clz(newline_bits16(v)));
   }
-  if (lane == 0) sums[tile] = HgTileSum{nl_count, first_nl, last_nl, nl_count ? nl_count - 1 : 0};
+  if (lane_off == 0) sums[tile] = HgTileSum{nl_count, first_nl, last_nl, nl_count ? nl_count - 1 : 0};
 }
 
 }  // namespace
@@ -587,7 +647,7 @@ __device__ __forceinline__ void stream_tile(const StreamCtx &cx, uint64_t tile, 
 // that had three workgroups per CU to itself did better with one: deeper prefetch thrashed the L2).
 // JOIN: the launch that joins a chunk behind the previous chunk's side passes (hg_stream_join_kernel, same code under its
 // own name so that profiles keep the two kinds of launch apart); it also counts the tiles it took (HG_CNT_JOIN_TILES).
-template <int LOG2, bool WIDE, int DENSE, int DEPTH, bool JOIN, bool FOLD>
+template <int LOG2, bool WIDE, int DENSE, int DEPTH, bool JOIN, bool FOLD, bool CTX>
 __device__ __forceinline__ void stream_body(const uint4 *__restrict__ text16, uint64_t nbytes, uint64_t tile_begin, uint64_t tile_end, const uint4 *__restrict__ filter16,
                                             const uint4 *__restrict__ ext16, uint32_t fold, uint32_t wa, uint32_t wb, HgTileSum *__restrict__ sums, HgCand *__restrict__ cands,
                                             uint32_t seg_cap, uint32_t *__restrict__ seg_count, uint32_t *__restrict__ counters, uint32_t cursor_slot) {
@@ -634,11 +694,11 @@ __device__ __forceinline__ void stream_body(const uint4 *__restrict__ text16, ui
     const uint32_t r1 = r0 + HG_STREAM_GRAB < ntile ? r0 + HG_STREAM_GRAB : ntile;
     if (JOIN) joined += r1 - r0;
     for (uint32_t r = r0 + wave; r < r1; r += WG_WAVES) {
-      if (r < nfull) stream_tile<LOG2, WIDE, DENSE, true, DEPTH, FOLD>(cx, tile_begin + r, sums, lane, qn);
-      else stream_tile<LOG2, WIDE, DENSE, false, DEPTH, FOLD>(cx, tile_begin + r, sums, lane, qn);
+      if (r < nfull) stream_tile<LOG2, WIDE, DENSE, true, DEPTH, FOLD, CTX>(cx, tile_begin + r, sums, lane, qn);
+      else stream_tile<LOG2, WIDE, DENSE, false, DEPTH, FOLD, CTX>(cx, tile_begin + r, sums, lane, qn);
     }
   }
-  if (qn) drain_batch<LOG2, WIDE, DENSE>(cx, 0u, qn, lane);
+  if (qn) drain_batch<LOG2, WIDE, DENSE, CTX>(cx, 0u, qn);
   __syncthreads();
   if (threadIdx.x == 0) {
     const uint32_t n = *cx.cand_count;
@@ -656,7 +716,7 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(HG_S
 #ifdef HG_STREAM_PRIO  // (experiment builds: a higher wave priority next to the side kernels changed nothing, profiles/r03_experiments.txt)
   __builtin_amdgcn_s_setprio(HG_STREAM_PRIO);
 #endif
-  stream_body<LOG2, WIDE, DENSE, DEPTH, false, FOLD>(text16, nbytes, tile_begin, tile_end, filter16, ext16, fold, wa, wb, sums, cands, seg_cap, seg_count, counters, cursor_slot);
+  stream_body<LOG2, WIDE, DENSE, DEPTH, false, FOLD, !WIDE && DENSE == 0>(text16, nbytes, tile_begin, tile_end, filter16, ext16, fold, wa, wb, sums, cands, seg_cap, seg_count, counters, cursor_slot);
 }
 template <int LOG2, int DENSE, bool FOLD = true>  // (only where three workgroups fit on a CU: filters of up to 32 KiB, single-probe mode)
 __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(HG_STREAM_WAVES, 8))) void hg_stream_join_kernel(
@@ -666,7 +726,23 @@ __global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(HG_S
 #ifdef HG_STREAM_PRIO
   __builtin_amdgcn_s_setprio(HG_STREAM_PRIO);
 #endif
-  stream_body<LOG2, false, DENSE, HG_DEPTH_SHARED, true, FOLD>(text16, nbytes, tile_begin, tile_end, filter16, ext16, fold, wa, wb, sums, cands, seg_cap, seg_count, counters, cursor_slot);
+  stream_body<LOG2, false, DENSE, HG_DEPTH_SHARED, true, FOLD, DENSE == 0>(text16, nbytes, tile_begin, tile_end, filter16, ext16, fold, wa, wb, sums, cands, seg_cap, seg_count, counters, cursor_slot);
+}
+// The dword-aligned single-probe kernels WITHOUT the context byte (HgDb::filter_use_ctx == 0: a text sample said that the
+// byte spares too few iterations to pay for its instructions, hg_compile.cpp hgc_tune): the first level on hash C alone.
+template <int LOG2, int DEPTH, bool FOLD>
+__global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(HG_STREAM_WAVES, 8))) void hg_stream_plain_kernel(
+    const uint4 *__restrict__ text16, uint64_t nbytes, uint64_t tile_begin, uint64_t tile_end, const uint4 *__restrict__ filter16, const uint4 *__restrict__ ext16, uint32_t fold,
+    uint32_t wa, uint32_t wb, HgTileSum *__restrict__ sums, HgCand *__restrict__ cands, uint32_t seg_cap, uint32_t *__restrict__ seg_count, uint32_t *__restrict__ counters,
+    uint32_t cursor_slot) {
+  stream_body<LOG2, false, 0, DEPTH, false, FOLD, false>(text16, nbytes, tile_begin, tile_end, filter16, ext16, fold, wa, wb, sums, cands, seg_cap, seg_count, counters, cursor_slot);
+}
+template <int LOG2, bool FOLD>
+__global__ __launch_bounds__(WG_THREADS) __attribute__((amdgpu_waves_per_eu(HG_STREAM_WAVES, 8))) void hg_stream_plain_join_kernel(
+    const uint4 *__restrict__ text16, uint64_t nbytes, uint64_t tile_begin, uint64_t tile_end, const uint4 *__restrict__ filter16, const uint4 *__restrict__ ext16, uint32_t fold,
+    uint32_t wa, uint32_t wb, HgTileSum *__restrict__ sums, HgCand *__restrict__ cands, uint32_t seg_cap, uint32_t *__restrict__ seg_count, uint32_t *__restrict__ counters,
+    uint32_t cursor_slot) {
+  stream_body<LOG2, false, 0, HG_DEPTH_SHARED, true, FOLD, false>(text16, nbytes, tile_begin, tile_end, filter16, ext16, fold, wa, wb, sums, cands, seg_cap, seg_count, counters, cursor_slot);
 }
 
 // Host-side launcher: picks the instantiation for the database's filter size / mode.
@@ -676,6 +752,17 @@ void launch_depth(const HgStreamArgs &a, uint32_t grid, hipStream_t stream) {
   const uint4 *t = reinterpret_cast<const uint4 *>(a.text);
   const uint4 *f = reinterpret_cast<const uint4 *>(a.filter);
   const uint4 *x = reinterpret_cast<const uint4 *>(a.ext);
+  if constexpr (!W && !B) {
+    if (!a.ctx) {  // (the filter in LDS is HgDb::filter)
+      if (a.db.fold_mask == 0)
+        hipLaunchKernelGGL((hg_stream_plain_kernel<L, D, false>), dim3(grid), dim3(WG_THREADS), 0, stream, t, a.nbytes, a.tile_begin, a.tile_end, f, x, a.db.fold_mask,
+                           a.weights_a, a.weights_b, a.sums, a.cands, a.cand_seg_cap, a.seg_count, a.counters, a.cursor_slot);
+      else
+        hipLaunchKernelGGL((hg_stream_plain_kernel<L, D, true>), dim3(grid), dim3(WG_THREADS), 0, stream, t, a.nbytes, a.tile_begin, a.tile_end, f, x, a.db.fold_mask,
+                           a.weights_a, a.weights_b, a.sums, a.cands, a.cand_seg_cap, a.seg_count, a.counters, a.cursor_slot);
+      return;
+    }
+  }
   // (dword-aligned single-probe filters of sets that fold nothing: the variant without the fold instruction)
   if constexpr (!W && !B) {
     if (a.db.fold_mask == 0) {
@@ -704,6 +791,18 @@ int blocks_one() {
 namespace {
 template <int L, int B>
 void launch_join(const HgStreamArgs &a, uint32_t grid, hipStream_t stream) {
+  if constexpr (B == 0) {
+    if (!a.ctx) {
+      const uint4 *t = reinterpret_cast<const uint4 *>(a.text), *f = reinterpret_cast<const uint4 *>(a.filter), *x = reinterpret_cast<const uint4 *>(a.ext);
+      if (a.db.fold_mask == 0)
+        hipLaunchKernelGGL((hg_stream_plain_join_kernel<L, false>), dim3(grid), dim3(WG_THREADS), 0, stream, t, a.nbytes, a.tile_begin, a.tile_end, f, x, a.db.fold_mask,
+                           a.weights_a, a.weights_b, a.sums, a.cands, a.cand_seg_cap, a.seg_count, a.counters, a.cursor_slot);
+      else
+        hipLaunchKernelGGL((hg_stream_plain_join_kernel<L, true>), dim3(grid), dim3(WG_THREADS), 0, stream, t, a.nbytes, a.tile_begin, a.tile_end, f, x, a.db.fold_mask,
+                           a.weights_a, a.weights_b, a.sums, a.cands, a.cand_seg_cap, a.seg_count, a.counters, a.cursor_slot);
+      return;
+    }
+  }
   if constexpr (B == 0) {
     if (a.db.fold_mask == 0) {
       hipLaunchKernelGGL((hg_stream_join_kernel<L, B, false>), dim3(grid), dim3(WG_THREADS), 0, stream, reinterpret_cast<const uint4 *>(a.text), a.nbytes, a.tile_begin, a.tile_end,

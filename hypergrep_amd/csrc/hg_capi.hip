@@ -20,8 +20,10 @@ struct hg_scanner {
   HgScanner *sc;
   hg_scan_result_t last;
   const uint32_t *d_from;  // the last scan's hit starts (SOM databases), else nullptr: every start is 0
+  hg_context_result_t last_ctx;  // the last scan's context records (hg_scan_device_context), else zeroes
 };
 
+static_assert(HG_ID_CONTEXT == HG_CTX_ID_CONTEXT && HG_ID_CONTEXT_TAIL == HG_CTX_ID_TAIL, "the context records carry the ids the header names");
 static_assert(sizeof(hg_hit_t) == sizeof(HgHit) && sizeof(hg_hit_aux_t) == sizeof(HgHitAux), "ABI records mirror the device records");
 
 static void put_err(char *err, size_t errlen, const std::string &msg) {
@@ -89,7 +91,7 @@ int hg_scanner_create(const hg_database_t *db, int device, hg_scanner_t **scanne
     put_err(err, errlen, msg);
     return rc;
   }
-  *scanner = new hg_scanner{sc, {}, nullptr};
+  *scanner = new hg_scanner{sc, {}, nullptr, {}};
   return HG_OK;
 }
 
@@ -102,11 +104,21 @@ void hg_scanner_destroy(hg_scanner_t *scanner) {
 const char *hg_scanner_error(const hg_scanner_t *scanner) { return scanner ? scanner->sc->last_error().c_str() : "null scanner"; }
 
 static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, void *stream,
-                       hg_scan_result_t *result, bool invert) {
+                       hg_scan_result_t *result, bool invert, const hg_context_t *context = nullptr, hg_context_result_t *context_result = nullptr) {
   if (!scanner || !result) return HG_ERR_ARG;
   HgScanOutput o{};
-  int rc = scanner->sc->scan(d_text, nbytes, buffer_size, line_base, static_cast<hipStream_t>(stream), &o, invert);
+  HgContextOutput c{};
+  int rc;
+  if (context) {
+    const HgContextParams params{context->before, context->after, context->carry_after, (context->flags & HG_CONTEXT_TAIL) != 0};
+    rc = scanner->sc->scan_context(d_text, nbytes, buffer_size, line_base, static_cast<hipStream_t>(stream), params, invert, &o, &c);
+  } else {
+    rc = scanner->sc->scan(d_text, nbytes, buffer_size, line_base, static_cast<hipStream_t>(stream), &o, invert);
+  }
   if (rc != HG_OK) return rc;
+  scanner->last_ctx = hg_context_result_t{c.n_context, c.n_tail, c.owed_after, reinterpret_cast<const hg_hit_t *>(c.d_hits), reinterpret_cast<const hg_hit_aux_t *>(c.d_aux),
+                                          static_cast<uint32_t>(c.ms_context * 1000.0f + 0.5f), 0};
+  if (context_result) *context_result = scanner->last_ctx;
   result->n_hits = o.n_hits;
   result->n_lines = o.n_pieces;
   result->n_candidates = o.n_cands;
@@ -133,6 +145,32 @@ int hg_scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, i
 int hg_scan_device_invert(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, void *stream,
                           hg_scan_result_t *result) {
   return scan_device(scanner, d_text, nbytes, buffer_size, line_base, stream, result, true);
+}
+
+int hg_scan_device_context(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, void *stream,
+                           const hg_context_t *context, int invert, hg_scan_result_t *result, hg_context_result_t *context_result) {
+  if (!context || !context_result || (context->flags & ~HG_CONTEXT_TAIL)) return HG_ERR_ARG;
+  return scan_device(scanner, d_text, nbytes, buffer_size, line_base, stream, result, invert != 0, context, context_result);
+}
+
+int hg_copy_context(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max) {
+  if (!scanner || !hits) return HG_ERR_ARG;
+  uint64_t n = scanner->last_ctx.n_context < max ? scanner->last_ctx.n_context : max;
+  if (!n) return HG_OK;
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  if (hipMemcpy(hits, scanner->last_ctx.d_ctx_hits, n * sizeof(hg_hit_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (aux && hipMemcpy(aux, scanner->last_ctx.d_ctx_aux, n * sizeof(hg_hit_aux_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
+}
+
+int hg_copy_context_device(hg_scanner_t *scanner, void *d_dst, uint64_t max, void *stream) {
+  if (!scanner || !d_dst) return HG_ERR_ARG;
+  uint64_t n = scanner->last_ctx.n_context < max ? scanner->last_ctx.n_context : max;
+  if (!n) return HG_OK;
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  if (hipMemcpyAsync(d_dst, scanner->last_ctx.d_ctx_hits, n * sizeof(hg_hit_t), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)) != hipSuccess)
+    return HG_ERR_HIP;
+  return HG_OK;
 }
 
 int hg_copy_hits(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max) {

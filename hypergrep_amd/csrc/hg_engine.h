@@ -9,6 +9,7 @@
 #include "hg_compile.h"
 #include "hg_core.h"
 #include "hg_invert.h"
+#include "hg_context.h"
 #include "hg_post.h"
 
 // Waves per stream workgroup (one 16 KiB tile per wave at a time); shared by the kernel and the grid sizing.
@@ -175,6 +176,24 @@ hipError_t hg_comb_launch(const HgCombArgs &a, bool emit, hipStream_t stream);
 // pass, on `stream`, in a grid sized for num_cus compute units.
 hipError_t hg_invert_launch(const HgInvertArgs &a, bool write, uint32_t num_cus, hipStream_t stream);
 
+// The context stage (hg_context.hip), launched like the invert stage.
+hipError_t hg_context_launch(const HgContextArgs &a, bool write, uint32_t num_cus, hipStream_t stream);
+// What a call asks of it (hg_context_t of the C ABI) and what it leaves (hg_context_result_t).
+struct HgContextParams {
+  uint32_t before, after;
+  uint64_t carry_after;  // after-context the previous buffer still owes, in pieces
+  bool tail;             // also deliver the last `before` pieces that are neither match nor context, as tail records
+  bool any() const { return before || after || carry_after || tail; }
+};
+struct HgContextOutput {
+  uint64_t n_context;  // context and tail records, ordered by line
+  uint64_t n_tail;     // the tail records among them
+  uint64_t owed_after; // after-context owed past the buffer's end (hg_context_owed)
+  const HgHit *d_hits; // device arrays, valid until the next scan on this scanner
+  const HgHitAux *d_aux;
+  float ms_context;    // the stage: count, scan, the host sync that sizes the output, write
+};
+
 // Test / experiment knobs of the engine, read from the environment ONCE, when a scanner is created (never during a scan:
 // getenv is not safe against a concurrent setenv, and a scan must not change behaviour half-way).  None is needed in normal
 // use.  The limit-lowering ones exist so that tests reach segmented scans / chunk halving on small texts.
@@ -205,6 +224,9 @@ class HgScanner {
   // d_text: device pointer, 16-byte aligned, readable up to nbytes rounded up to 16.
   // invert: the result is the pieces WITHOUT a delivered report (hg_scan_device_invert), one record each.
   int scan(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, hipStream_t stream, HgScanOutput *out, bool invert = false);
+  // The same scan (inverted or not) with the context stage behind it: *out is exactly scan()'s, *ctx the pieces around its records.
+  int scan_context(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, hipStream_t stream, const HgContextParams &params, bool invert,
+                   HgScanOutput *out, HgContextOutput *ctx);
   // Block mode (hs_scan): the whole buffer is one scan unit; hits carry line_no 0 and `to` relative to the buffer start.
   int scan_block(const void *d_text, uint64_t nbytes, hipStream_t stream, HgScanOutput *out);
   // Block mode for short blocks held in PINNED host memory (readable up to nbytes rounded up to 16): one launch, raw
@@ -247,6 +269,8 @@ class HgScanner {
   int comb_pass(HgScanOutput *out, uint64_t bs1, uint64_t line_bound, hipStream_t stream);
   int minlen_pass(const uint8_t *text, uint32_t *n, hipStream_t stream);
   int invert_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, hipStream_t stream, HgScanOutput *out);
+  int context_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const HgContextParams &params, hipStream_t stream, const HgScanOutput &out,
+                   HgContextOutput *ctx);
   int huge_lds_error() { return error(HG_ERR_HIP, "the huge-automaton kernel cannot have its LDS"); }
   bool fail(hipError_t e, const char *what);
   int error(int rc, const std::string &what) { err_ = what; return rc; }
@@ -338,6 +362,15 @@ class HgScanner {
   HgHit *d_inv_hits_ = nullptr;
   HgHitAux *d_inv_aux_ = nullptr;
   uint64_t inv_cap_ = 0;
+  // context stage (calls with context only, allocated by the first one): as the invert stage's; d_ctx_count_ has one word more,
+  // the number of tail records
+  uint64_t *d_ctx_count_ = nullptr, *d_ctx_pos_ = nullptr;
+  uint64_t ctx_tiles_cap_ = 0;
+  uint8_t *d_ctx_temp_ = nullptr;
+  size_t ctx_temp_bytes_ = 0;
+  HgHit *d_ctx_hits_ = nullptr;
+  HgHitAux *d_ctx_aux_ = nullptr;
+  uint64_t ctx_cap_ = 0;
   uint32_t *d_seg_count2_ = nullptr;  // second set for double buffering
   HgCand *d_cands2_ = nullptr;
 };

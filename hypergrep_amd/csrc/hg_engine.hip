@@ -241,7 +241,8 @@ HgScanner::~HgScanner() {
                   d_agg_, d_cands_, d_hits_raw_, d_hits_out_, d_aux_raw_, d_aux_out_,
                   d_key_a_, d_key_b_, d_perm_a_, d_perm_b_, d_keep_, d_counters_, d_temp_, d_seg_count_, d_pflags_, d_deferred_, d_defer_count_, d_seg_count2_, d_cands2_, d_disc_, d_bucket2_, d_windows2_, d_groups_, d_acc_hits_, d_acc_aux_, d_huge_claim_, d_wtab_, d_from_, d_fin_fill_, d_fin_kept_, d_fin_big_,
                   d_combs_, d_comb_words_, d_comb_feed_, d_comb_count_, d_comb_pos_, d_comb_hits_, d_comb_aux_, d_comb_temp_, d_bounds_,
-                  d_min_lengths_, d_minlen_hits_, d_minlen_aux_, d_inv_count_, d_inv_pos_, d_inv_temp_, d_inv_hits_, d_inv_aux_};
+                  d_min_lengths_, d_minlen_hits_, d_minlen_aux_, d_inv_count_, d_inv_pos_, d_inv_temp_, d_inv_hits_, d_inv_aux_,
+                  d_ctx_count_, d_ctx_pos_, d_ctx_temp_, d_ctx_hits_, d_ctx_aux_};
   for (void *p : ptrs) hgmem::dev_free(p, "scanner");
   hgmem::host_free(h_counters_, "h_counters_");
   for (auto &ev : ev_)
@@ -930,6 +931,74 @@ int HgScanner::invert_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, u
   out->d_hits = d_inv_hits_;
   out->d_aux = d_inv_aux_;
   return HG_OK;
+}
+
+// The context stage over a finished call (`out`: its final records, ordered by line, and its piece count; untouched): the
+// count pass over the scan's tile states and the records' lines, an exclusive scan of the per-tile counts, and the write pass
+// (hg_context.hip).  For an inverted call the records are the selected pieces, so their context is matching pieces.  Like
+// the invert stage it runs once over the whole buffer, however many segments or pipeline chunks the scan took.
+int HgScanner::context_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const HgContextParams &params, hipStream_t stream,
+                            const HgScanOutput &out, HgContextOutput *ctx) {
+  const uint64_t ntiles = (nbytes + HG_TILE_BYTES - 1) / HG_TILE_BYTES;
+  ctx->owed_after = hg_context_owed(0, 0, line_base, out.n_pieces, params.after, params.carry_after);
+  if (ntiles == 0) return HG_OK;
+  if (ntiles + 2 > ctx_tiles_cap_) {
+    const uint64_t cap = std::max<uint64_t>(ntiles + ntiles / 4 + 2, 4096);
+    ctx_tiles_cap_ = 0;
+    HG_TRY(realloc_dev(d_ctx_count_, cap, "d_ctx_count_"), "alloc (context stage)");
+    HG_TRY(realloc_dev(d_ctx_pos_, cap, "d_ctx_pos_"), "alloc (context stage)");
+    ctx_tiles_cap_ = cap;
+  }
+  size_t tb = 0;  // the scan's scratch, asked for the size that is scanned
+  HG_TRY(rocprim::exclusive_scan(nullptr, tb, d_ctx_count_, d_ctx_pos_, uint64_t{0}, ntiles + 1, rocprim::plus<uint64_t>(), stream), "scan (context stage)");
+  if (tb > ctx_temp_bytes_ || !d_ctx_temp_) {
+    ctx_temp_bytes_ = 0;
+    HG_TRY(realloc_dev(d_ctx_temp_, tb + tb / 4, "d_ctx_temp_"), "alloc (context stage)");
+    ctx_temp_bytes_ = tb + tb / 4;
+  }
+  uint64_t *d_n_tail = d_ctx_count_ + ntiles + 1;  // (behind the scanned words)
+  HgContextArgs a{text, nbytes, bs1, ntiles, hg_context_win(line_base, out.n_pieces, params.before, params.after, params.carry_after, params.tail),
+                  d_sums_, d_bases_, out.d_hits, out.n_hits, d_ctx_count_, d_n_tail, d_ctx_pos_, nullptr, nullptr};
+  HG_TRY(hipEventRecord(ev_[0], stream), "event");
+  HG_TRY(hipMemsetAsync(d_n_tail, 0, sizeof(uint64_t), stream), "memset (context stage)");
+  HG_TRY(hg_context_launch(a, false, static_cast<uint32_t>(num_cus_), stream), "context stage launch (count)");
+  HG_TRY(rocprim::exclusive_scan(d_ctx_temp_, tb, d_ctx_count_, d_ctx_pos_, uint64_t{0}, ntiles + 1, rocprim::plus<uint64_t>(), stream), "scan (context stage)");
+  uint64_t total = 0, n_tail = 0, last_line = 0;
+  HG_TRY(hipMemcpyAsync(&total, d_ctx_pos_ + ntiles, sizeof total, hipMemcpyDeviceToHost, stream), "copy count");
+  HG_TRY(hipMemcpyAsync(&n_tail, d_n_tail, sizeof n_tail, hipMemcpyDeviceToHost, stream), "copy count");
+  if (out.n_hits) HG_TRY(hipMemcpyAsync(&last_line, &out.d_hits[out.n_hits - 1].line_no, sizeof last_line, hipMemcpyDeviceToHost, stream), "copy last line");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (context stage)");
+  if (total > out.n_pieces || n_tail > total) return error(HG_ERR_HIP, "the context stage counted more pieces than the buffer has");
+  if (total > ctx_cap_) {
+    const uint64_t cap = std::max<uint64_t>(total + total / 4, 4096);
+    ctx_cap_ = 0;
+    HG_TRY(realloc_dev(d_ctx_hits_, cap, "d_ctx_hits_"), "alloc (context stage records)");
+    HG_TRY(realloc_dev(d_ctx_aux_, cap, "d_ctx_aux_"), "alloc (context stage records)");
+    ctx_cap_ = cap;
+  }
+  if (total) {
+    a.out_hits = d_ctx_hits_;
+    a.out_aux = d_ctx_aux_;
+    HG_TRY(hg_context_launch(a, true, static_cast<uint32_t>(num_cus_), stream), "context stage launch (write)");
+  }
+  HG_TRY(hipEventRecord(ev_[3], stream), "event");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (context stage)");
+  (void)hipEventElapsedTime(&ctx->ms_context, ev_[0], ev_[3]);
+  ctx->n_context = total;
+  ctx->n_tail = n_tail;
+  ctx->owed_after = hg_context_owed(out.n_hits, last_line, line_base, out.n_pieces, params.after, params.carry_after);
+  ctx->d_hits = d_ctx_hits_;
+  ctx->d_aux = d_ctx_aux_;
+  return HG_OK;
+}
+
+int HgScanner::scan_context(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, hipStream_t stream, const HgContextParams &params, bool invert,
+                            HgScanOutput *out, HgContextOutput *ctx) {
+  if (!ctx) return error(HG_ERR_ARG, "invalid arguments");
+  *ctx = HgContextOutput{};
+  if (int rc = scan_impl(d_text, nbytes, buffer_size, line_base, false, invert, stream, out)) return rc;
+  if (!params.any()) return HG_OK;  // no context asked for: the stage is skipped
+  return context_pass(static_cast<const uint8_t *>(d_text), nbytes, static_cast<uint64_t>(buffer_size) - 1, line_base, params, stream, *out, ctx);
 }
 
 int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const PassRange &range, bool block_mode, hipStream_t stream,

@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -577,9 +578,13 @@ extern "C" int hyperscan(char *file_name, const char *const *patterns, const uns
 }
 
 // Face B's file scan: the reports of the file's pieces, or (invert) one HG_ID_INVERT result per piece without a report.
+// With context lines (before / after, hg_hyperscan_context) each chunk is scanned with the context stage behind it and the
+// two ordered lists are merged; between chunks the call carries what the device API's chaining identity needs: the
+// after-context still owed (owed_after -> carry_after) and the bytes of the previous chunks' tail pieces, `before` at most.
 static int scan_file(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
                      const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hs_event on_event,
-                     const int buffer_size, int buffer_count, unsigned long long max_match_count, const bool invert) {
+                     const int buffer_size, int buffer_count, unsigned long long max_match_count, const bool invert, const uint32_t before = 0,
+                     const uint32_t after = 0) {
   if (max_match_count > 0 && max_match_count < static_cast<unsigned long long>(buffer_count)) buffer_count = static_cast<int>(max_match_count);
   if (buffer_count < 1 || buffer_size < 1 || !on_event) return HYPERSCANNER_STATE_MEM;
   Ring ring;
@@ -692,6 +697,19 @@ static int scan_file(char *file_name, const char *const *patterns, const unsigne
   // ---- stages 2 and 3: copy to HBM (one chunk ahead when the reader is), scan, deliver
   uint64_t line_base = 0;  // pieces delivered to the scanner so far == reference line_number of the chunk's first piece
   bool stop = false;
+  // context lines
+  const bool with_context = before || after;
+  uint64_t carry_after = 0;  // after-context the chunks so far still owe
+  struct HeldPiece {
+    uint64_t line_no;
+    std::string bytes;
+  };
+  std::deque<HeldPiece> held;  // tail pieces of the chunks so far: the next match's before-context, maybe (`before` at most)
+  std::vector<HgHit> ctx_hits;
+  std::vector<HgHitAux> ctx_aux;
+  unsigned long long matches = 0;  // match results delivered (max_match_count counts those, not the context lines)
+  bool trailing = false;           // the limit is reached: only the last delivered line's after-context still goes out
+  uint64_t trailing_next = 0, trailing_end = 0;  // ... the pieces [trailing_next, trailing_end), up to the next matching piece
   int rc = 0;
   bool copied[Ctx::kSlots] = {false, false, false};
   auto issue_copy = [&](unsigned k) -> bool {  // slot k -> device buffer k % 2, asynchronously
@@ -738,7 +756,15 @@ static int scan_file(char *file_name, const char *const *patterns, const unsigne
         break;
       }
       HgScanOutput out{};
-      int src = ctx->sc->scan(d_text, cut, buffer_size, line_base, ctx->stream, &out, invert);
+      HgContextOutput cout{};
+      int src;
+      if (with_context) {
+        // (after the limit: the owed pieces only, as carry; no new windows, no tail)
+        const HgContextParams cp{trailing ? 0u : before, trailing ? 0u : after, trailing ? trailing_end - trailing_next : carry_after, !trailing && before != 0};
+        src = ctx->sc->scan_context(d_text, cut, buffer_size, line_base, ctx->stream, cp, invert, &out, &cout);
+      } else {
+        src = ctx->sc->scan(d_text, cut, buffer_size, line_base, ctx->stream, &out, invert);
+      }
       if (src != HG_OK) {
         std::fprintf(stderr, "ERROR: Unable to scan buffer. Exiting. (%s)\n", ctx->sc->last_error().c_str());
         rc = HYPERSCANNER_SCAN;
@@ -756,11 +782,52 @@ static int scan_file(char *file_name, const char *const *patterns, const unsigne
           break;
         }
       }
+      ctx_hits.resize(cout.n_context);
+      ctx_aux.resize(cout.n_context);
+      if (cout.n_context) {
+        if (hipMemcpyAsync(ctx_hits.data(), cout.d_hits, cout.n_context * sizeof(HgHit), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(ctx_aux.data(), cout.d_aux, cout.n_context * sizeof(HgHitAux), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess) {
+          rc = HYPERSCANNER_SCAN;
+          healthy = false;
+          break;
+        }
+      }
       const double t_scanned = now();
       t_scan += t_scanned - t_begin;
+      size_t ci = 0;  // cursor into the context records
+      // the owed after-context of the last delivered line: consecutive pieces, ending before the next matching piece (which is
+      // no context record) or when all are out
+      auto deliver_trailing = [&] {
+        while (ci < ctx_hits.size() && ctx_hits[ci].line_no < trailing_next) ci++;
+        while (trailing_next < trailing_end && ci < ctx_hits.size() && ctx_hits[ci].line_no == trailing_next && ctx_hits[ci].id == HG_CTX_ID_CONTEXT) {
+          ring.push(HG_CTX_ID_CONTEXT, trailing_next, host + ctx_aux[ci].start, ctx_aux[ci].len);
+          ci++;
+          trailing_next++;
+        }
+        if (trailing_next < line_base + out.n_pieces) trailing_end = trailing_next;  // stopped inside the chunk: nothing is owed any more
+      };
+      std::vector<size_t> tails;  // this chunk's tail records
+      // context records below `upto`, in order; tail records are set aside
+      auto deliver_context = [&](uint64_t upto) {
+        for (; ci < ctx_hits.size() && ctx_hits[ci].line_no < upto; ci++) {
+          if (ctx_hits[ci].id == HG_CTX_ID_TAIL) tails.push_back(ci);
+          else ring.push(HG_CTX_ID_CONTEXT, ctx_hits[ci].line_no, host + ctx_aux[ci].start, ctx_aux[ci].len);
+        }
+      };
+      const bool was_trailing = trailing;
+      if (trailing) {
+        deliver_trailing();
+        stop = trailing_next >= trailing_end;
+      } else if (with_context && !ctx->hits.empty()) {  // the held tail pieces within `before` of the chunk's first match
+        for (const HeldPiece &hp : held)
+          if (hp.line_no + before >= ctx->hits[0].line_no) ring.push(HG_CTX_ID_CONTEXT, hp.line_no, reinterpret_cast<const uint8_t *>(hp.bytes.data()), static_cast<uint32_t>(hp.bytes.size()));
+        held.clear();
+      }
       // deliver line by line; inside a line reports go out by ascending end offset, then id (hs_scan order)
       size_t i = 0;
-      while (i < ctx->hits.size() && !stop) {
+      while (i < ctx->hits.size() && !stop && !was_trailing) {
+        if (with_context) deliver_context(ctx->hits[i].line_no);
         size_t j = i;
         while (j < ctx->hits.size() && ctx->hits[j].line_no == ctx->hits[i].line_no) j++;
         if (j - i > 1) {
@@ -775,8 +842,26 @@ static int scan_file(char *file_name, const char *const *patterns, const unsigne
           ring.push(ctx->hits[i].id, ctx->hits[i].line_no, host + ctx->aux[i].start, ctx->aux[i].len);
         }
         // the reference checks the limit after each line's hs_scan returns (hyperscanner.c:222-224)
-        if (max_match_count > 0 && ring.delivered >= max_match_count) stop = true;
+        matches += j - i;
+        if (max_match_count > 0 && matches >= max_match_count) {
+          stop = true;
+          if (after) {  // GNU grep's -m with -A: the trailing context of the last delivered line still goes out
+            trailing = true;
+            trailing_next = ctx->hits[i].line_no + 1;
+            trailing_end = hg_sat_add(trailing_next, after);
+            deliver_trailing();
+            stop = trailing_next >= trailing_end;  // else the chunk ended first: the next one is read for what is still owed
+            break;
+          }
+        }
         i = j;
+      }
+      if (with_context && !trailing && !stop) {  // (a call that ends at the limit delivers nothing behind its last line but that line's after-context)
+        deliver_context(~0ull);
+        // the tail pieces' bytes leave the pinned slot before it goes back to the reader
+        for (size_t t : tails) held.push_back(HeldPiece{ctx_hits[t].line_no, std::string(reinterpret_cast<const char *>(host) + ctx_aux[t].start, ctx_aux[t].len)});
+        while (held.size() > before) held.pop_front();
+        carry_after = cout.owed_after;
       }
       line_base += out.n_pieces;
       t_deliver += now() - t_scanned;
@@ -809,4 +894,14 @@ extern "C" int hg_hyperscan_invert(char *file_name, const char *const *patterns,
                                    const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hs_event on_event,
                                    const int buffer_size, int buffer_count, unsigned long long max_match_count) {
   return scan_file(file_name, patterns, pattern_flags, pattern_ids, ext, elements, on_event, buffer_size, buffer_count, max_match_count, true);
+}
+
+extern "C" int hg_hyperscan_context(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                                    const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hs_event on_event,
+                                    const int buffer_size, int buffer_count, unsigned long long max_match_count, unsigned int before, unsigned int after,
+                                    int invert) {
+  // an expression with one of the context ids could not be told from a context line by the callback
+  for (unsigned int i = 0; pattern_ids && i < elements; i++)
+    if (pattern_ids[i] >= HG_CTX_ID_TAIL) return HYPERSCANNER_DB;
+  return scan_file(file_name, patterns, pattern_flags, pattern_ids, ext, elements, on_event, buffer_size, buffer_count, max_match_count, invert != 0, before, after);
 }

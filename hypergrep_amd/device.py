@@ -17,6 +17,9 @@ HS_FLAG_SOM_LEFTMOST = 256
 HS_FLAG_COMBINATION = utils.HS_FLAG_COMBINATION
 HS_FLAG_QUIET = utils.HS_FLAG_QUIET
 HG_ID_INVERT = utils.HG_ID_INVERT  # the id of an inverted scan's records (Scanner.scan(invert=True)): no expression
+HG_ID_CONTEXT = utils.HG_ID_CONTEXT  # the ids of Scanner.context()'s records: a context piece, a tail candidate (scan(tail=True))
+HG_ID_CONTEXT_TAIL = utils.HG_ID_CONTEXT_TAIL
+HG_CONTEXT_TAIL = 1  # hg_context_t.flags
 
 
 class HgHit(ctypes.Structure):
@@ -34,6 +37,15 @@ class HgScanResult(ctypes.Structure):
         ("ms_stream", ctypes.c_float), ("ms_total", ctypes.c_float), ("reruns", ctypes.c_uint32), ("stream_launches", ctypes.c_uint32),
         ("joiner_tiles", ctypes.c_uint64), ("joiner_launches", ctypes.c_uint32), ("invert_us", ctypes.c_uint32),
     ]
+
+
+class HgContext(ctypes.Structure):
+    _fields_ = [("before", ctypes.c_uint32), ("after", ctypes.c_uint32), ("carry_after", ctypes.c_uint64), ("flags", ctypes.c_uint32)]
+
+
+class HgContextResult(ctypes.Structure):
+    _fields_ = [("n_context", ctypes.c_uint64), ("n_tail", ctypes.c_uint64), ("owed_after", ctypes.c_uint64), ("d_ctx_hits", ctypes.c_void_p),
+                ("d_ctx_aux", ctypes.c_void_p), ("context_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class HgDbInfo(ctypes.Structure):
@@ -73,6 +85,11 @@ def lib() -> ctypes.CDLL:
                                      ctypes.POINTER(HgScanResult)]
         if hasattr(l, "hg_scan_device_invert"):  # (absent from a build before the inverted match: HG_LIB comparisons with an older library)
             l.hg_scan_device_invert.argtypes = l.hg_scan_device.argtypes
+        if hasattr(l, "hg_scan_device_context"):  # (absent from a build before the context lines)
+            l.hg_scan_device_context.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p,
+                                                 ctypes.POINTER(HgContext), ctypes.c_int, ctypes.POINTER(HgScanResult), ctypes.POINTER(HgContextResult)]
+            l.hg_copy_context.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
+            l.hg_copy_context_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hits.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
         l.hg_copy_hits_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hit_starts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
@@ -144,6 +161,10 @@ class ScanStats:
     joiner_launches: int = 0
     joiner_tiles: int = 0
     invert_us: int = 0  # inverted scans: the invert stage alone, microseconds
+    n_context: int = 0  # scans with context: the records of Scanner.context() (context and tail pieces)
+    owed_after: int = 0  # ... the after-context pieces still owed past the buffer's end (the next buffer's carry_after)
+    n_tail: int = 0  # ... the tail records among n_context
+    context_us: int = 0  # ... the context stage alone, microseconds
 
 
 class Scanner:
@@ -157,18 +178,45 @@ class Scanner:
         if rc != 0:
             raise DeviceError(f"hg_scanner_create failed ({rc}): {err.value.decode(errors='replace')}")
         self._last = HgScanResult()
+        self._last_ctx = HgContextResult()
 
-    def scan(self, d_text: int, nbytes: int, buffer_size: int = 262140, line_base: int = 0, stream: int = 0, invert: bool = False) -> ScanStats:
+    def scan(self, d_text: int, nbytes: int, buffer_size: int = 262140, line_base: int = 0, stream: int = 0, invert: bool = False,
+             context: tuple[int, int] | None = None, carry_after: int = 0, tail: bool = False) -> ScanStats:
         """invert: the result is the line pieces without any report (grep -v; hg_scan_device_invert): n_hits of them, and
-        hits() gives (line_number, HG_ID_INVERT, 0, start, len) per piece in line order."""
+        hits() gives (line_number, HG_ID_INVERT, 0, start, len) per piece in line order.
+        context = (before, after): grep -B / -A in line pieces (hg_scan_device_context).  hits() is what it is without context;
+        context() gives the pieces around them.  carry_after: the owed_after of the previous buffer of a chain; tail: also
+        deliver the last `before` pieces that are neither match nor context, as HG_ID_CONTEXT_TAIL records."""
         res = HgScanResult()
-        name = "hg_scan_device_invert" if invert else "hg_scan_device"
-        rc = getattr(lib(), name)(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, line_base, ctypes.c_void_p(stream), ctypes.byref(res))
+        cres = HgContextResult()
+        if context is not None or carry_after or tail:
+            before, after = context or (0, 0)
+            name = "hg_scan_device_context"
+            ctx = HgContext(before, after, carry_after, HG_CONTEXT_TAIL if tail else 0)
+            rc = lib().hg_scan_device_context(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, line_base, ctypes.c_void_p(stream), ctypes.byref(ctx),
+                                              1 if invert else 0, ctypes.byref(res), ctypes.byref(cres))
+        else:
+            name = "hg_scan_device_invert" if invert else "hg_scan_device"
+            rc = getattr(lib(), name)(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, line_base, ctypes.c_void_p(stream), ctypes.byref(res))
         if rc != 0:
             raise DeviceError(f"{name} failed ({rc}): {lib().hg_scanner_error(self._h).decode(errors='replace')}")
         self._last = res
+        self._last_ctx = cres
         return ScanStats(res.n_hits, res.n_lines, res.n_candidates, res.n_raw_hits, res.ms_stream, res.ms_total, res.reruns, res.stream_launches, res.joiner_launches, res.joiner_tiles,
-                         res.invert_us)
+                         res.invert_us, cres.n_context, cres.owed_after, cres.n_tail, cres.context_us)
+
+    def context(self, limit: int | None = None):
+        """Last scan's context records as a list of (line_number, HG_ID_CONTEXT | HG_ID_CONTEXT_TAIL, 0, start, len), in line
+        order; empty after a scan without context."""
+        n = self._last_ctx.n_context if limit is None else min(limit, self._last_ctx.n_context)
+        if not n:
+            return []
+        hits = (HgHit * n)()
+        aux = (HgHitAux * n)()
+        rc = lib().hg_copy_context(self._h, hits, aux, n)
+        if rc != 0:
+            raise DeviceError(f"hg_copy_context failed ({rc})")
+        return [(hits[i].line_number, hits[i].id, hits[i].to, aux[i].start, aux[i].len) for i in range(n)]
 
     @property
     def d_hits(self) -> int:

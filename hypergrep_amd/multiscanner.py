@@ -78,6 +78,7 @@ class _Replay:
         self.total = 0
         self.matched = False
         self.errored = False
+        self.context_state = {"printed": False}  # context output: something was printed, so the next group is set off by "--"
 
     def accept(self, index: int, outcome: Any) -> None:
         if self.opt["ordered_results"] and index != self.due:
@@ -114,7 +115,10 @@ class _Replay:
             print(f"{name}:{found}" if opt["with_file_name"] else f"{found}")
         elif not opt["rows_unprinted"]:  # (-o -v: the selected lines decide the exit code, and none has a matched part to print)
             try:
-                print_results(found, name, with_file_name=opt["with_file_name"], with_line_number=opt["with_line_number"])
+                if opt["context"]:
+                    print(format_context_results(found, name, opt["with_file_name"], opt["with_line_number"], opt["only_matching"], self.context_state), end="")
+                else:
+                    print_results(found, name, with_file_name=opt["with_file_name"], with_line_number=opt["with_line_number"])
             except BrokenPipeError:
                 pass  # `| head` closed stdout: keep draining jobs quietly
         self.due += 1
@@ -137,6 +141,8 @@ def parallel_grep(  # pylint: disable=too-many-arguments,too-many-locals
     files_with_matches: bool = False,
     quiet: bool = False,
     invert_match: bool = False,
+    before_context: int = 0,
+    after_context: int = 0,
 ) -> int:
     """Search files for the patterns and print what grep would print.
 
@@ -156,17 +162,22 @@ def parallel_grep(  # pylint: disable=too-many-arguments,too-many-locals
         quiet: print nothing and stop everything at the first match.
         invert_match: select the lines NO pattern matches (grep -v).  Counts, totals, -l / -L / -q and max_match_count then
             go by the selected lines; with only_matching nothing is printed, and the exit code still goes by the selected lines.
+        before_context / after_context: also print that many lines before / after each selected line (grep -B / -A), in GNU
+            grep's format: "-" instead of ":" after the prefixes of a context line, "--" between groups that are not adjacent.
+            They change nothing where lines are only counted or files only listed.
 
     Returns:
         grep's exit code: 2 after any error, else 1 without a match, else 0.
     """
     if files_without_match or files_with_matches or quiet:
         max_match_count = 1  # these modes only ask "is there a match"
+    listing = count_results or total_results or files_without_match or files_with_matches or quiet
+    context = bool(before_context or after_context) and not listing
     replay = _Replay(
         files,
         {"ordered_results": ordered_results, "count_results": count_results, "total_results": total_results, "with_file_name": with_file_name,
          "with_line_number": with_line_number, "files_without_match": files_without_match, "files_with_matches": files_with_matches, "quiet": quiet,
-         "rows_unprinted": only_matching and invert_match},
+         "rows_unprinted": only_matching and invert_match, "context": context, "only_matching": only_matching},
     )
     job_kwargs = {
         "ignore_case": ignore_case,
@@ -176,6 +187,8 @@ def parallel_grep(  # pylint: disable=too-many-arguments,too-many-locals
         "max_match_count": max_match_count,
         "invert": invert_match,
     }
+    if context:
+        job_kwargs.update(before_context=before_context, after_context=after_context)
     # the reference runs one job per core; here a job is a GPU scan with its own reader threads and pinned buffers, so a
     # handful in flight already keeps every GPU of the node busy
     workers = max(1, min(len(files), max((os.cpu_count() or 2) - 1, 1), 16))
@@ -207,6 +220,27 @@ def print_results(results: list, file_name: str, with_file_name: bool = False, w
         chunks = [f"{head}{line}" for _number, line in results]
     if chunks:
         print("".join(chunks), end="")
+
+
+def format_context_results(results: list, file_name: str, with_file_name: bool = False, with_line_number: bool = False, only_matching: bool = False,
+                           state: dict | None = None) -> str:
+    """GNU grep's output for (line number, line, is_match) rows in line order (grep() with context): a context line has "-" where
+    a matching line has ":" after the file name and the line number, and a "--" line stands between groups whose line numbers
+    are not adjacent, also from one file to the next.  only_matching: the context lines are not printed (they still make the
+    groups).  state: {"printed": bool}, carried from file to file."""
+    state = state if state is not None else {"printed": False}
+    out = []
+    previous = None
+    for number, line, is_match in results:
+        if previous is not None and number > previous + 1 or previous is None and state["printed"]:
+            out.append("--\n")
+        previous = number
+        state["printed"] = True
+        if only_matching and not is_match:
+            continue
+        mark = ":" if is_match else "-"
+        out.append((f"{file_name}{mark}" if with_file_name else "") + (f"{number}{mark}" if with_line_number else "") + line)
+    return "".join(out)
 
 
 def read_stdin() -> Generator[str, None, None]:
@@ -265,6 +299,17 @@ def to_gnu_regular_expressions(patterns: list[str]) -> list[str]:
     return converted
 
 
+def _context_length(text: str) -> int:
+    """-A / -B / -C take a non-negative number; anything else ends the command with exit code 2, as in GNU grep."""
+    try:
+        value = int(text)
+    except ValueError:
+        value = -1
+    if value < 0:
+        raise argparse.ArgumentTypeError(f"{text}: invalid context length argument")
+    return value
+
+
 def parse_args(args: list = None) -> argparse.Namespace:
     """Command line of the `hyperscanner` command: grep's option letters where grep has them."""
     parser = argparse.ArgumentParser(
@@ -297,6 +342,11 @@ def parse_args(args: list = None) -> argparse.Namespace:
     matching.add_argument("-i", "--ignore-case", action="store_true", help="Case-insensitive matching.")
     # (no attribute unless given: tests/test_multiscanner.py compares the whole namespace of the reference's command lines)
     matching.add_argument("-v", "--invert-match", action="store_true", default=argparse.SUPPRESS, help="Select the lines that match NO pattern.")
+
+    context = parser.add_argument_group("Context Line Control")
+    context.add_argument("-A", "--after-context", type=_context_length, metavar="NUM", default=argparse.SUPPRESS, help="Print NUM lines of trailing context after matching lines.")
+    context.add_argument("-B", "--before-context", type=_context_length, metavar="NUM", default=argparse.SUPPRESS, help="Print NUM lines of leading context before matching lines.")
+    context.add_argument("-C", "--context", type=_context_length, metavar="NUM", default=argparse.SUPPRESS, help="Print NUM lines of output context.")
 
     output = parser.add_argument_group("General Output Control")
     output.add_argument("-c", "--count", action="store_true", help="Print the number of matching lines per file.")
@@ -372,6 +422,8 @@ def main() -> None:
             files_without_match=args.files_without_match,
             files_with_matches=args.files_with_matches,
             invert_match=getattr(args, "invert_match", False),
+            before_context=getattr(args, "before_context", getattr(args, "context", 0)),
+            after_context=getattr(args, "after_context", getattr(args, "context", 0)),
         )
     )
 

@@ -31,6 +31,8 @@ HS_FLAG_CASELESS, HS_FLAG_DOTALL, HS_FLAG_MULTILINE, HS_FLAG_SINGLEMATCH = 1, 2,
 # (include/hypergrep_amd.h has the contract).
 HS_FLAG_COMBINATION, HS_FLAG_QUIET = 512, 1024
 HG_ID_INVERT = 0xFFFFFFFF  # Result.id of an inverted scan (scan(invert=True)): no expression
+HG_ID_CONTEXT = 0xFFFFFFFE  # Result.id of a context line (scan(before_context=, after_context=)); a context record of the device API
+HG_ID_CONTEXT_TAIL = 0xFFFFFFFD  # device API: a tail record (the next buffer's before-context, maybe)
 _GREP_FLAGS = HS_FLAG_DOTALL | HS_FLAG_MULTILINE | HS_FLAG_SINGLEMATCH  # what grep() and the default of scan() use
 
 RC_INVALID_FILE = 101  # grep(): the path is missing or a directory (utils.py:16)
@@ -170,11 +172,16 @@ def scan(  # pylint: disable=too-many-arguments
     max_match_count: int = 0,
     ext=None,
     invert: bool = False,
+    before_context: int = 0,
+    after_context: int = 0,
 ) -> int:
     """Scan a plain / gzip / zstd text file; `callback(matches, count)` receives the hits in batches of `buffer_count`.
     `ext`: one ExprExt (extended parameters: approximate matching, offset bounds, min_length) or None per pattern.
     `invert` (grep -v): the callback receives the lines NO pattern matches instead, one Result with id HG_ID_INVERT each, in
     line order; `max_match_count` then bounds those lines.
+    `before_context` / `after_context` (grep -B / -A, in line pieces): the callback also receives the lines around the delivered
+    ones, one Result with id HG_ID_CONTEXT each, merged in line order (hg_hyperscan_context); `max_match_count` does not count
+    them, and pattern ids of 0xFFFFFFFD and above are refused (return code 4).
 
     The native call runs on a daemon thread so that Ctrl-C reaches Python (return code 130); otherwise the shim's
     return code (0 = fine, 1-7 as in hyperscanner.c:25-33) comes back.
@@ -186,7 +193,13 @@ def scan(  # pylint: disable=too-many-arguments
     outcome = [0]
 
     def native_call() -> None:
-        if invert:
+        if before_context or after_context:
+            engine.hg_hyperscan_context.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
+                                                    ctypes.POINTER(ctypes.POINTER(ExprExt)), ctypes.c_uint, CALLBACK_TYPE, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, ctypes.c_int]
+            outcome[0] = engine.hg_hyperscan_context(path.encode(), c_patterns, c_flags, c_ids, c_ext, len(c_patterns), c_callback, buffer_size,
+                                                     buffer_count, max_match_count, before_context, after_context, 1 if invert else 0)
+        elif invert:
             engine.hg_hyperscan_invert.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
                                                    ctypes.POINTER(ctypes.POINTER(ExprExt)), ctypes.c_uint, CALLBACK_TYPE, ctypes.c_int, ctypes.c_int,
                                                    ctypes.c_ulonglong]
@@ -212,8 +225,17 @@ class _GrepSink:
     """on_match for grep(): counts, keeps whole lines, or keeps the matched parts (`re.finditer` of the pattern whose
     id the hit carries — with grep()'s all-zero ids that is the first pattern, as in the reference)."""
 
-    def __init__(self, patterns: list[str], count_only: bool, only_matching: bool, errors: str, invert: bool = False):
+    def __init__(self, patterns: list[str], count_only: bool, only_matching: bool, errors: str, invert: bool = False, context: bool = False,
+                 limit: int = 0, after: int = 0):
         self.invert = invert  # the hits are the lines without a match: no matched parts to show
+        self.context = context  # rows are (line number, line, is_match); context lines (id HG_ID_CONTEXT) are rows, not counted
+        # GNU grep's -m NUM with -A NUM (3.5 and later): after the NUM-th selected line the next `after` lines still go out, all of
+        # them as context, selected or not.  The file API ends that trailing context before the next selected piece, so grep()
+        # asks it for `after` selected lines more (grep()) and draws the line here.
+        self.limit = limit if context and after else 0
+        self.after = after
+        self.selected = 0  # selected lines seen
+        self.last_line = -1  # the line number of the limit-th selected line
         self.count = 0
         self.rows: list[tuple[int, str]] = []
         self.count_only = count_only
@@ -222,11 +244,25 @@ class _GrepSink:
 
     def __call__(self, matches, count: int) -> None:
         if self.count_only:
-            self.count += count
+            self.count += sum(1 for i in range(count) if matches[i].id != HG_ID_CONTEXT) if self.context else count
             return
         for hit in (matches[i] for i in range(count)):
             text = hit.line.decode(errors=self.errors)
-            if self.finders is None:
+            if self.context:
+                if self.limit and self.selected >= self.limit:  # behind the limit: trailing context only, whatever the line is
+                    if hit.line_number <= self.last_line + self.after:
+                        self.rows.append((hit.line_number + 1, text, False))
+                    continue
+                if hit.id != HG_ID_CONTEXT:
+                    self.selected += 1
+                    self.last_line = hit.line_number
+                if hit.id == HG_ID_CONTEXT:
+                    self.rows.append((hit.line_number + 1, text, False))
+                elif self.finders is None:
+                    self.rows.append((hit.line_number + 1, text, True))
+                elif not self.invert:
+                    self.rows.extend((hit.line_number + 1, f"{part.group()}\n", True) for part in self.finders[hit.id].finditer(text))
+            elif self.finders is None:
                 self.rows.append((hit.line_number + 1, text))
             elif not self.invert:
                 self.rows.extend((hit.line_number + 1, f"{part.group()}\n") for part in self.finders[hit.id].finditer(text))
@@ -245,17 +281,27 @@ def grep(  # pylint: disable=too-many-arguments
     errors: str = "ignore",
     max_match_count: int = 0,
     invert: bool = False,
+    before_context: int = 0,
+    after_context: int = 0,
 ) -> tuple[int | list[tuple[int, str]], int]:
     """grep for Python: (number of matching lines | [(1-based line number, line)], return code).
 
     `invert` (grep -v): the lines no pattern matches are selected instead: counted, listed, and bounded by `max_match_count`;
     with `only_matching` nothing is listed (a line without a match has no matched part): the result is [] even where lines
     were selected, so a caller that needs to know whether any were asks without `only_matching`, as multiscanner does.
+    `before_context` / `after_context` (grep -B / -A): with either, the rows are (1-based line number, line, is_match) in line
+    order, the context lines among them with is_match False (also with `only_matching`, where the matching rows are the matched
+    parts); counts (`count_only`) and `max_match_count` go by the matching lines only.  Without them rows are as ever.
+    With `max_match_count` and `after_context` the rows end as GNU grep's output (3.5 and later) does: the `after_context` lines
+    behind the last counted line are all rows with is_match False, matching or not.  (scan() / hg_hyperscan_context end that
+    trailing context before the next matching line instead, as the file API's contract states.)
 
     A missing path raises FileNotFoundError and a directory ValueError — or, with `no_messages`, comes back as
     (nothing found, 101).  Invalid regexes raise `re.error` before anything is scanned.
     """
-    sink = _GrepSink(patterns, count_only, only_matching, errors, invert)
+    sink = _GrepSink(patterns, count_only, only_matching, errors, invert, bool(before_context or after_context), max_match_count, after_context)
+    if max_match_count and after_context and not count_only:
+        max_match_count += after_context  # (the trailing `after_context` lines hold that many selected lines at most: _GrepSink)
     if not only_matching:
         for pattern in patterns:  # the reference compiles them for -o in every mode: same early failure for bad syntax
             re.compile(pattern)
@@ -269,5 +315,6 @@ def grep(  # pylint: disable=too-many-arguments
             raise problem
         return sink.result(), RC_INVALID_FILE
     flags = _GREP_FLAGS | (HS_FLAG_CASELESS if ignore_case else 0)
-    return_code = scan(file, patterns, sink, flags=[flags] * len(patterns), max_match_count=max_match_count, invert=invert)
+    return_code = scan(file, patterns, sink, flags=[flags] * len(patterns), max_match_count=max_match_count, invert=invert,
+                       before_context=before_context, after_context=after_context)
     return sink.result(), return_code

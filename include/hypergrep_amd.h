@@ -191,6 +191,20 @@ int hg_hyperscan_invert(char *file_name, const char *const *patterns, const unsi
                         const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements,
                         hs_event on_event, const int buffer_size, int buffer_count, unsigned long long max_match_count);
 
+/* Context lines (grep -A / -B / -C) for files: hg_hyperscan_ext's (invert == 0) or hg_hyperscan_invert's (invert != 0) call
+ * with `before` and `after` line pieces of context around every line it delivers (hg_scan_device_context below has the
+ * classes).  `on_event` receives the merged order: the call's own results, and one Result{id = HG_ID_CONTEXT, line_number,
+ * line} per context line; a gap in the line numbers is where grep prints "--".  Context does not stop at the cuts between the
+ * chunks a file is scanned in: the after-context still owed and the last `before` pieces of a chunk are carried into the next.
+ * max_match_count counts the call's own results only; once it is reached the after-context of the last delivered line still
+ * goes out, up to `after` pieces and ending before the next matching piece (GNU grep's -m with -A up to 3.4; grep() in
+ * hypergrep_amd/utils.py builds the rule of 3.5 and later on top: all `after` lines, matching ones as context).  A pattern id of
+ * 0xFFFFFFFD or above is refused (HYPERSCANNER_DB): the callback could not tell it from a context line. */
+int hg_hyperscan_context(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                         const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements,
+                         hs_event on_event, const int buffer_size, int buffer_count, unsigned long long max_match_count,
+                         unsigned int before, unsigned int after, int invert);
+
 /* call site hyperscanner.c:136 */
 int hs_compile_multi(const char *const *expressions, const unsigned int *flags, const unsigned int *ids,
                      unsigned int elements, unsigned int mode, const hs_platform_info_t *platform,
@@ -417,6 +431,58 @@ int hg_scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, i
 #define HG_ID_INVERT 0xFFFFFFFFu /* the id of an inverted result's records: no expression */
 int hg_scan_device_invert(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base,
                           void *stream, hg_scan_result_t *result);
+
+/* Context lines (grep -A / -B / -C): hg_scan_device (invert == 0) or hg_scan_device_invert (invert != 0) with a second
+ * ordered list, the line pieces AROUND the pieces the call delivers a record for.  `result` is filled exactly as that call
+ * fills it (same records, same order; hg_copy_hits* unchanged).
+ * Units and classes.  Context is counted in line pieces, the unit hg_scan_device numbers (see hg_scan_device_invert above).
+ * Let M be the piece numbers for which the call delivers a record: the hits after every report rule, or the selected pieces
+ * of an inverted call.  With B = before and A = after, a piece q of the buffer falls in exactly one class:
+ *   match    q is in M: its records are those in `result`, untouched;
+ *   context  q is not in M, and some m in M has q - A <= m <= q + B, or q < line_base + carry_after (after-context the
+ *            previous buffer still owes);
+ *   tail     (only with HG_CONTEXT_TAIL) q is neither and lies among the buffer's last B pieces: a candidate for the next
+ *            buffer's before-context, which the caller keeps or drops;
+ *   otherwise nothing.
+ * The context records: d_ctx_hits / d_ctx_aux hold n_context entries in ascending line_number, one hg_hit_t{line_number, id,
+ * to = 0} + hg_hit_aux_t{start, len, pattern = 0xFFFFFFFF} per context or tail piece, id = HG_ID_CONTEXT or
+ * HG_ID_CONTEXT_TAIL, `start` and `len` as for hits.  Both lists are ordered by line and share no line number: a consumer
+ * merges them with two cursors, and a gap in the merged line numbers is where grep prints "--".
+ * owed_after: the after-context pieces still owed past the buffer's end; with a record in M max(0, last m + A - last piece),
+ * without one max(0, carry_after - n_lines).  n_tail: the tail records among the n_context.  context_us: the added stage in
+ * microseconds (HIP events, as invert_us).  With A = B = 0, no carry and no tail flag the stage is skipped: n_context = 0.
+ * before and after may be any uint32_t: the arithmetic saturates at piece 0 and at the buffer's end.
+ * Chaining identity.  Cut a text at any piece boundary into buffers and scan them in order with line_base advanced by
+ * n_lines, carry_after = the previous owed_after, and HG_CONTEXT_TAIL.  Of each buffer's tail records keep those with
+ * line_number >= (first m of the next buffer with a record) - B, none if no later buffer has a record.  The merged output
+ * equals that of the whole text scanned at once.
+ * The stage runs on the GPU behind the scan (hypergrep_amd/csrc/hg_context.hip): per-tile counts from the scan's line geometry
+ * and the records' lines (no text read), their exclusive scan, one pass over the tiles that hold context, written in order. */
+#define HG_ID_CONTEXT 0xFFFFFFFEu      /* the id of a context record */
+#define HG_ID_CONTEXT_TAIL 0xFFFFFFFDu /* the id of a tail record */
+#define HG_CONTEXT_TAIL 1u             /* hg_context_t.flags: deliver tail records */
+typedef struct hg_context {
+    uint32_t before, after; /* B and A, in line pieces */
+    uint64_t carry_after;   /* after-context owed by the previous buffer (its owed_after), 0 for the first */
+    uint32_t flags;         /* 0 or HG_CONTEXT_TAIL */
+} hg_context_t;
+typedef struct hg_context_result {
+    uint64_t n_context;  /* context and tail records */
+    uint64_t n_tail;     /* the tail records among them */
+    uint64_t owed_after; /* after-context still owed past the buffer's end */
+    const hg_hit_t *d_ctx_hits; /* DEVICE pointers, valid until the next scan on this scanner */
+    const hg_hit_aux_t *d_ctx_aux;
+    uint32_t context_us; /* the context stage alone (count launch, scan, the host synchronisation that sizes the output, write launch) */
+    uint32_t reserved;
+} hg_context_result_t;
+int hg_scan_device_context(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base,
+                           void *stream, const hg_context_t *context, int invert, hg_scan_result_t *result,
+                           hg_context_result_t *context_result);
+/* Copy the last scan's first `max` context records (and aux records, if aux != NULL) to host memory; none after a scan
+ * without context. */
+int hg_copy_context(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max);
+/* The same (16-byte records only) into a DEVICE buffer, asynchronously on `stream`. */
+int hg_copy_context_device(hg_scanner_t *scanner, void *d_dst, uint64_t max, void *stream);
 
 /* Copy the last scan's first `max` hits (and aux records, if aux != NULL) to host memory. */
 int hg_copy_hits(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max);

@@ -17,8 +17,10 @@ from hypergrep_amd.utils import (  # the reference package re-exports exactly th
     check_compatibility,
     configure_libraries,
     grep,
+    grep_files,
     prepare_patterns,
     scan,
+    scan_files,
 )
 
 __all__ = [
@@ -27,5 +29,7 @@ __all__ = [
     # extended parameters (approximate matching), beyond the reference's names
     "ExprExt", "HS_EXT_FLAG_MIN_OFFSET", "HS_EXT_FLAG_MAX_OFFSET", "HS_EXT_FLAG_MIN_LENGTH", "HS_EXT_FLAG_EDIT_DISTANCE",
     "HS_EXT_FLAG_HAMMING_DISTANCE",
+    # many files in one native call
+    "grep_files", "scan_files",
 ]
 __version__ = "0.1.0"

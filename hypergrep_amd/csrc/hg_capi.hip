@@ -21,6 +21,8 @@ struct hg_scanner {
   hg_scan_result_t last;
   const uint32_t *d_from;  // the last scan's hit starts (SOM databases), else nullptr: every start is 0
   hg_context_result_t last_ctx;  // the last scan's context records (hg_scan_device_context), else zeroes
+  hg_segment_result_t last_seg;  // the last scan's per-segment arrays (hg_scan_device_segments), else zeroes
+  uint32_t last_n_seg;
 };
 
 static_assert(HG_ID_CONTEXT == HG_CTX_ID_CONTEXT && HG_ID_CONTEXT_TAIL == HG_CTX_ID_TAIL, "the context records carry the ids the header names");
@@ -91,7 +93,7 @@ int hg_scanner_create(const hg_database_t *db, int device, hg_scanner_t **scanne
     put_err(err, errlen, msg);
     return rc;
   }
-  *scanner = new hg_scanner{sc, {}, nullptr, {}};
+  *scanner = new hg_scanner{sc, {}, nullptr, {}, {}, 0};
   return HG_OK;
 }
 
@@ -104,12 +106,23 @@ void hg_scanner_destroy(hg_scanner_t *scanner) {
 const char *hg_scanner_error(const hg_scanner_t *scanner) { return scanner ? scanner->sc->last_error().c_str() : "null scanner"; }
 
 static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, void *stream,
-                       hg_scan_result_t *result, bool invert, const hg_context_t *context = nullptr, hg_context_result_t *context_result = nullptr) {
+                       hg_scan_result_t *result, bool invert, const hg_context_t *context = nullptr, hg_context_result_t *context_result = nullptr,
+                       const hg_segments_t *segments = nullptr, hg_segment_result_t *segment_result = nullptr) {
   if (!scanner || !result) return HG_ERR_ARG;
   HgScanOutput o{};
   HgContextOutput c{};
+  HgSegOutput g{};
   int rc;
-  if (context) {
+  scanner->last_seg = hg_segment_result_t{};
+  scanner->last_n_seg = 0;
+  if (segments) {
+    const HgSegParams params{segments->d_seg_start, segments->d_seg_end, segments->n_seg, segments->max_per_segment};
+    rc = scanner->sc->scan_packed(d_text, nbytes, buffer_size, static_cast<hipStream_t>(stream), params, invert, &o, &g);
+    if (rc != HG_OK) {  // (nothing was scanned, or the scan failed: no records to copy)
+      scanner->last = hg_scan_result_t{};
+      scanner->d_from = nullptr;
+    }
+  } else if (context) {
     const HgContextParams params{context->before, context->after, context->carry_after, (context->flags & HG_CONTEXT_TAIL) != 0};
     rc = scanner->sc->scan_context(d_text, nbytes, buffer_size, line_base, static_cast<hipStream_t>(stream), params, invert, &o, &c);
   } else {
@@ -119,6 +132,11 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
   scanner->last_ctx = hg_context_result_t{c.n_context, c.n_tail, c.owed_after, reinterpret_cast<const hg_hit_t *>(c.d_hits), reinterpret_cast<const hg_hit_aux_t *>(c.d_aux),
                                           static_cast<uint32_t>(c.ms_context * 1000.0f + 0.5f), 0};
   if (context_result) *context_result = scanner->last_ctx;
+  if (segments) {
+    scanner->last_seg = hg_segment_result_t{g.d_record_segment, g.d_first_record, g.d_n_lines, g.d_n_selected, static_cast<uint32_t>(g.ms_segments * 1000.0f + 0.5f), 0};
+    scanner->last_n_seg = segments->n_seg;
+    *segment_result = scanner->last_seg;
+  }
   result->n_hits = o.n_hits;
   result->n_lines = o.n_pieces;
   result->n_candidates = o.n_cands;
@@ -151,6 +169,26 @@ int hg_scan_device_context(hg_scanner_t *scanner, const void *d_text, uint64_t n
                            const hg_context_t *context, int invert, hg_scan_result_t *result, hg_context_result_t *context_result) {
   if (!context || !context_result || (context->flags & ~HG_CONTEXT_TAIL)) return HG_ERR_ARG;
   return scan_device(scanner, d_text, nbytes, buffer_size, line_base, stream, result, invert != 0, context, context_result);
+}
+
+int hg_scan_device_segments(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, void *stream, const hg_segments_t *segments, int invert,
+                            hg_scan_result_t *result, hg_segment_result_t *segment_result) {
+  if (!segments || !segment_result) return HG_ERR_ARG;
+  *segment_result = hg_segment_result_t{};
+  return scan_device(scanner, d_text, nbytes, buffer_size, 0, stream, result, invert != 0, nullptr, nullptr, segments, segment_result);
+}
+
+int hg_copy_segments(hg_scanner_t *scanner, uint32_t *record_segment, uint64_t *first_record, uint64_t *n_lines, uint64_t *n_selected) {
+  if (!scanner) return HG_ERR_ARG;
+  const hg_segment_result_t &g = scanner->last_seg;
+  if (!g.d_first_record) return HG_ERR_ARG;  // the last scan had no segments
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  const uint64_t n = scanner->last.n_hits, n_seg = scanner->last_n_seg;
+  if (record_segment && n && hipMemcpy(record_segment, g.d_record_segment, n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (first_record && hipMemcpy(first_record, g.d_first_record, (n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (n_lines && n_seg && hipMemcpy(n_lines, g.d_n_lines, n_seg * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (n_selected && n_seg && hipMemcpy(n_selected, g.d_n_selected, n_seg * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
 }
 
 int hg_copy_context(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max) {

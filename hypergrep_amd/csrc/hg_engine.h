@@ -10,6 +10,7 @@
 #include "hg_core.h"
 #include "hg_invert.h"
 #include "hg_context.h"
+#include "hg_segments.h"
 #include "hg_post.h"
 
 // Waves per stream workgroup (one 16 KiB tile per wave at a time); shared by the kernel and the grid sizing.
@@ -194,6 +195,22 @@ struct HgContextOutput {
   float ms_context;    // the stage: count, scan, the host sync that sizes the output, write
 };
 
+// The segment stage (hg_segments.hip), one step per launch on `stream`: the argument check (before the scan), the segments'
+// line bases (a wave per tile), the segments' runs of surviving records, and the ordered write of those runs.
+enum class HgSegStep { Check, PadFlag, PadWrite, Bases, Runs, Write };
+hipError_t hg_segments_launch(const HgSegArgs &a, HgSegStep step, uint32_t num_cus, hipStream_t stream);
+// What a call asks of it (hg_segments_t of the C ABI) and what it leaves (hg_segment_result_t).
+struct HgSegParams {
+  const uint64_t *d_seg_start, *d_seg_end;
+  uint32_t n_seg;
+  uint64_t max_per_segment;
+};
+struct HgSegOutput {
+  const uint32_t *d_record_segment;  // device arrays, valid until the next scan on this scanner
+  const uint64_t *d_first_record, *d_n_lines, *d_n_selected;
+  float ms_segments;  // the stage: check, bases, runs, scan, the host syncs, write
+};
+
 // Test / experiment knobs of the engine, read from the environment ONCE, when a scanner is created (never during a scan:
 // getenv is not safe against a concurrent setenv, and a scan must not change behaviour half-way).  None is needed in normal
 // use.  The limit-lowering ones exist so that tests reach segmented scans / chunk halving on small texts.
@@ -227,6 +244,11 @@ class HgScanner {
   // The same scan (inverted or not) with the context stage behind it: *out is exactly scan()'s, *ctx the pieces around its records.
   int scan_context(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, hipStream_t stream, const HgContextParams &params, bool invert,
                    HgScanOutput *out, HgContextOutput *ctx);
+  // The same scan (inverted or not) of a buffer of many files with the segment stage behind it: *out's records are the
+  // segments' surviving records, file-relative; its counters stay the packed scan's.  HG_ERR_ARG (nothing scanned) for
+  // malformed segments.
+  int scan_packed(const void *d_text, uint64_t nbytes, int buffer_size, hipStream_t stream, const HgSegParams &params, bool invert, HgScanOutput *out,
+                  HgSegOutput *seg);
   // Block mode (hs_scan): the whole buffer is one scan unit; hits carry line_no 0 and `to` relative to the buffer start.
   int scan_block(const void *d_text, uint64_t nbytes, hipStream_t stream, HgScanOutput *out);
   // Block mode for short blocks held in PINNED host memory (readable up to nbytes rounded up to 16): one launch, raw
@@ -271,6 +293,10 @@ class HgScanner {
   int invert_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, hipStream_t stream, HgScanOutput *out);
   int context_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const HgContextParams &params, hipStream_t stream, const HgScanOutput &out,
                    HgContextOutput *ctx);
+  int segment_alloc(uint64_t n_seg);
+  int segment_records(uint64_t n);
+  int pad_filter(const HgSegArgs &checked, float *ms, hipStream_t stream, HgScanOutput *out);
+  int segment_pass(const HgSegArgs &checked, float ms_check, hipStream_t stream, HgScanOutput *out, HgSegOutput *seg);
   int huge_lds_error() { return error(HG_ERR_HIP, "the huge-automaton kernel cannot have its LDS"); }
   bool fail(hipError_t e, const char *what);
   int error(int rc, const std::string &what) { err_ = what; return rc; }
@@ -371,6 +397,20 @@ class HgScanner {
   HgHit *d_ctx_hits_ = nullptr;
   HgHitAux *d_ctx_aux_ = nullptr;
   uint64_t ctx_cap_ = 0;
+  // segment stage (calls with segments only, allocated by the first one): per segment the line base / end, the first record
+  // and the length of its run, the exclusive scan of the lengths, n_lines and n_selected (seven arrays of seg_cap_ words in one
+  // block), the flag word of the argument check, the scan's scratch, and the compacted records with their segments and starts
+  uint64_t *d_segw_ = nullptr;
+  uint64_t seg_cap_ = 0;
+  uint32_t *d_seg_flag_ = nullptr;
+  uint8_t *d_seg_temp_ = nullptr;
+  size_t seg_temp_bytes_ = 0;
+  HgHit *d_seg_hits_ = nullptr;
+  HgHitAux *d_seg_aux_ = nullptr;
+  uint32_t *d_seg_of_ = nullptr, *d_seg_from_ = nullptr;
+  uint64_t seg_rec_cap_ = 0;
+  uint64_t *d_pad_keep_ = nullptr, *d_pad_pos_ = nullptr;  // pad filter of inverted calls: a flag per hit and their exclusive scan
+  uint64_t pad_cap_ = 0;
   uint32_t *d_seg_count2_ = nullptr;  // second set for double buffering
   HgCand *d_cands2_ = nullptr;
 };

@@ -242,7 +242,8 @@ HgScanner::~HgScanner() {
                   d_key_a_, d_key_b_, d_perm_a_, d_perm_b_, d_keep_, d_counters_, d_temp_, d_seg_count_, d_pflags_, d_deferred_, d_defer_count_, d_seg_count2_, d_cands2_, d_disc_, d_bucket2_, d_windows2_, d_groups_, d_acc_hits_, d_acc_aux_, d_huge_claim_, d_wtab_, d_from_, d_fin_fill_, d_fin_kept_, d_fin_big_,
                   d_combs_, d_comb_words_, d_comb_feed_, d_comb_count_, d_comb_pos_, d_comb_hits_, d_comb_aux_, d_comb_temp_, d_bounds_,
                   d_min_lengths_, d_minlen_hits_, d_minlen_aux_, d_inv_count_, d_inv_pos_, d_inv_temp_, d_inv_hits_, d_inv_aux_,
-                  d_ctx_count_, d_ctx_pos_, d_ctx_temp_, d_ctx_hits_, d_ctx_aux_};
+                  d_ctx_count_, d_ctx_pos_, d_ctx_temp_, d_ctx_hits_, d_ctx_aux_,
+                  d_segw_, d_seg_flag_, d_seg_temp_, d_seg_hits_, d_seg_aux_, d_seg_of_, d_seg_from_, d_pad_keep_, d_pad_pos_};
   for (void *p : ptrs) hgmem::dev_free(p, "scanner");
   hgmem::host_free(h_counters_, "h_counters_");
   for (auto &ev : ev_)
@@ -999,6 +1000,181 @@ int HgScanner::scan_context(const void *d_text, uint64_t nbytes, int buffer_size
   if (int rc = scan_impl(d_text, nbytes, buffer_size, line_base, false, invert, stream, out)) return rc;
   if (!params.any()) return HG_OK;  // no context asked for: the stage is skipped
   return context_pass(static_cast<const uint8_t *>(d_text), nbytes, static_cast<uint64_t>(buffer_size) - 1, line_base, params, stream, *out, ctx);
+}
+
+// The per-segment arrays of the segment stage, for n_seg segments (n_seg + 1 words each).
+int HgScanner::segment_alloc(uint64_t n_seg) {
+  if (n_seg + 1 > seg_cap_) {
+    const uint64_t cap = std::max<uint64_t>(n_seg + n_seg / 4 + 1, 4096);
+    seg_cap_ = 0;
+    HG_TRY(realloc_dev(d_segw_, 7 * cap, "d_segw_"), "alloc (segment stage)");
+    seg_cap_ = cap;
+  }
+  if (!d_seg_flag_) HG_TRY(realloc_dev(d_seg_flag_, 4, "d_seg_flag_"), "alloc (segment stage)");
+  size_t tb = 0;
+  HG_TRY(rocprim::exclusive_scan(nullptr, tb, d_segw_, d_segw_, uint64_t{0}, n_seg + 1, rocprim::plus<uint64_t>(), hipStream_t(nullptr)), "scan (segment stage)");
+  if (tb > seg_temp_bytes_ || !d_seg_temp_) {
+    seg_temp_bytes_ = 0;
+    HG_TRY(realloc_dev(d_seg_temp_, tb + tb / 4, "d_seg_temp_"), "alloc (segment stage)");
+    seg_temp_bytes_ = tb + tb / 4;
+  }
+  return HG_OK;
+}
+
+// Room for n compacted records (with their segments and starts of match).
+int HgScanner::segment_records(uint64_t n) {
+  if (n > seg_rec_cap_) {
+    const uint64_t cap = std::max<uint64_t>(n + n / 4, 4096);
+    seg_rec_cap_ = 0;
+    HG_TRY(realloc_dev(d_seg_hits_, cap, "d_seg_hits_"), "alloc (segment stage records)");
+    HG_TRY(realloc_dev(d_seg_aux_, cap, "d_seg_aux_"), "alloc (segment stage records)");
+    HG_TRY(realloc_dev(d_seg_of_, cap, "d_seg_of_"), "alloc (segment stage records)");
+    HG_TRY(realloc_dev(d_seg_from_, cap, "d_seg_from_"), "alloc (segment stage records)");
+    seg_rec_cap_ = cap;
+  }
+  return HG_OK;
+}
+
+// The pad filter of an inverted call, between the scan and the invert stage: the hits whose scanned bytes begin in a pad
+// belong to no file and must not deselect a piece (hg_seg_pad_hit).  Flags, their exclusive scan, an ordered write; *out
+// then describes the remaining hits (in the stage's record arrays: the invert stage reads them and writes its own).
+int HgScanner::pad_filter(const HgSegArgs &checked, float *ms, hipStream_t stream, HgScanOutput *out) {
+  const uint64_t n = out->n_hits;
+  out->d_from = nullptr;
+  if (!n) return HG_OK;
+  if (int rc = segment_records(n)) return rc;
+  if (n + 1 > pad_cap_) {
+    const uint64_t cap = std::max<uint64_t>(n + n / 4 + 1, 4096);
+    pad_cap_ = 0;
+    HG_TRY(realloc_dev(d_pad_keep_, cap, "d_pad_keep_"), "alloc (pad filter)");
+    HG_TRY(realloc_dev(d_pad_pos_, cap, "d_pad_pos_"), "alloc (pad filter)");
+    pad_cap_ = cap;
+  }
+  size_t tb = 0;
+  HG_TRY(rocprim::exclusive_scan(nullptr, tb, d_pad_keep_, d_pad_pos_, uint64_t{0}, n + 1, rocprim::plus<uint64_t>(), hipStream_t(nullptr)), "scan (pad filter)");
+  if (tb > seg_temp_bytes_ || !d_seg_temp_) {
+    seg_temp_bytes_ = 0;
+    HG_TRY(realloc_dev(d_seg_temp_, tb + tb / 4, "d_seg_temp_"), "alloc (pad filter)");
+    seg_temp_bytes_ = tb + tb / 4;
+  }
+  HgSegArgs a = checked;
+  a.hits = out->d_hits;
+  a.aux = out->d_aux;
+  a.n_hits = n;
+  a.pad_keep = d_pad_keep_;
+  a.pad_pos = d_pad_pos_;
+  a.out_hits = d_seg_hits_;
+  a.out_aux = d_seg_aux_;
+  HG_TRY(hipEventRecord(ev_[0], stream), "event");
+  HG_TRY(hg_segments_launch(a, HgSegStep::PadFlag, static_cast<uint32_t>(num_cus_), stream), "pad filter launch (flags)");
+  HG_TRY(rocprim::exclusive_scan(d_seg_temp_, tb, d_pad_keep_, d_pad_pos_, uint64_t{0}, n + 1, rocprim::plus<uint64_t>(), stream), "scan (pad filter)");
+  HG_TRY(hg_segments_launch(a, HgSegStep::PadWrite, static_cast<uint32_t>(num_cus_), stream), "pad filter launch (write)");
+  uint64_t total = 0;
+  HG_TRY(hipMemcpyAsync(&total, d_pad_pos_ + n, sizeof total, hipMemcpyDeviceToHost, stream), "copy count");
+  HG_TRY(hipEventRecord(ev_[3], stream), "event");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (pad filter)");
+  if (total > n) return error(HG_ERR_HIP, "the pad filter kept more hits than the scan has");
+  float t = 0;
+  (void)hipEventElapsedTime(&t, ev_[0], ev_[3]);
+  *ms += t;
+  out->n_hits = total;
+  out->d_hits = d_seg_hits_;
+  out->d_aux = d_seg_aux_;
+  return HG_OK;
+}
+
+// The segment stage over a finished call (*out: its final records, ordered by line, with their starts of match if any): the
+// segments' line bases from the scan's tile states (a wave per tile that holds a boundary), their runs of surviving records,
+// an exclusive scan of the runs' lengths, and the ordered write of the file-relative records (hg_segments.hip).  *out then
+// describes the surviving records; its counters and timings stay the packed scan's.
+int HgScanner::segment_pass(const HgSegArgs &checked, float ms_check, hipStream_t stream, HgScanOutput *out, HgSegOutput *seg) {
+  HgSegArgs a = checked;
+  a.end_piece = out->n_pieces;
+  a.sums = d_sums_;  // (the scan may have grown them: taken after it)
+  a.bases = d_bases_;
+  a.hits = out->d_hits;
+  a.aux = out->d_aux;
+  a.from = out->d_from;
+  a.n_hits = out->n_hits;
+  if (int rc = segment_records(out->n_hits)) return rc;
+  a.out_hits = d_seg_hits_;
+  a.out_aux = d_seg_aux_;
+  a.out_seg = d_seg_of_;
+  a.out_from = d_seg_from_;
+  size_t tb = seg_temp_bytes_;
+  uint64_t *first = const_cast<uint64_t *>(a.first);
+  HG_TRY(hipEventRecord(ev_[0], stream), "event");
+  HG_TRY(hg_segments_launch(a, HgSegStep::Bases, static_cast<uint32_t>(num_cus_), stream), "segment stage launch (bases)");
+  HG_TRY(hg_segments_launch(a, HgSegStep::Runs, static_cast<uint32_t>(num_cus_), stream), "segment stage launch (runs)");
+  HG_TRY(rocprim::exclusive_scan(d_seg_temp_, tb, a.kept, first, uint64_t{0}, a.n_seg + 1, rocprim::plus<uint64_t>(), stream), "scan (segment stage)");
+  HG_TRY(hg_segments_launch(a, HgSegStep::Write, static_cast<uint32_t>(num_cus_), stream), "segment stage launch (write)");
+  uint64_t total = 0;
+  HG_TRY(hipMemcpyAsync(&total, first + a.n_seg, sizeof total, hipMemcpyDeviceToHost, stream), "copy count");
+  HG_TRY(hipEventRecord(ev_[3], stream), "event");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (segment stage)");
+  if (total > out->n_hits) return error(HG_ERR_HIP, "the segment stage kept more records than the scan has");
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, ev_[0], ev_[3]);
+  seg->ms_segments = ms_check + ms;
+  seg->d_record_segment = d_seg_of_;
+  seg->d_first_record = a.first;
+  seg->d_n_lines = a.n_lines;
+  seg->d_n_selected = a.n_selected;
+  out->n_hits = total;
+  out->d_hits = d_seg_hits_;
+  out->d_aux = d_seg_aux_;
+  if (out->d_from) out->d_from = d_seg_from_;
+  return HG_OK;
+}
+
+int HgScanner::scan_packed(const void *d_text, uint64_t nbytes, int buffer_size, hipStream_t stream, const HgSegParams &params, bool invert, HgScanOutput *out,
+                           HgSegOutput *seg) {
+  if (!out || !seg || (!d_text && nbytes) || buffer_size < 2 || (params.n_seg && (!params.d_seg_start || !params.d_seg_end)))
+    return error(HG_ERR_ARG, "invalid arguments");
+  if ((reinterpret_cast<uintptr_t>(d_text) & 15u) != 0) return error(HG_ERR_ARG, "text pointer must be 16-byte aligned");
+  *seg = HgSegOutput{};
+  HG_TRY(hipSetDevice(device_), "hipSetDevice");
+  const uint64_t n_seg = params.n_seg;
+  if (int rc = segment_alloc(n_seg)) return rc;
+  HgSegArgs a{};
+  a.text = static_cast<const uint8_t *>(d_text);
+  a.nbytes = nbytes;
+  a.bs1 = static_cast<uint64_t>(buffer_size) - 1;
+  a.ntiles = (nbytes + HG_TILE_BYTES - 1) / HG_TILE_BYTES;
+  a.seg_start = params.d_seg_start;
+  a.seg_end = params.d_seg_end;
+  a.n_seg = n_seg;
+  a.limit = params.max_per_segment;
+  a.invert = invert ? 1u : 0u;
+  a.flag = d_seg_flag_;
+  a.B = d_segw_;
+  a.E = d_segw_ + seg_cap_;
+  a.r0 = d_segw_ + 2 * seg_cap_;
+  a.kept = d_segw_ + 3 * seg_cap_;
+  a.first = d_segw_ + 4 * seg_cap_;
+  a.n_lines = d_segw_ + 5 * seg_cap_;
+  a.n_selected = d_segw_ + 6 * seg_cap_;
+  // the argument check comes first: malformed segments scan nothing
+  uint32_t bad = 0;
+  HG_TRY(hipEventRecord(ev_[0], stream), "event");
+  HG_TRY(hipMemsetAsync(d_seg_flag_, 0, sizeof(uint32_t), stream), "memset (segment stage)");
+  HG_TRY(hg_segments_launch(a, HgSegStep::Check, static_cast<uint32_t>(num_cus_), stream), "segment stage launch (check)");
+  HG_TRY(hipMemcpyAsync(&bad, d_seg_flag_, sizeof bad, hipMemcpyDeviceToHost, stream), "copy flag");
+  HG_TRY(hipEventRecord(ev_[3], stream), "event");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (segment check)");
+  if (bad)
+    return error(HG_ERR_ARG, bad & HG_SEG_BAD_ORDER ? "segments are not ascending or overlap"
+                             : bad & HG_SEG_BAD_END ? "a segment ends past the buffer"
+                                                    : "a segment does not start at a line start");
+  float ms_check = 0;
+  (void)hipEventElapsedTime(&ms_check, ev_[0], ev_[3]);
+  // an inverted call: the plain scan, the pad filter, then the invert stage on the hits that belong to a file
+  if (int rc = scan_impl(d_text, nbytes, buffer_size, 0, false, false, stream, out)) return rc;
+  if (invert) {
+    if (int rc = pad_filter(a, &ms_check, stream, out)) return rc;
+    if (int rc = invert_pass(a.text, nbytes, a.bs1, 0, stream, out)) return rc;
+  }
+  return segment_pass(a, ms_check, stream, out, seg);
 }
 
 int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const PassRange &range, bool block_mode, hipStream_t stream,

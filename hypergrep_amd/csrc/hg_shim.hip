@@ -29,6 +29,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -517,14 +518,14 @@ struct Ring {
   char *storage = nullptr;  // buffer_count line buffers of buffer_size bytes (hyperscanner.c:277-291); malloc, not a zero-filled
                             // vector: with a large buffer_count most of it is never touched (1 GiB for 4096 x 262140)
   int fill = 0;
-  hs_event cb = nullptr;
+  std::function<void(hyperscanner_result_t *, int)> cb;  // (hs_event, or hg_hyperscan_files' event with its file index)
   unsigned long long delivered = 0;
   Ring() = default;
   Ring(const Ring &) = delete;
   Ring &operator=(const Ring &) = delete;
   ~Ring() { std::free(storage); }
-  bool init(int count, int buffer_size, hs_event on_event) {
-    cb = on_event;
+  bool init(int count, int buffer_size, std::function<void(hyperscanner_result_t *, int)> on_event) {
+    cb = std::move(on_event);
     try {
       slots.resize(static_cast<size_t>(count));
     } catch (const std::bad_alloc &) {
@@ -581,10 +582,11 @@ extern "C" int hyperscan(char *file_name, const char *const *patterns, const uns
 // With context lines (before / after, hg_hyperscan_context) each chunk is scanned with the context stage behind it and the
 // two ordered lists are merged; between chunks the call carries what the device API's chaining identity needs: the
 // after-context still owed (owed_after -> carry_after) and the bytes of the previous chunks' tail pieces, `before` at most.
-static int scan_file(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
-                     const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hs_event on_event,
+using FileEvent = std::function<void(hyperscanner_result_t *, int)>;
+static int scan_file(const char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                     const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, FileEvent on_event,
                      const int buffer_size, int buffer_count, unsigned long long max_match_count, const bool invert, const uint32_t before = 0,
-                     const uint32_t after = 0) {
+                     const uint32_t after = 0, uint64_t *pieces_scanned = nullptr) {
   if (max_match_count > 0 && max_match_count < static_cast<unsigned long long>(buffer_count)) buffer_count = static_cast<int>(max_match_count);
   if (buffer_count < 1 || buffer_size < 1 || !on_event) return HYPERSCANNER_STATE_MEM;
   Ring ring;
@@ -877,11 +879,201 @@ static int scan_file(char *file_name, const char *const *patterns, const unsigne
   stop_reader();
   (void)hipStreamSynchronize(ctx->copy_stream);  // a copy issued ahead may still be in flight
   ring.flush();
+  if (pieces_scanned) *pieces_scanned = line_base;
   if (trace)
     std::fprintf(stderr, "[hypergrep_amd] %s: %.1f MiB in %.4f s; reader filling slots %.4f s; consumer: waiting for data %.4f s, window tuning + scanner %.4f s (%s), copy + scan %.4f s, delivering %llu hits %.4f s\n",
                  file_name, bytes_in / 1048576.0, now() - t_call, t_read, t_wait_slot, t_setup, db->tuned ? "tuned windows" : "static windows", t_scan,
                  static_cast<unsigned long long>(ring.delivered), t_deliver);
   return rc;
+}
+
+// Many files in one call (grep -r): the files are packed, in the given order, into buffers of at most the file path's chunk
+// size by the packing rule of hg_scan_device_segments (an unterminated file is followed by "\0\n"), and each pack is ONE scan
+// with the segment stage behind it.  A file that does not fit a pack, a compressed one (the decoder of the per-file route reads
+// it), a pipe or the like, and everything when buffer_size < 2, takes scan_file inside the call; the call never holds a
+// context of the pool while scan_file takes one.  An empty regular file is an empty segment.  Batches go out in file
+// order and no batch mixes files; a file's results and rc are those of hg_hyperscan_ext / hg_hyperscan_invert for that file.
+// The line bytes of a result come from the pack's host copy: only the 32-byte records and the per-file arrays leave the GPU.
+extern "C" int hg_hyperscan_files(const char *const *file_names, unsigned int n_files, const char *const *patterns, const unsigned int *pattern_flags,
+                                  const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hg_files_event on_event,
+                                  void *context, const int buffer_size, int buffer_count, unsigned long long max_match_count, int invert,
+                                  hg_file_summary_t *summaries) {
+  if (!summaries || (!file_names && n_files) || buffer_count < 1 || buffer_size < 1) return HYPERSCANNER_STATE_MEM;
+  if (max_match_count > 0 && max_match_count < static_cast<unsigned long long>(buffer_count)) buffer_count = static_cast<int>(max_match_count);
+  for (unsigned int i = 0; i < n_files; i++) summaries[i] = hg_file_summary_t{0, 0, 0};
+  std::string err;
+  std::shared_ptr<const HgDb> db = get_db(patterns, pattern_flags, pattern_ids, ext, elements, &err);
+  if (!db) {
+    std::fprintf(stderr, "ERROR: Unable to create database. Exiting.\n");
+    return HYPERSCANNER_DB;
+  }
+  // one file through the per-file route: its events carry its index, its distinct lines are counted on the way
+  auto single = [&](unsigned int f) {
+    uint64_t selected = 0, last = ~0ull, pieces = 0;
+    FileEvent ev = [&](hyperscanner_result_t *r, int n) {
+      for (int i = 0; i < n; i++)
+        if (r[i].line_number != last) {
+          last = r[i].line_number;
+          selected++;
+        }
+      if (on_event) on_event(f, r, n, context);
+    };
+    const int rc = scan_file(file_names[f], patterns, pattern_flags, pattern_ids, ext, elements, ev, buffer_size, buffer_count, max_match_count, invert != 0, 0, 0, &pieces);
+    summaries[f] = hg_file_summary_t{rc, pieces, selected};
+  };
+  const size_t cap = chunk_bytes();
+  Ctx *ctx = nullptr;
+  bool healthy = true;
+  struct Return {
+    Ctx **c;
+    bool *healthy;
+    ~Return() {
+      if (*c) checkin(*c, *healthy);
+    }
+  } ret_guard{&ctx, &healthy};
+  uint64_t *d_segs = nullptr;  // seg_start and seg_end of the pack, one after the other
+  size_t d_segs_cap = 0;
+  struct FreeSegs {
+    uint64_t **p;
+    ~FreeSegs() { hgmem::dev_free(*p, "d_segs"); }
+  } free_segs{&d_segs};
+  std::vector<uint64_t> seg_start, seg_end, first, n_lines, n_selected;
+  std::vector<unsigned int> seg_file;
+  size_t fill = 0;  // bytes of the pack so far (in ctx->h_slot[0])
+  Ring ring;
+  unsigned int cur_file = 0;
+  if (on_event && !ring.init(buffer_count, std::max(buffer_size, 2), [&](hyperscanner_result_t *r, int n) { on_event(cur_file, r, n, context); }))
+    return HYPERSCANNER_COMPILE_MEM;
+  auto fail_pack = [&](int rc) {
+    for (unsigned int f : seg_file) summaries[f].rc = rc;
+    healthy = false;
+  };
+  // scan the pack and deliver its files
+  auto flush_pack = [&]() {
+    if (seg_file.empty()) return;
+    const size_t n_seg = seg_file.size();
+    bool ok = hipSetDevice(ctx->device) == hipSuccess && ensure_scanner(ctx, db, &err);
+    if (ok && 2 * n_seg > d_segs_cap) {
+      hgmem::dev_free(d_segs, "d_segs");
+      d_segs = nullptr;
+      d_segs_cap = std::max<size_t>(2 * n_seg + n_seg / 2, 4096);
+      ok = hgmem::dev_alloc(&d_segs, d_segs_cap * sizeof(uint64_t), "d_segs") == hipSuccess;
+      if (!ok) d_segs_cap = 0;
+    }
+    if (!ok) {
+      std::fprintf(stderr, "ERROR: Unable to allocate scratch space. Exiting. (%s)\n", err.c_str());
+      fail_pack(HYPERSCANNER_SCRATCH);
+    } else {
+      const uint8_t *host = ctx->h_slot[0];
+      HgScanOutput out{};
+      HgSegOutput seg{};
+      const HgSegParams params{d_segs, d_segs + n_seg, static_cast<uint32_t>(n_seg), max_match_count};
+      first.resize(n_seg + 1);
+      n_lines.resize(n_seg);
+      n_selected.resize(n_seg);
+      bool copied = (!fill || hipMemcpyAsync(ctx->d_text[0], host, fill, hipMemcpyHostToDevice, ctx->stream) == hipSuccess) &&
+                    hipMemcpyAsync(d_segs, seg_start.data(), n_seg * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+                    hipMemcpyAsync(d_segs + n_seg, seg_end.data(), n_seg * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+                    hipStreamSynchronize(ctx->stream) == hipSuccess;
+      int src = copied ? ctx->sc->scan_packed(ctx->d_text[0], fill, buffer_size, ctx->stream, params, invert != 0, &out, &seg) : HG_ERR_HIP;
+      if (src == HG_OK) {
+        const bool rows = on_event != nullptr && out.n_hits;  // counts only: no record leaves the GPU
+        ctx->hits.resize(rows ? out.n_hits : 0);
+        ctx->aux.resize(rows ? out.n_hits : 0);
+        if ((rows && (hipMemcpyAsync(ctx->hits.data(), out.d_hits, out.n_hits * sizeof(HgHit), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                      hipMemcpyAsync(ctx->aux.data(), out.d_aux, out.n_hits * sizeof(HgHitAux), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) ||
+            hipMemcpyAsync(first.data(), seg.d_first_record, (n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(n_lines.data(), seg.d_n_lines, n_seg * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(n_selected.data(), seg.d_n_selected, n_seg * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess)
+          src = HG_ERR_HIP;
+      }
+      if (src != HG_OK) {
+        std::fprintf(stderr, "ERROR: Unable to scan buffer. Exiting. (%s)\n", ctx->sc ? ctx->sc->last_error().c_str() : "copy");
+        fail_pack(HYPERSCANNER_SCAN);
+      } else {
+        for (size_t s = 0; s < n_seg; s++) {
+          cur_file = seg_file[s];
+          summaries[cur_file] = hg_file_summary_t{0, n_lines[s], n_selected[s]};
+          if (!on_event) continue;
+          const uint8_t *base = host + seg_start[s];  // the records are file-relative
+          // line by line; inside a line reports go out by ascending end offset, then id (as scan_file)
+          for (size_t i = first[s], j; i < first[s + 1]; i = j) {
+            for (j = i; j < first[s + 1] && ctx->hits[j].line_no == ctx->hits[i].line_no; j++) {}
+            std::vector<size_t> order(j - i);
+            for (size_t q = 0; q < order.size(); q++) order[q] = i + q;
+            std::sort(order.begin(), order.end(), [&](size_t x, size_t y) {
+              if (ctx->hits[x].to != ctx->hits[y].to) return ctx->hits[x].to < ctx->hits[y].to;
+              return ctx->hits[x].id < ctx->hits[y].id;
+            });
+            for (size_t q : order) ring.push(ctx->hits[q].id, ctx->hits[q].line_no, base + ctx->aux[q].start, ctx->aux[q].len);
+          }
+          ring.flush();  // no batch mixes files
+        }
+      }
+    }
+    seg_start.clear();
+    seg_end.clear();
+    seg_file.clear();
+    fill = 0;
+  };
+  for (unsigned int f = 0; f < n_files; f++) {
+    if (!healthy) {  // a device error ended the packs: the rest is not scanned
+      summaries[f].rc = HYPERSCANNER_SCAN;
+      continue;
+    }
+    Reader in;
+    if (!file_names[f] || !in.open(file_names[f])) {
+      summaries[f].rc = HYPERSCANNER_GZ_OPEN;
+      continue;
+    }
+    const size_t size = in.size_hint();
+    struct stat st;
+    const bool empty_regular = !in.compressed() && !size && ::stat(file_names[f], &st) == 0 && S_ISREG(st.st_mode) && st.st_size == 0;
+    if (buffer_size < 2 || in.compressed() || (!size && !empty_regular) || size + 2 > cap) {  // the per-file route, in its place in the order
+      flush_pack();
+      // scan_file takes a context of its own from the bounded pool: this call's goes back first (a call that held one while
+      // it waited for a second could wait for ever: HYPERGREP_POOL=1, or as many concurrent calls as the pool holds)
+      if (ctx) {
+        checkin(ctx, healthy);
+        ctx = nullptr;
+      }
+      if (healthy) single(f);
+      else summaries[f].rc = HYPERSCANNER_SCAN;
+      continue;
+    }
+    if (fill + size + 2 > cap) flush_pack();
+    if (!healthy) {
+      summaries[f].rc = HYPERSCANNER_SCAN;
+      continue;
+    }
+    if (!ctx) {
+      ctx = checkout(db, &err);
+      if (!ctx || hipSetDevice(ctx->device) != hipSuccess || !ensure_buffers(ctx, cap, 1)) {
+        std::fprintf(stderr, "ERROR: Unable to allocate scratch space. Exiting. (%s)\n", err.c_str());
+        if (ctx) healthy = false;
+        for (unsigned int g = f; g < n_files; g++) summaries[g].rc = HYPERSCANNER_SCRATCH;
+        return 0;
+      }
+    }
+    uint8_t *buf = ctx->h_slot[0];
+    size_t got = 0;
+    while (got < size) {  // (the size seen at open: a file that grows meanwhile is read up to it)
+      const long r = in.read(buf + fill + got, size - got);
+      if (r <= 0) break;
+      got += static_cast<size_t>(r);
+    }
+    seg_start.push_back(fill);
+    seg_end.push_back(fill + got);
+    seg_file.push_back(f);
+    fill += got;
+    if (got && buf[fill - 1] != '\n') {  // the pad behind an unterminated file
+      buf[fill++] = 0;
+      buf[fill++] = '\n';
+    }
+  }
+  if (healthy) flush_pack();
+  return 0;
 }
 
 extern "C" int hg_hyperscan_ext(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,

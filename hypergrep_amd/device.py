@@ -48,6 +48,15 @@ class HgContextResult(ctypes.Structure):
                 ("d_ctx_aux", ctypes.c_void_p), ("context_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class HgSegments(ctypes.Structure):
+    _fields_ = [("d_seg_start", ctypes.c_void_p), ("d_seg_end", ctypes.c_void_p), ("n_seg", ctypes.c_uint32), ("max_per_segment", ctypes.c_uint64)]
+
+
+class HgSegmentResult(ctypes.Structure):
+    _fields_ = [("d_record_segment", ctypes.c_void_p), ("d_first_record", ctypes.c_void_p), ("d_n_lines", ctypes.c_void_p), ("d_n_selected", ctypes.c_void_p),
+                ("segments_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class HgDbInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("n_patterns", "n_literal_anchored", "n_always_on", "n_factors", "n_windows",
                                                "fold_mask", "max_state_words", "table_bytes", "byte_windows")]
@@ -90,6 +99,11 @@ def lib() -> ctypes.CDLL:
                                                  ctypes.POINTER(HgContext), ctypes.c_int, ctypes.POINTER(HgScanResult), ctypes.POINTER(HgContextResult)]
             l.hg_copy_context.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
             l.hg_copy_context_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        if hasattr(l, "hg_scan_device_segments"):  # (absent from a build before the segment stage)
+            l.hg_scan_device_segments.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(HgSegments),
+                                                  ctypes.c_int, ctypes.POINTER(HgScanResult), ctypes.POINTER(HgSegmentResult)]
+            l.hg_copy_segments.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                           ctypes.POINTER(ctypes.c_uint64)]
         l.hg_copy_hits.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
         l.hg_copy_hits_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hit_starts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
@@ -165,6 +179,7 @@ class ScanStats:
     owed_after: int = 0  # ... the after-context pieces still owed past the buffer's end (the next buffer's carry_after)
     n_tail: int = 0  # ... the tail records among n_context
     context_us: int = 0  # ... the context stage alone, microseconds
+    segments_us: int = 0  # scans with segments: the segment stage alone, microseconds
 
 
 class Scanner:
@@ -174,22 +189,59 @@ class Scanner:
         self.db = db
         self._h = ctypes.c_void_p()
         err = ctypes.create_string_buffer(512)
+        self._device = device
         rc = lib().hg_scanner_create(db._h, device, ctypes.byref(self._h), err, 512)
         if rc != 0:
             raise DeviceError(f"hg_scanner_create failed ({rc}): {err.value.decode(errors='replace')}")
         self._last = HgScanResult()
         self._last_ctx = HgContextResult()
+        self._last_seg = None  # (HgSegmentResult, n_seg) of the last scan, if it had segments
+        self._seg_arena = None
+
+    def _place_segments(self, starts, ends):
+        """The two offset lists as device arrays (one guarded allocation of the scanner's, grown when needed)."""
+        import struct
+
+        n = len(starts)
+        if len(ends) != n:
+            raise ValueError("segments: as many ends as starts")
+        blob = struct.pack(f"<{2 * n}Q", *starts, *ends)
+        if self._seg_arena is None or self._seg_arena.capacity < len(blob):
+            if self._seg_arena is not None:
+                self._seg_arena.free()
+            self._seg_arena = GuardedArena(max(2 * len(blob), 1 << 16), self._device)
+        ptr = self._seg_arena.place(blob)
+        return ptr, ptr + 8 * n, n
 
     def scan(self, d_text: int, nbytes: int, buffer_size: int = 262140, line_base: int = 0, stream: int = 0, invert: bool = False,
-             context: tuple[int, int] | None = None, carry_after: int = 0, tail: bool = False) -> ScanStats:
+             context: tuple[int, int] | None = None, carry_after: int = 0, tail: bool = False, segments=None, max_per_segment: int = 0) -> ScanStats:
         """invert: the result is the line pieces without any report (grep -v; hg_scan_device_invert): n_hits of them, and
         hits() gives (line_number, HG_ID_INVERT, 0, start, len) per piece in line order.
         context = (before, after): grep -B / -A in line pieces (hg_scan_device_context).  hits() is what it is without context;
         context() gives the pieces around them.  carry_after: the owed_after of the previous buffer of a chain; tail: also
-        deliver the last `before` pieces that are neither match nor context, as HG_ID_CONTEXT_TAIL records."""
+        deliver the last `before` pieces that are neither match nor context, as HG_ID_CONTEXT_TAIL records.
+        segments = (starts, ends): the text holds many files one after the other (hg_scan_device_segments has the packing
+        rule); two sequences of offsets, or (d_starts, d_ends, n) for arrays already on the device.  hits() then gives every
+        file's records as a scan of the file alone would, file after file, and segments() says which are whose.
+        max_per_segment: keep a file's records up to the line on which their count reaches it (0: all)."""
         res = HgScanResult()
         cres = HgContextResult()
-        if context is not None or carry_after or tail:
+        sres = HgSegmentResult()
+        self._last_seg = None
+        if segments is not None:
+            if context is not None or carry_after or tail or line_base:
+                raise ValueError("segments: context lines and line_base are not supported")
+            d_starts, d_ends, n_seg = segments if len(segments) == 3 else self._place_segments(*segments)
+            name = "hg_scan_device_segments"
+            seg = HgSegments(d_starts, d_ends, n_seg, max_per_segment)
+            rc = lib().hg_scan_device_segments(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, ctypes.c_void_p(stream), ctypes.byref(seg), 1 if invert else 0,
+                                               ctypes.byref(res), ctypes.byref(sres))
+            if rc == -1:  # HG_ERR_ARG: nothing was scanned
+                self._last = HgScanResult()
+                raise ValueError(f"{name}: {lib().hg_scanner_error(self._h).decode(errors='replace')}")
+            if rc == 0:
+                self._last_seg = (sres, n_seg)
+        elif context is not None or carry_after or tail:
             before, after = context or (0, 0)
             name = "hg_scan_device_context"
             ctx = HgContext(before, after, carry_after, HG_CONTEXT_TAIL if tail else 0)
@@ -203,7 +255,25 @@ class Scanner:
         self._last = res
         self._last_ctx = cres
         return ScanStats(res.n_hits, res.n_lines, res.n_candidates, res.n_raw_hits, res.ms_stream, res.ms_total, res.reruns, res.stream_launches, res.joiner_launches, res.joiner_tiles,
-                         res.invert_us, cres.n_context, cres.owed_after, cres.n_tail, cres.context_us)
+                         res.invert_us, cres.n_context, cres.owed_after, cres.n_tail, cres.context_us, sres.segments_us)
+
+    def segments(self):
+        """The per-file arrays of the last scan with segments, as uint64 / uint32 numpy arrays: a dict with record_segment (one
+        per record of hits()), first_record (n + 1: file s owns hits()[first_record[s]:first_record[s + 1]]), n_lines and
+        n_selected (n each)."""
+        import numpy as np
+
+        if self._last_seg is None:
+            raise ValueError("the last scan had no segments")
+        _, n_seg = self._last_seg
+        out = {"record_segment": np.zeros(self._last.n_hits, dtype=np.uint32), "first_record": np.zeros(n_seg + 1, dtype=np.uint64),
+               "n_lines": np.zeros(n_seg, dtype=np.uint64), "n_selected": np.zeros(n_seg, dtype=np.uint64)}
+        p64 = ctypes.POINTER(ctypes.c_uint64)
+        rc = lib().hg_copy_segments(self._h, out["record_segment"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), out["first_record"].ctypes.data_as(p64),
+                                    out["n_lines"].ctypes.data_as(p64), out["n_selected"].ctypes.data_as(p64))
+        if rc != 0:
+            raise DeviceError(f"hg_copy_segments failed ({rc})")
+        return out
 
     def context(self, limit: int | None = None):
         """Last scan's context records as a list of (line_number, HG_ID_CONTEXT | HG_ID_CONTEXT_TAIL, 0, start, len), in line
@@ -282,6 +352,9 @@ class Scanner:
         if getattr(self, "_h", None) and lib is not None:  # (module globals are gone at interpreter shutdown)
             lib().hg_scanner_destroy(self._h)
             self._h = None
+            if getattr(self, "_seg_arena", None) is not None:
+                self._seg_arena.free()
+                self._seg_arena = None
 
 
 def _spec(seed: int, first_block: int, hit_per_million: int, needles):

@@ -43,6 +43,24 @@ def get_argparse_files(args: argparse.Namespace) -> list[str]:
     return named
 
 
+def expand_directories(names: list[str], sort_files: bool = True) -> list[str]:
+    """-r / -R: every directory among `names` is replaced by the regular files below it (walked top down; sorted by path unless
+    sort_files is False, then in the order the directory listing gives them).  Other names stay as they are."""
+    found: list[str] = []
+    for name in names:
+        if not os.path.isdir(name):
+            found.append(name)
+            continue
+        below = []
+        for root, directories, members in os.walk(name):
+            if sort_files:
+                directories.sort()
+                members = sorted(members)
+            below.extend(path for path in (os.path.join(root, member) for member in members) if os.path.isfile(path))
+        found.extend(sorted(below) if sort_files else below)
+    return found
+
+
 def get_argparse_patterns(args: argparse.Namespace) -> list[str]:
     """Patterns from -e, -f FILE (one per line) or, without either, the first positional.
 
@@ -189,6 +207,21 @@ def parallel_grep(  # pylint: disable=too-many-arguments,too-many-locals
     }
     if context:
         job_kwargs.update(before_context=before_context, after_context=after_context)
+    # More than one file, no context, threads: the batch route.  The files share one native call, small ones one GPU scan
+    # (hypergrep_amd.grep_files); the outcomes are replayed exactly as the per-file jobs' are.  HYPERGREP_BATCH_FILES=0 keeps
+    # the per-file route (A/B runs).
+    if len(files) > 1 and not context and use_multithreading and os.environ.get("HYPERGREP_BATCH_FILES", "1") != "0":
+        try:
+            outcomes = hypergrep_amd.utils.grep_files_outcomes(files, patterns, **job_kwargs)
+        except Exception as error:  # pylint: disable=broad-except
+            outcomes = [error] * len(files)  # (what every per-file job would have raised: a pattern `re` rejects)
+        for index, outcome in enumerate(outcomes):
+            replay.accept(index, outcome)
+            if quiet and replay.matched:
+                break
+        if total_results:
+            print(replay.total)
+        return 2 if replay.errored else (0 if replay.matched else 1)
     # the reference runs one job per core; here a job is a GPU scan with its own reader threads and pinned buffers, so a
     # handful in flight already keeps every GPU of the node busy
     workers = max(1, min(len(files), max((os.cpu_count() or 2) - 1, 1), 16))
@@ -363,9 +396,12 @@ def parse_args(args: list = None) -> argparse.Namespace:
     names.add_argument("-h", "--no-filename", action="store_true", default=None, help="No file name prefix (default with one file).")
     prefix.add_argument("-n", "--line-number", action="store_true", help="Prefix lines with their 1-based line number.")
 
-    parser.add_argument_group("File and Directory Selection").add_argument(
-        "-a", "--text", action="store_true", help="Accepted for grep compatibility; files are always read as bytes."
-    )
+    selection = parser.add_argument_group("File and Directory Selection")
+    selection.add_argument("-a", "--text", action="store_true", help="Accepted for grep compatibility; files are always read as bytes.")
+    # (no attribute unless given, like -v)
+    selection.add_argument("-r", "-R", "--recursive", dest="recursive", action="store_true", default=argparse.SUPPRESS,
+                           help="Read all regular files under each directory; -H becomes the default.  -R is a synonym: symbolic links to\n"
+                                "directories are not followed, symbolic links to files are read.")
 
     own = parser.add_argument_group("Unique arguments to hyperscanner")
     own.add_argument("-t", "--total", action="store_true", help="Print one count of matching lines over all files.")
@@ -393,6 +429,9 @@ def main() -> None:
     if args.gnu_regexp and args.regexp != "pcre":
         patterns = to_gnu_regular_expressions(patterns)
     files = get_argparse_files(args) or list(read_stdin())
+    recursive = getattr(args, "recursive", False)
+    if recursive:  # (without -r a directory stays an error of its own, reported in its place)
+        files = expand_directories(files, args.sort_files)
     if args.sort_files:
         files = sorted(files)
     if not files:
@@ -403,7 +442,7 @@ def main() -> None:
     elif args.with_filename is not None:
         with_file_name = True
     else:
-        with_file_name = len(files) > 1
+        with_file_name = recursive or len(files) > 1
     raise SystemExit(
         parallel_grep(
             files=files,

@@ -221,6 +221,63 @@ def scan(  # pylint: disable=too-many-arguments
     return outcome[0]
 
 
+# void on_event(unsigned file_index, Result *batch, int count, void *context)  (hg_files_event)
+FILES_CALLBACK_TYPE = ctypes.CFUNCTYPE(None, ctypes.c_uint, ctypes.POINTER(Result), ctypes.c_int, ctypes.c_void_p, use_errno=False, use_last_error=False)
+
+
+class FileSummary(ctypes.Structure):
+    """hg_file_summary_t: a file's return code (scan()'s), its line pieces and the distinct lines among its results."""
+
+    _fields_ = [("rc", ctypes.c_int), ("n_lines", ctypes.c_uint64), ("n_selected", ctypes.c_uint64)]
+
+
+def scan_files(  # pylint: disable=too-many-arguments
+    files: Sequence[str],
+    patterns: list[str],
+    on_match: Callable | None,
+    flags: list[int] = (),
+    ids: list[int] = (),
+    buffer_size: int = 262140,
+    buffer_count: int = 16,
+    max_match_count: int = 0,
+    ext=None,
+    invert: bool = False,
+) -> list[tuple[int, int, int]]:
+    """scan() for many files in ONE native call (hg_hyperscan_files): small files are packed into one buffer and share one GPU
+    scan.  `on_match(file_index, matches, count)` receives each file's results in batches of `buffer_count`, in file order, no
+    batch mixing files; every file's results are those scan() gives for it alone (`max_match_count` bounds each file).  Without
+    a callback (None) only the per-file summaries are produced.  Returns one (return code, line pieces, distinct result lines)
+    per file; a missing or unreadable file has return code 6 and does not disturb the others.  Context lines are not offered."""
+    names = [os.fspath(name) for name in files]
+    c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags, ids=ids)
+    c_ext = None if ext is None else ext_array(ext, len(c_patterns))
+    c_names = (ctypes.c_char_p * max(len(names), 1))(*[name.encode() for name in names])
+    summaries = (FileSummary * max(len(names), 1))()
+    if on_match is None:
+        c_callback = ctypes.cast(None, FILES_CALLBACK_TYPE)
+    else:
+        c_callback = FILES_CALLBACK_TYPE(lambda index, matches, count, _context: on_match(index, matches, count))  # referenced until the call is over
+    engine = _get_hyperscanner_lib()
+    engine.hg_hyperscan_files.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint),
+                                          ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.POINTER(ExprExt)), ctypes.c_uint, FILES_CALLBACK_TYPE,
+                                          ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, ctypes.POINTER(FileSummary)]
+    outcome = [0]
+
+    def native_call() -> None:
+        outcome[0] = engine.hg_hyperscan_files(c_names, len(names), c_patterns, c_flags, c_ids, c_ext, len(c_patterns), c_callback, None, buffer_size,
+                                               buffer_count, max_match_count, 1 if invert else 0, summaries)
+
+    worker = threading.Thread(target=native_call, daemon=True)
+    worker.start()
+    try:
+        worker.join(timeout=_JOIN_TIMEOUT_S)
+    except KeyboardInterrupt:
+        return [(_RC_INTERRUPTED, 0, 0)] * len(names)
+    if outcome[0]:  # a failure of the whole call (the expressions do not compile): every file reports it, as scan() would
+        return [(outcome[0], 0, 0)] * len(names)
+    return [(summaries[i].rc, summaries[i].n_lines, summaries[i].n_selected) for i in range(len(names))]
+
+
 class _GrepSink:
     """on_match for grep(): counts, keeps whole lines, or keeps the matched parts (`re.finditer` of the pattern whose
     id the hit carries — with grep()'s all-zero ids that is the first pattern, as in the reference)."""
@@ -318,3 +375,58 @@ def grep(  # pylint: disable=too-many-arguments
     return_code = scan(file, patterns, sink, flags=[flags] * len(patterns), max_match_count=max_match_count, invert=invert,
                        before_context=before_context, after_context=after_context)
     return sink.result(), return_code
+
+
+def grep_files_outcomes(files: Sequence[str], patterns: list[str], **grep_kwargs) -> list:
+    """What grep(file, patterns, **grep_kwargs) gives for every file, in order: its result, or the exception it raises (not
+    raised here).  The files share one native call (scan_files); with context lines each file takes grep()."""
+    names = list(files)
+    outcomes: list = [None] * len(names)
+    if grep_kwargs.get("before_context") or grep_kwargs.get("after_context"):
+        for index, name in enumerate(names):
+            try:
+                outcomes[index] = grep(name, patterns, **grep_kwargs)
+            except Exception as error:  # pylint: disable=broad-except
+                outcomes[index] = error
+        return outcomes
+    ignore_case = grep_kwargs.get("ignore_case", False)
+    count_only = grep_kwargs.get("count_only", False)
+    only_matching = grep_kwargs.get("only_matching", False)
+    no_messages = grep_kwargs.get("no_messages", False)
+    invert = grep_kwargs.get("invert", False)
+    max_match_count = grep_kwargs.get("max_match_count", 0)
+    unknown = set(grep_kwargs) - {"ignore_case", "count_only", "only_matching", "no_messages", "errors", "max_match_count", "invert", "before_context", "after_context"}
+    if unknown:
+        raise TypeError(f"grep_files() got unexpected keyword arguments {sorted(unknown)}")
+    sinks = [_GrepSink(patterns, count_only, only_matching, grep_kwargs.get("errors", "ignore"), invert) for _name in names]
+    if not only_matching:
+        for pattern in patterns:  # (grep()'s early failure for bad syntax)
+            re.compile(pattern)
+    scanned = []
+    for index, name in enumerate(names):
+        problem = None
+        if not os.path.exists(name):
+            problem = FileNotFoundError("No such file or directory")
+        elif os.path.isdir(name):
+            problem = ValueError("is a directory")
+        if problem is None:
+            scanned.append(index)
+        else:
+            outcomes[index] = problem if not no_messages else (sinks[index].result(), RC_INVALID_FILE)
+    if scanned:
+        flags = _GREP_FLAGS | (HS_FLAG_CASELESS if ignore_case else 0)
+        summaries = scan_files([names[i] for i in scanned], patterns, lambda which, matches, count: sinks[scanned[which]](matches, count),
+                               flags=[flags] * len(patterns), max_match_count=max_match_count, invert=invert)
+        for which, index in enumerate(scanned):
+            outcomes[index] = (sinks[index].result(), summaries[which][0])
+    return outcomes
+
+
+def grep_files(files: Sequence[str], patterns: list[str], **grep_kwargs) -> list:
+    """[grep(file, patterns, **grep_kwargs) for file in files], with the files sharing one native call and small files one
+    GPU scan (scan_files).  Raises what the first failing grep() of that list raises."""
+    outcomes = grep_files_outcomes(files, patterns, **grep_kwargs)
+    for outcome in outcomes:
+        if isinstance(outcome, Exception):
+            raise outcome
+    return outcomes

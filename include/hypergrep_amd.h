@@ -191,6 +191,28 @@ int hg_hyperscan_invert(char *file_name, const char *const *patterns, const unsi
                         const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements,
                         hs_event on_event, const int buffer_size, int buffer_count, unsigned long long max_match_count);
 
+/* Many files in one call (grep -r).  The files are packed in the given order into buffers of at most the chunk size of the
+ * file path (256 MiB) by the packing rule of hg_scan_device_segments below, and each pack is ONE GPU scan with the segment
+ * stage behind it.  on_event receives the results of file `file_index` in batches of at most buffer_count, in file order;
+ * no batch mixes files.  Each file's results, and summaries[i].rc, are those hg_hyperscan_ext (invert == 0) or
+ * hg_hyperscan_invert gives for that file alone with the same max_match_count.  A file that does not fit a pack, a gzip /
+ * zstd file, and every file when buffer_size < 2 is scanned by that per-file route inside the call (the call holds no
+ * context of the HYPERGREP_POOL pool meanwhile); an empty file is an empty segment; a file that cannot be
+ * opened sets only its own rc (HYPERSCANNER_GZ_OPEN).  summaries[i].n_selected: the distinct line numbers among the
+ * file's results; n_lines: the file's line pieces (for a file of the per-file route: those scanned before
+ * max_match_count stopped it).  With on_event == NULL only the summaries are produced and no record leaves the GPU for
+ * packed files (what -c, -l, -L, -q need).  Context lines are not offered here.  Returns 0, or the code of a failure
+ * that concerns the whole call (HYPERSCANNER_DB: the expressions do not compile). */
+typedef void (*hg_files_event)(unsigned int file_index, hyperscanner_result_t *results, int result_count, void *context);
+typedef struct hg_file_summary {
+    int rc;
+    uint64_t n_lines, n_selected;
+} hg_file_summary_t;
+int hg_hyperscan_files(const char *const *file_names, unsigned int n_files, const char *const *patterns,
+                       const unsigned int *pattern_flags, const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext,
+                       const unsigned int elements, hg_files_event on_event, void *context, const int buffer_size,
+                       int buffer_count, unsigned long long max_match_count, int invert, hg_file_summary_t *summaries);
+
 /* Context lines (grep -A / -B / -C) for files: hg_hyperscan_ext's (invert == 0) or hg_hyperscan_invert's (invert != 0) call
  * with `before` and `after` line pieces of context around every line it delivers (hg_scan_device_context below has the
  * classes).  `on_event` receives the merged order: the call's own results, and one Result{id = HG_ID_CONTEXT, line_number,
@@ -483,6 +505,55 @@ int hg_scan_device_context(hg_scanner_t *scanner, const void *d_text, uint64_t n
 int hg_copy_context(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max);
 /* The same (16-byte records only) into a DEVICE buffer, asynchronously on `stream`. */
 int hg_copy_context_device(hg_scanner_t *scanner, void *d_dst, uint64_t max, void *stream);
+
+/* Many files in one scan (grep -r): hg_scan_device (invert == 0) or hg_scan_device_invert (invert != 0) of a buffer that
+ * holds many files one after the other, with per-file results.
+ * Packing rule.  Segment s is the bytes [seg_start[s], seg_end[s]) of the buffer: seg_start[s] is the offset of the file's
+ * first byte, seg_end[s] the offset just past its own content, seg_end[s] <= seg_start[s + 1]; equal neighbours are empty
+ * files.  A file whose content is empty or ends in '\n' is packed as it is.  A file whose last line is unterminated is
+ * followed by the two pad bytes "\0\n", which are not content: a piece's scanned bytes run from after its leading NULs to its
+ * first NUL (hg_scan_device_invert above), so the last line's scanned bytes, and what $, \z and \Z see, are those of the file
+ * scanned alone; the '\n' ends the line, so no piece spans two files.  Every seg_start[s] > 0 therefore follows a '\n'.
+ * Phantom rule.  The pad can make a piece of its own (a last line of k * (buffer_size - 1) bytes leaves "\0\n", one of
+ * k * (buffer_size - 1) - 1 bytes leaves "\n" one byte past the content, which may even match).  A piece that starts at or
+ * after seg_end[s], and a hit whose hg_hit_aux_t.start is at or after seg_end[s], belongs to no file: it is dropped, it is
+ * not counted in the segment's n_lines and it does not count against the limit.
+ * Equivalence.  For every segment s, the records with segment s are those of a scan of the bytes [seg_start[s], seg_end[s])
+ * alone with line_base = 0 (hg_scan_device, or hg_scan_device_invert when invert != 0), as hg_copy_hits and
+ * hg_copy_hit_starts give them: line_number counts from the file's first piece, hg_hit_aux_t.start from its first byte.
+ * n_lines[s] is that scan's n_lines, n_selected[s] the distinct line_number values among the segment's records.
+ * With max_per_segment = m > 0 a segment keeps its records up to and including the line on which its running record count
+ * reaches m (hyperscan()'s max_match_count rule, per file; an inverted record is one piece), and first_record / n_selected
+ * describe what is kept.  An inverted call removes the hits that lie in a pad before it
+ * selects: a last piece of NULs only, whose scanned bytes are the pad's "\n", is selected with len == 0 as the file alone
+ * has it, whatever the expressions match.
+ * `result` is filled as by the underlying call, except that n_hits, d_hits and d_aux describe the surviving records, in
+ * segment order; n_lines, n_candidates and n_raw_hits stay those of the packed scan.  hg_copy_hits, hg_copy_hits_device and
+ * hg_copy_hit_starts follow the surviving records.
+ * HG_ERR_ARG, with nothing scanned: segments that are not ascending or overlap, a seg_end[s] past nbytes, a seg_start[s] > 0
+ * whose preceding byte is not '\n'.  The arrays are checked on the device; they are never copied to the host.
+ * The stage runs on the GPU around the scan (hypergrep_amd/csrc/hg_segments.hip): the check, then behind the scan the
+ * segments' line bases from the scan's line geometry (one wavefront per 16 KiB tile that holds a boundary, however many),
+ * each segment's run of surviving records, an exclusive scan, and one ordered write. */
+typedef struct hg_segments {
+    const uint64_t *d_seg_start, *d_seg_end; /* DEVICE arrays, n_seg ascending entries each */
+    uint32_t n_seg;
+    uint64_t max_per_segment; /* 0 = no limit */
+} hg_segments_t;
+typedef struct hg_segment_result {
+    const uint32_t *d_record_segment; /* DEVICE pointers, valid until the next scan: the segment of each record of `result` */
+    const uint64_t *d_first_record;   /* n_seg + 1: segment s owns the records [first_record[s], first_record[s + 1]) */
+    const uint64_t *d_n_lines, *d_n_selected; /* n_seg each */
+    uint32_t segments_us; /* the added stage (its launches, scan and host synchronisations) */
+    uint32_t reserved;
+} hg_segment_result_t;
+int hg_scan_device_segments(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, void *stream,
+                            const hg_segments_t *segments, int invert, hg_scan_result_t *result,
+                            hg_segment_result_t *segment_result);
+/* Copy the last scan's per-segment arrays to host memory (any pointer may be NULL): record_segment holds result.n_hits
+ * entries, first_record n_seg + 1, n_lines and n_selected n_seg.  HG_ERR_ARG after a scan without segments. */
+int hg_copy_segments(hg_scanner_t *scanner, uint32_t *record_segment, uint64_t *first_record, uint64_t *n_lines,
+                     uint64_t *n_selected);
 
 /* Copy the last scan's first `max` hits (and aux records, if aux != NULL) to host memory. */
 int hg_copy_hits(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max);

@@ -23,9 +23,11 @@ struct hg_scanner {
   hg_context_result_t last_ctx;  // the last scan's context records (hg_scan_device_context), else zeroes
   hg_segment_result_t last_seg;  // the last scan's per-segment arrays (hg_scan_device_segments), else zeroes
   uint32_t last_n_seg;
+  hg_parts_result_t last_parts;  // the last scan's parts (hg_scan_device_parts), else zeroes
 };
 
 static_assert(HG_ID_CONTEXT == HG_CTX_ID_CONTEXT && HG_ID_CONTEXT_TAIL == HG_CTX_ID_TAIL, "the context records carry the ids the header names");
+static_assert(sizeof(hg_part_t) == sizeof(HgPart) && sizeof(hg_parts_result_t) == 32, "ABI records mirror the device records");
 static_assert(sizeof(hg_hit_t) == sizeof(HgHit) && sizeof(hg_hit_aux_t) == sizeof(HgHitAux), "ABI records mirror the device records");
 
 static void put_err(char *err, size_t errlen, const std::string &msg) {
@@ -93,7 +95,7 @@ int hg_scanner_create(const hg_database_t *db, int device, hg_scanner_t **scanne
     put_err(err, errlen, msg);
     return rc;
   }
-  *scanner = new hg_scanner{sc, {}, nullptr, {}, {}, 0};
+  *scanner = new hg_scanner{sc, {}, nullptr, {}, {}, 0, {}};
   return HG_OK;
 }
 
@@ -107,9 +109,11 @@ const char *hg_scanner_error(const hg_scanner_t *scanner) { return scanner ? sca
 
 static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, void *stream,
                        hg_scan_result_t *result, bool invert, const hg_context_t *context = nullptr, hg_context_result_t *context_result = nullptr,
-                       const hg_segments_t *segments = nullptr, hg_segment_result_t *segment_result = nullptr) {
+                       const hg_segments_t *segments = nullptr, hg_segment_result_t *segment_result = nullptr, hg_parts_result_t *parts_result = nullptr) {
   if (!scanner || !result) return HG_ERR_ARG;
   HgScanOutput o{};
+  HgPartsOutput pt{};
+  scanner->last_parts = hg_parts_result_t{};
   HgContextOutput c{};
   HgSegOutput g{};
   int rc;
@@ -125,10 +129,16 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
   } else if (context) {
     const HgContextParams params{context->before, context->after, context->carry_after, (context->flags & HG_CONTEXT_TAIL) != 0};
     rc = scanner->sc->scan_context(d_text, nbytes, buffer_size, line_base, static_cast<hipStream_t>(stream), params, invert, &o, &c);
+  } else if (parts_result) {
+    rc = scanner->sc->scan_parts(d_text, nbytes, buffer_size, line_base, static_cast<hipStream_t>(stream), &o, &pt);
   } else {
     rc = scanner->sc->scan(d_text, nbytes, buffer_size, line_base, static_cast<hipStream_t>(stream), &o, invert);
   }
   if (rc != HG_OK) return rc;
+  if (parts_result) {
+    scanner->last_parts = hg_parts_result_t{pt.n_parts, reinterpret_cast<const hg_part_t *>(pt.d_parts), pt.d_pattern, static_cast<uint32_t>(pt.ms_parts * 1000.0f + 0.5f), 0};
+    *parts_result = scanner->last_parts;
+  }
   scanner->last_ctx = hg_context_result_t{c.n_context, c.n_tail, c.owed_after, reinterpret_cast<const hg_hit_t *>(c.d_hits), reinterpret_cast<const hg_hit_aux_t *>(c.d_aux),
                                           static_cast<uint32_t>(c.ms_context * 1000.0f + 0.5f), 0};
   if (context_result) *context_result = scanner->last_ctx;
@@ -176,6 +186,33 @@ int hg_scan_device_segments(hg_scanner_t *scanner, const void *d_text, uint64_t 
   if (!segments || !segment_result) return HG_ERR_ARG;
   *segment_result = hg_segment_result_t{};
   return scan_device(scanner, d_text, nbytes, buffer_size, 0, stream, result, invert != 0, nullptr, nullptr, segments, segment_result);
+}
+
+int hg_scan_device_parts(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, void *stream, hg_scan_result_t *result,
+                         hg_parts_result_t *parts) {
+  if (!parts) return HG_ERR_ARG;
+  *parts = hg_parts_result_t{};
+  return scan_device(scanner, d_text, nbytes, buffer_size, line_base, stream, result, false, nullptr, nullptr, nullptr, nullptr, parts);
+}
+
+int hg_copy_parts(hg_scanner_t *scanner, hg_part_t *parts, uint32_t *pattern, uint64_t max) {
+  if (!scanner || !parts) return HG_ERR_ARG;
+  uint64_t n = scanner->last_parts.n_parts < max ? scanner->last_parts.n_parts : max;
+  if (!n) return HG_OK;
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  if (hipMemcpy(parts, scanner->last_parts.d_parts, n * sizeof(hg_part_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (pattern && hipMemcpy(pattern, scanner->last_parts.d_part_pattern, n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
+}
+
+int hg_copy_parts_device(hg_scanner_t *scanner, void *d_dst, uint64_t max, void *stream) {
+  if (!scanner || !d_dst) return HG_ERR_ARG;
+  uint64_t n = scanner->last_parts.n_parts < max ? scanner->last_parts.n_parts : max;
+  if (!n) return HG_OK;
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  if (hipMemcpyAsync(d_dst, scanner->last_parts.d_parts, n * sizeof(hg_part_t), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)) != hipSuccess)
+    return HG_ERR_HIP;
+  return HG_OK;
 }
 
 int hg_copy_segments(hg_scanner_t *scanner, uint32_t *record_segment, uint64_t *first_record, uint64_t *n_lines, uint64_t *n_selected) {

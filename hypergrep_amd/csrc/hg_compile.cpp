@@ -2329,6 +2329,7 @@ int hgc_compile_ext(const char *const *exprs, const unsigned *flags, const unsig
       if (f & ~HG_FLAGS_SUPPORTED) throw CompileError("unsupported flag bits");
       const hs_expr_ext_t *x = (ext && ext[at] && ext[at]->flags) ? ext[at] : nullptr;
       if (x) check_ext_fields(*x, f);
+      if (x) db->n_ext++;
       if (f & HG_FLAG_COMBINATION) {
         db->patterns.push_back(compile_combination(*db, exprs[at], f, id, programs[at]));
         db->max_id = std::max(db->max_id, id);

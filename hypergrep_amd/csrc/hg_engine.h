@@ -11,6 +11,7 @@
 #include "hg_invert.h"
 #include "hg_context.h"
 #include "hg_segments.h"
+#include "hg_parts.h"
 #include "hg_post.h"
 
 // Waves per stream workgroup (one 16 KiB tile per wave at a time); shared by the kernel and the grid sizing.
@@ -211,6 +212,33 @@ struct HgSegOutput {
   float ms_segments;  // the stage: check, bases, runs, scan, the host syncs, write
 };
 
+// The parts stage (hg_parts.hip) over the n_hits final hits of a scan, on `stream`: count (write == false: count[i] = parts of
+// the piece whose first hit is hit i, 0 for its other hits, count[n_hits] = 0), or write the parts of that piece to
+// out / out_pattern [pos[i] ..].  max_nw: the most state words of any expression (multi-word walks keep their state in LDS).
+struct HgPartsArgs {
+  const uint8_t *text;
+  const HgHit *hits;
+  const HgHitAux *aux;
+  uint64_t n_hits;
+  const HgPattern *patterns;
+  const uint32_t *pool;
+  uint32_t npatterns;
+  const uint32_t *first;  // first[c * first_words + (j >> 5)] bit (j & 31): expression j has a node that init enters on byte c
+  uint32_t first_words;   // ceil(npatterns / 32)
+  uint64_t *count;
+  const uint64_t *pos;
+  HgPart *out;
+  uint32_t *out_pattern;
+};
+hipError_t hg_parts_launch(const HgPartsArgs &a, bool write, uint32_t max_nw, uint32_t num_cus, hipStream_t stream);
+// What the stage leaves (hg_parts_result_t of the C ABI).
+struct HgPartsOutput {
+  uint64_t n_parts;           // ordered by (line, from)
+  const HgPart *d_parts;      // device arrays, valid until the next scan on this scanner
+  const uint32_t *d_pattern;  // the expression index of each part
+  float ms_parts;             // the stage: count, scan, the host sync that sizes the output, write
+};
+
 // Test / experiment knobs of the engine, read from the environment ONCE, when a scanner is created (never during a scan:
 // getenv is not safe against a concurrent setenv, and a scan must not change behaviour half-way).  None is needed in normal
 // use.  The limit-lowering ones exist so that tests reach segmented scans / chunk halving on small texts.
@@ -249,6 +277,9 @@ class HgScanner {
   // malformed segments.
   int scan_packed(const void *d_text, uint64_t nbytes, int buffer_size, hipStream_t stream, const HgSegParams &params, bool invert, HgScanOutput *out,
                   HgSegOutput *seg);
+  // The plain scan with the parts stage behind it: *out is exactly scan()'s, *parts the matched parts of the pieces that have a
+  // hit.  HG_ERR_ARG (nothing scanned, the reason in last_error()) for a database the stage is not offered for (hg_parts_refusal).
+  int scan_parts(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, hipStream_t stream, HgScanOutput *out, HgPartsOutput *parts);
   // Block mode (hs_scan): the whole buffer is one scan unit; hits carry line_no 0 and `to` relative to the buffer start.
   int scan_block(const void *d_text, uint64_t nbytes, hipStream_t stream, HgScanOutput *out);
   // Block mode for short blocks held in PINNED host memory (readable up to nbytes rounded up to 16): one launch, raw
@@ -293,6 +324,7 @@ class HgScanner {
   int invert_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, hipStream_t stream, HgScanOutput *out);
   int context_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const HgContextParams &params, hipStream_t stream, const HgScanOutput &out,
                    HgContextOutput *ctx);
+  int parts_pass(const uint8_t *text, hipStream_t stream, const HgScanOutput &out, HgPartsOutput *parts);
   int segment_alloc(uint64_t n_seg);
   int segment_records(uint64_t n);
   int pad_filter(const HgSegArgs &checked, float *ms, hipStream_t stream, HgScanOutput *out);
@@ -397,6 +429,16 @@ class HgScanner {
   HgHit *d_ctx_hits_ = nullptr;
   HgHitAux *d_ctx_aux_ = nullptr;
   uint64_t ctx_cap_ = 0;
+  // parts stage (calls with parts only, allocated by the first one): the first-byte bitmap over the expressions, parts per hit
+  // and their exclusive scan, the scan's scratch, and the parts with their expressions (sized from the count before the write)
+  uint32_t *d_parts_first_ = nullptr;  // HgPartsArgs::first, built from the database by the first call
+  uint64_t *d_parts_count_ = nullptr, *d_parts_pos_ = nullptr;
+  uint64_t parts_hits_cap_ = 0;
+  uint8_t *d_parts_temp_ = nullptr;
+  size_t parts_temp_bytes_ = 0;
+  HgPart *d_parts_ = nullptr;
+  uint32_t *d_part_pattern_ = nullptr;
+  uint64_t parts_cap_ = 0;
   // segment stage (calls with segments only, allocated by the first one): per segment the line base / end, the first record
   // and the length of its run, the exclusive scan of the lengths, n_lines and n_selected (seven arrays of seg_cap_ words in one
   // block), the flag word of the argument check, the scan's scratch, and the compacted records with their segments and starts

@@ -243,6 +243,7 @@ HgScanner::~HgScanner() {
                   d_combs_, d_comb_words_, d_comb_feed_, d_comb_count_, d_comb_pos_, d_comb_hits_, d_comb_aux_, d_comb_temp_, d_bounds_,
                   d_min_lengths_, d_minlen_hits_, d_minlen_aux_, d_inv_count_, d_inv_pos_, d_inv_temp_, d_inv_hits_, d_inv_aux_,
                   d_ctx_count_, d_ctx_pos_, d_ctx_temp_, d_ctx_hits_, d_ctx_aux_,
+                  d_parts_first_, d_parts_count_, d_parts_pos_, d_parts_temp_, d_parts_, d_part_pattern_,
                   d_segw_, d_seg_flag_, d_seg_temp_, d_seg_hits_, d_seg_aux_, d_seg_of_, d_seg_from_, d_pad_keep_, d_pad_pos_};
   for (void *p : ptrs) hgmem::dev_free(p, "scanner");
   hgmem::host_free(h_counters_, "h_counters_");
@@ -1000,6 +1001,81 @@ int HgScanner::scan_context(const void *d_text, uint64_t nbytes, int buffer_size
   if (int rc = scan_impl(d_text, nbytes, buffer_size, line_base, false, invert, stream, out)) return rc;
   if (!params.any()) return HG_OK;  // no context asked for: the stage is skipped
   return context_pass(static_cast<const uint8_t *>(d_text), nbytes, static_cast<uint64_t>(buffer_size) - 1, line_base, params, stream, *out, ctx);
+}
+
+// The parts stage over a finished scan (`out`: its final hits, ordered by line; untouched): the count pass over the hits (a
+// wave per piece that has a hit walks it), an exclusive scan of the per-hit counts, and the write pass (hg_parts.hip).  Like
+// the invert stage it runs once over the whole buffer, however many segments or pipeline chunks the scan took.
+int HgScanner::parts_pass(const uint8_t *text, hipStream_t stream, const HgScanOutput &out, HgPartsOutput *parts) {
+  const uint64_t n = out.n_hits;
+  if (n == 0) return HG_OK;
+  if (n + 1 > parts_hits_cap_) {
+    const uint64_t cap = std::max<uint64_t>(n + n / 4 + 1, 4096);
+    parts_hits_cap_ = 0;
+    HG_TRY(realloc_dev(d_parts_count_, cap, "d_parts_count_"), "alloc (parts stage)");
+    HG_TRY(realloc_dev(d_parts_pos_, cap, "d_parts_pos_"), "alloc (parts stage)");
+    parts_hits_cap_ = cap;
+  }
+  size_t tb = 0;  // the scan's scratch, asked for the size that is scanned
+  HG_TRY(rocprim::exclusive_scan(nullptr, tb, d_parts_count_, d_parts_pos_, uint64_t{0}, n + 1, rocprim::plus<uint64_t>(), stream), "scan (parts stage)");
+  if (tb > parts_temp_bytes_ || !d_parts_temp_) {
+    parts_temp_bytes_ = 0;
+    HG_TRY(realloc_dev(d_parts_temp_, tb + tb / 4, "d_parts_temp_"), "alloc (parts stage)");
+    parts_temp_bytes_ = tb + tb / 4;
+  }
+  const HgDb &db = *db_;
+  const uint32_t npatterns = static_cast<uint32_t>(db.patterns.size()), first_words = (npatterns + 31) / 32;
+  if (!d_parts_first_) {  // which expressions can start with byte c: those whose init meets reach[c] (conditions left out: a superset)
+    std::vector<uint32_t> first(static_cast<size_t>(256) * first_words, 0u);
+    for (uint32_t j = 0; j < npatterns; j++) {
+      const HgPattern &p = db.patterns[j];
+      if (p.nw == 0 || p.nw > HG_MAX_W) continue;
+      const uint32_t *init = db.pool.data() + p.init_off, *reach = db.pool.data() + p.reach_off;
+      for (uint32_t c = 0; c < 256; c++) {
+        uint32_t any = 0;
+        for (uint32_t w = 0; w < p.nw; w++) any |= init[w] & reach[c * p.nw + w];
+        if (any) first[static_cast<size_t>(c) * first_words + (j >> 5)] |= 1u << (j & 31);
+      }
+    }
+    HG_TRY(realloc_dev(d_parts_first_, first.size(), "d_parts_first_"), "alloc (parts stage)");
+    HG_TRY(hipMemcpyAsync(d_parts_first_, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream), "copy (parts stage)");
+    HG_TRY(hipStreamSynchronize(stream), "stream sync (parts stage)");  // (the host vector goes out of scope)
+  }
+  HgPartsArgs a{text, out.d_hits, out.d_aux, n, static_cast<const HgPattern *>(d_patterns_), static_cast<const uint32_t *>(d_pool_),
+                npatterns, d_parts_first_, first_words, d_parts_count_, d_parts_pos_, nullptr, nullptr};
+  HG_TRY(hipEventRecord(ev_[0], stream), "event");
+  HG_TRY(hg_parts_launch(a, false, db.max_nw, static_cast<uint32_t>(num_cus_), stream), "parts stage launch (count)");
+  HG_TRY(rocprim::exclusive_scan(d_parts_temp_, tb, d_parts_count_, d_parts_pos_, uint64_t{0}, n + 1, rocprim::plus<uint64_t>(), stream), "scan (parts stage)");
+  uint64_t total = 0;
+  HG_TRY(hipMemcpyAsync(&total, d_parts_pos_ + n, sizeof total, hipMemcpyDeviceToHost, stream), "copy count");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (parts stage)");
+  if (total > parts_cap_) {
+    const uint64_t cap = std::max<uint64_t>(total + total / 4, 4096);
+    parts_cap_ = 0;
+    HG_TRY(realloc_dev(d_parts_, cap, "d_parts_"), "alloc (parts stage records)");
+    HG_TRY(realloc_dev(d_part_pattern_, cap, "d_part_pattern_"), "alloc (parts stage records)");
+    parts_cap_ = cap;
+  }
+  if (total) {
+    a.out = d_parts_;
+    a.out_pattern = d_part_pattern_;
+    HG_TRY(hg_parts_launch(a, true, db.max_nw, static_cast<uint32_t>(num_cus_), stream), "parts stage launch (write)");
+  }
+  HG_TRY(hipEventRecord(ev_[3], stream), "event");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (parts stage)");
+  (void)hipEventElapsedTime(&parts->ms_parts, ev_[0], ev_[3]);
+  parts->n_parts = total;
+  parts->d_parts = d_parts_;
+  parts->d_pattern = d_part_pattern_;
+  return HG_OK;
+}
+
+int HgScanner::scan_parts(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, hipStream_t stream, HgScanOutput *out, HgPartsOutput *parts) {
+  if (!parts) return error(HG_ERR_ARG, "invalid arguments");
+  *parts = HgPartsOutput{};
+  if (const char *why = hg_parts_refusal(db_->nhuge, db_->ncomb, db_->nquiet, db_->n_ext != 0)) return error(HG_ERR_ARG, why);
+  if (int rc = scan_impl(d_text, nbytes, buffer_size, line_base, false, false, stream, out)) return rc;
+  return parts_pass(static_cast<const uint8_t *>(d_text), stream, *out, parts);
 }
 
 // The per-segment arrays of the segment stage, for n_seg segments (n_seg + 1 words each).

@@ -586,7 +586,7 @@ using FileEvent = std::function<void(hyperscanner_result_t *, int)>;
 static int scan_file(const char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
                      const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, FileEvent on_event,
                      const int buffer_size, int buffer_count, unsigned long long max_match_count, const bool invert, const uint32_t before = 0,
-                     const uint32_t after = 0, uint64_t *pieces_scanned = nullptr) {
+                     const uint32_t after = 0, uint64_t *pieces_scanned = nullptr, const bool parts = false) {
   if (max_match_count > 0 && max_match_count < static_cast<unsigned long long>(buffer_count)) buffer_count = static_cast<int>(max_match_count);
   if (buffer_count < 1 || buffer_size < 1 || !on_event) return HYPERSCANNER_STATE_MEM;
   Ring ring;
@@ -597,6 +597,12 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
   if (!db) {
     std::fprintf(stderr, "ERROR: Unable to create database. Exiting.\n");
     return HYPERSCANNER_DB;
+  }
+  if (parts) {
+    if (const char *why = hg_parts_refusal(db->nhuge, db->ncomb, db->nquiet, db->n_ext != 0)) {
+      std::fprintf(stderr, "ERROR: Unable to create database. Exiting. (%s)\n", why);
+      return HYPERSCANNER_DB;
+    }
   }
   // the file is opened before any device resource is taken: a missing file is HYPERSCANNER_GZ_OPEN with or without a GPU
   // (the reference's scratch allocation cannot fail for want of a device; its order is database, scratch, file)
@@ -709,6 +715,8 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
   std::deque<HeldPiece> held;  // tail pieces of the chunks so far: the next match's before-context, maybe (`before` at most)
   std::vector<HgHit> ctx_hits;
   std::vector<HgHitAux> ctx_aux;
+  std::vector<HgPart> part_recs;  // matched parts (hg_hyperscan_parts): the chunk's parts and their expressions
+  std::vector<uint32_t> part_pattern;
   unsigned long long matches = 0;  // match results delivered (max_match_count counts those, not the context lines)
   bool trailing = false;           // the limit is reached: only the last delivered line's after-context still goes out
   uint64_t trailing_next = 0, trailing_end = 0;  // ... the pieces [trailing_next, trailing_end), up to the next matching piece
@@ -759,8 +767,11 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
       }
       HgScanOutput out{};
       HgContextOutput cout{};
+      HgPartsOutput pout{};
       int src;
-      if (with_context) {
+      if (parts) {
+        src = ctx->sc->scan_parts(d_text, cut, buffer_size, line_base, ctx->stream, &out, &pout);
+      } else if (with_context) {
         // (after the limit: the owed pieces only, as carry; no new windows, no tail)
         const HgContextParams cp{trailing ? 0u : before, trailing ? 0u : after, trailing ? trailing_end - trailing_next : carry_after, !trailing && before != 0};
         src = ctx->sc->scan_context(d_text, cut, buffer_size, line_base, ctx->stream, cp, invert, &out, &cout);
@@ -795,6 +806,18 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
           break;
         }
       }
+      part_recs.resize(pout.n_parts);
+      part_pattern.resize(pout.n_parts);
+      if (pout.n_parts) {
+        if (hipMemcpyAsync(part_recs.data(), pout.d_parts, pout.n_parts * sizeof(HgPart), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(part_pattern.data(), pout.d_pattern, pout.n_parts * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess) {
+          rc = HYPERSCANNER_SCAN;
+          healthy = false;
+          break;
+        }
+      }
+      size_t pi = 0;  // cursor into the parts
       const double t_scanned = now();
       t_scan += t_scanned - t_begin;
       size_t ci = 0;  // cursor into the context records
@@ -832,7 +855,11 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
         if (with_context) deliver_context(ctx->hits[i].line_no);
         size_t j = i;
         while (j < ctx->hits.size() && ctx->hits[j].line_no == ctx->hits[i].line_no) j++;
-        if (j - i > 1) {
+        if (parts) {  // every part of the line, in order, in place of its reports (which still count for the limit)
+          while (pi < part_recs.size() && part_recs[pi].line_no < ctx->hits[i].line_no) pi++;
+          for (; pi < part_recs.size() && part_recs[pi].line_no == ctx->hits[i].line_no; pi++)
+            ring.push(db->patterns[part_pattern[pi]].id, part_recs[pi].line_no, host + ctx->aux[i].start + part_recs[pi].from, part_recs[pi].to - part_recs[pi].from);
+        } else if (j - i > 1) {
           std::vector<size_t> order(j - i);
           for (size_t q = 0; q < order.size(); q++) order[q] = i + q;
           std::sort(order.begin(), order.end(), [&](size_t x, size_t y) {
@@ -1086,6 +1113,12 @@ extern "C" int hg_hyperscan_invert(char *file_name, const char *const *patterns,
                                    const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hs_event on_event,
                                    const int buffer_size, int buffer_count, unsigned long long max_match_count) {
   return scan_file(file_name, patterns, pattern_flags, pattern_ids, ext, elements, on_event, buffer_size, buffer_count, max_match_count, true);
+}
+
+extern "C" int hg_hyperscan_parts(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                                  const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hs_event on_event,
+                                  const int buffer_size, int buffer_count, unsigned long long max_match_count) {
+  return scan_file(file_name, patterns, pattern_flags, pattern_ids, ext, elements, on_event, buffer_size, buffer_count, max_match_count, false, 0, 0, nullptr, true);
 }
 
 extern "C" int hg_hyperscan_context(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,

@@ -48,6 +48,15 @@ class HgContextResult(ctypes.Structure):
                 ("d_ctx_aux", ctypes.c_void_p), ("context_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class HgPart(ctypes.Structure):
+    _fields_ = [("line_number", ctypes.c_uint64), ("from_", ctypes.c_uint32), ("to", ctypes.c_uint32)]
+
+
+class HgPartsResult(ctypes.Structure):
+    _fields_ = [("n_parts", ctypes.c_uint64), ("d_parts", ctypes.c_void_p), ("d_part_pattern", ctypes.c_void_p), ("parts_us", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
 class HgSegments(ctypes.Structure):
     _fields_ = [("d_seg_start", ctypes.c_void_p), ("d_seg_end", ctypes.c_void_p), ("n_seg", ctypes.c_uint32), ("max_per_segment", ctypes.c_uint64)]
 
@@ -104,6 +113,11 @@ def lib() -> ctypes.CDLL:
                                                   ctypes.c_int, ctypes.POINTER(HgScanResult), ctypes.POINTER(HgSegmentResult)]
             l.hg_copy_segments.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint64)]
+        if hasattr(l, "hg_scan_device_parts"):  # (absent from a build before the matched parts)
+            l.hg_scan_device_parts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p,
+                                               ctypes.POINTER(HgScanResult), ctypes.POINTER(HgPartsResult)]
+            l.hg_copy_parts.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgPart), ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
+            l.hg_copy_parts_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hits.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
         l.hg_copy_hits_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hit_starts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
@@ -180,6 +194,8 @@ class ScanStats:
     n_tail: int = 0  # ... the tail records among n_context
     context_us: int = 0  # ... the context stage alone, microseconds
     segments_us: int = 0  # scans with segments: the segment stage alone, microseconds
+    n_parts: int = 0  # scans with parts: the records of Scanner.parts()
+    parts_us: int = 0  # ... the parts stage alone, microseconds
 
 
 class Scanner:
@@ -195,6 +211,7 @@ class Scanner:
             raise DeviceError(f"hg_scanner_create failed ({rc}): {err.value.decode(errors='replace')}")
         self._last = HgScanResult()
         self._last_ctx = HgContextResult()
+        self._last_parts = HgPartsResult()
         self._last_seg = None  # (HgSegmentResult, n_seg) of the last scan, if it had segments
         self._seg_arena = None
 
@@ -214,7 +231,7 @@ class Scanner:
         return ptr, ptr + 8 * n, n
 
     def scan(self, d_text: int, nbytes: int, buffer_size: int = 262140, line_base: int = 0, stream: int = 0, invert: bool = False,
-             context: tuple[int, int] | None = None, carry_after: int = 0, tail: bool = False, segments=None, max_per_segment: int = 0) -> ScanStats:
+             context: tuple[int, int] | None = None, carry_after: int = 0, tail: bool = False, segments=None, max_per_segment: int = 0, parts: bool = False) -> ScanStats:
         """invert: the result is the line pieces without any report (grep -v; hg_scan_device_invert): n_hits of them, and
         hits() gives (line_number, HG_ID_INVERT, 0, start, len) per piece in line order.
         context = (before, after): grep -B / -A in line pieces (hg_scan_device_context).  hits() is what it is without context;
@@ -223,8 +240,14 @@ class Scanner:
         segments = (starts, ends): the text holds many files one after the other (hg_scan_device_segments has the packing
         rule); two sequences of offsets, or (d_starts, d_ends, n) for arrays already on the device.  hits() then gives every
         file's records as a scan of the file alone would, file after file, and segments() says which are whose.
-        max_per_segment: keep a file's records up to the line on which their count reaches it (0: all)."""
+        max_per_segment: keep a file's records up to the line on which their count reaches it (0: all).
+        parts: the plain scan with the matched parts of every line that has a hit (grep -o over all expressions;
+        hg_scan_device_parts has the definition).  hits() is what it is without; parts() gives the parts.  Not combined with
+        invert, context or segments (ValueError), and ValueError with the reason for a database the stage is not offered for."""
+        if parts and (invert or context is not None or carry_after or tail or segments is not None):
+            raise ValueError("parts: not combined with invert, context or segments")
         res = HgScanResult()
+        pres = HgPartsResult()
         cres = HgContextResult()
         sres = HgSegmentResult()
         self._last_seg = None
@@ -247,6 +270,13 @@ class Scanner:
             ctx = HgContext(before, after, carry_after, HG_CONTEXT_TAIL if tail else 0)
             rc = lib().hg_scan_device_context(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, line_base, ctypes.c_void_p(stream), ctypes.byref(ctx),
                                               1 if invert else 0, ctypes.byref(res), ctypes.byref(cres))
+        elif parts:
+            name = "hg_scan_device_parts"
+            rc = lib().hg_scan_device_parts(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, line_base, ctypes.c_void_p(stream), ctypes.byref(res), ctypes.byref(pres))
+            if rc == -1:  # HG_ERR_ARG: nothing was scanned
+                self._last = HgScanResult()
+                self._last_parts = HgPartsResult()
+                raise ValueError(f"{name}: {lib().hg_scanner_error(self._h).decode(errors='replace')}")
         else:
             name = "hg_scan_device_invert" if invert else "hg_scan_device"
             rc = getattr(lib(), name)(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, line_base, ctypes.c_void_p(stream), ctypes.byref(res))
@@ -254,8 +284,9 @@ class Scanner:
             raise DeviceError(f"{name} failed ({rc}): {lib().hg_scanner_error(self._h).decode(errors='replace')}")
         self._last = res
         self._last_ctx = cres
+        self._last_parts = pres
         return ScanStats(res.n_hits, res.n_lines, res.n_candidates, res.n_raw_hits, res.ms_stream, res.ms_total, res.reruns, res.stream_launches, res.joiner_launches, res.joiner_tiles,
-                         res.invert_us, cres.n_context, cres.owed_after, cres.n_tail, cres.context_us, sres.segments_us)
+                         res.invert_us, cres.n_context, cres.owed_after, cres.n_tail, cres.context_us, sres.segments_us, pres.n_parts, pres.parts_us)
 
     def segments(self):
         """The per-file arrays of the last scan with segments, as uint64 / uint32 numpy arrays: a dict with record_segment (one
@@ -287,6 +318,27 @@ class Scanner:
         if rc != 0:
             raise DeviceError(f"hg_copy_context failed ({rc})")
         return [(hits[i].line_number, hits[i].id, hits[i].to, aux[i].start, aux[i].len) for i in range(n)]
+
+    def parts(self, limit: int | None = None):
+        """Last scan's matched parts as a list of (line_number, from, to, pattern), ordered by (line_number, from): the bytes
+        [from, to) of the line's scanned bytes, and the index of the expression; empty after a scan without parts."""
+        n = self._last_parts.n_parts if limit is None else min(limit, self._last_parts.n_parts)
+        if not n:
+            return []
+        recs = (HgPart * n)()
+        pattern = (ctypes.c_uint32 * n)()
+        rc = lib().hg_copy_parts(self._h, recs, pattern, n)
+        if rc != 0:
+            raise DeviceError(f"hg_copy_parts failed ({rc})")
+        return [(recs[i].line_number, recs[i].from_, recs[i].to, pattern[i]) for i in range(n)]
+
+    def copy_parts_to(self, d_dst: int, limit: int, stream: int = 0) -> int:
+        """Device-to-device copy of up to `limit` part records (16 B each: line_number, from, to) into d_dst; returns the count."""
+        n = min(limit, self._last_parts.n_parts)
+        rc = lib().hg_copy_parts_device(self._h, ctypes.c_void_p(d_dst), n, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise DeviceError(f"hg_copy_parts_device failed ({rc})")
+        return n
 
     @property
     def d_hits(self) -> int:

@@ -159,6 +159,7 @@ def parallel_grep(  # pylint: disable=too-many-arguments,too-many-locals
     files_with_matches: bool = False,
     quiet: bool = False,
     invert_match: bool = False,
+    gnu_parts: bool = False,
     before_context: int = 0,
     after_context: int = 0,
 ) -> int:
@@ -180,6 +181,8 @@ def parallel_grep(  # pylint: disable=too-many-arguments,too-many-locals
         quiet: print nothing and stop everything at the first match.
         invert_match: select the lines NO pattern matches (grep -v).  Counts, totals, -l / -L / -q and max_match_count then
             go by the selected lines; with only_matching nothing is printed, and the exit code still goes by the selected lines.
+        gnu_parts: with only_matching, print the parts the GPU computes (grep(matched_parts=True)): GNU grep's -o over all
+            patterns at once, leftmost-longest.  Without only_matching, with invert_match or with context lines it changes nothing.
         before_context / after_context: also print that many lines before / after each selected line (grep -B / -A), in GNU
             grep's format: "-" instead of ":" after the prefixes of a context line, "--" between groups that are not adjacent.
             They change nothing where lines are only counted or files only listed.
@@ -207,6 +210,8 @@ def parallel_grep(  # pylint: disable=too-many-arguments,too-many-locals
     }
     if context:
         job_kwargs.update(before_context=before_context, after_context=after_context)
+    elif gnu_parts and only_matching and not invert_match:
+        job_kwargs["matched_parts"] = True
     # More than one file, no context, threads: the batch route.  The files share one native call, small ones one GPU scan
     # (hypergrep_amd.grep_files); the outcomes are replayed exactly as the per-file jobs' are.  HYPERGREP_BATCH_FILES=0 keeps
     # the per-file route (A/B runs).
@@ -409,6 +414,10 @@ def parse_args(args: list = None) -> argparse.Namespace:
     own.add_argument("--no-order", dest="ordered", action="store_false", help="Print each file's results as soon as it finishes.")
     own.add_argument("--no-sort", dest="sort_files", action="store_false", help="Keep the given file order instead of sorting the names.")
     own.add_argument("--mp", action="store_false", dest="use_multithreading", help="Worker processes instead of threads.")
+    # (no attribute unless given, like -v)
+    own.add_argument("--gnu-parts", dest="gnu_parts", action="store_true", default=argparse.SUPPRESS,
+                     help="With -o: print the matched parts of ALL patterns, leftmost-longest, computed on the GPU (GNU grep's -o\n"
+                          "output for several patterns and alternations).  Without -o it has no effect.")
     parser.set_defaults(parser=parser)
     return parser.parse_intermixed_args(args=args)
 
@@ -461,6 +470,7 @@ def main() -> None:
             files_without_match=args.files_without_match,
             files_with_matches=args.files_with_matches,
             invert_match=getattr(args, "invert_match", False),
+            gnu_parts=getattr(args, "gnu_parts", False),
             before_context=getattr(args, "before_context", getattr(args, "context", 0)),
             after_context=getattr(args, "after_context", getattr(args, "context", 0)),
         )

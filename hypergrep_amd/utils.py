@@ -174,6 +174,7 @@ def scan(  # pylint: disable=too-many-arguments
     invert: bool = False,
     before_context: int = 0,
     after_context: int = 0,
+    parts: bool = False,
 ) -> int:
     """Scan a plain / gzip / zstd text file; `callback(matches, count)` receives the hits in batches of `buffer_count`.
     `ext`: one ExprExt (extended parameters: approximate matching, offset bounds, min_length) or None per pattern.
@@ -182,10 +183,16 @@ def scan(  # pylint: disable=too-many-arguments
     `before_context` / `after_context` (grep -B / -A, in line pieces): the callback also receives the lines around the delivered
     ones, one Result with id HG_ID_CONTEXT each, merged in line order (hg_hyperscan_context); `max_match_count` does not count
     them, and pattern ids of 0xFFFFFFFD and above are refused (return code 4).
+    `parts` (grep -o over all patterns, hg_hyperscan_parts): the callback receives, for every line it would receive, the
+    line's matched parts instead: one Result per part with the id of the part's pattern and the part's bytes as `line`, in
+    (line, offset) order; `max_match_count` still goes by the reports.  Not combined with `invert` or context (ValueError);
+    pattern sets with `ext`, combinations, QUIET or automata above 1024 nodes are refused (return code 4).
 
     The native call runs on a daemon thread so that Ctrl-C reaches Python (return code 130); otherwise the shim's
     return code (0 = fine, 1-7 as in hyperscanner.c:25-33) comes back.
     """
+    if parts and (invert or before_context or after_context):
+        raise ValueError("parts: not combined with invert or context lines")
     c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags, ids=ids)
     c_ext = None if ext is None else ext_array(ext, len(c_patterns))
     c_callback = CALLBACK_TYPE(callback)  # referenced until the call is over
@@ -193,7 +200,13 @@ def scan(  # pylint: disable=too-many-arguments
     outcome = [0]
 
     def native_call() -> None:
-        if before_context or after_context:
+        if parts:
+            engine.hg_hyperscan_parts.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
+                                                  ctypes.POINTER(ctypes.POINTER(ExprExt)), ctypes.c_uint, CALLBACK_TYPE, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_ulonglong]
+            outcome[0] = engine.hg_hyperscan_parts(path.encode(), c_patterns, c_flags, c_ids, c_ext, len(c_patterns), c_callback, buffer_size,
+                                                   buffer_count, max_match_count)
+        elif before_context or after_context:
             engine.hg_hyperscan_context.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
                                                     ctypes.POINTER(ctypes.POINTER(ExprExt)), ctypes.c_uint, CALLBACK_TYPE, ctypes.c_int, ctypes.c_int,
                                                     ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, ctypes.c_int]
@@ -283,7 +296,8 @@ class _GrepSink:
     id the hit carries — with grep()'s all-zero ids that is the first pattern, as in the reference)."""
 
     def __init__(self, patterns: list[str], count_only: bool, only_matching: bool, errors: str, invert: bool = False, context: bool = False,
-                 limit: int = 0, after: int = 0):
+                 limit: int = 0, after: int = 0, parts: bool = False):
+        self.parts = parts  # the hits are matched parts already (scan(parts=True)): one trailing newline off, a bare newline dropped
         self.invert = invert  # the hits are the lines without a match: no matched parts to show
         self.context = context  # rows are (line number, line, is_match); context lines (id HG_ID_CONTEXT) are rows, not counted
         # GNU grep's -m NUM with -A NUM (3.5 and later): after the NUM-th selected line the next `after` lines still go out, all of
@@ -305,6 +319,11 @@ class _GrepSink:
             return
         for hit in (matches[i] for i in range(count)):
             text = hit.line.decode(errors=self.errors)
+            if self.parts:
+                text = text[:-1] if text.endswith("\n") else text
+                if text:
+                    self.rows.append((hit.line_number + 1, text + "\n"))
+                continue
             if self.context:
                 if self.limit and self.selected >= self.limit:  # behind the limit: trailing context only, whatever the line is
                     if hit.line_number <= self.last_line + self.after:
@@ -340,6 +359,7 @@ def grep(  # pylint: disable=too-many-arguments
     invert: bool = False,
     before_context: int = 0,
     after_context: int = 0,
+    matched_parts: bool = False,
 ) -> tuple[int | list[tuple[int, str]], int]:
     """grep for Python: (number of matching lines | [(1-based line number, line)], return code).
 
@@ -352,11 +372,21 @@ def grep(  # pylint: disable=too-many-arguments
     With `max_match_count` and `after_context` the rows end as GNU grep's output (3.5 and later) does: the `after_context` lines
     behind the last counted line are all rows with is_match False, matching or not.  (scan() / hg_hyperscan_context end that
     trailing context before the next matching line instead, as the file API's contract states.)
+    `matched_parts`: the rows are [(1-based line number, part + "\\n")] with the parts the GPU computes (scan(parts=True)): GNU
+    grep's -o over ALL patterns at once, leftmost-longest, honouring `ignore_case`; one trailing "\\n" of a part is stripped
+    first and a part that was only "\\n" is dropped.  It takes precedence over `only_matching`, which alone stays the
+    reference's route (`re.finditer` of the first pattern).  With `invert` the result is [], with `count_only` lines are
+    counted as ever, with context arguments it raises ValueError.
 
     A missing path raises FileNotFoundError and a directory ValueError — or, with `no_messages`, comes back as
     (nothing found, 101).  Invalid regexes raise `re.error` before anything is scanned.
     """
-    sink = _GrepSink(patterns, count_only, only_matching, errors, invert, bool(before_context or after_context), max_match_count, after_context)
+    if matched_parts:
+        if before_context or after_context:
+            raise ValueError("matched_parts: context lines are not supported")
+        only_matching = False
+    with_parts = matched_parts and not invert and not count_only
+    sink = _GrepSink(patterns, count_only, only_matching, errors, invert, bool(before_context or after_context), max_match_count, after_context, with_parts)
     if max_match_count and after_context and not count_only:
         max_match_count += after_context  # (the trailing `after_context` lines hold that many selected lines at most: _GrepSink)
     if not only_matching:
@@ -372,17 +402,22 @@ def grep(  # pylint: disable=too-many-arguments
             raise problem
         return sink.result(), RC_INVALID_FILE
     flags = _GREP_FLAGS | (HS_FLAG_CASELESS if ignore_case else 0)
-    return_code = scan(file, patterns, sink, flags=[flags] * len(patterns), max_match_count=max_match_count, invert=invert,
-                       before_context=before_context, after_context=after_context)
+    if with_parts:
+        return_code = scan(file, patterns, sink, flags=[flags] * len(patterns), max_match_count=max_match_count, parts=True)
+    else:
+        return_code = scan(file, patterns, sink, flags=[flags] * len(patterns), max_match_count=max_match_count, invert=invert,
+                           before_context=before_context, after_context=after_context)
+    if matched_parts and invert and not count_only:
+        return [], return_code  # (a line without a match has no matched part)
     return sink.result(), return_code
 
 
 def grep_files_outcomes(files: Sequence[str], patterns: list[str], **grep_kwargs) -> list:
     """What grep(file, patterns, **grep_kwargs) gives for every file, in order: its result, or the exception it raises (not
-    raised here).  The files share one native call (scan_files); with context lines each file takes grep()."""
+    raised here).  The files share one native call (scan_files); with context lines or matched_parts each file takes grep()."""
     names = list(files)
     outcomes: list = [None] * len(names)
-    if grep_kwargs.get("before_context") or grep_kwargs.get("after_context"):
+    if grep_kwargs.get("before_context") or grep_kwargs.get("after_context") or grep_kwargs.get("matched_parts"):
         for index, name in enumerate(names):
             try:
                 outcomes[index] = grep(name, patterns, **grep_kwargs)

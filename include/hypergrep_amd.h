@@ -227,6 +227,16 @@ int hg_hyperscan_context(char *file_name, const char *const *patterns, const uns
                          hs_event on_event, const int buffer_size, int buffer_count, unsigned long long max_match_count,
                          unsigned int before, unsigned int after, int invert);
 
+/* Matched parts (grep -o) for files: hg_hyperscan_ext's arguments, reader, chunking (parts are per line piece, so the cuts
+ * between a file's chunks carry nothing), decompression and database cache, with the parts stage behind each scan
+ * (hg_scan_device_parts below has the definition).  `on_event` receives one Result{id = the report id of the part's
+ * expression, line_number, line = the part's bytes, NUL-terminated} per part, in (line_number, from) order.  max_match_count
+ * keeps hyperscan()'s rule on reports, which decides the delivered lines; every part of a delivered line goes out.  A
+ * database the stage is not offered for is refused with HYPERSCANNER_DB before anything is read. */
+int hg_hyperscan_parts(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                       const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements,
+                       hs_event on_event, const int buffer_size, int buffer_count, unsigned long long max_match_count);
+
 /* call site hyperscanner.c:136 */
 int hs_compile_multi(const char *const *expressions, const unsigned int *flags, const unsigned int *ids,
                      unsigned int elements, unsigned int mode, const hs_platform_info_t *platform,
@@ -505,6 +515,60 @@ int hg_scan_device_context(hg_scanner_t *scanner, const void *d_text, uint64_t n
 int hg_copy_context(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max);
 /* The same (16-byte records only) into a DEVICE buffer, asynchronously on `stream`. */
 int hg_copy_context_device(hg_scanner_t *scanner, void *d_dst, uint64_t max, void *stream);
+
+/* Matched parts (grep -o): hg_scan_device with a second ordered list, WHAT matched WHERE in every line piece the call
+ * delivers a record for, over all expressions of the database at once.  `result` is filled exactly as hg_scan_device fills it
+ * (same hits, same order; hg_copy_hits* and hg_copy_hit_starts* unchanged).
+ * Definition.  Let L[0, len) be the scanned bytes of a line piece, the unit hg_scan_device numbers (after leading NULs, up to
+ * the first NUL, the '\n' included: see hg_scan_device_invert above), and let the expressions be those of the database with
+ * the flags they were compiled with.
+ *   Expression p MATCHES EXACTLY [s, e), 0 <= s < e <= len, if it has a match spanning those bytes with every assertion
+ *   (^ $ \b \B \A \z \Z, multiline or not) evaluated in the piece's real context: the byte before s, the byte at e, and the
+ *   piece's ends.
+ *   The PARTS of a piece follow GNU grep's -o rule over all expressions at once.  Start with a cursor at 0 and repeat:
+ *   `from` is the smallest s >= cursor at which any expression matches exactly some [s, e); `to` is the largest such e over
+ *   all expressions; `pattern` is the lowest expression index that matches exactly [from, to); emit the part and set the
+ *   cursor to `to`; stop when there is no such s.
+ * Parts of a piece never overlap and never are empty (the compiler rejects expressions that match the empty string).
+ * HS_FLAG_SINGLEMATCH and HS_FLAG_SOM_LEFTMOST do not change the parts: they only govern reports.  A part may include the
+ * piece's '\n' when an expression consumes it (DOTALL `.`); it is reported as it is.
+ * Parts are computed for exactly the pieces for which hg_scan_device delivers at least one record: the distinct line_number
+ * values of the final hits, after every report rule.
+ * Identity, for every accepted database and buffer: the distinct line_number values among the parts equal the distinct
+ * line_number values among the hits.  Every part's `to` is an end the same expression would report on that piece without
+ * HS_FLAG_SINGLEMATCH.
+ * The records: d_parts holds n_parts entries ordered by (line_number, from), hg_part_t{line_number, from, to} with the
+ * offsets inside the scanned bytes (the origin of hg_hit_t.to); d_part_pattern holds the expression INDEX of each part (its
+ * report id is the one the expression was compiled with).  Both are DEVICE pointers, valid until the next scan on this
+ * scanner.  parts_us: the added stage in microseconds (HIP events, as invert_us).
+ * Not offered: the call returns HG_ERR_ARG, scans nothing, and hg_scanner_error names the reason, for a database with an
+ * automaton above 1024 nodes (HG_MAX_NODES: no dense tables to walk), with HS_FLAG_COMBINATION or HS_FLAG_QUIET expressions,
+ * or with any extended parameter (hs_expr_ext_t: distances, offset bounds, min_length): none of these has a part in the above
+ * sense without further rules.  Not combined with invert, context or segments.
+ * The stage runs on the GPU behind the scan (hypergrep_amd/csrc/hg_parts.hip): a wavefront per piece that has a hit, its
+ * lanes 64 consecutive candidate starts, each running an anchored forward walk per expression; per-hit counts, their
+ * exclusive scan, and a second walk that writes the records in order.  The text is read only inside pieces that have a hit.
+ * Cost: the walks of one start are bounded by the longest match from it, so an expression such as a.*b|a on a long line of
+ * `a` makes a piece quadratic in its length. */
+typedef struct hg_part {
+    uint64_t line_number; /* as hg_hit_t.line_number */
+    uint32_t from;        /* the part is the bytes [from, to) of the piece's scanned bytes */
+    uint32_t to;
+} hg_part_t;
+typedef struct hg_parts_result {
+    uint64_t n_parts;
+    const hg_part_t *d_parts;       /* DEVICE pointers, valid until the next scan on this scanner */
+    const uint32_t *d_part_pattern; /* expression index of each part */
+    uint32_t parts_us;              /* the parts stage alone (count launch, scan, the host synchronisation that sizes the output, write launch) */
+    uint32_t reserved;
+} hg_parts_result_t;
+int hg_scan_device_parts(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base,
+                         void *stream, hg_scan_result_t *result, hg_parts_result_t *parts);
+/* Copy the last scan's first `max` parts (and their expression indices, if pattern != NULL) to host memory; none after a
+ * scan without parts. */
+int hg_copy_parts(hg_scanner_t *scanner, hg_part_t *parts, uint32_t *pattern, uint64_t max);
+/* The same (16-byte records only) into a DEVICE buffer, asynchronously on `stream`. */
+int hg_copy_parts_device(hg_scanner_t *scanner, void *d_dst, uint64_t max, void *stream);
 
 /* Many files in one scan (grep -r): hg_scan_device (invert == 0) or hg_scan_device_invert (invert != 0) of a buffer that
  * holds many files one after the other, with per-file results.

@@ -347,6 +347,13 @@ void hg_debug_free_guarded(void *guard_handle) {
   delete g;
 }
 
+int hg_debug_finalize_info(hg_scanner_t *scanner, hg_finalize_info_t *info, uint32_t *fill, uint32_t max_fill) {
+  if (!scanner || !info) return HG_ERR_ARG;
+  const HgScanner::FinInfo &f = scanner->sc->finalize_info();
+  *info = hg_finalize_info_t{f.path, f.fin_shift, f.fin_nb, f.fin_cap, f.id_bits, f.to_bits, f.early_buckets, f.early_beside_stream, f.scan_blocks, scanner->sc->left_bucketed() ? 1u : 0u, 0u, 0u};
+  return fill ? scanner->sc->copy_fin_fill(fill, max_fill, &info->n_fill) : HG_OK;
+}
+
 int hg_debug_upload(void *d_dst, const void *src, uint64_t nbytes) {
   if (!nbytes) return HG_OK;
   if (!d_dst || !src) return HG_ERR_ARG;

@@ -291,6 +291,19 @@ class HgScanner {
   const std::string &last_error() const { return err_; }
   int device() const { return device_; }
   const HgDbView &view() const { return view_; }  // the database's device tables (stream mode: hg_flows.hip)
+  // What the finalize of the last pass did (hg_debug_finalize_info): noted by the host while it plans and queues the pass,
+  // nothing is launched or copied for it during a scan.  path: 0 no pass yet, 1 bucketed, 2 compact with one packed key,
+  // 3 compact with two sorts.
+  struct FinInfo {
+    uint32_t path, fin_shift, fin_nb, fin_cap, id_bits, to_bits;
+    uint32_t early_buckets;  // buckets finalized before the last chunk's side passes were through (the early range) ...
+    uint32_t early_beside_stream;  // ... those of them finalized beside the last stream launch, in front of the joiner
+    uint32_t scan_blocks;    // blocks of hg_fin_scan_kernel, the largest bucket range of the pass
+  };
+  const FinInfo &finalize_info() const { return fin_info_; }
+  bool left_bucketed() const { return fin_fallback_; }
+  // the first `max` bucket fill levels of the last pass, read from the device now (none unless that pass was bucketed)
+  int copy_fin_fill(uint32_t *dst, uint32_t max, uint32_t *n);
 
  private:
   HgScanner() = default;
@@ -385,6 +398,7 @@ class HgScanner {
   bool fin_fallback_ = false;
   uint32_t fin_alloc_ = 0;  // buckets the arrays above hold (they grow with the bucket count a pass asks for)
   uint32_t fin_epoch_ = 0;  // hg_fin_scan_kernel: a fresh value per launch marks the blocks' partial sums as this launch's
+  FinInfo fin_info_{};
   uint64_t fin_expect_hits_ = 0;  // raw hits of the last pass: the next one picks its bucket count for ~24 records a bucket
   void *d_huge_claim_ = nullptr;      // huge automata: (piece start, expression) pairs already run (hg_confirm_huge_kernel), 8-byte slots
   uint64_t huge_claim_slots_ = 0;

@@ -84,6 +84,8 @@ uint32_t bits_for(uint64_t v) {
   while (b < 64 && (v >> b)) b++;
   return b;
 }
+// compact finalize: line, id, `to` and the single bit in ONE 64-bit key (else two sorts)
+bool compact_key_packed(uint64_t line_bound, uint32_t id_bits, uint32_t to_bits) { return bits_for(line_bound) + id_bits + to_bits + 1 <= 64; }
 }  // namespace
 
 // (members of HgScanner) a failed HIP call: its message in err_, HG_ERR_HIP to the caller
@@ -533,6 +535,7 @@ int HgScanner::launch_fin(const PassPlan &p, hipStream_t s, uint32_t lo, uint32_
                        d_fin_total_ + 3, fin_cap, id_bits, to_bits, d_fin_kept_, d_selected_ + 1, d_key_a_, d_perm_b_);
   // (a block per 8192 buckets, 128 at most: their partial sums live behind the two work lists)
   const uint32_t scan_blocks = std::max<uint32_t>(1, std::min<uint32_t>(128, (nbk + 8191) / 8192));
+  fin_info_.scan_blocks = std::max(fin_info_.scan_blocks, scan_blocks);
   uint32_t *part = d_fin_big_ + 2 * static_cast<size_t>(fin_alloc_);
   const uint32_t epoch = ++fin_epoch_ ? fin_epoch_ : ++fin_epoch_;  // (never 0: the flags start out zeroed)
   if (beside_stream) hipLaunchKernelGGL(hg_fin_scan_kernel<512u>, dim3(scan_blocks), dim3(512), 0, s, d_fin_kept_, lo, hi, d_fin_total_, d_fin_fill_, fin_cap, part, epoch);
@@ -540,6 +543,16 @@ int HgScanner::launch_fin(const PassPlan &p, hipStream_t s, uint32_t lo, uint32_
   hipLaunchKernelGGL(hg_fin_gather_kernel, dim3(std::min<uint32_t>((nbk + 3) / 4, cu * 8)), dim3(256), 0, s, d_hits_raw_, d_aux_raw_, d_perm_a_, d_fin_kept_, d_fin_total_, lo, hi, fin_cap,
                      d_hits_out_, d_aux_out_);
   HG_TRY(hipGetLastError(), "finalize launch");
+  return HG_OK;
+}
+
+int HgScanner::copy_fin_fill(uint32_t *dst, uint32_t max, uint32_t *n) {
+  *n = 0;
+  if (fin_info_.path != 1u || !d_fin_fill_ || !dst) return HG_OK;
+  const uint32_t count = std::min(max, fin_info_.fin_nb);
+  HG_TRY(hipSetDevice(device_), "hipSetDevice");
+  if (count) HG_TRY(hipMemcpy(dst, d_fin_fill_, static_cast<size_t>(count) * sizeof(uint32_t), hipMemcpyDeviceToHost), "copy bucket fill levels");
+  *n = count;
   return HG_OK;
 }
 
@@ -580,6 +593,8 @@ int HgScanner::launch_stream(PassPlan &p, uint32_t c, HgScanOutput *out) {
     const uint32_t lim = p.settled_buckets(c);
     if (lim > p.fin_done) {
       if (int rc = launch_fin(p, p.side, p.fin_done, lim, true)) return rc;
+      fin_info_.early_buckets += lim - p.fin_done;
+      fin_info_.early_beside_stream += lim - p.fin_done;
       p.fin_done = lim;
     }
   }
@@ -695,6 +710,7 @@ int HgScanner::finalize_last(PassPlan &p, uint32_t c) {
       HG_TRY(hipStreamWaitEvent(p.stream, ev_tile_done_, 0), "stream wait");        // ... and the last chunk's tile scan (a one-block latency chain) is through
       if (int rc = launch_fin(p, p.stream, p.fin_done, lim)) return rc;
       HG_TRY(hipEventRecord(ev_fin_early_, p.stream), "event");
+      fin_info_.early_buckets += lim - p.fin_done;
       p.fin_done = lim;
       fin_early = true;
     }
@@ -778,7 +794,7 @@ int HgScanner::finalize_compact(const HgHit *hits, const HgHitAux *aux, uint32_t
   const uint32_t *perm = nullptr;
   uint32_t *pos = nullptr;
   size_t tb = temp_bytes_;
-  if (line_bits + id_bits + to_bits + 1 <= 64) {
+  if (compact_key_packed(line_bound, id_bits, to_bits)) {
     hipLaunchKernelGGL(hg_key_packed_kernel, dim3(blocks), dim3(256), 0, stream, hits, aux, pats, n, id_bits, to_bits, d_key_a_, d_perm_a_);
     HG_TRY(rocprim::radix_sort_pairs(d_temp_, tb, d_key_a_, d_key_b_, d_perm_a_, d_perm_b_, n, 0, line_bits + id_bits + to_bits + 1, stream), "radix sort");
     perm = d_perm_b_;
@@ -1264,6 +1280,7 @@ int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint
   p.bucketed = p.bucketed && d_fin_fill_;
   p.ca.bucket_cap = p.bucketed ? p.fin_cap : 0u;
   p.ca.bucket_fill = d_fin_fill_;
+  fin_info_ = FinInfo{p.bucketed ? 1u : 0u, p.fin_shift, p.fin_nb, p.fin_cap, p.id_bits, p.to_bits, 0, 0, 0};
   // one launch puts the device state in place (counters, cursors, finalize totals, tile-scan state, bucket fill levels, the
   // first chunk's verified-occurrence counts)
   hipLaunchKernelGGL(hg_reset_kernel, dim3(std::max<uint32_t>(1, std::min<uint32_t>((p.fin_nb + 255) / 256, 256))), dim3(256), 0, stream, d_counters_, static_cast<uint32_t>(HG_ST_ZERO_WORDS), d_final_,
@@ -1325,8 +1342,10 @@ int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint
     fin_hits = d_minlen_hits_;
     fin_aux = d_minlen_aux_;
   }
+  const uint64_t line_bound = line_base + (range.last ? n_pieces : nbytes) + 1;
+  if (!p.bucketed) fin_info_.path = compact_key_packed(line_bound, p.id_bits, p.to_bits) ? 2u : 3u;
   if (n && !p.bucketed)
-    if (int rc = finalize_compact(fin_hits, fin_aux, n, p.id_bits, p.to_bits, line_base + (range.last ? n_pieces : nbytes) + 1, p.stream)) return rc;
+    if (int rc = finalize_compact(fin_hits, fin_aux, n, p.id_bits, p.to_bits, line_bound, p.stream)) return rc;
   if (!p.bucketed) {
     HG_TRY(hipEventRecord(ev_[3], stream), "event");
     HG_TRY(hipStreamSynchronize(stream), "stream sync (finalize)");

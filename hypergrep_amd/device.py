@@ -66,6 +66,14 @@ class HgSegmentResult(ctypes.Structure):
                 ("segments_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class HgFinalizeInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("path", "fin_shift", "fin_nb", "fin_cap", "id_bits", "to_bits", "early_buckets", "early_beside_stream",
+                                               "scan_blocks", "left_bucketed", "n_fill", "reserved")]
+
+
+FIN_PATHS = ("none", "bucketed", "compact_packed", "compact_wide")  # hg_finalize_info_t.path
+
+
 class HgDbInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("n_patterns", "n_literal_anchored", "n_always_on", "n_factors", "n_windows",
                                                "fold_mask", "max_state_words", "table_bytes", "byte_windows")]
@@ -129,6 +137,7 @@ def lib() -> ctypes.CDLL:
         l.hg_debug_free_guarded.restype = None
         l.hg_debug_upload.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64]
         l.hg_debug_download.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint64]
+        l.hg_debug_finalize_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgFinalizeInfo), ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32]
         l.hg_faceb_next_device.argtypes = [ctypes.c_int]
         l.hg_faceb_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
         l.hg_faceb_stats.restype = None
@@ -357,8 +366,8 @@ class Scanner:
             raise DeviceError(f"hg_copy_hits failed ({rc})")
         return [(hits[i].line_number, hits[i].id, hits[i].to, aux[i].start, aux[i].len) for i in range(n)]
 
-    def hits_array(self):
-        """Last scan's hits as a uint64 numpy array [n_hits, 5], the columns of hits(), without one Python tuple per hit."""
+    def _hit_records(self):
+        """Last scan's hit and aux records as two numpy structured arrays (the layouts of hg_hit_t and hg_hit_aux_t)."""
         import numpy as np
 
         n = self._last.n_hits
@@ -368,7 +377,38 @@ class Scanner:
             rc = lib().hg_copy_hits(self._h, hits.ctypes.data_as(ctypes.POINTER(HgHit)), aux.ctypes.data_as(ctypes.POINTER(HgHitAux)), n)
             if rc != 0:
                 raise DeviceError(f"hg_copy_hits failed ({rc})")
+        return hits, aux
+
+    def hits_array(self):
+        """Last scan's hits as a uint64 numpy array [n_hits, 5], the columns of hits(), without one Python tuple per hit."""
+        import numpy as np
+
+        hits, aux = self._hit_records()
         return np.stack([hits["line_number"], hits["id"], hits["to"], aux["start"], aux["len"]], axis=1).astype(np.uint64)
+
+    def hit_patterns(self):
+        """The expression index (hg_hit_aux_t.pattern) of each of the last scan's hits, in the order of hits(), as a uint32 numpy array."""
+        return self._hit_records()[1]["pattern"].copy()
+
+    def finalize_info(self, fill: bool = False) -> dict:
+        """What the finalize stage of the last pass did (hg_debug_finalize_info): path (one of FIN_PATHS), fin_shift, fin_nb,
+        fin_cap, id_bits, to_bits, early_buckets, early_beside_stream, scan_blocks, left_bucketed; with fill=True also "fill", the raw reports of
+        every bucket as a uint32 numpy array (empty unless the pass was bucketed), read from the device now."""
+        import numpy as np
+
+        info = HgFinalizeInfo()
+        rc = lib().hg_debug_finalize_info(self._h, ctypes.byref(info), None, 0)
+        levels = np.zeros(info.fin_nb if fill and rc == 0 else 0, dtype=np.uint32)
+        if rc == 0 and fill and len(levels):
+            rc = lib().hg_debug_finalize_info(self._h, ctypes.byref(info), levels.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(levels))
+        if rc != 0:
+            raise DeviceError(f"hg_debug_finalize_info failed ({rc})")
+        out = {n: getattr(info, n) for n, _ in HgFinalizeInfo._fields_ if n not in ("n_fill", "reserved")}
+        out["path"] = FIN_PATHS[info.path]
+        out["left_bucketed"] = bool(info.left_bucketed)
+        if fill:
+            out["fill"] = levels[:info.n_fill]
+        return out
 
     def copy_hits_to(self, d_dst: int, limit: int, stream: int = 0) -> int:
         """Async device-to-device copy of the last scan's hit records (16 B each); returns the number copied."""

@@ -655,6 +655,27 @@ int hg_debug_alloc_guarded(uint64_t nbytes, int device, void **d_ptr, void **gua
 void hg_debug_free_guarded(void *guard_handle);
 int hg_debug_upload(void *d_dst, const void *src, uint64_t nbytes);
 int hg_debug_download(void *dst, const void *d_src, uint64_t nbytes);
+/* What the finalize stage of the scanner's last pass did (the last segment's pass, for a buffer scanned in segments), for
+ * tests that must know which of its paths ran.  The host notes it while it plans and queues a pass: a scan launches and
+ * copies nothing for it.  path: how the reports were ordered; fin_shift / fin_nb / fin_cap: buckets of 2^fin_shift text bytes
+ * by line start, their number, the records each may hold; id_bits / to_bits: the key fields' widths.  fill (may be NULL)
+ * receives the raw reports of the first min(max_fill, fin_nb) buckets, copied from the device when the call is made, and
+ * info->n_fill their number (0 unless the last pass was bucketed). */
+#define HG_FIN_PATH_NONE 0u           /* no pass yet */
+#define HG_FIN_PATH_BUCKETED 1u       /* every bucket ordered on its own */
+#define HG_FIN_PATH_COMPACT_PACKED 2u /* compact array, one sort of a packed 64-bit key */
+#define HG_FIN_PATH_COMPACT_WIDE 3u   /* compact array, two sorts: (id, to), then line */
+typedef struct hg_finalize_info {
+    uint32_t path;
+    uint32_t fin_shift, fin_nb, fin_cap, id_bits, to_bits;
+    uint32_t early_buckets; /* buckets finalized before the last pipeline chunk's side passes were through (the early range) */
+    uint32_t early_beside_stream; /* ... those of them finalized beside the last stream launch, in front of its joiner */
+    uint32_t scan_blocks;   /* blocks the position scan used for the pass's largest bucket range */
+    uint32_t left_bucketed; /* the scanner has left bucketed emission: its later passes are compact */
+    uint32_t n_fill;
+    uint32_t reserved;
+} hg_finalize_info_t;
+int hg_debug_finalize_info(hg_scanner_t *scanner, hg_finalize_info_t *info, uint32_t *fill, uint32_t max_fill);
 /* Face B bookkeeping, for tests and HYPERGREP_TRACE: the device the next scan context would be created on for a node of
  * `ndev` GPUs (HYPERGREP_DEVICE pins one, otherwise files round-robin; advances the round-robin), and the cache counters
  * {database cache hits, misses, entries, window tunings, contexts created, reused, re-bound to another pattern set, alive}. */

@@ -31,6 +31,13 @@ def oracle_hits(data, patterns, flags=None, ids=None, buffer_size=262140):
     return sorted(hits), nlines
 
 
+def ordered_hits(sc):
+    """The scanner's hits as delivered, which must already be strictly increasing in (line, id, to)."""
+    hits = sc.hits()
+    assert all(a[:3] < b[:3] for a, b in zip(hits, hits[1:])), "hits() is not strictly increasing in (line, id, to)"
+    return hits
+
+
 def guarded_cases():
     """(name, text, patterns, flags, ids, buffer_size): what a text buffer's last, partial tile can meet."""
     rng = random.Random(20261004)
@@ -85,7 +92,7 @@ def run_guarded() -> dict:
             compiled[key] = (db, device.Scanner(db, 0))
         db, sc = compiled[key]
         stats = sc.scan(arena.place(text), len(text), buffer_size=bs)
-        got = sorted(sc.hits())
+        got = ordered_hits(sc)
         tail = arena.tail(len(text))
         if got != want or stats.n_lines != nlines:
             bad.append({"case": name, "got": len(got), "want": len(want), "lines": [stats.n_lines, nlines], "bytes_after_text": tail.hex(),
@@ -155,7 +162,7 @@ def run_huge() -> dict:
             for bs in ((262140,) if kind == "a32767" else (262140, 2500)):
                 want, nlines = oracle_hits(text, pats, flags, ids, buffer_size=bs)
                 stats = sc.scan(arena.place(text), len(text), buffer_size=bs)
-                got = sorted(sc.hits())
+                got = ordered_hits(sc)
                 if got != want or stats.n_lines != nlines:
                     bad.append({"case": f"buffer-{ci}-{seed}-{bs}", "patterns": pats, "got": len(got), "want": len(want), "lines": [stats.n_lines, nlines],
                                 "extra": sorted(set(got) - set(want))[:6], "missing": sorted(set(want) - set(got))[:6]})
@@ -169,7 +176,7 @@ def run_huge() -> dict:
     db = device.Database(big, ids=[0, 1, 2])
     sc = device.Scanner(db, 0)
     stats = sc.scan(arena.place(text), len(text))
-    if sorted(sc.hits()) != want or stats.n_lines != nlines:
+    if ordered_hits(sc) != want or stats.n_lines != nlines:
         bad.append({"case": "monster", "got": stats.n_hits, "want": len(want)})
     n += 1
     # a huge expression among ordinary ones of every confirm mode, shared ids; then through the file API (batches, line bytes)
@@ -181,7 +188,7 @@ def run_huge() -> dict:
     db = device.Database(mixed, flags=mflags, ids=mids)
     sc = device.Scanner(db, 0)
     stats = sc.scan(arena.place(text), len(text))
-    if sorted(sc.hits()) != want or stats.n_lines != nlines:
+    if ordered_hits(sc) != want or stats.n_lines != nlines:
         bad.append({"case": "mixed-buffer", "got": stats.n_hits, "want": len(want)})
     n += 1
     with tempfile.TemporaryDirectory(dir="/dev/shm" if os.path.isdir("/dev/shm") else None) as tmp:

@@ -14,6 +14,7 @@ import random
 import pytest
 
 import accept_rules
+import gpu_cases
 import oracle_py
 import regex_gen
 
@@ -54,7 +55,7 @@ def gpu_scan_buffer(torch, data: bytes, patterns, flags=None, ids=None, buffer_s
     db = device.Database(patterns, flags=flags, ids=ids)
     sc = device.Scanner(db, 0)
     stats = sc.scan(buf.data_ptr(), n, buffer_size=buffer_size, line_base=line_base)
-    return sorted(sc.hits()), stats
+    return gpu_cases.ordered_hits(sc), stats
 
 
 def oracle_hits(data, patterns, flags=None, ids=None, buffer_size=262140):

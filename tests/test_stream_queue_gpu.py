@@ -7,6 +7,7 @@ import random
 
 import pytest
 
+import gpu_cases
 import oracle_py
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +36,7 @@ def _scan(torch, data: bytes, patterns, **kw):
     ids = list(range(len(patterns)))
     sc = device.Scanner(device.Database(patterns, ids=ids), 0)
     stats = sc.scan(buf.data_ptr(), n, **kw)
-    return sorted(sc.hits()), stats
+    return gpu_cases.ordered_hits(sc), stats
 
 
 def _check(torch, data: bytes, patterns=LITERALS, min_hits=1):

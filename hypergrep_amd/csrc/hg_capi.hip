@@ -24,6 +24,7 @@ struct hg_scanner {
   hg_segment_result_t last_seg;  // the last scan's per-segment arrays (hg_scan_device_segments), else zeroes
   uint32_t last_n_seg;
   hg_parts_result_t last_parts;  // the last scan's parts (hg_scan_device_parts), else zeroes
+  HgSegCtxOutput last_segctx;    // the last scan's per-segment context arrays (hg_scan_device_segments_context), else zeroes
 };
 
 static_assert(HG_ID_CONTEXT == HG_CTX_ID_CONTEXT && HG_ID_CONTEXT_TAIL == HG_CTX_ID_TAIL, "the context records carry the ids the header names");
@@ -95,7 +96,7 @@ int hg_scanner_create(const hg_database_t *db, int device, hg_scanner_t **scanne
     put_err(err, errlen, msg);
     return rc;
   }
-  *scanner = new hg_scanner{sc, {}, nullptr, {}, {}, 0, {}};
+  *scanner = new hg_scanner{sc, {}, nullptr, {}, {}, 0, {}, {}};
   return HG_OK;
 }
 
@@ -119,9 +120,14 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
   int rc;
   scanner->last_seg = hg_segment_result_t{};
   scanner->last_n_seg = 0;
+  scanner->last_segctx = HgSegCtxOutput{};
+  HgSegCtxOutput sx{};
   if (segments) {
     const HgSegParams params{segments->d_seg_start, segments->d_seg_end, segments->n_seg, segments->max_per_segment};
-    rc = scanner->sc->scan_packed(d_text, nbytes, buffer_size, static_cast<hipStream_t>(stream), params, invert, &o, &g);
+    if (context)  // (hg_scan_device_segments_context: per-file context, no carry and no tail)
+      rc = scanner->sc->scan_packed_context(d_text, nbytes, buffer_size, static_cast<hipStream_t>(stream), params, context->before, context->after, invert, &o, &g, &c, &sx);
+    else
+      rc = scanner->sc->scan_packed(d_text, nbytes, buffer_size, static_cast<hipStream_t>(stream), params, invert, &o, &g);
     if (rc != HG_OK) {  // (nothing was scanned, or the scan failed: no records to copy)
       scanner->last = hg_scan_result_t{};
       scanner->d_from = nullptr;
@@ -146,6 +152,7 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
     scanner->last_seg = hg_segment_result_t{g.d_record_segment, g.d_first_record, g.d_n_lines, g.d_n_selected, static_cast<uint32_t>(g.ms_segments * 1000.0f + 0.5f), 0};
     scanner->last_n_seg = segments->n_seg;
     *segment_result = scanner->last_seg;
+    scanner->last_segctx = sx;
   }
   result->n_hits = o.n_hits;
   result->n_lines = o.n_pieces;
@@ -188,6 +195,16 @@ int hg_scan_device_segments(hg_scanner_t *scanner, const void *d_text, uint64_t 
   return scan_device(scanner, d_text, nbytes, buffer_size, 0, stream, result, invert != 0, nullptr, nullptr, segments, segment_result);
 }
 
+int hg_scan_device_segments_context(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, void *stream, const hg_segments_t *segments,
+                                    uint32_t before, uint32_t after, int invert, hg_scan_result_t *result, hg_segment_result_t *segment_result,
+                                    hg_context_result_t *context_result) {
+  if (!segments || !segment_result || !context_result) return HG_ERR_ARG;
+  *segment_result = hg_segment_result_t{};
+  *context_result = hg_context_result_t{};
+  const hg_context_t context{before, after, 0, 0};
+  return scan_device(scanner, d_text, nbytes, buffer_size, 0, stream, result, invert != 0, &context, context_result, segments, segment_result);
+}
+
 int hg_scan_device_parts(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, void *stream, hg_scan_result_t *result,
                          hg_parts_result_t *parts) {
   if (!parts) return HG_ERR_ARG;
@@ -225,6 +242,17 @@ int hg_copy_segments(hg_scanner_t *scanner, uint32_t *record_segment, uint64_t *
   if (first_record && hipMemcpy(first_record, g.d_first_record, (n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
   if (n_lines && n_seg && hipMemcpy(n_lines, g.d_n_lines, n_seg * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
   if (n_selected && n_seg && hipMemcpy(n_selected, g.d_n_selected, n_seg * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
+}
+
+int hg_copy_segment_context(hg_scanner_t *scanner, uint32_t *context_segment, uint64_t *first_context) {
+  if (!scanner) return HG_ERR_ARG;
+  const HgSegCtxOutput &x = scanner->last_segctx;
+  if (!x.d_first_context) return HG_ERR_ARG;  // the last scan was not hg_scan_device_segments_context
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  const uint64_t n = scanner->last_ctx.n_context, n_seg = scanner->last_n_seg;
+  if (context_segment && n && hipMemcpy(context_segment, x.d_context_segment, n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (first_context && hipMemcpy(first_context, x.d_first_context, (n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
   return HG_OK;
 }
 

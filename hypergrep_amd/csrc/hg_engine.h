@@ -11,6 +11,7 @@
 #include "hg_invert.h"
 #include "hg_context.h"
 #include "hg_segments.h"
+#include "hg_segctx.h"
 #include "hg_parts.h"
 #include "hg_post.h"
 
@@ -212,6 +213,17 @@ struct HgSegOutput {
   float ms_segments;  // the stage: check, bases, runs, scan, the host syncs, write
 };
 
+// The per-file context stage (hg_segctx.hip) behind the segment stage, one step per launch on `stream`: the surviving records
+// in packed piece numbers with their segments' windows, the per-tile counts, the ordered write, the file-relative form of the
+// records, and the per-segment offsets.
+enum class HgSegCtxStep { Prep, Count, Write, Map, First };
+hipError_t hg_segctx_launch(const HgSegCtxArgs &a, HgSegCtxStep step, uint32_t num_cus, hipStream_t stream);
+// What it leaves beside HgContextOutput (hg_copy_segment_context of the C ABI).
+struct HgSegCtxOutput {
+  const uint32_t *d_context_segment;  // device arrays, valid until the next scan on this scanner: the segment of each context record
+  const uint64_t *d_first_context;    // n_seg + 1: segment s owns the context records [first_context[s], first_context[s + 1])
+};
+
 // The parts stage (hg_parts.hip) over the n_hits final hits of a scan, on `stream`: count (write == false: count[i] = parts of
 // the piece whose first hit is hit i, 0 for its other hits, count[n_hits] = 0), or write the parts of that piece to
 // out / out_pattern [pos[i] ..].  max_nw: the most state words of any expression (multi-word walks keep their state in LDS).
@@ -277,6 +289,10 @@ class HgScanner {
   // malformed segments.
   int scan_packed(const void *d_text, uint64_t nbytes, int buffer_size, hipStream_t stream, const HgSegParams &params, bool invert, HgScanOutput *out,
                   HgSegOutput *seg);
+  // The same with the per-file context stage behind it: *out and *seg are exactly scan_packed's, *ctx the pieces around each
+  // segment's surviving records inside that segment (file-relative, segment after segment), *sc says which are whose.
+  int scan_packed_context(const void *d_text, uint64_t nbytes, int buffer_size, hipStream_t stream, const HgSegParams &params, uint32_t before, uint32_t after,
+                          bool invert, HgScanOutput *out, HgSegOutput *seg, HgContextOutput *ctx, HgSegCtxOutput *sc);
   // The plain scan with the parts stage behind it: *out is exactly scan()'s, *parts the matched parts of the pieces that have a
   // hit.  HG_ERR_ARG (nothing scanned, the reason in last_error()) for a database the stage is not offered for (hg_parts_refusal).
   int scan_parts(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, hipStream_t stream, HgScanOutput *out, HgPartsOutput *parts);
@@ -342,6 +358,7 @@ class HgScanner {
   int segment_records(uint64_t n);
   int pad_filter(const HgSegArgs &checked, float *ms, hipStream_t stream, HgScanOutput *out);
   int segment_pass(const HgSegArgs &checked, float ms_check, hipStream_t stream, HgScanOutput *out, HgSegOutput *seg);
+  int segctx_pass(uint32_t before, uint32_t after, hipStream_t stream, const HgScanOutput &out, HgContextOutput *ctx, HgSegCtxOutput *sc);
   int huge_lds_error() { return error(HG_ERR_HIP, "the huge-automaton kernel cannot have its LDS"); }
   bool fail(hipError_t e, const char *what);
   int error(int rc, const std::string &what) { err_ = what; return rc; }
@@ -467,6 +484,18 @@ class HgScanner {
   uint64_t seg_rec_cap_ = 0;
   uint64_t *d_pad_keep_ = nullptr, *d_pad_pos_ = nullptr;  // pad filter of inverted calls: a flag per hit and their exclusive scan
   uint64_t pad_cap_ = 0;
+  // per-file context stage (calls with segments and context only): what the last segment pass worked on (its packed records
+  // and per-segment arrays stay valid behind it), first_context, the surviving records in packed numbers with their segments'
+  // windows, and the segment of each context record.  The per-tile counts,
+  // their scan and the context records are the context stage's own buffers.
+  HgSegArgs seg_last_{};
+  uint64_t *d_segctx_first_ = nullptr;
+  uint64_t segctx_seg_cap_ = 0;
+  HgHit *d_segctx_k_ = nullptr;
+  HgSegCtxWin *d_segctx_win_ = nullptr;
+  uint64_t segctx_k_cap_ = 0;
+  uint32_t *d_segctx_of_ = nullptr;
+  uint64_t segctx_of_cap_ = 0;
   uint32_t *d_seg_count2_ = nullptr;  // second set for double buffering
   HgCand *d_cands2_ = nullptr;
 };

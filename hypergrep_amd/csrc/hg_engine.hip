@@ -246,7 +246,8 @@ HgScanner::~HgScanner() {
                   d_min_lengths_, d_minlen_hits_, d_minlen_aux_, d_inv_count_, d_inv_pos_, d_inv_temp_, d_inv_hits_, d_inv_aux_,
                   d_ctx_count_, d_ctx_pos_, d_ctx_temp_, d_ctx_hits_, d_ctx_aux_,
                   d_parts_first_, d_parts_count_, d_parts_pos_, d_parts_temp_, d_parts_, d_part_pattern_,
-                  d_segw_, d_seg_flag_, d_seg_temp_, d_seg_hits_, d_seg_aux_, d_seg_of_, d_seg_from_, d_pad_keep_, d_pad_pos_};
+                  d_segw_, d_seg_flag_, d_seg_temp_, d_seg_hits_, d_seg_aux_, d_seg_of_, d_seg_from_, d_pad_keep_, d_pad_pos_,
+                  d_segctx_first_, d_segctx_k_, d_segctx_win_, d_segctx_of_};
   for (void *p : ptrs) hgmem::dev_free(p, "scanner");
   hgmem::host_free(h_counters_, "h_counters_");
   for (auto &ev : ev_)
@@ -1207,6 +1208,7 @@ int HgScanner::segment_pass(const HgSegArgs &checked, float ms_check, hipStream_
   if (total > out->n_hits) return error(HG_ERR_HIP, "the segment stage kept more records than the scan has");
   float ms = 0;
   (void)hipEventElapsedTime(&ms, ev_[0], ev_[3]);
+  seg_last_ = a;  // (what a per-file context stage behind this pass reads: the packed records stay where they are)
   seg->ms_segments = ms_check + ms;
   seg->d_record_segment = d_seg_of_;
   seg->d_first_record = a.first;
@@ -1267,6 +1269,129 @@ int HgScanner::scan_packed(const void *d_text, uint64_t nbytes, int buffer_size,
     if (int rc = invert_pass(a.text, nbytes, a.bs1, 0, stream, out)) return rc;
   }
   return segment_pass(a, ms_check, stream, out, seg);
+}
+
+// The per-file context stage over a finished segment pass (`out`: the surviving records, file-relative; seg_last_: the packed
+// records and the per-segment arrays they came from; all untouched): the surviving records' packed piece numbers and their segments'
+// windows, the per-tile counts from those alone, their exclusive scan, the ordered write pass over the tiles that hold
+// context, and the records made file-relative with their segments and per-segment offsets (hg_segctx.hip).  It shares the
+// context stage's per-tile and record buffers: a scanner runs one of the two per call.  Two host synchronisations, as in
+// context_pass: the one that sizes the output, and the one behind the write that the stage's time is read after.
+int HgScanner::segctx_pass(uint32_t before, uint32_t after, hipStream_t stream, const HgScanOutput &out, HgContextOutput *ctx, HgSegCtxOutput *sc) {
+  const HgSegArgs &g = seg_last_;
+  const uint64_t ntiles = g.ntiles, n_seg = g.n_seg;
+  if (n_seg + 1 > segctx_seg_cap_) {
+    const uint64_t cap = std::max<uint64_t>(n_seg + n_seg / 4 + 1, 4096);
+    segctx_seg_cap_ = 0;
+    HG_TRY(realloc_dev(d_segctx_first_, cap, "d_segctx_first_"), "alloc (per-file context stage)");
+    segctx_seg_cap_ = cap;
+  }
+  uint64_t *d_first = d_segctx_first_;
+  sc->d_first_context = d_first;
+  if ((!before && !after) || ntiles == 0 || out.n_hits == 0) {  // no context asked for, or no record to have any: the stage is skipped
+    HG_TRY(hipMemsetAsync(d_first, 0, (n_seg + 1) * sizeof(uint64_t), stream), "memset (per-file context stage)");
+    HG_TRY(hipStreamSynchronize(stream), "stream sync (per-file context stage)");
+    return HG_OK;
+  }
+  if (ntiles + 2 > ctx_tiles_cap_) {
+    const uint64_t cap = std::max<uint64_t>(ntiles + ntiles / 4 + 2, 4096);
+    ctx_tiles_cap_ = 0;
+    HG_TRY(realloc_dev(d_ctx_count_, cap, "d_ctx_count_"), "alloc (context stage)");
+    HG_TRY(realloc_dev(d_ctx_pos_, cap, "d_ctx_pos_"), "alloc (context stage)");
+    ctx_tiles_cap_ = cap;
+  }
+  size_t tb = 0;  // the scan's scratch, asked for the size that is scanned
+  HG_TRY(rocprim::exclusive_scan(nullptr, tb, d_ctx_count_, d_ctx_pos_, uint64_t{0}, ntiles + 1, rocprim::plus<uint64_t>(), stream), "scan (per-file context stage)");
+  if (tb > ctx_temp_bytes_ || !d_ctx_temp_) {
+    ctx_temp_bytes_ = 0;
+    HG_TRY(realloc_dev(d_ctx_temp_, tb + tb / 4, "d_ctx_temp_"), "alloc (context stage)");
+    ctx_temp_bytes_ = tb + tb / 4;
+  }
+  if (out.n_hits > segctx_k_cap_) {
+    const uint64_t cap = std::max<uint64_t>(out.n_hits + out.n_hits / 4, 4096);
+    segctx_k_cap_ = 0;
+    HG_TRY(realloc_dev(d_segctx_k_, cap, "d_segctx_k_"), "alloc (per-file context stage)");
+    HG_TRY(realloc_dev(d_segctx_win_, cap, "d_segctx_win_"), "alloc (per-file context stage)");
+    segctx_k_cap_ = cap;
+  }
+  HgSegCtxArgs a{};
+  a.text = g.text;
+  a.nbytes = g.nbytes;
+  a.bs1 = g.bs1;
+  a.ntiles = ntiles;
+  a.end_piece = g.end_piece;
+  a.before = before;
+  a.after = after;
+  a.sums = g.sums;
+  a.bases = g.bases;
+  a.hits = g.hits;
+  a.aux = g.aux;
+  a.n_hits = g.n_hits;
+  a.seg_start = g.seg_start;
+  a.seg_end = g.seg_end;
+  a.n_seg = n_seg;
+  a.limit = g.limit;
+  a.invert = g.invert;
+  a.B = g.B;
+  a.E = g.E;
+  a.r0 = g.r0;
+  a.kept = g.kept;
+  a.seg_hits = out.d_hits;
+  a.seg_of = d_seg_of_;
+  a.n_kept = out.n_hits;
+  a.K = d_segctx_k_;
+  a.W = d_segctx_win_;
+  a.count = d_ctx_count_;
+  a.pos = d_ctx_pos_;
+  a.first_ctx = d_first;
+  const uint32_t cus = static_cast<uint32_t>(num_cus_);
+  HG_TRY(hipEventRecord(ev_[0], stream), "event");
+  HG_TRY(hg_segctx_launch(a, HgSegCtxStep::Prep, cus, stream), "per-file context stage launch (prepare)");
+  HG_TRY(hg_segctx_launch(a, HgSegCtxStep::Count, cus, stream), "per-file context stage launch (count)");
+  HG_TRY(rocprim::exclusive_scan(d_ctx_temp_, tb, d_ctx_count_, d_ctx_pos_, uint64_t{0}, ntiles + 1, rocprim::plus<uint64_t>(), stream), "scan (per-file context stage)");
+  uint64_t total = 0;
+  HG_TRY(hipMemcpyAsync(&total, d_ctx_pos_ + ntiles, sizeof total, hipMemcpyDeviceToHost, stream), "copy count");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (per-file context stage)");
+  if (total > g.end_piece) return error(HG_ERR_HIP, "the per-file context stage counted more pieces than the buffer has");
+  if (total > ctx_cap_) {
+    const uint64_t cap = std::max<uint64_t>(total + total / 4, 4096);
+    ctx_cap_ = 0;
+    HG_TRY(realloc_dev(d_ctx_hits_, cap, "d_ctx_hits_"), "alloc (context stage records)");
+    HG_TRY(realloc_dev(d_ctx_aux_, cap, "d_ctx_aux_"), "alloc (context stage records)");
+    ctx_cap_ = cap;
+  }
+  if (total > segctx_of_cap_) {
+    const uint64_t cap = std::max<uint64_t>(total + total / 4, 4096);
+    segctx_of_cap_ = 0;
+    HG_TRY(realloc_dev(d_segctx_of_, cap, "d_segctx_of_"), "alloc (per-file context stage records)");
+    segctx_of_cap_ = cap;
+  }
+  a.n_ctx = total;
+  a.out_hits = d_ctx_hits_;
+  a.out_aux = d_ctx_aux_;
+  a.out_seg = d_segctx_of_;
+  if (total) {
+    HG_TRY(hg_segctx_launch(a, HgSegCtxStep::Write, cus, stream), "per-file context stage launch (write)");
+    HG_TRY(hg_segctx_launch(a, HgSegCtxStep::Map, cus, stream), "per-file context stage launch (map)");
+  }
+  HG_TRY(hg_segctx_launch(a, HgSegCtxStep::First, cus, stream), "per-file context stage launch (offsets)");
+  HG_TRY(hipEventRecord(ev_[3], stream), "event");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (per-file context stage)");
+  (void)hipEventElapsedTime(&ctx->ms_context, ev_[0], ev_[3]);
+  ctx->n_context = total;
+  ctx->d_hits = d_ctx_hits_;
+  ctx->d_aux = d_ctx_aux_;
+  sc->d_context_segment = d_segctx_of_;
+  return HG_OK;
+}
+
+int HgScanner::scan_packed_context(const void *d_text, uint64_t nbytes, int buffer_size, hipStream_t stream, const HgSegParams &params, uint32_t before,
+                                   uint32_t after, bool invert, HgScanOutput *out, HgSegOutput *seg, HgContextOutput *ctx, HgSegCtxOutput *sc) {
+  if (!ctx || !sc) return error(HG_ERR_ARG, "invalid arguments");
+  *ctx = HgContextOutput{};
+  *sc = HgSegCtxOutput{};
+  if (int rc = scan_packed(d_text, nbytes, buffer_size, stream, params, invert, out, seg)) return rc;
+  return segctx_pass(before, after, stream, *out, ctx, sc);
 }
 
 int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const PassRange &range, bool block_mode, hipStream_t stream,

@@ -921,10 +921,17 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
 // context of the pool while scan_file takes one.  An empty regular file is an empty segment.  Batches go out in file
 // order and no batch mixes files; a file's results and rc are those of hg_hyperscan_ext / hg_hyperscan_invert for that file.
 // The line bytes of a result come from the pack's host copy: only the 32-byte records and the per-file arrays leave the GPU.
-extern "C" int hg_hyperscan_files(const char *const *file_names, unsigned int n_files, const char *const *patterns, const unsigned int *pattern_flags,
-                                  const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hg_files_event on_event,
-                                  void *context, const int buffer_size, int buffer_count, unsigned long long max_match_count, int invert,
-                                  hg_file_summary_t *summaries) {
+//
+// With before / after (hg_hyperscan_files_context) each pack is one scan_packed_context: the per-file context stage runs behind
+// the segment stage, and a file's own results and its context records (file-relative both) are merged by line on the way into
+// the ring, as scan_file merges a chunk's.  The limit needs no trailing state here: the stage has already ended the last kept
+// line's after-context before the next matching piece.  Files of the per-file route take scan_file with the same before / after.
+static int files_impl(const char *const *file_names, unsigned int n_files, const char *const *patterns, const unsigned int *pattern_flags,
+                      const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hg_files_event on_event, void *context,
+                      const int buffer_size, int buffer_count, unsigned long long max_match_count, int invert, hg_file_summary_t *summaries, uint32_t before,
+                      uint32_t after) {
+  if (!on_event) before = after = 0;  // summaries only: they are those of the call without context
+  const bool with_context = before || after;
   if (!summaries || (!file_names && n_files) || buffer_count < 1 || buffer_size < 1) return HYPERSCANNER_STATE_MEM;
   if (max_match_count > 0 && max_match_count < static_cast<unsigned long long>(buffer_count)) buffer_count = static_cast<int>(max_match_count);
   for (unsigned int i = 0; i < n_files; i++) summaries[i] = hg_file_summary_t{0, 0, 0};
@@ -939,13 +946,13 @@ extern "C" int hg_hyperscan_files(const char *const *file_names, unsigned int n_
     uint64_t selected = 0, last = ~0ull, pieces = 0;
     FileEvent ev = [&](hyperscanner_result_t *r, int n) {
       for (int i = 0; i < n; i++)
-        if (r[i].line_number != last) {
+        if (r[i].line_number != last && !(with_context && r[i].id == HG_CTX_ID_CONTEXT)) {  // (a context line is no result of the file's)
           last = r[i].line_number;
           selected++;
         }
       if (on_event) on_event(f, r, n, context);
     };
-    const int rc = scan_file(file_names[f], patterns, pattern_flags, pattern_ids, ext, elements, ev, buffer_size, buffer_count, max_match_count, invert != 0, 0, 0, &pieces);
+    const int rc = scan_file(file_names[f], patterns, pattern_flags, pattern_ids, ext, elements, ev, buffer_size, buffer_count, max_match_count, invert != 0, before, after, &pieces);
     summaries[f] = hg_file_summary_t{rc, pieces, selected};
   };
   const size_t cap = chunk_bytes();
@@ -964,7 +971,9 @@ extern "C" int hg_hyperscan_files(const char *const *file_names, unsigned int n_
     uint64_t **p;
     ~FreeSegs() { hgmem::dev_free(*p, "d_segs"); }
   } free_segs{&d_segs};
-  std::vector<uint64_t> seg_start, seg_end, first, n_lines, n_selected;
+  std::vector<uint64_t> seg_start, seg_end, first, n_lines, n_selected, first_ctx;
+  std::vector<HgHit> ctx_hits;  // the pack's context records, file-relative, file after file
+  std::vector<HgHitAux> ctx_aux;
   std::vector<unsigned int> seg_file;
   size_t fill = 0;  // bytes of the pack so far (in ctx->h_slot[0])
   Ring ring;
@@ -1002,7 +1011,19 @@ extern "C" int hg_hyperscan_files(const char *const *file_names, unsigned int n_
                     hipMemcpyAsync(d_segs, seg_start.data(), n_seg * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
                     hipMemcpyAsync(d_segs + n_seg, seg_end.data(), n_seg * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
                     hipStreamSynchronize(ctx->stream) == hipSuccess;
-      int src = copied ? ctx->sc->scan_packed(ctx->d_text[0], fill, buffer_size, ctx->stream, params, invert != 0, &out, &seg) : HG_ERR_HIP;
+      HgContextOutput cout{};
+      HgSegCtxOutput sx{};
+      int src = !copied        ? HG_ERR_HIP
+                : with_context ? ctx->sc->scan_packed_context(ctx->d_text[0], fill, buffer_size, ctx->stream, params, before, after, invert != 0, &out, &seg, &cout, &sx)
+                               : ctx->sc->scan_packed(ctx->d_text[0], fill, buffer_size, ctx->stream, params, invert != 0, &out, &seg);
+      first_ctx.assign(n_seg + 1, 0);
+      ctx_hits.resize(src == HG_OK ? cout.n_context : 0);
+      ctx_aux.resize(ctx_hits.size());
+      if (src == HG_OK && with_context &&
+          ((cout.n_context && (hipMemcpyAsync(ctx_hits.data(), cout.d_hits, cout.n_context * sizeof(HgHit), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                               hipMemcpyAsync(ctx_aux.data(), cout.d_aux, cout.n_context * sizeof(HgHitAux), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) ||
+           hipMemcpyAsync(first_ctx.data(), sx.d_first_context, (n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
+        src = HG_ERR_HIP;  // (the synchronisation below waits for these copies too)
       if (src == HG_OK) {
         const bool rows = on_event != nullptr && out.n_hits;  // counts only: no record leaves the GPU
         ctx->hits.resize(rows ? out.n_hits : 0);
@@ -1019,13 +1040,22 @@ extern "C" int hg_hyperscan_files(const char *const *file_names, unsigned int n_
         std::fprintf(stderr, "ERROR: Unable to scan buffer. Exiting. (%s)\n", ctx->sc ? ctx->sc->last_error().c_str() : "copy");
         fail_pack(HYPERSCANNER_SCAN);
       } else {
+        if (std::getenv("HYPERGREP_TRACE"))  // the packed route: one line per pack
+          std::fprintf(stderr, "[hypergrep_amd] pack: %zu files, %.1f MiB in one scan; segment stage %.0f us, %llu records; context stage %.0f us, %llu context records\n", n_seg,
+                       fill / 1048576.0, seg.ms_segments * 1e3, static_cast<unsigned long long>(out.n_hits), cout.ms_context * 1e3,
+                       static_cast<unsigned long long>(cout.n_context));
         for (size_t s = 0; s < n_seg; s++) {
           cur_file = seg_file[s];
           summaries[cur_file] = hg_file_summary_t{0, n_lines[s], n_selected[s]};
           if (!on_event) continue;
           const uint8_t *base = host + seg_start[s];  // the records are file-relative
           // line by line; inside a line reports go out by ascending end offset, then id (as scan_file)
+          size_t ci = first_ctx[s];  // the file's context records below a line go out in front of it, the rest behind the last
+          const auto deliver_context = [&](uint64_t upto) {
+            for (; ci < first_ctx[s + 1] && ctx_hits[ci].line_no < upto; ci++) ring.push(HG_CTX_ID_CONTEXT, ctx_hits[ci].line_no, base + ctx_aux[ci].start, ctx_aux[ci].len);
+          };
           for (size_t i = first[s], j; i < first[s + 1]; i = j) {
+            deliver_context(ctx->hits[i].line_no);
             for (j = i; j < first[s + 1] && ctx->hits[j].line_no == ctx->hits[i].line_no; j++) {}
             std::vector<size_t> order(j - i);
             for (size_t q = 0; q < order.size(); q++) order[q] = i + q;
@@ -1035,6 +1065,7 @@ extern "C" int hg_hyperscan_files(const char *const *file_names, unsigned int n_
             });
             for (size_t q : order) ring.push(ctx->hits[q].id, ctx->hits[q].line_no, base + ctx->aux[q].start, ctx->aux[q].len);
           }
+          deliver_context(~0ull);
           ring.flush();  // no batch mixes files
         }
       }
@@ -1101,6 +1132,24 @@ extern "C" int hg_hyperscan_files(const char *const *file_names, unsigned int n_
   }
   if (healthy) flush_pack();
   return 0;
+}
+
+extern "C" int hg_hyperscan_files(const char *const *file_names, unsigned int n_files, const char *const *patterns, const unsigned int *pattern_flags,
+                                  const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hg_files_event on_event,
+                                  void *context, const int buffer_size, int buffer_count, unsigned long long max_match_count, int invert,
+                                  hg_file_summary_t *summaries) {
+  return files_impl(file_names, n_files, patterns, pattern_flags, pattern_ids, ext, elements, on_event, context, buffer_size, buffer_count, max_match_count, invert, summaries, 0, 0);
+}
+
+extern "C" int hg_hyperscan_files_context(const char *const *file_names, unsigned int n_files, const char *const *patterns, const unsigned int *pattern_flags,
+                                          const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hg_files_event on_event,
+                                          void *context, const int buffer_size, int buffer_count, unsigned long long max_match_count, int invert,
+                                          hg_file_summary_t *summaries, unsigned int before, unsigned int after) {
+  // an expression with one of the context ids could not be told from a context line by the callback
+  for (unsigned int i = 0; on_event && pattern_ids && i < elements; i++)
+    if (pattern_ids[i] >= HG_CTX_ID_TAIL) return HYPERSCANNER_DB;
+  return files_impl(file_names, n_files, patterns, pattern_flags, pattern_ids, ext, elements, on_event, context, buffer_size, buffer_count, max_match_count, invert, summaries, before,
+                    after);
 }
 
 extern "C" int hg_hyperscan_ext(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,

@@ -119,6 +119,11 @@ def lib() -> ctypes.CDLL:
         if hasattr(l, "hg_scan_device_segments"):  # (absent from a build before the segment stage)
             l.hg_scan_device_segments.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(HgSegments),
                                                   ctypes.c_int, ctypes.POINTER(HgScanResult), ctypes.POINTER(HgSegmentResult)]
+            if hasattr(l, "hg_scan_device_segments_context"):  # (absent from a build before the per-file context stage)
+                l.hg_scan_device_segments_context.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(HgSegments),
+                                                              ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(HgScanResult), ctypes.POINTER(HgSegmentResult),
+                                                              ctypes.POINTER(HgContextResult)]
+                l.hg_copy_segment_context.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]
             l.hg_copy_segments.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint64)]
         if hasattr(l, "hg_scan_device_parts"):  # (absent from a build before the matched parts)
@@ -246,6 +251,9 @@ class Scanner:
         context = (before, after): grep -B / -A in line pieces (hg_scan_device_context).  hits() is what it is without context;
         context() gives the pieces around them.  carry_after: the owed_after of the previous buffer of a chain; tail: also
         deliver the last `before` pieces that are neither match nor context, as HG_ID_CONTEXT_TAIL records.
+        With segments, context is per file (hg_scan_device_segments_context): context() gives every file's context pieces as a
+        scan of the file alone would, file after file, and segment_context() says which are whose; carry_after, tail and
+        line_base are refused, because nothing chains across files.
         segments = (starts, ends): the text holds many files one after the other (hg_scan_device_segments has the packing
         rule); two sequences of offsets, or (d_starts, d_ends, n) for arrays already on the device.  hits() then gives every
         file's records as a scan of the file alone would, file after file, and segments() says which are whose.
@@ -261,15 +269,22 @@ class Scanner:
         sres = HgSegmentResult()
         self._last_seg = None
         if segments is not None:
-            if context is not None or carry_after or tail or line_base:
-                raise ValueError("segments: context lines and line_base are not supported")
+            if carry_after or tail or line_base:
+                raise ValueError("segments: carry_after, tail and line_base are not supported (nothing chains across files)")
             d_starts, d_ends, n_seg = segments if len(segments) == 3 else self._place_segments(*segments)
-            name = "hg_scan_device_segments"
             seg = HgSegments(d_starts, d_ends, n_seg, max_per_segment)
-            rc = lib().hg_scan_device_segments(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, ctypes.c_void_p(stream), ctypes.byref(seg), 1 if invert else 0,
-                                               ctypes.byref(res), ctypes.byref(sres))
+            if context is not None:
+                before, after = context
+                name = "hg_scan_device_segments_context"
+                rc = lib().hg_scan_device_segments_context(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, ctypes.c_void_p(stream), ctypes.byref(seg), before, after,
+                                                           1 if invert else 0, ctypes.byref(res), ctypes.byref(sres), ctypes.byref(cres))
+            else:
+                name = "hg_scan_device_segments"
+                rc = lib().hg_scan_device_segments(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, ctypes.c_void_p(stream), ctypes.byref(seg), 1 if invert else 0,
+                                                   ctypes.byref(res), ctypes.byref(sres))
             if rc == -1:  # HG_ERR_ARG: nothing was scanned
                 self._last = HgScanResult()
+                self._last_ctx = HgContextResult()
                 raise ValueError(f"{name}: {lib().hg_scanner_error(self._h).decode(errors='replace')}")
             if rc == 0:
                 self._last_seg = (sres, n_seg)
@@ -313,6 +328,24 @@ class Scanner:
                                     out["n_lines"].ctypes.data_as(p64), out["n_selected"].ctypes.data_as(p64))
         if rc != 0:
             raise DeviceError(f"hg_copy_segments failed ({rc})")
+        return out
+
+    def segment_context(self):
+        """Whose the context records of the last scan with segments and context are, as numpy arrays: a dict with
+        context_segment (uint32, one per record of context()) and first_context (uint64, n + 1: file s owns
+        context()[first_context[s]:first_context[s + 1]]).  ValueError after a scan of any other kind."""
+        import numpy as np
+
+        if self._last_seg is None:
+            raise ValueError("the last scan had no segments")
+        _, n_seg = self._last_seg
+        out = {"context_segment": np.zeros(self._last_ctx.n_context, dtype=np.uint32), "first_context": np.zeros(n_seg + 1, dtype=np.uint64)}
+        rc = lib().hg_copy_segment_context(self._h, out["context_segment"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                           out["first_context"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+        if rc == -1:
+            raise ValueError("the last scan had segments without context")
+        if rc != 0:
+            raise DeviceError(f"hg_copy_segment_context failed ({rc})")
         return out
 
     def context(self, limit: int | None = None):

@@ -212,10 +212,10 @@ def parallel_grep(  # pylint: disable=too-many-arguments,too-many-locals
         job_kwargs.update(before_context=before_context, after_context=after_context)
     elif gnu_parts and only_matching and not invert_match:
         job_kwargs["matched_parts"] = True
-    # More than one file, no context, threads: the batch route.  The files share one native call, small ones one GPU scan
-    # (hypergrep_amd.grep_files); the outcomes are replayed exactly as the per-file jobs' are.  HYPERGREP_BATCH_FILES=0 keeps
-    # the per-file route (A/B runs).
-    if len(files) > 1 and not context and use_multithreading and os.environ.get("HYPERGREP_BATCH_FILES", "1") != "0":
+    # More than one file, threads: the batch route, with or without context lines.  The files share one native call, small ones
+    # one GPU scan (hypergrep_amd.grep_files); the outcomes are replayed exactly as the per-file jobs' are.
+    # HYPERGREP_BATCH_FILES=0 keeps the per-file route (A/B runs).
+    if len(files) > 1 and use_multithreading and os.environ.get("HYPERGREP_BATCH_FILES", "1") != "0":
         try:
             outcomes = hypergrep_amd.utils.grep_files_outcomes(files, patterns, **job_kwargs)
         except Exception as error:  # pylint: disable=broad-except

@@ -255,12 +255,18 @@ def scan_files(  # pylint: disable=too-many-arguments
     max_match_count: int = 0,
     ext=None,
     invert: bool = False,
+    before_context: int = 0,
+    after_context: int = 0,
 ) -> list[tuple[int, int, int]]:
     """scan() for many files in ONE native call (hg_hyperscan_files): small files are packed into one buffer and share one GPU
     scan.  `on_match(file_index, matches, count)` receives each file's results in batches of `buffer_count`, in file order, no
     batch mixing files; every file's results are those scan() gives for it alone (`max_match_count` bounds each file).  Without
     a callback (None) only the per-file summaries are produced.  Returns one (return code, line pieces, distinct result lines)
-    per file; a missing or unreadable file has return code 6 and does not disturb the others.  Context lines are not offered."""
+    per file; a missing or unreadable file has return code 6 and does not disturb the others.
+    `before_context` / `after_context` (hg_hyperscan_files_context): each file's batches also hold the lines around its results,
+    one Result with id HG_ID_CONTEXT each, merged in line order, exactly as scan() with the same arguments gives them for the
+    file alone; the context stays inside the file, the summaries do not count it, and pattern ids of 0xFFFFFFFD and above are
+    refused (return code 4)."""
     names = [os.fspath(name) for name in files]
     c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags, ids=ids)
     c_ext = None if ext is None else ext_array(ext, len(c_patterns))
@@ -277,6 +283,11 @@ def scan_files(  # pylint: disable=too-many-arguments
     outcome = [0]
 
     def native_call() -> None:
+        if before_context or after_context:
+            engine.hg_hyperscan_files_context.argtypes = engine.hg_hyperscan_files.argtypes + [ctypes.c_uint, ctypes.c_uint]
+            outcome[0] = engine.hg_hyperscan_files_context(c_names, len(names), c_patterns, c_flags, c_ids, c_ext, len(c_patterns), c_callback, None, buffer_size,
+                                                           buffer_count, max_match_count, 1 if invert else 0, summaries, before_context, after_context)
+            return
         outcome[0] = engine.hg_hyperscan_files(c_names, len(names), c_patterns, c_flags, c_ids, c_ext, len(c_patterns), c_callback, None, buffer_size,
                                                buffer_count, max_match_count, 1 if invert else 0, summaries)
 
@@ -414,10 +425,11 @@ def grep(  # pylint: disable=too-many-arguments
 
 def grep_files_outcomes(files: Sequence[str], patterns: list[str], **grep_kwargs) -> list:
     """What grep(file, patterns, **grep_kwargs) gives for every file, in order: its result, or the exception it raises (not
-    raised here).  The files share one native call (scan_files); with context lines or matched_parts each file takes grep()."""
+    raised here).  The files share one native call (scan_files), with context lines too (every file has a sink built as grep()
+    builds it); with matched_parts each file takes grep()."""
     names = list(files)
     outcomes: list = [None] * len(names)
-    if grep_kwargs.get("before_context") or grep_kwargs.get("after_context") or grep_kwargs.get("matched_parts"):
+    if grep_kwargs.get("matched_parts"):
         for index, name in enumerate(names):
             try:
                 outcomes[index] = grep(name, patterns, **grep_kwargs)
@@ -430,10 +442,16 @@ def grep_files_outcomes(files: Sequence[str], patterns: list[str], **grep_kwargs
     no_messages = grep_kwargs.get("no_messages", False)
     invert = grep_kwargs.get("invert", False)
     max_match_count = grep_kwargs.get("max_match_count", 0)
-    unknown = set(grep_kwargs) - {"ignore_case", "count_only", "only_matching", "no_messages", "errors", "max_match_count", "invert", "before_context", "after_context"}
+    before_context, after_context = grep_kwargs.get("before_context", 0), grep_kwargs.get("after_context", 0)
+    unknown = set(grep_kwargs) - {"ignore_case", "count_only", "only_matching", "no_messages", "errors", "max_match_count", "invert", "before_context", "after_context",
+                                  "matched_parts"}
     if unknown:
         raise TypeError(f"grep_files() got unexpected keyword arguments {sorted(unknown)}")
-    sinks = [_GrepSink(patterns, count_only, only_matching, grep_kwargs.get("errors", "ignore"), invert) for _name in names]
+    # (exactly grep()'s sink and its limit: the trailing rule of GNU grep 3.5 and later is the sink's)
+    sinks = [_GrepSink(patterns, count_only, only_matching, grep_kwargs.get("errors", "ignore"), invert, bool(before_context or after_context), max_match_count,
+                       after_context) for _name in names]
+    if max_match_count and after_context and not count_only:
+        max_match_count += after_context
     if not only_matching:
         for pattern in patterns:  # (grep()'s early failure for bad syntax)
             re.compile(pattern)
@@ -451,7 +469,8 @@ def grep_files_outcomes(files: Sequence[str], patterns: list[str], **grep_kwargs
     if scanned:
         flags = _GREP_FLAGS | (HS_FLAG_CASELESS if ignore_case else 0)
         summaries = scan_files([names[i] for i in scanned], patterns, lambda which, matches, count: sinks[scanned[which]](matches, count),
-                               flags=[flags] * len(patterns), max_match_count=max_match_count, invert=invert)
+                               flags=[flags] * len(patterns), max_match_count=max_match_count, invert=invert, before_context=before_context,
+                               after_context=after_context)
         for which, index in enumerate(scanned):
             outcomes[index] = (sinks[index].result(), summaries[which][0])
     return outcomes

@@ -201,8 +201,8 @@ int hg_hyperscan_invert(char *file_name, const char *const *patterns, const unsi
  * opened sets only its own rc (HYPERSCANNER_GZ_OPEN).  summaries[i].n_selected: the distinct line numbers among the
  * file's results; n_lines: the file's line pieces (for a file of the per-file route: those scanned before
  * max_match_count stopped it).  With on_event == NULL only the summaries are produced and no record leaves the GPU for
- * packed files (what -c, -l, -L, -q need).  Context lines are not offered here.  Returns 0, or the code of a failure
- * that concerns the whole call (HYPERSCANNER_DB: the expressions do not compile). */
+ * packed files (what -c, -l, -L, -q need).  Context lines: hg_hyperscan_files_context below.  Returns 0, or the code of a
+ * failure that concerns the whole call (HYPERSCANNER_DB: the expressions do not compile). */
 typedef void (*hg_files_event)(unsigned int file_index, hyperscanner_result_t *results, int result_count, void *context);
 typedef struct hg_file_summary {
     int rc;
@@ -212,6 +212,21 @@ int hg_hyperscan_files(const char *const *file_names, unsigned int n_files, cons
                        const unsigned int *pattern_flags, const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext,
                        const unsigned int elements, hg_files_event on_event, void *context, const int buffer_size,
                        int buffer_count, unsigned long long max_match_count, int invert, hg_file_summary_t *summaries);
+
+/* hg_hyperscan_files with context lines (grep -r -A / -B / -C): each pack is one GPU scan with the segment stage and the
+ * per-file context stage behind it (hg_scan_device_segments_context below).  Each file's results go out in merged line order:
+ * its own results, and one Result{id = HG_ID_CONTEXT, line_number, line} per context piece; this is exactly what
+ * hg_hyperscan_context (declared below) delivers for that file alone with the same arguments, the max_match_count rule
+ * included (it counts own results only).  Files of the per-file route (gzip, zstd, larger than a pack, pipes, every file when
+ * buffer_size < 2) go through hg_hyperscan_context's code inside the call, in their place in the order; the call gives its
+ * pooled context back first.  The summaries are those of hg_hyperscan_files: context lines are not counted.  A pattern id of
+ * 0xFFFFFFFD or above is refused (HYPERSCANNER_DB), as in hg_hyperscan_context.  With on_event == NULL the call is
+ * hg_hyperscan_files. */
+int hg_hyperscan_files_context(const char *const *file_names, unsigned int n_files, const char *const *patterns,
+                               const unsigned int *pattern_flags, const unsigned int *pattern_ids,
+                               const hs_expr_ext_t *const *ext, const unsigned int elements, hg_files_event on_event,
+                               void *context, const int buffer_size, int buffer_count, unsigned long long max_match_count,
+                               int invert, hg_file_summary_t *summaries, unsigned int before, unsigned int after);
 
 /* Context lines (grep -A / -B / -C) for files: hg_hyperscan_ext's (invert == 0) or hg_hyperscan_invert's (invert != 0) call
  * with `before` and `after` line pieces of context around every line it delivers (hg_scan_device_context below has the
@@ -618,6 +633,40 @@ int hg_scan_device_segments(hg_scanner_t *scanner, const void *d_text, uint64_t 
  * entries, first_record n_seg + 1, n_lines and n_selected n_seg.  HG_ERR_ARG after a scan without segments. */
 int hg_copy_segments(hg_scanner_t *scanner, uint32_t *record_segment, uint64_t *first_record, uint64_t *n_lines,
                      uint64_t *n_selected);
+
+/* Context lines of many files in one scan (grep -r -A / -B / -C): hg_scan_device_segments with `before` and `after` line
+ * pieces of context around every record a segment keeps, per file.  `result` and `segment_result` are filled exactly as
+ * hg_scan_device_segments fills them: the same records, order, first_record, n_lines and n_selected.  In `context_result`,
+ * n_context, d_ctx_hits and d_ctx_aux describe the context records of all segments, in segment order and then line order;
+ * n_tail = 0 and owed_after = 0: a pack has no carry and no tail, because nothing chains across files (a single file scanned
+ * in chunks stays on hg_scan_device_context).  hg_copy_context and hg_copy_context_device work unchanged on these records;
+ * hg_copy_segment_context gives each context record's segment and the per-segment offsets.
+ * Contract.  For every segment s, the context records with segment s are those that hg_scan_device_context gives for the
+ * bytes [seg_start[s], seg_end[s]) scanned alone with line_base = 0, carry_after = 0, no tail flag, and the same before, after
+ * and invert: line_number counts from the file's first piece, hg_hit_aux_t.start from its first byte.  In particular:
+ *  - Context never crosses a file boundary.  A match in the last line of file s gives no after-context in file s + 1; a match
+ *    in the first line of file s + 1 gives no before-context in file s.
+ *  - A phantom piece (one that starts at or after seg_end[s]) is never a context record.
+ *  - A file's last piece of NULs only is the file's own piece: its scanned bytes begin in the pad, and a hit there has been
+ *    dropped, so it may be context.  Its record has start = seg_end[s] - seg_start[s] and len = 0, as the inverted records of
+ *    hg_scan_device_segments have.
+ *  - With max_per_segment = m > 0 the matching lines are the KEPT records.  The after-context of the last kept line goes out
+ *    up to `after` pieces and ends before the next matching piece of that file, which is the first record the limit removed
+ *    (hg_hyperscan_context's rule, GNU grep up to 3.4, per file).  Nothing behind that piece is context, and the removed
+ *    records give no before-context.
+ *  - before == after == 0 makes the call equal to hg_scan_device_segments: n_context = 0, context_us = 0, the stage skipped.
+ *  - Malformed segments give HG_ERR_ARG with nothing scanned, as for hg_scan_device_segments.
+ * The stage runs on the GPU behind the segment stage (hypergrep_amd/csrc/hg_segctx.hip): one window of piece numbers per
+ * segment, per-tile counts from the kept records' lines and the windows alone (no text read), their exclusive scan, one
+ * ordered write pass over the tiles that hold context, and the records made file-relative.  No sort, no per-record atomic. */
+int hg_scan_device_segments_context(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, void *stream,
+                                    const hg_segments_t *segments, uint32_t before, uint32_t after, int invert,
+                                    hg_scan_result_t *result, hg_segment_result_t *segment_result,
+                                    hg_context_result_t *context_result);
+/* Copy the last scan's per-segment context arrays to host memory (either pointer may be NULL): context_segment holds
+ * context_result.n_context entries, first_context n_seg + 1 (segment s owns the context records [first_context[s],
+ * first_context[s + 1])).  HG_ERR_ARG after a scan of any other kind. */
+int hg_copy_segment_context(hg_scanner_t *scanner, uint32_t *context_segment, uint64_t *first_context);
 
 /* Copy the last scan's first `max` hits (and aux records, if aux != NULL) to host memory. */
 int hg_copy_hits(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max);

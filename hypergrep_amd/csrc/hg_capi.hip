@@ -25,6 +25,7 @@ struct hg_scanner {
   uint32_t last_n_seg;
   hg_parts_result_t last_parts;  // the last scan's parts (hg_scan_device_parts), else zeroes
   HgSegCtxOutput last_segctx;    // the last scan's per-segment context arrays (hg_scan_device_segments_context), else zeroes
+  HgSegPartsOutput last_segparts;  // the last scan's per-segment parts arrays (hg_scan_device_segments_parts), else zeroes
 };
 
 static_assert(HG_ID_CONTEXT == HG_CTX_ID_CONTEXT && HG_ID_CONTEXT_TAIL == HG_CTX_ID_TAIL, "the context records carry the ids the header names");
@@ -96,7 +97,7 @@ int hg_scanner_create(const hg_database_t *db, int device, hg_scanner_t **scanne
     put_err(err, errlen, msg);
     return rc;
   }
-  *scanner = new hg_scanner{sc, {}, nullptr, {}, {}, 0, {}, {}};
+  *scanner = new hg_scanner{sc, {}, nullptr, {}, {}, 0, {}, {}, {}};
   return HG_OK;
 }
 
@@ -110,7 +111,8 @@ const char *hg_scanner_error(const hg_scanner_t *scanner) { return scanner ? sca
 
 static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, void *stream,
                        hg_scan_result_t *result, bool invert, const hg_context_t *context = nullptr, hg_context_result_t *context_result = nullptr,
-                       const hg_segments_t *segments = nullptr, hg_segment_result_t *segment_result = nullptr, hg_parts_result_t *parts_result = nullptr) {
+                       const hg_segments_t *segments = nullptr, hg_segment_result_t *segment_result = nullptr, hg_parts_result_t *parts_result = nullptr,
+                       hg_segment_parts_result_t *segment_parts = nullptr) {
   if (!scanner || !result) return HG_ERR_ARG;
   HgScanOutput o{};
   HgPartsOutput pt{};
@@ -122,9 +124,13 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
   scanner->last_n_seg = 0;
   scanner->last_segctx = HgSegCtxOutput{};
   HgSegCtxOutput sx{};
+  scanner->last_segparts = HgSegPartsOutput{};
+  HgSegPartsOutput sp{};
   if (segments) {
     const HgSegParams params{segments->d_seg_start, segments->d_seg_end, segments->n_seg, segments->max_per_segment};
-    if (context)  // (hg_scan_device_segments_context: per-file context, no carry and no tail)
+    if (parts_result)  // (hg_scan_device_segments_parts: per-file parts, never inverted)
+      rc = scanner->sc->scan_packed_parts(d_text, nbytes, buffer_size, static_cast<hipStream_t>(stream), params, &o, &g, &pt, &sp);
+    else if (context)  // (hg_scan_device_segments_context: per-file context, no carry and no tail)
       rc = scanner->sc->scan_packed_context(d_text, nbytes, buffer_size, static_cast<hipStream_t>(stream), params, context->before, context->after, invert, &o, &g, &c, &sx);
     else
       rc = scanner->sc->scan_packed(d_text, nbytes, buffer_size, static_cast<hipStream_t>(stream), params, invert, &o, &g);
@@ -153,6 +159,8 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
     scanner->last_n_seg = segments->n_seg;
     *segment_result = scanner->last_seg;
     scanner->last_segctx = sx;
+    scanner->last_segparts = sp;
+    if (segment_parts) *segment_parts = hg_segment_parts_result_t{sp.d_part_segment, sp.d_first_part};
   }
   result->n_hits = o.n_hits;
   result->n_lines = o.n_pieces;
@@ -210,6 +218,26 @@ int hg_scan_device_parts(hg_scanner_t *scanner, const void *d_text, uint64_t nby
   if (!parts) return HG_ERR_ARG;
   *parts = hg_parts_result_t{};
   return scan_device(scanner, d_text, nbytes, buffer_size, line_base, stream, result, false, nullptr, nullptr, nullptr, nullptr, parts);
+}
+
+int hg_scan_device_segments_parts(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, void *stream, const hg_segments_t *segments,
+                                  hg_scan_result_t *result, hg_segment_result_t *segment_result, hg_parts_result_t *parts, hg_segment_parts_result_t *segment_parts) {
+  if (!segments || !segment_result || !parts || !segment_parts) return HG_ERR_ARG;
+  *segment_result = hg_segment_result_t{};
+  *parts = hg_parts_result_t{};
+  *segment_parts = hg_segment_parts_result_t{};
+  return scan_device(scanner, d_text, nbytes, buffer_size, 0, stream, result, false, nullptr, nullptr, segments, segment_result, parts, segment_parts);
+}
+
+int hg_copy_segment_parts(hg_scanner_t *scanner, uint32_t *part_segment, uint64_t *first_part) {
+  if (!scanner) return HG_ERR_ARG;
+  const HgSegPartsOutput &x = scanner->last_segparts;
+  if (!x.d_first_part) return HG_ERR_ARG;  // the last scan was not hg_scan_device_segments_parts
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  const uint64_t n = scanner->last_parts.n_parts, n_seg = scanner->last_n_seg;
+  if (part_segment && n && hipMemcpy(part_segment, x.d_part_segment, n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (first_part && hipMemcpy(first_part, x.d_first_part, (n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
 }
 
 int hg_copy_parts(hg_scanner_t *scanner, hg_part_t *parts, uint32_t *pattern, uint64_t max) {

@@ -13,6 +13,7 @@
 #include "hg_segments.h"
 #include "hg_segctx.h"
 #include "hg_parts.h"
+#include "hg_segparts.h"
 #include "hg_post.h"
 
 // Waves per stream workgroup (one 16 KiB tile per wave at a time); shared by the kernel and the grid sizing.
@@ -251,6 +252,16 @@ struct HgPartsOutput {
   float ms_parts;             // the stage: count, scan, the host sync that sizes the output, write
 };
 
+// The per-file parts stage (hg_segparts.hip) behind the segment stage, one step per launch on `stream`: the count pass over the
+// surviving records, the write pass, and the per-segment offsets.  max_nw as for hg_parts_launch.
+enum class HgSegPartsStep { Count, Write, First };
+hipError_t hg_segparts_launch(const HgSegPartsArgs &a, HgSegPartsStep step, uint32_t max_nw, uint32_t num_cus, hipStream_t stream);
+// What it leaves beside HgPartsOutput (hg_copy_segment_parts of the C ABI).
+struct HgSegPartsOutput {
+  const uint32_t *d_part_segment;  // device arrays, valid until the next scan on this scanner: the segment of each part
+  const uint64_t *d_first_part;    // n_seg + 1: segment s owns the parts [first_part[s], first_part[s + 1])
+};
+
 // Test / experiment knobs of the engine, read from the environment ONCE, when a scanner is created (never during a scan:
 // getenv is not safe against a concurrent setenv, and a scan must not change behaviour half-way).  None is needed in normal
 // use.  The limit-lowering ones exist so that tests reach segmented scans / chunk halving on small texts.
@@ -293,6 +304,11 @@ class HgScanner {
   // segment's surviving records inside that segment (file-relative, segment after segment), *sc says which are whose.
   int scan_packed_context(const void *d_text, uint64_t nbytes, int buffer_size, hipStream_t stream, const HgSegParams &params, uint32_t before, uint32_t after,
                           bool invert, HgScanOutput *out, HgSegOutput *seg, HgContextOutput *ctx, HgSegCtxOutput *sc);
+  // scan_packed (not inverted) with the per-file parts stage behind it: *out and *seg are exactly scan_packed's, *parts the matched
+  // parts of the pieces each segment keeps a record of (file-relative, segment after segment), *sp says which are whose.
+  // HG_ERR_ARG (nothing scanned) for a database the parts stage is not offered for, and for malformed segments.
+  int scan_packed_parts(const void *d_text, uint64_t nbytes, int buffer_size, hipStream_t stream, const HgSegParams &params, HgScanOutput *out, HgSegOutput *seg,
+                        HgPartsOutput *parts, HgSegPartsOutput *sp);
   // The plain scan with the parts stage behind it: *out is exactly scan()'s, *parts the matched parts of the pieces that have a
   // hit.  HG_ERR_ARG (nothing scanned, the reason in last_error()) for a database the stage is not offered for (hg_parts_refusal).
   int scan_parts(const void *d_text, uint64_t nbytes, int buffer_size, uint64_t line_base, hipStream_t stream, HgScanOutput *out, HgPartsOutput *parts);
@@ -354,6 +370,9 @@ class HgScanner {
   int context_pass(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const HgContextParams &params, hipStream_t stream, const HgScanOutput &out,
                    HgContextOutput *ctx);
   int parts_pass(const uint8_t *text, hipStream_t stream, const HgScanOutput &out, HgPartsOutput *parts);
+  int parts_alloc(uint64_t n, size_t *tb, hipStream_t stream);
+  int parts_records(uint64_t total);
+  int segparts_pass(hipStream_t stream, const HgScanOutput &out, HgPartsOutput *parts, HgSegPartsOutput *sp);
   int segment_alloc(uint64_t n_seg);
   int segment_records(uint64_t n);
   int pad_filter(const HgSegArgs &checked, float *ms, hipStream_t stream, HgScanOutput *out);
@@ -496,6 +515,12 @@ class HgScanner {
   uint64_t segctx_k_cap_ = 0;
   uint32_t *d_segctx_of_ = nullptr;
   uint64_t segctx_of_cap_ = 0;
+  // per-file parts stage (calls with segments and parts only): first_part and the segment of each part.  The per-record
+  // counts, their scan, the first-byte bitmap and the part records are the parts stage's own buffers.
+  uint64_t *d_segparts_first_ = nullptr;
+  uint64_t segparts_seg_cap_ = 0;
+  uint32_t *d_segparts_of_ = nullptr;
+  uint64_t segparts_of_cap_ = 0;
   uint32_t *d_seg_count2_ = nullptr;  // second set for double buffering
   HgCand *d_cands2_ = nullptr;
 };

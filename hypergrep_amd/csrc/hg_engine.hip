@@ -247,7 +247,7 @@ HgScanner::~HgScanner() {
                   d_ctx_count_, d_ctx_pos_, d_ctx_temp_, d_ctx_hits_, d_ctx_aux_,
                   d_parts_first_, d_parts_count_, d_parts_pos_, d_parts_temp_, d_parts_, d_part_pattern_,
                   d_segw_, d_seg_flag_, d_seg_temp_, d_seg_hits_, d_seg_aux_, d_seg_of_, d_seg_from_, d_pad_keep_, d_pad_pos_,
-                  d_segctx_first_, d_segctx_k_, d_segctx_win_, d_segctx_of_};
+                  d_segctx_first_, d_segctx_k_, d_segctx_win_, d_segctx_of_, d_segparts_first_, d_segparts_of_};
   for (void *p : ptrs) hgmem::dev_free(p, "scanner");
   hgmem::host_free(h_counters_, "h_counters_");
   for (auto &ev : ev_)
@@ -1026,6 +1026,36 @@ int HgScanner::scan_context(const void *d_text, uint64_t nbytes, int buffer_size
 int HgScanner::parts_pass(const uint8_t *text, hipStream_t stream, const HgScanOutput &out, HgPartsOutput *parts) {
   const uint64_t n = out.n_hits;
   if (n == 0) return HG_OK;
+  size_t tb = 0;
+  if (int rc = parts_alloc(n, &tb, stream)) return rc;
+  const HgDb &db = *db_;
+  const uint32_t npatterns = static_cast<uint32_t>(db.patterns.size()), first_words = (npatterns + 31) / 32;
+  HgPartsArgs a{text, out.d_hits, out.d_aux, n, static_cast<const HgPattern *>(d_patterns_), static_cast<const uint32_t *>(d_pool_),
+                npatterns, d_parts_first_, first_words, d_parts_count_, d_parts_pos_, nullptr, nullptr};
+  HG_TRY(hipEventRecord(ev_[0], stream), "event");
+  HG_TRY(hg_parts_launch(a, false, db.max_nw, static_cast<uint32_t>(num_cus_), stream), "parts stage launch (count)");
+  HG_TRY(rocprim::exclusive_scan(d_parts_temp_, tb, d_parts_count_, d_parts_pos_, uint64_t{0}, n + 1, rocprim::plus<uint64_t>(), stream), "scan (parts stage)");
+  uint64_t total = 0;
+  HG_TRY(hipMemcpyAsync(&total, d_parts_pos_ + n, sizeof total, hipMemcpyDeviceToHost, stream), "copy count");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (parts stage)");
+  if (int rc = parts_records(total)) return rc;
+  if (total) {
+    a.out = d_parts_;
+    a.out_pattern = d_part_pattern_;
+    HG_TRY(hg_parts_launch(a, true, db.max_nw, static_cast<uint32_t>(num_cus_), stream), "parts stage launch (write)");
+  }
+  HG_TRY(hipEventRecord(ev_[3], stream), "event");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (parts stage)");
+  (void)hipEventElapsedTime(&parts->ms_parts, ev_[0], ev_[3]);
+  parts->n_parts = total;
+  parts->d_parts = d_parts_;
+  parts->d_pattern = d_part_pattern_;
+  return HG_OK;
+}
+
+// What the parts stage and the per-file parts stage share, for n records: the per-record counts and their scan, the scan's
+// scratch (*tb: its size for n + 1 entries) and the first-byte bitmap over the expressions, built once per scanner.
+int HgScanner::parts_alloc(uint64_t n, size_t *tb_out, hipStream_t stream) {
   if (n + 1 > parts_hits_cap_) {
     const uint64_t cap = std::max<uint64_t>(n + n / 4 + 1, 4096);
     parts_hits_cap_ = 0;
@@ -1040,9 +1070,10 @@ int HgScanner::parts_pass(const uint8_t *text, hipStream_t stream, const HgScanO
     HG_TRY(realloc_dev(d_parts_temp_, tb + tb / 4, "d_parts_temp_"), "alloc (parts stage)");
     parts_temp_bytes_ = tb + tb / 4;
   }
-  const HgDb &db = *db_;
-  const uint32_t npatterns = static_cast<uint32_t>(db.patterns.size()), first_words = (npatterns + 31) / 32;
+  *tb_out = tb;
   if (!d_parts_first_) {  // which expressions can start with byte c: those whose init meets reach[c] (conditions left out: a superset)
+    const HgDb &db = *db_;
+    const uint32_t npatterns = static_cast<uint32_t>(db.patterns.size()), first_words = (npatterns + 31) / 32;
     std::vector<uint32_t> first(static_cast<size_t>(256) * first_words, 0u);
     for (uint32_t j = 0; j < npatterns; j++) {
       const HgPattern &p = db.patterns[j];
@@ -1058,14 +1089,11 @@ int HgScanner::parts_pass(const uint8_t *text, hipStream_t stream, const HgScanO
     HG_TRY(hipMemcpyAsync(d_parts_first_, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream), "copy (parts stage)");
     HG_TRY(hipStreamSynchronize(stream), "stream sync (parts stage)");  // (the host vector goes out of scope)
   }
-  HgPartsArgs a{text, out.d_hits, out.d_aux, n, static_cast<const HgPattern *>(d_patterns_), static_cast<const uint32_t *>(d_pool_),
-                npatterns, d_parts_first_, first_words, d_parts_count_, d_parts_pos_, nullptr, nullptr};
-  HG_TRY(hipEventRecord(ev_[0], stream), "event");
-  HG_TRY(hg_parts_launch(a, false, db.max_nw, static_cast<uint32_t>(num_cus_), stream), "parts stage launch (count)");
-  HG_TRY(rocprim::exclusive_scan(d_parts_temp_, tb, d_parts_count_, d_parts_pos_, uint64_t{0}, n + 1, rocprim::plus<uint64_t>(), stream), "scan (parts stage)");
-  uint64_t total = 0;
-  HG_TRY(hipMemcpyAsync(&total, d_parts_pos_ + n, sizeof total, hipMemcpyDeviceToHost, stream), "copy count");
-  HG_TRY(hipStreamSynchronize(stream), "stream sync (parts stage)");
+  return HG_OK;
+}
+
+// Room for `total` parts with their expressions.
+int HgScanner::parts_records(uint64_t total) {
   if (total > parts_cap_) {
     const uint64_t cap = std::max<uint64_t>(total + total / 4, 4096);
     parts_cap_ = 0;
@@ -1073,17 +1101,6 @@ int HgScanner::parts_pass(const uint8_t *text, hipStream_t stream, const HgScanO
     HG_TRY(realloc_dev(d_part_pattern_, cap, "d_part_pattern_"), "alloc (parts stage records)");
     parts_cap_ = cap;
   }
-  if (total) {
-    a.out = d_parts_;
-    a.out_pattern = d_part_pattern_;
-    HG_TRY(hg_parts_launch(a, true, db.max_nw, static_cast<uint32_t>(num_cus_), stream), "parts stage launch (write)");
-  }
-  HG_TRY(hipEventRecord(ev_[3], stream), "event");
-  HG_TRY(hipStreamSynchronize(stream), "stream sync (parts stage)");
-  (void)hipEventElapsedTime(&parts->ms_parts, ev_[0], ev_[3]);
-  parts->n_parts = total;
-  parts->d_parts = d_parts_;
-  parts->d_pattern = d_part_pattern_;
   return HG_OK;
 }
 
@@ -1392,6 +1409,88 @@ int HgScanner::scan_packed_context(const void *d_text, uint64_t nbytes, int buff
   *sc = HgSegCtxOutput{};
   if (int rc = scan_packed(d_text, nbytes, buffer_size, stream, params, invert, out, seg)) return rc;
   return segctx_pass(before, after, stream, *out, ctx, sc);
+}
+
+// The per-file parts stage over a finished segment pass (`out`: the surviving records, file-relative, untouched; d_seg_of_:
+// their segments; seg_last_: the caller's segment arrays and first_record): the count pass over the surviving records where
+// they lie (a wave per piece a file keeps a record of), an exclusive scan of the per-record counts, the write pass with each
+// part's segment beside it, and first_part from the scan and first_record (hg_segparts.hip).  No packed copy of the records
+// and no second pass over the parts.  It shares the parts stage's count, scan, bitmap and record buffers: a scanner runs one
+// of the two per call.  One host synchronisation sizes the output, one behind the write is where the stage's time is read.
+int HgScanner::segparts_pass(hipStream_t stream, const HgScanOutput &out, HgPartsOutput *parts, HgSegPartsOutput *sp) {
+  const HgSegArgs &g = seg_last_;
+  const uint64_t n = out.n_hits, n_seg = g.n_seg;
+  if (n_seg + 1 > segparts_seg_cap_) {
+    const uint64_t cap = std::max<uint64_t>(n_seg + n_seg / 4 + 1, 4096);
+    segparts_seg_cap_ = 0;
+    HG_TRY(realloc_dev(d_segparts_first_, cap, "d_segparts_first_"), "alloc (per-file parts stage)");
+    segparts_seg_cap_ = cap;
+  }
+  sp->d_first_part = d_segparts_first_;
+  if (n == 0) {  // no record, no part
+    HG_TRY(hipMemsetAsync(d_segparts_first_, 0, (n_seg + 1) * sizeof(uint64_t), stream), "memset (per-file parts stage)");
+    HG_TRY(hipStreamSynchronize(stream), "stream sync (per-file parts stage)");
+    return HG_OK;
+  }
+  size_t tb = 0;
+  if (int rc = parts_alloc(n, &tb, stream)) return rc;
+  const HgDb &db = *db_;
+  const uint32_t npatterns = static_cast<uint32_t>(db.patterns.size()), cus = static_cast<uint32_t>(num_cus_);
+  HgSegPartsArgs a{};
+  a.text = g.text;
+  a.hits = out.d_hits;
+  a.aux = out.d_aux;
+  a.seg_of = d_seg_of_;
+  a.n_hits = n;
+  a.seg_start = g.seg_start;
+  a.first_record = g.first;
+  a.n_seg = n_seg;
+  a.patterns = static_cast<const HgPattern *>(d_patterns_);
+  a.pool = static_cast<const uint32_t *>(d_pool_);
+  a.npatterns = npatterns;
+  a.first = d_parts_first_;
+  a.first_words = (npatterns + 31) / 32;
+  a.count = d_parts_count_;
+  a.pos = d_parts_pos_;
+  a.first_part = d_segparts_first_;
+  HG_TRY(hipEventRecord(ev_[0], stream), "event");
+  HG_TRY(hg_segparts_launch(a, HgSegPartsStep::Count, db.max_nw, cus, stream), "per-file parts stage launch (count)");
+  HG_TRY(rocprim::exclusive_scan(d_parts_temp_, tb, d_parts_count_, d_parts_pos_, uint64_t{0}, n + 1, rocprim::plus<uint64_t>(), stream), "scan (per-file parts stage)");
+  uint64_t total = 0;
+  HG_TRY(hipMemcpyAsync(&total, d_parts_pos_ + n, sizeof total, hipMemcpyDeviceToHost, stream), "copy count");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (per-file parts stage)");
+  if (int rc = parts_records(total)) return rc;
+  if (total > segparts_of_cap_) {
+    const uint64_t cap = std::max<uint64_t>(total + total / 4, 4096);
+    segparts_of_cap_ = 0;
+    HG_TRY(realloc_dev(d_segparts_of_, cap, "d_segparts_of_"), "alloc (per-file parts stage records)");
+    segparts_of_cap_ = cap;
+  }
+  if (total) {
+    a.out = d_parts_;
+    a.out_pattern = d_part_pattern_;
+    a.out_seg = d_segparts_of_;
+    HG_TRY(hg_segparts_launch(a, HgSegPartsStep::Write, db.max_nw, cus, stream), "per-file parts stage launch (write)");
+  }
+  HG_TRY(hg_segparts_launch(a, HgSegPartsStep::First, db.max_nw, cus, stream), "per-file parts stage launch (offsets)");
+  HG_TRY(hipEventRecord(ev_[3], stream), "event");
+  HG_TRY(hipStreamSynchronize(stream), "stream sync (per-file parts stage)");
+  (void)hipEventElapsedTime(&parts->ms_parts, ev_[0], ev_[3]);
+  parts->n_parts = total;
+  parts->d_parts = d_parts_;
+  parts->d_pattern = d_part_pattern_;
+  sp->d_part_segment = d_segparts_of_;
+  return HG_OK;
+}
+
+int HgScanner::scan_packed_parts(const void *d_text, uint64_t nbytes, int buffer_size, hipStream_t stream, const HgSegParams &params, HgScanOutput *out,
+                                 HgSegOutput *seg, HgPartsOutput *parts, HgSegPartsOutput *sp) {
+  if (!parts || !sp) return error(HG_ERR_ARG, "invalid arguments");
+  *parts = HgPartsOutput{};
+  *sp = HgSegPartsOutput{};
+  if (const char *why = hg_parts_refusal(db_->nhuge, db_->ncomb, db_->nquiet, db_->n_ext != 0)) return error(HG_ERR_ARG, why);
+  if (int rc = scan_packed(d_text, nbytes, buffer_size, stream, params, false, out, seg)) return rc;  // (the segment check comes before its scan)
+  return segparts_pass(stream, *out, parts, sp);
 }
 
 int HgScanner::run_once(const uint8_t *text, uint64_t nbytes, uint64_t bs1, uint64_t line_base, const PassRange &range, bool block_mode, hipStream_t stream,

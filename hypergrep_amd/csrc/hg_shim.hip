@@ -926,10 +926,14 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
 // the segment stage, and a file's own results and its context records (file-relative both) are merged by line on the way into
 // the ring, as scan_file merges a chunk's.  The limit needs no trailing state here: the stage has already ended the last kept
 // line's after-context before the next matching piece.  Files of the per-file route take scan_file with the same before / after.
+//
+// With parts (hg_hyperscan_files_parts) each pack is one scan_packed_parts: the per-file parts stage runs behind the segment
+// stage, and a file's batches hold one Result per part of each line it keeps (the bytes from the pack's host copy), as
+// scan_file delivers a chunk's.  Files of the per-file route take scan_file with parts.
 static int files_impl(const char *const *file_names, unsigned int n_files, const char *const *patterns, const unsigned int *pattern_flags,
                       const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hg_files_event on_event, void *context,
                       const int buffer_size, int buffer_count, unsigned long long max_match_count, int invert, hg_file_summary_t *summaries, uint32_t before,
-                      uint32_t after) {
+                      uint32_t after, bool parts = false) {
   if (!on_event) before = after = 0;  // summaries only: they are those of the call without context
   const bool with_context = before || after;
   if (!summaries || (!file_names && n_files) || buffer_count < 1 || buffer_size < 1) return HYPERSCANNER_STATE_MEM;
@@ -940,6 +944,13 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
   if (!db) {
     std::fprintf(stderr, "ERROR: Unable to create database. Exiting.\n");
     return HYPERSCANNER_DB;
+  }
+  if (parts) {  // refused for the whole call, before anything is read (as hg_hyperscan_parts)
+    if (const char *why = hg_parts_refusal(db->nhuge, db->ncomb, db->nquiet, db->n_ext != 0)) {
+      std::fprintf(stderr, "ERROR: Unable to create database. Exiting. (%s)\n", why);
+      return HYPERSCANNER_DB;
+    }
+    if (!on_event) parts = false;  // summaries only: they are those of the call without parts
   }
   // one file through the per-file route: its events carry its index, its distinct lines are counted on the way
   auto single = [&](unsigned int f) {
@@ -952,7 +963,7 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
         }
       if (on_event) on_event(f, r, n, context);
     };
-    const int rc = scan_file(file_names[f], patterns, pattern_flags, pattern_ids, ext, elements, ev, buffer_size, buffer_count, max_match_count, invert != 0, before, after, &pieces);
+    const int rc = scan_file(file_names[f], patterns, pattern_flags, pattern_ids, ext, elements, ev, buffer_size, buffer_count, max_match_count, invert != 0, before, after, &pieces, parts);
     summaries[f] = hg_file_summary_t{rc, pieces, selected};
   };
   const size_t cap = chunk_bytes();
@@ -974,6 +985,9 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
   std::vector<uint64_t> seg_start, seg_end, first, n_lines, n_selected, first_ctx;
   std::vector<HgHit> ctx_hits;  // the pack's context records, file-relative, file after file
   std::vector<HgHitAux> ctx_aux;
+  std::vector<HgPart> part_recs;  // matched parts (hg_hyperscan_files_parts): the pack's parts, file-relative, file after file
+  std::vector<uint32_t> part_pattern;
+  std::vector<uint64_t> first_part;
   std::vector<unsigned int> seg_file;
   size_t fill = 0;  // bytes of the pack so far (in ctx->h_slot[0])
   Ring ring;
@@ -1013,7 +1027,10 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
                     hipStreamSynchronize(ctx->stream) == hipSuccess;
       HgContextOutput cout{};
       HgSegCtxOutput sx{};
+      HgPartsOutput pout{};
+      HgSegPartsOutput spo{};
       int src = !copied        ? HG_ERR_HIP
+                : parts        ? ctx->sc->scan_packed_parts(ctx->d_text[0], fill, buffer_size, ctx->stream, params, &out, &seg, &pout, &spo)
                 : with_context ? ctx->sc->scan_packed_context(ctx->d_text[0], fill, buffer_size, ctx->stream, params, before, after, invert != 0, &out, &seg, &cout, &sx)
                                : ctx->sc->scan_packed(ctx->d_text[0], fill, buffer_size, ctx->stream, params, invert != 0, &out, &seg);
       first_ctx.assign(n_seg + 1, 0);
@@ -1024,6 +1041,14 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
                                hipMemcpyAsync(ctx_aux.data(), cout.d_aux, cout.n_context * sizeof(HgHitAux), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) ||
            hipMemcpyAsync(first_ctx.data(), sx.d_first_context, (n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
         src = HG_ERR_HIP;  // (the synchronisation below waits for these copies too)
+      first_part.assign(n_seg + 1, 0);
+      part_recs.resize(src == HG_OK ? pout.n_parts : 0);
+      part_pattern.resize(part_recs.size());
+      if (src == HG_OK && parts &&
+          ((pout.n_parts && (hipMemcpyAsync(part_recs.data(), pout.d_parts, pout.n_parts * sizeof(HgPart), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                             hipMemcpyAsync(part_pattern.data(), pout.d_pattern, pout.n_parts * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) ||
+           hipMemcpyAsync(first_part.data(), spo.d_first_part, (n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
+        src = HG_ERR_HIP;
       if (src == HG_OK) {
         const bool rows = on_event != nullptr && out.n_hits;  // counts only: no record leaves the GPU
         ctx->hits.resize(rows ? out.n_hits : 0);
@@ -1049,6 +1074,16 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
           summaries[cur_file] = hg_file_summary_t{0, n_lines[s], n_selected[s]};
           if (!on_event) continue;
           const uint8_t *base = host + seg_start[s];  // the records are file-relative
+          if (parts) {  // every part of each kept line, in order, in place of its reports (as scan_file)
+            size_t pi = first_part[s];
+            for (size_t i = first[s], j; i < first[s + 1]; i = j) {
+              for (j = i; j < first[s + 1] && ctx->hits[j].line_no == ctx->hits[i].line_no; j++) {}
+              for (; pi < first_part[s + 1] && part_recs[pi].line_no == ctx->hits[i].line_no; pi++)
+                ring.push(db->patterns[part_pattern[pi]].id, part_recs[pi].line_no, base + ctx->aux[i].start + part_recs[pi].from, part_recs[pi].to - part_recs[pi].from);
+            }
+            ring.flush();  // no batch mixes files
+            continue;
+          }
           // line by line; inside a line reports go out by ascending end offset, then id (as scan_file)
           size_t ci = first_ctx[s];  // the file's context records below a line go out in front of it, the rest behind the last
           const auto deliver_context = [&](uint64_t upto) {
@@ -1150,6 +1185,13 @@ extern "C" int hg_hyperscan_files_context(const char *const *file_names, unsigne
     if (pattern_ids[i] >= HG_CTX_ID_TAIL) return HYPERSCANNER_DB;
   return files_impl(file_names, n_files, patterns, pattern_flags, pattern_ids, ext, elements, on_event, context, buffer_size, buffer_count, max_match_count, invert, summaries, before,
                     after);
+}
+
+extern "C" int hg_hyperscan_files_parts(const char *const *file_names, unsigned int n_files, const char *const *patterns, const unsigned int *pattern_flags,
+                                        const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hg_files_event on_event,
+                                        void *context, const int buffer_size, int buffer_count, unsigned long long max_match_count,
+                                        hg_file_summary_t *summaries) {
+  return files_impl(file_names, n_files, patterns, pattern_flags, pattern_ids, ext, elements, on_event, context, buffer_size, buffer_count, max_match_count, 0, summaries, 0, 0, true);
 }
 
 extern "C" int hg_hyperscan_ext(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,

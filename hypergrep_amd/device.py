@@ -66,6 +66,10 @@ class HgSegmentResult(ctypes.Structure):
                 ("segments_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class HgSegmentPartsResult(ctypes.Structure):
+    _fields_ = [("d_part_segment", ctypes.c_void_p), ("d_first_part", ctypes.c_void_p)]
+
+
 class HgFinalizeInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("path", "fin_shift", "fin_nb", "fin_cap", "id_bits", "to_bits", "early_buckets", "early_beside_stream",
                                                "scan_blocks", "left_bucketed", "n_fill", "reserved")]
@@ -124,6 +128,11 @@ def lib() -> ctypes.CDLL:
                                                               ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(HgScanResult), ctypes.POINTER(HgSegmentResult),
                                                               ctypes.POINTER(HgContextResult)]
                 l.hg_copy_segment_context.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]
+            if hasattr(l, "hg_scan_device_segments_parts"):  # (absent from a build before the per-file parts stage)
+                l.hg_scan_device_segments_parts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(HgSegments),
+                                                            ctypes.POINTER(HgScanResult), ctypes.POINTER(HgSegmentResult), ctypes.POINTER(HgPartsResult),
+                                                            ctypes.POINTER(HgSegmentPartsResult)]
+                l.hg_copy_segment_parts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]
             l.hg_copy_segments.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint64)]
         if hasattr(l, "hg_scan_device_parts"):  # (absent from a build before the matched parts)
@@ -227,6 +236,7 @@ class Scanner:
         self._last_ctx = HgContextResult()
         self._last_parts = HgPartsResult()
         self._last_seg = None  # (HgSegmentResult, n_seg) of the last scan, if it had segments
+        self._last_segment_parts = False  # the last scan was one with segment_parts
         self._seg_arena = None
 
     def _place_segments(self, starts, ends):
@@ -245,7 +255,8 @@ class Scanner:
         return ptr, ptr + 8 * n, n
 
     def scan(self, d_text: int, nbytes: int, buffer_size: int = 262140, line_base: int = 0, stream: int = 0, invert: bool = False,
-             context: tuple[int, int] | None = None, carry_after: int = 0, tail: bool = False, segments=None, max_per_segment: int = 0, parts: bool = False) -> ScanStats:
+             context: tuple[int, int] | None = None, carry_after: int = 0, tail: bool = False, segments=None, max_per_segment: int = 0, parts: bool = False,
+             segment_parts: bool = False) -> ScanStats:
         """invert: the result is the line pieces without any report (grep -v; hg_scan_device_invert): n_hits of them, and
         hits() gives (line_number, HG_ID_INVERT, 0, start, len) per piece in line order.
         context = (before, after): grep -B / -A in line pieces (hg_scan_device_context).  hits() is what it is without context;
@@ -260,20 +271,34 @@ class Scanner:
         max_per_segment: keep a file's records up to the line on which their count reaches it (0: all).
         parts: the plain scan with the matched parts of every line that has a hit (grep -o over all expressions;
         hg_scan_device_parts has the definition).  hits() is what it is without; parts() gives the parts.  Not combined with
-        invert, context or segments (ValueError), and ValueError with the reason for a database the stage is not offered for."""
+        invert, context or segments (ValueError), and ValueError with the reason for a database the stage is not offered for.
+        segment_parts: with segments, the matched parts per file (hg_scan_device_segments_parts): hits() and segments() are what
+        they are without; parts() gives every file's parts as scan(parts=True) of the file alone would, restricted to the lines
+        the file keeps, file after file, and segment_parts() says which are whose.  It needs segments and is not combined with
+        invert, context, carry_after, tail, line_base or parts (ValueError)."""
         if parts and (invert or context is not None or carry_after or tail or segments is not None):
-            raise ValueError("parts: not combined with invert, context or segments")
+            raise ValueError("parts: not combined with invert, context or segments (with segments: segment_parts=True)")
+        if segment_parts and segments is None:
+            raise ValueError("segment_parts: needs segments")
+        if segment_parts and (invert or context is not None or carry_after or tail or line_base or parts):
+            raise ValueError("segment_parts: not combined with invert, context, carry_after, tail, line_base or parts")
         res = HgScanResult()
         pres = HgPartsResult()
         cres = HgContextResult()
         sres = HgSegmentResult()
         self._last_seg = None
+        self._last_segment_parts = False
         if segments is not None:
             if carry_after or tail or line_base:
                 raise ValueError("segments: carry_after, tail and line_base are not supported (nothing chains across files)")
             d_starts, d_ends, n_seg = segments if len(segments) == 3 else self._place_segments(*segments)
             seg = HgSegments(d_starts, d_ends, n_seg, max_per_segment)
-            if context is not None:
+            if segment_parts:
+                name = "hg_scan_device_segments_parts"
+                spres = HgSegmentPartsResult()
+                rc = lib().hg_scan_device_segments_parts(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, ctypes.c_void_p(stream), ctypes.byref(seg), ctypes.byref(res),
+                                                         ctypes.byref(sres), ctypes.byref(pres), ctypes.byref(spres))
+            elif context is not None:
                 before, after = context
                 name = "hg_scan_device_segments_context"
                 rc = lib().hg_scan_device_segments_context(self._h, ctypes.c_void_p(d_text), nbytes, buffer_size, ctypes.c_void_p(stream), ctypes.byref(seg), before, after,
@@ -285,9 +310,11 @@ class Scanner:
             if rc == -1:  # HG_ERR_ARG: nothing was scanned
                 self._last = HgScanResult()
                 self._last_ctx = HgContextResult()
+                self._last_parts = HgPartsResult()
                 raise ValueError(f"{name}: {lib().hg_scanner_error(self._h).decode(errors='replace')}")
             if rc == 0:
                 self._last_seg = (sres, n_seg)
+                self._last_segment_parts = segment_parts
         elif context is not None or carry_after or tail:
             before, after = context or (0, 0)
             name = "hg_scan_device_context"
@@ -346,6 +373,24 @@ class Scanner:
             raise ValueError("the last scan had segments without context")
         if rc != 0:
             raise DeviceError(f"hg_copy_segment_context failed ({rc})")
+        return out
+
+    def segment_parts(self):
+        """Whose the parts of the last scan with segments and segment_parts are, as numpy arrays: a dict with part_segment
+        (uint32, one per record of parts()) and first_part (uint64, n + 1: file s owns parts()[first_part[s]:first_part[s + 1]]).
+        ValueError after a scan of any other kind."""
+        import numpy as np
+
+        if self._last_seg is None or not self._last_segment_parts:
+            raise ValueError("the last scan was not one with segments and segment_parts")
+        _, n_seg = self._last_seg
+        out = {"part_segment": np.zeros(self._last_parts.n_parts, dtype=np.uint32), "first_part": np.zeros(n_seg + 1, dtype=np.uint64)}
+        rc = lib().hg_copy_segment_parts(self._h, out["part_segment"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                         out["first_part"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+        if rc == -1:
+            raise ValueError("the last scan was not one with segments and segment_parts")
+        if rc != 0:
+            raise DeviceError(f"hg_copy_segment_parts failed ({rc})")
         return out
 
     def context(self, limit: int | None = None):

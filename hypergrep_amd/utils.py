@@ -257,6 +257,7 @@ def scan_files(  # pylint: disable=too-many-arguments
     invert: bool = False,
     before_context: int = 0,
     after_context: int = 0,
+    parts: bool = False,
 ) -> list[tuple[int, int, int]]:
     """scan() for many files in ONE native call (hg_hyperscan_files): small files are packed into one buffer and share one GPU
     scan.  `on_match(file_index, matches, count)` receives each file's results in batches of `buffer_count`, in file order, no
@@ -266,7 +267,13 @@ def scan_files(  # pylint: disable=too-many-arguments
     `before_context` / `after_context` (hg_hyperscan_files_context): each file's batches also hold the lines around its results,
     one Result with id HG_ID_CONTEXT each, merged in line order, exactly as scan() with the same arguments gives them for the
     file alone; the context stays inside the file, the summaries do not count it, and pattern ids of 0xFFFFFFFD and above are
-    refused (return code 4)."""
+    refused (return code 4).
+    `parts` (grep -r -o, hg_hyperscan_files_parts): each file's batches hold its matched parts instead, one Result per part with
+    the id of the part's pattern and the part's bytes as `line`, exactly as scan(parts=True) gives them for the file alone; the
+    summaries are those without parts.  Not combined with `invert` or context (ValueError); a pattern set scan(parts=True)
+    refuses fails the whole call (return code 4 for every file)."""
+    if parts and (invert or before_context or after_context):
+        raise ValueError("parts: not combined with invert or context lines")
     names = [os.fspath(name) for name in files]
     c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags, ids=ids)
     c_ext = None if ext is None else ext_array(ext, len(c_patterns))
@@ -283,6 +290,12 @@ def scan_files(  # pylint: disable=too-many-arguments
     outcome = [0]
 
     def native_call() -> None:
+        if parts:
+            argtypes = engine.hg_hyperscan_files.argtypes
+            engine.hg_hyperscan_files_parts.argtypes = argtypes[:12] + argtypes[13:]  # (no `invert`)
+            outcome[0] = engine.hg_hyperscan_files_parts(c_names, len(names), c_patterns, c_flags, c_ids, c_ext, len(c_patterns), c_callback, None, buffer_size,
+                                                         buffer_count, max_match_count, summaries)
+            return
         if before_context or after_context:
             engine.hg_hyperscan_files_context.argtypes = engine.hg_hyperscan_files.argtypes + [ctypes.c_uint, ctypes.c_uint]
             outcome[0] = engine.hg_hyperscan_files_context(c_names, len(names), c_patterns, c_flags, c_ids, c_ext, len(c_patterns), c_callback, None, buffer_size,
@@ -426,10 +439,15 @@ def grep(  # pylint: disable=too-many-arguments
 def grep_files_outcomes(files: Sequence[str], patterns: list[str], **grep_kwargs) -> list:
     """What grep(file, patterns, **grep_kwargs) gives for every file, in order: its result, or the exception it raises (not
     raised here).  The files share one native call (scan_files), with context lines too (every file has a sink built as grep()
-    builds it); with matched_parts each file takes grep()."""
+    builds it), and with matched_parts when two or more files can be scanned (scan_files(parts=True); one file has nothing to
+    share and takes grep())."""
     names = list(files)
     outcomes: list = [None] * len(names)
-    if grep_kwargs.get("matched_parts"):
+    known = {"ignore_case", "count_only", "only_matching", "no_messages", "errors", "max_match_count", "invert", "before_context", "after_context", "matched_parts"}
+    matched_parts = grep_kwargs.get("matched_parts", False)
+    # (context arguments, which grep() refuses for every file, and unknown ones: grep() raises what it raises)
+    if matched_parts and (sum(1 for name in names if os.path.exists(name) and not os.path.isdir(name)) < 2 or grep_kwargs.get("before_context") or
+                          grep_kwargs.get("after_context") or set(grep_kwargs) - known):
         for index, name in enumerate(names):
             try:
                 outcomes[index] = grep(name, patterns, **grep_kwargs)
@@ -443,13 +461,15 @@ def grep_files_outcomes(files: Sequence[str], patterns: list[str], **grep_kwargs
     invert = grep_kwargs.get("invert", False)
     max_match_count = grep_kwargs.get("max_match_count", 0)
     before_context, after_context = grep_kwargs.get("before_context", 0), grep_kwargs.get("after_context", 0)
-    unknown = set(grep_kwargs) - {"ignore_case", "count_only", "only_matching", "no_messages", "errors", "max_match_count", "invert", "before_context", "after_context",
-                                  "matched_parts"}
+    unknown = set(grep_kwargs) - known
+    if matched_parts:
+        only_matching = False  # (as in grep(): matched_parts takes precedence)
+    with_parts = matched_parts and not invert and not count_only
     if unknown:
         raise TypeError(f"grep_files() got unexpected keyword arguments {sorted(unknown)}")
     # (exactly grep()'s sink and its limit: the trailing rule of GNU grep 3.5 and later is the sink's)
     sinks = [_GrepSink(patterns, count_only, only_matching, grep_kwargs.get("errors", "ignore"), invert, bool(before_context or after_context), max_match_count,
-                       after_context) for _name in names]
+                       after_context, with_parts) for _name in names]
     if max_match_count and after_context and not count_only:
         max_match_count += after_context
     if not only_matching:
@@ -470,9 +490,10 @@ def grep_files_outcomes(files: Sequence[str], patterns: list[str], **grep_kwargs
         flags = _GREP_FLAGS | (HS_FLAG_CASELESS if ignore_case else 0)
         summaries = scan_files([names[i] for i in scanned], patterns, lambda which, matches, count: sinks[scanned[which]](matches, count),
                                flags=[flags] * len(patterns), max_match_count=max_match_count, invert=invert, before_context=before_context,
-                               after_context=after_context)
+                               after_context=after_context, **({"parts": True} if with_parts else {}))
         for which, index in enumerate(scanned):
-            outcomes[index] = (sinks[index].result(), summaries[which][0])
+            # (matched_parts with invert: a line without a match has no matched part, as in grep())
+            outcomes[index] = ([] if matched_parts and invert and not count_only else sinks[index].result(), summaries[which][0])
     return outcomes
 
 

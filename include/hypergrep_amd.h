@@ -252,6 +252,21 @@ int hg_hyperscan_parts(char *file_name, const char *const *patterns, const unsig
                        const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements,
                        hs_event on_event, const int buffer_size, int buffer_count, unsigned long long max_match_count);
 
+/* hg_hyperscan_files with matched parts (grep -r -o): the parameters of hg_hyperscan_files without `invert` (a line without a
+ * match has no part).  Each pack is one GPU scan with the segment stage and the per-file parts stage behind it
+ * (hg_scan_device_segments_parts below).  A file's batches hold one Result{id = the report id of the part's expression,
+ * line_number, line = the part's bytes} per part, in (line_number, from) order: exactly what hg_hyperscan_parts delivers for
+ * that file alone with the same arguments; max_match_count goes by the reports, and every part of a delivered line goes
+ * out.  The summaries are those of hg_hyperscan_files.  Files of the per-file route (gzip, zstd, larger than a pack, pipes,
+ * every file when buffer_size < 2) go through hg_hyperscan_parts' code inside the call.  A database the parts stage is not
+ * offered for fails the whole call with HYPERSCANNER_DB before anything is read.  With on_event == NULL the call is
+ * hg_hyperscan_files. */
+int hg_hyperscan_files_parts(const char *const *file_names, unsigned int n_files, const char *const *patterns,
+                             const unsigned int *pattern_flags, const unsigned int *pattern_ids,
+                             const hs_expr_ext_t *const *ext, const unsigned int elements, hg_files_event on_event,
+                             void *context, const int buffer_size, int buffer_count, unsigned long long max_match_count,
+                             hg_file_summary_t *summaries);
+
 /* call site hyperscanner.c:136 */
 int hs_compile_multi(const char *const *expressions, const unsigned int *flags, const unsigned int *ids,
                      unsigned int elements, unsigned int mode, const hs_platform_info_t *platform,
@@ -559,7 +574,8 @@ int hg_copy_context_device(hg_scanner_t *scanner, void *d_dst, uint64_t max, voi
  * Not offered: the call returns HG_ERR_ARG, scans nothing, and hg_scanner_error names the reason, for a database with an
  * automaton above 1024 nodes (HG_MAX_NODES: no dense tables to walk), with HS_FLAG_COMBINATION or HS_FLAG_QUIET expressions,
  * or with any extended parameter (hs_expr_ext_t: distances, offset bounds, min_length): none of these has a part in the above
- * sense without further rules.  Not combined with invert, context or segments.
+ * sense without further rules.  Not combined with invert or context; with segments the call is
+ * hg_scan_device_segments_parts below.
  * The stage runs on the GPU behind the scan (hypergrep_amd/csrc/hg_parts.hip): a wavefront per piece that has a hit, its
  * lanes 64 consecutive candidate starts, each running an anchored forward walk per expression; per-hit counts, their
  * exclusive scan, and a second walk that writes the records in order.  The text is read only inside pieces that have a hit.
@@ -667,6 +683,43 @@ int hg_scan_device_segments_context(hg_scanner_t *scanner, const void *d_text, u
  * context_result.n_context entries, first_context n_seg + 1 (segment s owns the context records [first_context[s],
  * first_context[s + 1])).  HG_ERR_ARG after a scan of any other kind. */
 int hg_copy_segment_context(hg_scanner_t *scanner, uint32_t *context_segment, uint64_t *first_context);
+
+/* Matched parts of many files in one scan (grep -r -o): hg_scan_device_segments (invert == 0) with the matched parts of every
+ * line piece a segment keeps a record of, per file.  `result` and `segment_result` are filled exactly as
+ * hg_scan_device_segments(..., invert = 0, ...) fills them: the same records, order, first_record, n_lines, n_selected and
+ * starts of match.  `parts` is hg_scan_device_parts' struct over the parts of all segments, in (segment, line_number, from)
+ * order; hg_copy_parts and hg_copy_parts_device work unchanged on them.  `segment_parts` and hg_copy_segment_parts give each
+ * part's segment and the per-segment offsets.  parts_us is this stage alone.
+ * Equivalence.  For every segment s, the parts with segment s are those hg_scan_device_parts gives for the bytes
+ * [seg_start[s], seg_end[s]) scanned alone with line_base = 0, restricted to the lines of the records the segment keeps:
+ * line_number counts from the file's first piece, from / to lie inside the piece's scanned bytes, `pattern` is the
+ * expression index.  With max_per_segment = 0 the restriction removes nothing.  In particular:
+ *  - A hit that the phantom rule or the pad rule dropped heads no piece: the pad's "\n" under an expression that matches a
+ *    bare newline, and a last piece of NULs only, have no part.
+ *  - With max_per_segment = m > 0 the lines behind the limit have no parts; the line on which the count reaches m has all of
+ *    its parts.
+ *  - An unterminated last line has the parts the file alone has: $, \z and \Z see the file's end, not the pad.
+ *  - A piece is named by (segment, line_number): two files whose matching lines have the same file-relative number stay two
+ *    pieces (every one-line file's line is line 0).
+ * HG_ERR_ARG, with nothing scanned and the reason in hg_scanner_error: a database hg_scan_device_parts refuses, and malformed
+ * segments as for hg_scan_device_segments.  There is no invert argument (a line without a match has no part), and context
+ * stays uncombined: parts with invert and parts with context remain refused.
+ * The stage runs on the GPU behind the segment stage (hypergrep_amd/csrc/hg_segparts.hip) directly on the surviving,
+ * file-relative records: a wavefront per record that is the first of its (segment, line) walks the piece at
+ * seg_start[segment] + start (64-bit offsets) with the parts stage's walk; per-record counts, their exclusive scan, a write
+ * pass that stores each part with its segment, and first_part[s] = pos[first_record[s]].  No packed copy of the records, no
+ * renumbering pass. */
+typedef struct hg_segment_parts_result {
+    const uint32_t *d_part_segment; /* DEVICE, valid until the next scan: the segment of each part */
+    const uint64_t *d_first_part;   /* n_seg + 1: segment s owns the parts [first_part[s], first_part[s + 1]) */
+} hg_segment_parts_result_t;
+int hg_scan_device_segments_parts(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size, void *stream,
+                                  const hg_segments_t *segments, hg_scan_result_t *result,
+                                  hg_segment_result_t *segment_result, hg_parts_result_t *parts,
+                                  hg_segment_parts_result_t *segment_parts);
+/* Copy the last scan's per-segment parts arrays to host memory (either pointer may be NULL): part_segment holds
+ * parts.n_parts entries, first_part n_seg + 1.  HG_ERR_ARG after a scan of any other kind. */
+int hg_copy_segment_parts(hg_scanner_t *scanner, uint32_t *part_segment, uint64_t *first_part);
 
 /* Copy the last scan's first `max` hits (and aux records, if aux != NULL) to host memory. */
 int hg_copy_hits(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max);

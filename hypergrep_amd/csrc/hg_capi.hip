@@ -26,11 +26,23 @@ struct hg_scanner {
   hg_parts_result_t last_parts;  // the last scan's parts (hg_scan_device_parts), else zeroes
   HgSegCtxOutput last_segctx;    // the last scan's per-segment context arrays (hg_scan_device_segments_context), else zeroes
   HgSegPartsOutput last_segparts;  // the last scan's per-segment parts arrays (hg_scan_device_segments_parts), else zeroes
+  // what hg_gather_lines needs of the last successful scan (scanned == false: none yet, or the last one failed), the stage's
+  // own buffers (made by the first gather), and the last gather's result (zeroes after a scan)
+  bool scanned;
+  const void *last_text;
+  uint64_t last_nbytes;
+  const uint64_t *last_seg_start;
+  HgGather *gather;
+  hg_lines_result_t last_lines;
 };
 
 static_assert(HG_ID_CONTEXT == HG_CTX_ID_CONTEXT && HG_ID_CONTEXT_TAIL == HG_CTX_ID_TAIL, "the context records carry the ids the header names");
 static_assert(sizeof(hg_part_t) == sizeof(HgPart) && sizeof(hg_parts_result_t) == 32, "ABI records mirror the device records");
 static_assert(sizeof(hg_hit_t) == sizeof(HgHit) && sizeof(hg_hit_aux_t) == sizeof(HgHitAux), "ABI records mirror the device records");
+static_assert(HG_LINES_CONTEXT == HG_GATHER_CONTEXT && HG_LINES_TERMINATE == HG_GATHER_TERMINATE && HG_LINES_NUMBER == HG_GATHER_NUMBER &&
+                  HG_LINES_SEPARATOR == HG_GATHER_SEPARATOR && HG_LINE_MATCH == HG_GATHER_MATCH && HG_LINE_CONTEXT == HG_GATHER_KIND_CONTEXT &&
+                  HG_LINE_TAIL == HG_GATHER_KIND_TAIL && sizeof(hg_lines_result_t) == 72,
+              "the gather stage's flags and kinds are the header's");
 
 static void put_err(char *err, size_t errlen, const std::string &msg) {
   if (err && errlen) std::snprintf(err, errlen, "%s", msg.c_str());
@@ -97,12 +109,13 @@ int hg_scanner_create(const hg_database_t *db, int device, hg_scanner_t **scanne
     put_err(err, errlen, msg);
     return rc;
   }
-  *scanner = new hg_scanner{sc, {}, nullptr, {}, {}, 0, {}, {}, {}};
+  *scanner = new hg_scanner{sc, {}, nullptr, {}, {}, 0, {}, {}, {}, false, nullptr, 0, nullptr, nullptr, {}};
   return HG_OK;
 }
 
 void hg_scanner_destroy(hg_scanner_t *scanner) {
   if (!scanner) return;
+  delete scanner->gather;
   delete scanner->sc;
   delete scanner;
 }
@@ -116,6 +129,8 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
   if (!scanner || !result) return HG_ERR_ARG;
   HgScanOutput o{};
   HgPartsOutput pt{};
+  scanner->scanned = false;
+  scanner->last_lines = hg_lines_result_t{};
   scanner->last_parts = hg_parts_result_t{};
   HgContextOutput c{};
   HgSegOutput g{};
@@ -177,6 +192,10 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
   result->invert_us = static_cast<uint32_t>(o.ms_invert * 1000.0f + 0.5f);
   scanner->last = *result;
   scanner->d_from = o.d_from;
+  scanner->scanned = true;
+  scanner->last_text = d_text;
+  scanner->last_nbytes = nbytes;
+  scanner->last_seg_start = segments ? segments->d_seg_start : nullptr;
   return HG_OK;
 }
 
@@ -227,6 +246,76 @@ int hg_scan_device_segments_parts(hg_scanner_t *scanner, const void *d_text, uin
   *parts = hg_parts_result_t{};
   *segment_parts = hg_segment_parts_result_t{};
   return scan_device(scanner, d_text, nbytes, buffer_size, 0, stream, result, false, nullptr, nullptr, segments, segment_result, parts, segment_parts);
+}
+
+int hg_gather_lines(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, uint32_t flags, void *stream, hg_lines_result_t *result) {
+  if (!scanner) return HG_ERR_ARG;
+  if (result) *result = hg_lines_result_t{};
+  const char *why = !result                                                                      ? "hg_gather_lines: result is NULL"
+                    : !scanner->scanned                                                          ? "hg_gather_lines: no successful scan to gather the lines of"
+                    : (d_text != scanner->last_text || nbytes != scanner->last_nbytes)           ? "hg_gather_lines: d_text and nbytes are not those of the last scan"
+                    : (flags & ~(HG_LINES_CONTEXT | HG_LINES_TERMINATE | HG_LINES_NUMBER | HG_LINES_SEPARATOR)) ? "hg_gather_lines: unknown flag bits"
+                                                                                                 : nullptr;
+  if (why) return scanner->sc->set_error(HG_ERR_ARG, why);
+  scanner->last_lines = hg_lines_result_t{};
+  if (!scanner->gather) scanner->gather = new HgGather(scanner->sc->device());
+  const bool seg = scanner->last_seg.d_first_record != nullptr, ctx = (flags & HG_LINES_CONTEXT) && scanner->last_ctx.n_context;
+  HgGatherInput in{};
+  in.text = static_cast<const uint8_t *>(d_text);
+  in.main = HgGatherList{reinterpret_cast<const HgHit *>(scanner->last.d_hits), reinterpret_cast<const HgHitAux *>(scanner->last.d_aux),
+                         seg ? scanner->last_seg.d_record_segment : nullptr, scanner->last.n_hits};
+  if (ctx)
+    in.ctx = HgGatherList{reinterpret_cast<const HgHit *>(scanner->last_ctx.d_ctx_hits), reinterpret_cast<const HgHitAux *>(scanner->last_ctx.d_ctx_aux),
+                          seg ? scanner->last_segctx.d_context_segment : nullptr, scanner->last_ctx.n_context};
+  if (seg) {
+    in.seg_start = scanner->last_seg_start;
+    in.first_record = scanner->last_seg.d_first_record;
+    in.first_context = ctx ? scanner->last_segctx.d_first_context : nullptr;
+    in.n_seg = scanner->last_n_seg;
+  }
+  in.flags = flags;
+  HgGatherOutput o{};
+  std::string err;
+  const int rc = scanner->gather->run(in, static_cast<hipStream_t>(stream), &o, &err);
+  if (rc != HG_OK) return scanner->sc->set_error(rc, err);
+  scanner->last_lines = hg_lines_result_t{o.n_entries, o.n_bytes, o.d_bytes, o.d_entry_off, o.d_line_number, o.d_kind, o.d_segment, o.d_first_entry,
+                                          static_cast<uint32_t>(o.ms_gather * 1000.0f + 0.5f), 0};
+  *result = scanner->last_lines;
+  return HG_OK;
+}
+
+int hg_copy_lines(hg_scanner_t *scanner, uint8_t *bytes, uint64_t max_bytes, uint64_t *entry_off, uint64_t *line_number, uint32_t *kind, uint32_t *segment,
+                  uint64_t max_entries) {
+  if (!scanner) return HG_ERR_ARG;
+  const hg_lines_result_t &g = scanner->last_lines;
+  if (!g.d_entry_off) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_lines: no gather since the last scan");
+  if (segment && !g.d_segment) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_lines: the last scan had no segments");
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  const uint64_t nb = std::min(g.n_bytes, max_bytes), ne = std::min(g.n_entries, max_entries);
+  if (bytes && nb && hipMemcpy(bytes, g.d_bytes, nb, hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (entry_off && hipMemcpy(entry_off, g.d_entry_off, (ne + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (line_number && ne && hipMemcpy(line_number, g.d_line_number, ne * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (kind && ne && hipMemcpy(kind, g.d_kind, ne * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (segment && ne && hipMemcpy(segment, g.d_segment, ne * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
+}
+
+int hg_copy_lines_first(hg_scanner_t *scanner, uint64_t *first_entry) {
+  if (!scanner || !first_entry) return HG_ERR_ARG;
+  const hg_lines_result_t &g = scanner->last_lines;
+  if (!g.d_first_entry) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_lines_first: no gather after a scan with segments");
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  return hipMemcpy(first_entry, g.d_first_entry, (scanner->last_n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) == hipSuccess ? HG_OK : HG_ERR_HIP;
+}
+
+int hg_copy_lines_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes, void *stream) {
+  if (!scanner || !d_dst) return HG_ERR_ARG;
+  const hg_lines_result_t &g = scanner->last_lines;
+  if (!g.d_entry_off) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_lines_device: no gather since the last scan");
+  const uint64_t nb = std::min(g.n_bytes, max_bytes);
+  if (!nb) return HG_OK;
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  return hipMemcpyAsync(d_dst, g.d_bytes, nb, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)) == hipSuccess ? HG_OK : HG_ERR_HIP;
 }
 
 int hg_copy_segment_parts(hg_scanner_t *scanner, uint32_t *part_segment, uint64_t *first_part) {

@@ -14,6 +14,8 @@
 #include "hg_segctx.h"
 #include "hg_parts.h"
 #include "hg_segparts.h"
+#include "hg_gather.h"
+#include "hg_mem.h"
 #include "hg_post.h"
 
 // Waves per stream workgroup (one 16 KiB tile per wave at a time); shared by the kernel and the grid sizing.
@@ -262,6 +264,48 @@ struct HgSegPartsOutput {
   const uint64_t *d_first_part;    // n_seg + 1: segment s owns the parts [first_part[s], first_part[s + 1])
 };
 
+// The gather stage (hg_gather.hip) over the records a scan left, one step per launch on `stream`: the head flags, the entries
+// (index, fields, size), the per-segment offsets, the first entry of every output span of HG_GATHER_TILE bytes, and the copy pass
+// over those spans.
+enum class HgGatherStep { Flag, Entry, First, Span, Copy };
+hipError_t hg_gather_launch(const HgGatherArgs &a, HgGatherStep step, hipStream_t stream);
+// What a gather works on (the last scan's lists, as hg_capi.hip remembers them) and what it leaves (hg_lines_result_t).
+struct HgGatherInput {
+  const uint8_t *text;
+  HgGatherList main, ctx;  // ctx.n == 0: no context list, or not asked for
+  const uint64_t *seg_start, *first_record, *first_context;  // nullptr without segments (first_context: without a per-file context list)
+  uint64_t n_seg;
+  uint32_t flags;
+};
+struct HgGatherOutput {
+  uint64_t n_entries, n_bytes;
+  const uint8_t *d_bytes;  // device arrays, valid until the next gather on this object
+  const uint64_t *d_entry_off, *d_line_number;
+  const uint32_t *d_kind, *d_segment;
+  const uint64_t *d_first_entry;
+  float ms_gather;  // the stage: flags, scan, entries, scan, the host sync that sizes the output, spans, copy
+};
+// The stage's buffers and launch sequence.  It owns its scratch (hgmem::Buf: freed with the object, every allocation logged)
+// and touches nothing of the scanner's.
+class HgGather {
+ public:
+  explicit HgGather(int device) : device_(device) {}
+  ~HgGather();
+  int run(const HgGatherInput &in, hipStream_t stream, HgGatherOutput *out, std::string *err);
+
+ private:
+  template <typename T>
+  using DevBuf = hgmem::Buf<T, hgmem::Space::Dev>;
+  int device_;
+  hipEvent_t ev_[2] = {nullptr, nullptr};
+  DevBuf<uint64_t> head_{"gather head", 0}, F_{"gather F", 0}, size_{"gather size", 0}, off_{"gather off", 0}, line_{"gather line", 0}, first_{"gather first", 0},
+      span_{"gather span", 0};
+  DevBuf<uint32_t> kind_{"gather kind", 0}, seg_{"gather seg", 0};
+  DevBuf<HgGatherEntry> entries_{"gather entries", 0};
+  DevBuf<uint8_t> temp_{"gather temp", 0}, bytes_{"gather bytes", 16};
+  hgmem::Buf<uint64_t, hgmem::Space::Host> totals_{"gather totals", 0};  // pinned: {entries, bytes}
+};
+
 // Test / experiment knobs of the engine, read from the environment ONCE, when a scanner is created (never during a scan:
 // getenv is not safe against a concurrent setenv, and a scan must not change behaviour half-way).  None is needed in normal
 // use.  The limit-lowering ones exist so that tests reach segmented scans / chunk halving on small texts.
@@ -321,6 +365,7 @@ class HgScanner {
   // *h_flag (pinned) receives `seq` when every segment is written: the caller may poll it instead of synchronising.
   uint32_t launch_block_small(const uint8_t *h_text, uint32_t nbytes, hipStream_t stream, HgHit *h_out, uint32_t *h_counts, uint32_t *h_flag, uint32_t seq);
   const std::string &last_error() const { return err_; }
+  int set_error(int rc, const std::string &what) { return error(rc, what); }  // (stages that live outside the scanner report through it)
   int device() const { return device_; }
   const HgDbView &view() const { return view_; }  // the database's device tables (stream mode: hg_flows.hip)
   // What the finalize of the last pass did (hg_debug_finalize_info): noted by the host while it plans and queues the pass,

@@ -1737,3 +1737,98 @@ int HgScanner::scan_segments(const uint8_t *text, uint64_t nbytes, uint64_t bs1,
   *out = sum;
   return HG_OK;
 }
+
+// ---------------------------------------------------------------- gather stage (hg_gather_lines): buffers and launch sequence
+HgGather::~HgGather() {
+  (void)hipSetDevice(device_);  // (the buffers are freed behind this body)
+  for (hipEvent_t e : ev_)
+    if (e) (void)hipEventDestroy(e);
+}
+
+#define HG_GATHER_TRY(expr, what)                                                                    \
+  do {                                                                                               \
+    const hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess) {                                                                          \
+      *err = std::string("gather stage: ") + (what) + ": " + hipGetErrorString(e_);                 \
+      return HG_ERR_HIP;                                                                             \
+    }                                                                                                \
+  } while (0)
+
+int HgGather::run(const HgGatherInput &in, hipStream_t stream, HgGatherOutput *out, std::string *err) {
+  *out = HgGatherOutput{};
+  HG_GATHER_TRY(hipSetDevice(device_), "hipSetDevice");
+  for (hipEvent_t &e : ev_)
+    if (!e) HG_GATHER_TRY(hipEventCreate(&e), "event");
+  const uint64_t n = in.main.n + in.ctx.n, cap = n + 1;
+  size_t tb = 0;
+  HG_GATHER_TRY(rocprim::exclusive_scan(nullptr, tb, static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), uint64_t{0}, cap, rocprim::plus<uint64_t>(), stream),
+                "scan size");
+  tb = std::max<size_t>(tb, 16);
+  const size_t grow = cap + cap / 4;
+  const bool ok = head_.reserve(cap, grow) && F_.reserve(cap, grow) && size_.reserve(cap, grow) && off_.reserve(cap, grow) && line_.reserve(cap, grow) &&
+                  kind_.reserve(cap, grow) && (!in.seg_start || (seg_.reserve(cap, grow) && first_.reserve(in.n_seg + 1, in.n_seg + 1))) && entries_.reserve(cap, grow) &&
+                  temp_.reserve(tb, tb + tb / 4) && totals_.reserve(2, 2);
+  if (!ok) {
+    *err = "gather stage: out of memory";
+    return HG_ERR_NOMEM;
+  }
+  HgGatherArgs a{};
+  a.text = HgGatherText{in.text};
+  a.main = in.main;
+  a.ctx = in.ctx;
+  a.seg_start = in.seg_start;
+  a.first_record = in.first_record;
+  a.first_context = in.first_context;
+  a.n_seg = in.n_seg;
+  a.flags = in.flags;
+  a.head = head_.get();
+  a.F = F_.get();
+  a.size = size_.get();
+  a.entries = entries_.get();
+  a.line_number = line_.get();
+  a.kind = kind_.get();
+  a.segment = in.seg_start ? seg_.get() : nullptr;
+  a.first_entry = in.seg_start ? first_.get() : nullptr;
+  a.off = off_.get();
+  HG_GATHER_TRY(hipEventRecord(ev_[0], stream), "event");
+  HG_GATHER_TRY(hg_gather_launch(a, HgGatherStep::Flag, stream), "launch (flags)");
+  size_t t = temp_.cap();
+  HG_GATHER_TRY(rocprim::exclusive_scan(temp_.get(), t, head_.get(), F_.get(), uint64_t{0}, cap, rocprim::plus<uint64_t>(), stream), "scan (heads)");
+  HG_GATHER_TRY(hipMemsetAsync(size_.get(), 0, cap * sizeof(uint64_t), stream), "memset");
+  HG_GATHER_TRY(hg_gather_launch(a, HgGatherStep::Entry, stream), "launch (entries)");
+  if (in.seg_start) HG_GATHER_TRY(hg_gather_launch(a, HgGatherStep::First, stream), "launch (first_entry)");
+  t = temp_.cap();
+  HG_GATHER_TRY(rocprim::exclusive_scan(temp_.get(), t, size_.get(), off_.get(), uint64_t{0}, cap, rocprim::plus<uint64_t>(), stream), "scan (sizes)");
+  uint64_t *totals = totals_.get();
+  HG_GATHER_TRY(hipMemcpyAsync(totals, F_.get() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "copy count");
+  HG_GATHER_TRY(hipMemcpyAsync(totals + 1, off_.get() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "copy count");
+  HG_GATHER_TRY(hipStreamSynchronize(stream), "stream sync");
+  a.n_entries = totals[0];
+  a.n_bytes = totals[1];
+  const uint64_t padded = (a.n_bytes + 15) & ~static_cast<uint64_t>(15);
+  if (!bytes_.reserve(std::max<uint64_t>(padded, 16), std::max<uint64_t>(padded + padded / 8, 16))) {
+    *err = "gather stage: out of memory for " + std::to_string(a.n_bytes) + " bytes of lines";
+    return HG_ERR_NOMEM;
+  }
+  a.out = bytes_.get();
+  const uint64_t n_spans = (a.n_bytes + HG_GATHER_TILE - 1) / HG_GATHER_TILE;
+  if (!span_.reserve(n_spans + 1, n_spans + n_spans / 8 + 1)) {
+    *err = "gather stage: out of memory";
+    return HG_ERR_NOMEM;
+  }
+  a.span = span_.get();
+  HG_GATHER_TRY(hg_gather_launch(a, HgGatherStep::Span, stream), "launch (spans)");
+  HG_GATHER_TRY(hg_gather_launch(a, HgGatherStep::Copy, stream), "launch (copy)");
+  HG_GATHER_TRY(hipEventRecord(ev_[1], stream), "event");
+  HG_GATHER_TRY(hipStreamSynchronize(stream), "stream sync");
+  HG_GATHER_TRY(hipEventElapsedTime(&out->ms_gather, ev_[0], ev_[1]), "event time");
+  out->n_entries = a.n_entries;
+  out->n_bytes = a.n_bytes;
+  out->d_bytes = bytes_.get();
+  out->d_entry_off = off_.get();
+  out->d_line_number = line_.get();
+  out->d_kind = kind_.get();
+  out->d_segment = a.segment;
+  out->d_first_entry = a.first_entry;
+  return HG_OK;
+}

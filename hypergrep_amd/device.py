@@ -20,6 +20,10 @@ HG_ID_INVERT = utils.HG_ID_INVERT  # the id of an inverted scan's records (Scann
 HG_ID_CONTEXT = utils.HG_ID_CONTEXT  # the ids of Scanner.context()'s records: a context piece, a tail candidate (scan(tail=True))
 HG_ID_CONTEXT_TAIL = utils.HG_ID_CONTEXT_TAIL
 HG_CONTEXT_TAIL = 1  # hg_context_t.flags
+# Scanner.gather (hg_gather_lines): the flags, the kinds of an entry, and the output bytes one workgroup of the copy pass writes
+HG_LINES_CONTEXT, HG_LINES_TERMINATE, HG_LINES_NUMBER, HG_LINES_SEPARATOR = 1, 2, 4, 8
+HG_LINE_MATCH, HG_LINE_CONTEXT, HG_LINE_TAIL = 0, 1, 2
+HG_GATHER_TILE = 16384
 
 
 class HgHit(ctypes.Structure):
@@ -68,6 +72,12 @@ class HgSegmentResult(ctypes.Structure):
 
 class HgSegmentPartsResult(ctypes.Structure):
     _fields_ = [("d_part_segment", ctypes.c_void_p), ("d_first_part", ctypes.c_void_p)]
+
+
+class HgLinesResult(ctypes.Structure):
+    _fields_ = [("n_entries", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("d_bytes", ctypes.c_void_p), ("d_entry_off", ctypes.c_void_p),
+                ("d_line_number", ctypes.c_void_p), ("d_kind", ctypes.c_void_p), ("d_segment", ctypes.c_void_p), ("d_first_entry", ctypes.c_void_p),
+                ("gather_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class HgFinalizeInfo(ctypes.Structure):
@@ -140,6 +150,12 @@ def lib() -> ctypes.CDLL:
                                                ctypes.POINTER(HgScanResult), ctypes.POINTER(HgPartsResult)]
             l.hg_copy_parts.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgPart), ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
             l.hg_copy_parts_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        if hasattr(l, "hg_gather_lines"):  # (absent from a build before the gather stage)
+            p8, p32, p64 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+            l.hg_gather_lines.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(HgLinesResult)]
+            l.hg_copy_lines.argtypes = [ctypes.c_void_p, p8, ctypes.c_uint64, p64, p64, p32, p32, ctypes.c_uint64]
+            l.hg_copy_lines_first.argtypes = [ctypes.c_void_p, p64]
+            l.hg_copy_lines_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hits.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
         l.hg_copy_hits_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hit_starts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
@@ -221,6 +237,13 @@ class ScanStats:
     parts_us: int = 0  # ... the parts stage alone, microseconds
 
 
+@dataclass
+class GatherStats:
+    n_entries: int  # distinct (segment, line) of the gathered records
+    n_bytes: int  # bytes of all entries
+    gather_us: int  # the gather stage alone, microseconds
+
+
 class Scanner:
     """Database + workspace resident on one GPU."""
 
@@ -237,6 +260,7 @@ class Scanner:
         self._last_parts = HgPartsResult()
         self._last_seg = None  # (HgSegmentResult, n_seg) of the last scan, if it had segments
         self._last_segment_parts = False  # the last scan was one with segment_parts
+        self._last_lines = None  # HgLinesResult of the last gather, None after a scan
         self._seg_arena = None
 
     def _place_segments(self, starts, ends):
@@ -286,6 +310,7 @@ class Scanner:
         pres = HgPartsResult()
         cres = HgContextResult()
         sres = HgSegmentResult()
+        self._last_lines = None
         self._last_seg = None
         self._last_segment_parts = False
         if segments is not None:
@@ -392,6 +417,72 @@ class Scanner:
         if rc != 0:
             raise DeviceError(f"hg_copy_segment_parts failed ({rc})")
         return out
+
+    def gather(self, d_text: int, nbytes: int, context: bool = False, terminate: bool = False, number: bool = False, separator: bool = False,
+               stream: int = 0) -> GatherStats:
+        """The lines themselves (hg_gather_lines): the scanned bytes of every line piece the last scan left a record for, one
+        entry per distinct (file, line) in the records' order, gathered on the GPU into one device buffer.  d_text and nbytes
+        must be the last scan's.  context: merge the last scan's context (and tail) pieces in, in line order; terminate: every
+        entry ends in a newline; number: every entry begins with its 1-based line number and ':' (match) or '-' (context, tail);
+        separator: "--\n" between entries that are not neighbours (another file, or a gap in the line numbers).
+        lines(), lines_arrays() and copy_lines_to() give the result; hits(), context(), segments() ... are unchanged by it.
+        ValueError with the reason when there is no scan to gather from, or d_text / nbytes are not the last scan's."""
+        flags = (HG_LINES_CONTEXT if context else 0) | (HG_LINES_TERMINATE if terminate else 0) | (HG_LINES_NUMBER if number else 0) | (HG_LINES_SEPARATOR if separator else 0)
+        return self._gather(d_text, nbytes, flags, stream)
+
+    def _gather(self, d_text: int, nbytes: int, flags: int, stream: int = 0) -> GatherStats:
+        res = HgLinesResult()
+        self._last_lines = None
+        rc = lib().hg_gather_lines(self._h, ctypes.c_void_p(d_text), nbytes, flags, ctypes.c_void_p(stream), ctypes.byref(res))
+        if rc == -1:  # HG_ERR_ARG: nothing was launched
+            raise ValueError(lib().hg_scanner_error(self._h).decode(errors="replace"))
+        if rc != 0:
+            raise DeviceError(f"hg_gather_lines failed ({rc}): {lib().hg_scanner_error(self._h).decode(errors='replace')}")
+        self._last_lines = res
+        return GatherStats(res.n_entries, res.n_bytes, res.gather_us)
+
+    def lines_arrays(self):
+        """The last gather as a dict: bytes (the blob), and numpy arrays entry_off (uint64, n + 1: entry j is
+        bytes[entry_off[j]:entry_off[j + 1]]), line_number (uint64), kind (uint32, HG_LINE_*), and after a scan with segments
+        segment (uint32) and first_entry (uint64, files + 1), else None.  ValueError without a gather since the last scan."""
+        import numpy as np
+
+        g = self._last_lines
+        if g is None:
+            raise ValueError("no gather since the last scan")
+        n = g.n_entries
+        blob = np.zeros(max(g.n_bytes, 1), dtype=np.uint8)
+        out = {"entry_off": np.zeros(n + 1, dtype=np.uint64), "line_number": np.zeros(n, dtype=np.uint64), "kind": np.zeros(n, dtype=np.uint32),
+               "segment": np.zeros(n, dtype=np.uint32) if g.d_segment else None, "first_entry": None}
+        p8, p32, p64 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+        rc = lib().hg_copy_lines(self._h, blob.ctypes.data_as(p8), g.n_bytes, out["entry_off"].ctypes.data_as(p64), out["line_number"].ctypes.data_as(p64),
+                                 out["kind"].ctypes.data_as(p32), out["segment"].ctypes.data_as(p32) if g.d_segment else None, n)
+        if rc != 0:
+            raise DeviceError(f"hg_copy_lines failed ({rc})")
+        if g.d_first_entry:
+            _, n_seg = self._last_seg
+            out["first_entry"] = np.zeros(n_seg + 1, dtype=np.uint64)
+            rc = lib().hg_copy_lines_first(self._h, out["first_entry"].ctypes.data_as(p64))
+            if rc != 0:
+                raise DeviceError(f"hg_copy_lines_first failed ({rc})")
+        out["bytes"] = blob[:g.n_bytes].tobytes()
+        return out
+
+    def lines(self):
+        """The last gather's entries as a list of bytes, in order."""
+        a = self.lines_arrays()
+        off = a["entry_off"].tolist()
+        return [a["bytes"][off[j]:off[j + 1]] for j in range(len(off) - 1)]
+
+    def copy_lines_to(self, d_dst: int, max_bytes: int, stream: int = 0) -> int:
+        """Async device-to-device copy of the last gather's bytes (the first max_bytes of them); returns the number copied."""
+        if self._last_lines is None:
+            raise ValueError("no gather since the last scan")
+        n = min(max_bytes, self._last_lines.n_bytes)
+        rc = lib().hg_copy_lines_device(self._h, ctypes.c_void_p(d_dst), n, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise DeviceError(f"hg_copy_lines_device failed ({rc})")
+        return n
 
     def context(self, limit: int | None = None):
         """Last scan's context records as a list of (line_number, HG_ID_CONTEXT | HG_ID_CONTEXT_TAIL, 0, start, len), in line

@@ -721,6 +721,71 @@ int hg_scan_device_segments_parts(hg_scanner_t *scanner, const void *d_text, uin
  * parts.n_parts entries, first_part n_seg + 1.  HG_ERR_ARG after a scan of any other kind. */
 int hg_copy_segment_parts(hg_scanner_t *scanner, uint32_t *part_segment, uint64_t *first_part);
 
+/* The lines themselves: the bytes of every line piece the last scan on this scanner left a record for, gathered on the GPU into
+ * one compact, ordered, optionally print-ready DEVICE buffer that goes to the host or to another GPU in a single transfer.  The
+ * stage runs after a scan, on that scan's records; it scans nothing and changes nothing about scanning.
+ * Entries.  An entry is a distinct (segment, line_number) among the last scan's final records: the hits (several reports on
+ * one line give one entry), the selected pieces of an inverted scan, or the surviving records of a scan with segments.  Every
+ * hg_scan_device* call is accepted as the last scan; after a scan with parts the hits are used, parts are not gathered.
+ * Entries come in the records' order.
+ * Entry j is the bytes d_bytes[d_entry_off[j], d_entry_off[j + 1]) = [separator][number prefix] body [terminator]:
+ *   body        exactly the piece's scanned bytes text[start, start + len) (hg_hit_aux_t); after a scan with segments `start`
+ *               counts from seg_start[segment], and the sum is taken in 64 bits.  The segments' d_seg_start array must still
+ *               be valid when the gather runs;
+ *   terminator  with HG_LINES_TERMINATE, a '\n' where the body does not end in one (len == 0 included);
+ *   number      with HG_LINES_NUMBER, the decimal line_number + 1 followed by ':' for a match and '-' for a context or tail
+ *               piece (grep -n);
+ *   separator   with HG_LINES_SEPARATOR, "--\n" in front of entry j > 0 when its segment differs from that of entry j - 1 or
+ *               its line_number is not that entry's + 1 (what grep prints between groups).
+ * Context.  With HG_LINES_CONTEXT the last scan's context list (hg_scan_device_context, hg_scan_device_segments_context) is
+ * merged in by (segment, line_number); the two lists share no line.  Context records give entries of kind HG_LINE_CONTEXT, tail
+ * records (HG_CONTEXT_TAIL) of kind HG_LINE_TAIL, the scan's own records HG_LINE_MATCH.  Without the flag the context list is
+ * ignored.
+ * The per-entry arrays: d_line_number as in the records (file-relative after a scan with segments), d_kind, and after a scan
+ * with segments d_segment and d_first_entry (n_seg + 1: file s owns the entries [first_entry[s], first_entry[s + 1])); both are
+ * NULL otherwise.  Zero entries give n_entries = n_bytes = 0 and entry_off[0] = 0.
+ * Identity, for flags = 0: n_bytes is the sum of `len` over the distinct pieces and n_entries the distinct (segment,
+ * line_number) of the records; after hg_scan_device_invert n_entries = n_hits, the complement identity's second term.
+ * HG_ERR_ARG, with nothing launched and the reason in hg_scanner_error: no successful scan on this scanner yet (or the last
+ * one failed); d_text or nbytes differ from the last scan's (the scanner remembers them); unknown flag bits; result == NULL.
+ * Lifetime.  The result stays valid until the next scan or gather on this scanner.  A gather leaves the scan's own results
+ * untouched: hg_copy_hits*, hg_copy_context*, hg_copy_segments, hg_copy_segment_context, hg_copy_parts* and
+ * hg_copy_segment_parts work after it as before.  gather_us: the stage in microseconds (HIP events, as invert_us: the host
+ * synchronisation that sizes the output included).
+ * The stage runs on the GPU (hypergrep_amd/csrc/hg_gather.hip): head flags of the records and their exclusive scan; a pass
+ * that gives every head its entry index (a lower bound in the other list: no sort), fields and size; a 64-bit exclusive scan
+ * of the sizes; and a copy pass divided by OUTPUT bytes, HG_GATHER_TILE per workgroup, which finds its entries by binary
+ * search and writes whole aligned 16-byte words.  One piece of a gigabyte and ten million short lines spread over the chip
+ * alike.  The text is read inside the gathered pieces only (whole aligned dwords: never past nbytes rounded up to 4). */
+#define HG_LINES_CONTEXT 1u   /* merge the last scan's context list into the output, in line order */
+#define HG_LINES_TERMINATE 2u /* every entry ends in '\n': one is appended where the piece's scanned bytes do not end in one */
+#define HG_LINES_NUMBER 4u    /* every entry begins with the decimal line_number + 1 and ':' (match) or '-' (context, tail) */
+#define HG_LINES_SEPARATOR 8u /* "--\n" in front of entry j > 0 when its segment differs from entry j-1's or its line_number != that one's + 1 */
+#define HG_LINE_MATCH 0u
+#define HG_LINE_CONTEXT 1u
+#define HG_LINE_TAIL 2u
+#define HG_GATHER_TILE 16384u /* output bytes per workgroup of the copy pass */
+typedef struct hg_lines_result {
+    uint64_t n_entries, n_bytes;
+    const uint8_t *d_bytes;        /* DEVICE, valid until the next scan or gather on this scanner */
+    const uint64_t *d_entry_off;   /* n_entries + 1 */
+    const uint64_t *d_line_number; /* as in the records (file-relative after a scan with segments) */
+    const uint32_t *d_kind;        /* HG_LINE_* */
+    const uint32_t *d_segment;     /* NULL unless the last scan had segments */
+    const uint64_t *d_first_entry; /* n_seg + 1, NULL unless segments */
+    uint32_t gather_us, reserved;
+} hg_lines_result_t;
+int hg_gather_lines(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, uint32_t flags, void *stream, hg_lines_result_t *result);
+/* Copy the last gather's first max_bytes bytes and the per-entry arrays of its first max_entries entries to host memory (any
+ * pointer may be NULL; entry_off receives min(n_entries, max_entries) + 1 values).  HG_ERR_ARG without a gather since the last
+ * scan, and for `segment` after a scan without segments. */
+int hg_copy_lines(hg_scanner_t *scanner, uint8_t *bytes, uint64_t max_bytes, uint64_t *entry_off, uint64_t *line_number, uint32_t *kind,
+                  uint32_t *segment, uint64_t max_entries);
+/* first_entry (n_seg + 1 values) of the last gather; HG_ERR_ARG unless it followed a scan with segments. */
+int hg_copy_lines_first(hg_scanner_t *scanner, uint64_t *first_entry);
+/* The bytes (the first max_bytes of them) into a DEVICE buffer, asynchronously on `stream`. */
+int hg_copy_lines_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes, void *stream);
+
 /* Copy the last scan's first `max` hits (and aux records, if aux != NULL) to host memory. */
 int hg_copy_hits(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max);
 

@@ -71,6 +71,11 @@ def guarded_cases():
     import confirm_cells
 
     yield from confirm_cells.guarded_edge_cases()
+    # the text-edge class of three always-on cells (tests/always_on_cells.py): a match, a near miss and a cut match at the last
+    # byte of texts whose lengths are no multiple of 16
+    import always_on_cells
+
+    yield from always_on_cells.guarded_edge_cases()
 
 
 def regex_gen_escape(word: str) -> str:

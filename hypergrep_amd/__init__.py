@@ -16,6 +16,8 @@ from hypergrep_amd.utils import (  # the reference package re-exports exactly th
     Result,
     check_compatibility,
     configure_libraries,
+    count,
+    count_files,
     grep,
     grep_files,
     prepare_patterns,
@@ -31,5 +33,7 @@ __all__ = [
     "HS_EXT_FLAG_HAMMING_DISTANCE",
     # many files in one native call
     "grep_files", "scan_files",
+    # counts per report id, taken on the GPU
+    "count", "count_files",
 ]
 __version__ = "0.1.0"

@@ -29,9 +29,9 @@ if os.environ.get("HG_BUILD_OUT"):
     OBJ = LIB + ".obj"
     LIBHS_NAME = os.path.basename(LIB) + ".libhs.so.5"
 
-HIP_SOURCES = ["hg_stream.hip", "hg_kernels.hip", "hg_always_on.hip", "hg_huge.hip", "hg_som.hip", "hg_comb.hip", "hg_invert.hip", "hg_context.hip", "hg_parts.hip", "hg_segments.hip", "hg_segctx.hip", "hg_segparts.hip", "hg_gather.hip", "hg_flows.hip", "hg_batch.hip", "hg_engine.hip", "hg_capi.hip", "hg_shim.hip", "hg_hsface.hip"]
+HIP_SOURCES = ["hg_stream.hip", "hg_kernels.hip", "hg_always_on.hip", "hg_huge.hip", "hg_som.hip", "hg_comb.hip", "hg_invert.hip", "hg_context.hip", "hg_parts.hip", "hg_segments.hip", "hg_segctx.hip", "hg_segparts.hip", "hg_gather.hip", "hg_counts.hip", "hg_flows.hip", "hg_batch.hip", "hg_engine.hip", "hg_capi.hip", "hg_shim.hip", "hg_hsface.hip"]
 CXX_SOURCES = ["hg_compile.cpp"]
-HEADERS = ["hg_mem.h", "hg_db.h", "hg_core.h", "hg_post.h", "hg_engine.h", "hg_compile.h", "hg_synth.h", "hg_confirm_dev.h", "hg_sink_dev.h", "hg_tables_dev.h", "hg_som.h", "hg_comb.h", "hg_invert.h", "hg_context.h", "hg_parts.h", "hg_parts_dev.h", "hg_segments.h", "hg_segctx.h", "hg_segparts.h", "hg_gather.h", "hg_wave_dev.h", "hg_flows.h", "hg_flow_rules.h", "hg_batch.h", "hg_batch_launch.h"]
+HEADERS = ["hg_mem.h", "hg_db.h", "hg_core.h", "hg_post.h", "hg_engine.h", "hg_compile.h", "hg_synth.h", "hg_confirm_dev.h", "hg_sink_dev.h", "hg_tables_dev.h", "hg_som.h", "hg_comb.h", "hg_invert.h", "hg_context.h", "hg_parts.h", "hg_parts_dev.h", "hg_segments.h", "hg_segctx.h", "hg_segparts.h", "hg_gather.h", "hg_counts.h", "hg_wave_dev.h", "hg_flows.h", "hg_flow_rules.h", "hg_batch.h", "hg_batch_launch.h"]
 
 
 def _hipcc() -> str:
@@ -48,7 +48,7 @@ def _stale(target: str, deps: list[str]) -> bool:
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 
-KERNEL_SOURCES = ("hg_stream.hip", "hg_kernels.hip", "hg_always_on.hip", "hg_huge.hip", "hg_som.hip", "hg_comb.hip", "hg_invert.hip", "hg_context.hip", "hg_parts.hip", "hg_segments.hip", "hg_segctx.hip", "hg_segparts.hip", "hg_gather.hip", "hg_flows.hip", "hg_batch.hip")  # their per-kernel resources are recorded
+KERNEL_SOURCES = ("hg_stream.hip", "hg_kernels.hip", "hg_always_on.hip", "hg_huge.hip", "hg_som.hip", "hg_comb.hip", "hg_invert.hip", "hg_context.hip", "hg_parts.hip", "hg_segments.hip", "hg_segctx.hip", "hg_segparts.hip", "hg_gather.hip", "hg_counts.hip", "hg_flows.hip", "hg_batch.hip")  # their per-kernel resources are recorded
 
 
 def _compile_kernels(cmd: list[str], table_path: str) -> None:
@@ -113,6 +113,8 @@ def _merge_resources() -> None:
             raise RuntimeError(f"{kernel} uses {res['ScratchSize [bytes/lane]']} bytes of scratch per lane: the per-file parts stage keeps its walks in registers / LDS")
         if "hg_gather_" in kernel and (res.get("ScratchSize [bytes/lane]", 0) > 0 or res.get("VGPRs Spill", 0) > 0 or res.get("SGPRs Spill", 0) > 0):
             raise RuntimeError(f"{kernel} uses {res['ScratchSize [bytes/lane]']} bytes of scratch per lane: the gather stage builds its output words in registers")
+        if "hg_counts_" in kernel and (res.get("ScratchSize [bytes/lane]", 0) > 0 or res.get("VGPRs Spill", 0) > 0 or res.get("SGPRs Spill", 0) > 0):
+            raise RuntimeError(f"{kernel} uses {res['ScratchSize [bytes/lane]']} bytes of scratch per lane: the counts stage keeps a record and its neighbour in registers")
         if "hg_comb_kernel" in kernel and res.get("ScratchSize [bytes/lane]", 0) > 0:
             raise RuntimeError(f"{kernel} uses {res['ScratchSize [bytes/lane]']} bytes of scratch per lane: the combination pass keeps its evaluation stack in a register")
 

@@ -34,6 +34,11 @@ struct hg_scanner {
   const uint64_t *last_seg_start;
   HgGather *gather;
   hg_lines_result_t last_lines;
+  // what hg_count_records needs beside them: whether the last scan was inverted; the stage's own buffers and running totals
+  // (made by the first count), and the last count's result (its matrices are gone after a scan)
+  bool last_invert;
+  HgCounts *counts;
+  hg_counts_result_t last_counts;
 };
 
 static_assert(HG_ID_CONTEXT == HG_CTX_ID_CONTEXT && HG_ID_CONTEXT_TAIL == HG_CTX_ID_TAIL, "the context records carry the ids the header names");
@@ -43,6 +48,9 @@ static_assert(HG_LINES_CONTEXT == HG_GATHER_CONTEXT && HG_LINES_TERMINATE == HG_
                   HG_LINES_SEPARATOR == HG_GATHER_SEPARATOR && HG_LINE_MATCH == HG_GATHER_MATCH && HG_LINE_CONTEXT == HG_GATHER_KIND_CONTEXT &&
                   HG_LINE_TAIL == HG_GATHER_KIND_TAIL && sizeof(hg_lines_result_t) == 72,
               "the gather stage's flags and kinds are the header's");
+static_assert(HG_COUNTS_ACCUMULATE == HG_COUNTS_F_ACCUMULATE && HG_COUNTS_PER_SEGMENT == HG_COUNTS_F_PER_SEGMENT && HG_COUNTS_LDS_BINS == HG_COUNTS_LDS_MAX &&
+                  sizeof(hg_counts_result_t) == 64,
+              "the counts stage's flags and limit are the header's");
 
 static void put_err(char *err, size_t errlen, const std::string &msg) {
   if (err && errlen) std::snprintf(err, errlen, "%s", msg.c_str());
@@ -109,13 +117,14 @@ int hg_scanner_create(const hg_database_t *db, int device, hg_scanner_t **scanne
     put_err(err, errlen, msg);
     return rc;
   }
-  *scanner = new hg_scanner{sc, {}, nullptr, {}, {}, 0, {}, {}, {}, false, nullptr, 0, nullptr, nullptr, {}};
+  *scanner = new hg_scanner{sc, {}, nullptr, {}, {}, 0, {}, {}, {}, false, nullptr, 0, nullptr, nullptr, {}, false, nullptr, {}};
   return HG_OK;
 }
 
 void hg_scanner_destroy(hg_scanner_t *scanner) {
   if (!scanner) return;
   delete scanner->gather;
+  delete scanner->counts;
   delete scanner->sc;
   delete scanner;
 }
@@ -131,6 +140,8 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
   HgPartsOutput pt{};
   scanner->scanned = false;
   scanner->last_lines = hg_lines_result_t{};
+  scanner->last_counts.n_seg = 0;  // (the totals stay: HG_COUNTS_ACCUMULATE adds the next scan's)
+  scanner->last_counts.d_seg_lines = scanner->last_counts.d_seg_reports = nullptr;
   scanner->last_parts = hg_parts_result_t{};
   HgContextOutput c{};
   HgSegOutput g{};
@@ -193,6 +204,7 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
   scanner->last = *result;
   scanner->d_from = o.d_from;
   scanner->scanned = true;
+  scanner->last_invert = invert;
   scanner->last_text = d_text;
   scanner->last_nbytes = nbytes;
   scanner->last_seg_start = segments ? segments->d_seg_start : nullptr;
@@ -316,6 +328,66 @@ int hg_copy_lines_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes,
   if (!nb) return HG_OK;
   if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
   return hipMemcpyAsync(d_dst, g.d_bytes, nb, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)) == hipSuccess ? HG_OK : HG_ERR_HIP;
+}
+
+int hg_db_report_ids(const hg_database_t *db, uint32_t *ids, uint32_t max, uint32_t *n_bins) {
+  if (!db || !n_bins) return HG_ERR_ARG;
+  const std::vector<uint32_t> &r = db->db->report_ids;
+  *n_bins = static_cast<uint32_t>(r.size());
+  if (ids) std::copy(r.begin(), r.begin() + std::min<size_t>(r.size(), max), ids);
+  return HG_OK;
+}
+
+int hg_count_records(hg_scanner_t *scanner, uint32_t flags, void *stream, hg_counts_result_t *result) {
+  if (!scanner) return HG_ERR_ARG;
+  if (result) *result = hg_counts_result_t{};
+  const bool seg = scanner->last_seg.d_first_record != nullptr, per_seg = (flags & HG_COUNTS_PER_SEGMENT) != 0;
+  const uint64_t n_bins = scanner->sc->database()->report_ids.size();
+  const char *why = !result                                                        ? "hg_count_records: result is NULL"
+                    : !scanner->scanned                                            ? "hg_count_records: no successful scan to count the records of"
+                    : scanner->last_invert                                         ? "hg_count_records: the last scan was inverted (its records carry no expression)"
+                    : (flags & ~(HG_COUNTS_ACCUMULATE | HG_COUNTS_PER_SEGMENT))    ? "hg_count_records: unknown flag bits"
+                    : (per_seg && !seg)                                            ? "hg_count_records: HG_COUNTS_PER_SEGMENT after a scan without segments"
+                    : (per_seg && scanner->last_n_seg * n_bins > HG_COUNTS_MAX_CELLS) ? "hg_count_records: more than 2^28 cells (n_seg * n_bins)"
+                                                                                   : nullptr;
+  if (why) return scanner->sc->set_error(HG_ERR_ARG, why);
+  if (!scanner->counts) scanner->counts = new HgCounts(scanner->sc->device(), *scanner->sc->database());
+  HgCountsInput in{};
+  in.list = HgCountsList{reinterpret_cast<const HgHit *>(scanner->last.d_hits), seg ? scanner->last_seg.d_record_segment : nullptr, scanner->last.n_hits};
+  in.n_seg = per_seg ? scanner->last_n_seg : 0;
+  in.flags = flags;
+  HgCountsOutput o{};
+  std::string err;
+  const int rc = scanner->counts->run(in, static_cast<hipStream_t>(stream), &o, &err);
+  if (rc != HG_OK) return scanner->sc->set_error(rc, err);
+  scanner->last_counts = hg_counts_result_t{o.n_bins, o.n_seg, o.n_records, o.d_ids, o.d_n_lines, o.d_n_reports, o.d_seg_lines, o.d_seg_reports,
+                                            static_cast<uint32_t>(o.ms_counts * 1000.0f + 0.5f), 0};
+  *result = scanner->last_counts;
+  return HG_OK;
+}
+
+int hg_copy_counts(hg_scanner_t *scanner, uint32_t *ids, uint64_t *n_lines, uint64_t *n_reports, uint32_t max_bins) {
+  if (!scanner) return HG_ERR_ARG;
+  const hg_counts_result_t &c = scanner->last_counts;
+  if (!c.d_ids) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_counts: no count on this scanner");
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  const uint32_t n = std::min(c.n_bins, max_bins);
+  if (ids && n && hipMemcpy(ids, c.d_ids, n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (n_lines && n && hipMemcpy(n_lines, c.d_n_lines, n * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (n_reports && n && hipMemcpy(n_reports, c.d_n_reports, n * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
+}
+
+int hg_copy_segment_counts(hg_scanner_t *scanner, uint32_t *seg_lines, uint32_t *seg_reports, uint32_t first_seg, uint32_t n) {
+  if (!scanner) return HG_ERR_ARG;
+  const hg_counts_result_t &c = scanner->last_counts;
+  if (!c.d_seg_lines) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_segment_counts: no count with HG_COUNTS_PER_SEGMENT since the last scan");
+  if (first_seg > c.n_seg || n > c.n_seg - first_seg) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_segment_counts: rows out of range");
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  const uint64_t off = static_cast<uint64_t>(first_seg) * c.n_bins, cells = static_cast<uint64_t>(n) * c.n_bins;
+  if (seg_lines && cells && hipMemcpy(seg_lines, c.d_seg_lines + off, cells * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (seg_reports && cells && hipMemcpy(seg_reports, c.d_seg_reports + off, cells * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
 }
 
 int hg_copy_segment_parts(hg_scanner_t *scanner, uint32_t *part_segment, uint64_t *first_part) {

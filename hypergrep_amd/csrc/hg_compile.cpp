@@ -2145,6 +2145,17 @@ void link_som_ids(HgDb &db) {
   }
 }
 
+// The bins of the counts stage: the distinct report ids, ascending, and every expression's index in them.
+void link_report_bins(HgDb &db) {
+  db.report_ids.clear();
+  for (const HgPattern &p : db.patterns) db.report_ids.push_back(p.id);
+  std::sort(db.report_ids.begin(), db.report_ids.end());
+  db.report_ids.erase(std::unique(db.report_ids.begin(), db.report_ids.end()), db.report_ids.end());
+  db.pattern_bin.clear();
+  for (const HgPattern &p : db.patterns)
+    db.pattern_bin.push_back(static_cast<uint32_t>(std::lower_bound(db.report_ids.begin(), db.report_ids.end(), p.id) - db.report_ids.begin()));
+}
+
 // Combinations: their ids are unique, their operands name ids of expressions that are not combinations; expressions that
 // share an id are all QUIET or none is (else de-duplication would decide whether the report is delivered).  Builds the
 // combination records and the feed table.
@@ -2382,6 +2393,7 @@ int hgc_compile_ext(const char *const *exprs, const unsigned *flags, const unsig
     }
     link_som_ids(*db);
     link_combinations(*db, programs);
+    link_report_bins(*db);
     choose_windows(*db, covers, knobs);
   } catch (const CompileError &e) {
     if (err) *err = e.what();

@@ -70,6 +70,10 @@ struct HgDb {
   // without one; empty unless some expression has a min_length that can remove a report.  The scanner then runs the
   // match-length pass over each pass's raw reports (hg_som.h, hg_minlen_kernel)
   std::vector<uint32_t> min_lengths;
+  // The bins of the counts stage (hg_counts.h): the distinct report ids of the set, ascending (expressions that share an id
+  // share a bin; a combination's and a QUIET expression's id are bins like any other), and the bin of every expression
+  std::vector<uint32_t> report_ids;
+  std::vector<uint32_t> pattern_bin;
   uint32_t n_ext = 0;                // expressions compiled with any extended parameter (hs_expr_ext_t with flags): the parts stage refuses them (hg_parts.h)
   uint32_t n_confirm_mode[HG_CONFIRM_MODES] = {};  // tier-0 patterns by confirm routine (hg_confirm_mode)
   std::vector<std::string> exprs;

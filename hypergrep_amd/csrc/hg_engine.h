@@ -4,6 +4,7 @@
 
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../../include/hypergrep_amd.h"
 #include "hg_compile.h"
@@ -15,6 +16,7 @@
 #include "hg_parts.h"
 #include "hg_segparts.h"
 #include "hg_gather.h"
+#include "hg_counts.h"
 #include "hg_mem.h"
 #include "hg_post.h"
 
@@ -304,6 +306,43 @@ class HgGather {
   DevBuf<HgGatherEntry> entries_{"gather entries", 0};
   DevBuf<uint8_t> temp_{"gather temp", 0}, bytes_{"gather bytes", 16};
   hgmem::Buf<uint64_t, hgmem::Space::Host> totals_{"gather totals", 0};  // pinned: {entries, bytes}
+};
+
+// The counts stage (hg_counts.hip) over the record list a scan left: one launch on `stream` (nothing for an empty list).
+hipError_t hg_counts_launch(const HgCountsArgs &a, hipStream_t stream);
+// What a count works on (the last scan's list, as hg_capi.hip remembers it) and what it leaves (hg_counts_result_t).
+struct HgCountsInput {
+  HgCountsList list;  // seg_of == nullptr: the scan had no segments
+  uint32_t n_seg;     // with HG_COUNTS_F_PER_SEGMENT: the segments of the scan
+  uint32_t flags;     // HG_COUNTS_F_*
+};
+struct HgCountsOutput {
+  uint32_t n_bins, n_seg;
+  uint64_t n_records;
+  const uint32_t *d_ids;  // device arrays of the object: the totals live as long as it does, the matrices until its next run
+  const uint64_t *d_n_lines, *d_n_reports;
+  const uint32_t *d_seg_lines, *d_seg_reports;
+  float ms_counts;  // the stage: zeroing, the launch
+};
+// The stage's buffers and launch sequence.  It owns the bins of its database on the device and the running totals (zero when
+// made), and touches nothing of the scanner's.  Every size is known before the launch; run() blocks once, at the end.
+class HgCounts {
+ public:
+  HgCounts(int device, const HgDb &db) : device_(device), ids_host_(db.report_ids) {}
+  ~HgCounts();
+  int run(const HgCountsInput &in, hipStream_t stream, HgCountsOutput *out, std::string *err);
+  const std::vector<uint32_t> &ids() const { return ids_host_; }
+  // The running totals to host memory, ids().size() values each (zeroes before the first run); false on a HIP error.
+  bool copy_totals(uint64_t *n_lines, uint64_t *n_reports) const;
+
+ private:
+  template <typename T>
+  using DevBuf = hgmem::Buf<T, hgmem::Space::Dev>;
+  int device_;
+  std::vector<uint32_t> ids_host_;
+  hipEvent_t ev_[2] = {nullptr, nullptr};
+  DevBuf<uint32_t> ids_{"counts ids", 0}, seg_lines_{"counts seg lines", 0}, seg_reports_{"counts seg reports", 0};
+  DevBuf<unsigned long long> totals_{"counts totals", 0};  // n_lines[n_bins] then n_reports[n_bins]
 };
 
 // Test / experiment knobs of the engine, read from the environment ONCE, when a scanner is created (never during a scan:

@@ -1832,3 +1832,75 @@ int HgGather::run(const HgGatherInput &in, hipStream_t stream, HgGatherOutput *o
   out->d_first_entry = a.first_entry;
   return HG_OK;
 }
+
+// ---------------------------------------------------------------- counts stage (hg_count_records): buffers and launch sequence
+HgCounts::~HgCounts() {
+  (void)hipSetDevice(device_);  // (the buffers are freed behind this body)
+  for (hipEvent_t e : ev_)
+    if (e) (void)hipEventDestroy(e);
+}
+
+#define HG_COUNTS_TRY(expr, what)                                                   \
+  do {                                                                              \
+    const hipError_t e_ = (expr);                                                   \
+    if (e_ != hipSuccess) {                                                         \
+      *err = std::string("counts stage: ") + (what) + ": " + hipGetErrorString(e_); \
+      return HG_ERR_HIP;                                                            \
+    }                                                                               \
+  } while (0)
+
+int HgCounts::run(const HgCountsInput &in, hipStream_t stream, HgCountsOutput *out, std::string *err) {
+  *out = HgCountsOutput{};
+  HG_COUNTS_TRY(hipSetDevice(device_), "hipSetDevice");
+  for (hipEvent_t &e : ev_)
+    if (!e) HG_COUNTS_TRY(hipEventCreate(&e), "event");
+  const uint32_t n_bins = static_cast<uint32_t>(ids_host_.size());
+  const bool per_seg = (in.flags & HG_COUNTS_F_PER_SEGMENT) != 0;
+  const uint64_t cells = per_seg ? static_cast<uint64_t>(in.n_seg) * n_bins : 0;
+  const bool fresh = !totals_.get();  // the first run: the bins go up, the totals start from zero
+  if (!ids_.reserve(std::max<size_t>(n_bins, 1), std::max<size_t>(n_bins, 1)) || !totals_.reserve(std::max<size_t>(2 * n_bins, 1), std::max<size_t>(2 * n_bins, 1)) ||
+      (cells && (!seg_lines_.reserve(cells, cells + cells / 4) || !seg_reports_.reserve(cells, cells + cells / 4)))) {
+    *err = "counts stage: out of memory";
+    return HG_ERR_NOMEM;
+  }
+  HG_COUNTS_TRY(hipEventRecord(ev_[0], stream), "event");
+  if (fresh && n_bins) HG_COUNTS_TRY(hipMemcpyAsync(ids_.get(), ids_host_.data(), n_bins * sizeof(uint32_t), hipMemcpyHostToDevice, stream), "copy ids");
+  if ((fresh || !(in.flags & HG_COUNTS_F_ACCUMULATE)) && n_bins) HG_COUNTS_TRY(hipMemsetAsync(totals_.get(), 0, 2 * n_bins * sizeof(unsigned long long), stream), "memset");
+  if (cells) {
+    HG_COUNTS_TRY(hipMemsetAsync(seg_lines_.get(), 0, cells * sizeof(uint32_t), stream), "memset");
+    HG_COUNTS_TRY(hipMemsetAsync(seg_reports_.get(), 0, cells * sizeof(uint32_t), stream), "memset");
+  }
+  HgCountsArgs a{};
+  a.list = in.list;
+  a.ids = ids_.get();
+  a.n_bins = n_bins;
+  a.n_seg = per_seg ? in.n_seg : 0;
+  a.n_lines = totals_.get();
+  a.n_reports = totals_.get() + n_bins;
+  a.seg_lines = cells ? seg_lines_.get() : nullptr;
+  a.seg_reports = cells ? seg_reports_.get() : nullptr;
+  HG_COUNTS_TRY(hg_counts_launch(a, stream), "launch");
+  HG_COUNTS_TRY(hipEventRecord(ev_[1], stream), "event");
+  HG_COUNTS_TRY(hipStreamSynchronize(stream), "stream sync");
+  HG_COUNTS_TRY(hipEventElapsedTime(&out->ms_counts, ev_[0], ev_[1]), "event time");
+  out->n_bins = n_bins;
+  out->n_seg = per_seg ? in.n_seg : 0;
+  out->n_records = in.list.n;
+  out->d_ids = ids_.get();
+  out->d_n_lines = reinterpret_cast<const uint64_t *>(a.n_lines);
+  out->d_n_reports = reinterpret_cast<const uint64_t *>(a.n_reports);
+  out->d_seg_lines = a.seg_lines;
+  out->d_seg_reports = a.seg_reports;
+  return HG_OK;
+}
+
+bool HgCounts::copy_totals(uint64_t *n_lines, uint64_t *n_reports) const {
+  const size_t n = ids_host_.size();
+  if (!totals_.get()) {
+    std::fill(n_lines, n_lines + n, uint64_t{0});
+    std::fill(n_reports, n_reports + n, uint64_t{0});
+    return true;
+  }
+  return !n || (hipSetDevice(device_) == hipSuccess && hipMemcpy(n_lines, totals_.get(), n * sizeof(uint64_t), hipMemcpyDeviceToHost) == hipSuccess &&
+                hipMemcpy(n_reports, totals_.get() + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost) == hipSuccess);
+}

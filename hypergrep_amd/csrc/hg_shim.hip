@@ -582,11 +582,19 @@ extern "C" int hyperscan(char *file_name, const char *const *patterns, const uns
 // With context lines (before / after, hg_hyperscan_context) each chunk is scanned with the context stage behind it and the
 // two ordered lists are merged; between chunks the call carries what the device API's chaining identity needs: the
 // after-context still owed (owed_after -> carry_after) and the bytes of the previous chunks' tail pieces, `before` at most.
+//
+// With `fc` (hg_hyperscan_counts) nothing is delivered: the counts stage runs behind every chunk's scan, adding to its totals
+// (chunks are cut at piece boundaries, so they share no line), no record is downloaded, and the bins and totals come back once
+// at the end.  fc->ids is filled as soon as the database exists, the totals stay zero when the call fails.
 using FileEvent = std::function<void(hyperscanner_result_t *, int)>;
+struct FileCounts {
+  std::vector<uint32_t> ids;
+  std::vector<uint64_t> n_lines, n_reports;
+};
 static int scan_file(const char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
                      const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, FileEvent on_event,
                      const int buffer_size, int buffer_count, unsigned long long max_match_count, const bool invert, const uint32_t before = 0,
-                     const uint32_t after = 0, uint64_t *pieces_scanned = nullptr, const bool parts = false) {
+                     const uint32_t after = 0, uint64_t *pieces_scanned = nullptr, const bool parts = false, FileCounts *fc = nullptr) {
   if (max_match_count > 0 && max_match_count < static_cast<unsigned long long>(buffer_count)) buffer_count = static_cast<int>(max_match_count);
   if (buffer_count < 1 || buffer_size < 1 || !on_event) return HYPERSCANNER_STATE_MEM;
   Ring ring;
@@ -603,6 +611,12 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
       std::fprintf(stderr, "ERROR: Unable to create database. Exiting. (%s)\n", why);
       return HYPERSCANNER_DB;
     }
+  }
+  std::unique_ptr<HgCounts> counts;  // (made with the scanner; its buffers are its own)
+  if (fc) {
+    fc->ids = db->report_ids;
+    fc->n_lines.assign(fc->ids.size(), 0);
+    fc->n_reports.assign(fc->ids.size(), 0);
   }
   // the file is opened before any device resource is taken: a missing file is HYPERSCANNER_GZ_OPEN with or without a GPU
   // (the reference's scratch allocation cannot fail for want of a device; its order is database, scratch, file)
@@ -753,6 +767,7 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
         healthy = false;
         break;
       }
+      if (fc) counts = std::make_unique<HgCounts>(ctx->device, *db);
       t_setup = now() - t0;
     }
     if (cut) {
@@ -784,9 +799,19 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
         healthy = false;
         break;
       }
-      ctx->hits.resize(out.n_hits);
-      ctx->aux.resize(out.n_hits);
-      if (out.n_hits) {
+      if (counts) {  // the chunk's records are counted where they lie: none is downloaded, nothing is delivered below
+        HgCountsOutput co{};
+        if (counts->run(HgCountsInput{HgCountsList{out.d_hits, nullptr, out.n_hits}, 0, HG_COUNTS_F_ACCUMULATE}, ctx->stream, &co, &err) != HG_OK) {
+          std::fprintf(stderr, "ERROR: Unable to scan buffer. Exiting. (%s)\n", err.c_str());
+          rc = HYPERSCANNER_SCAN;
+          healthy = false;
+          break;
+        }
+      }
+      const uint64_t n_rows = counts ? 0 : out.n_hits;
+      ctx->hits.resize(n_rows);
+      ctx->aux.resize(n_rows);
+      if (n_rows) {
         if (hipMemcpyAsync(ctx->hits.data(), out.d_hits, out.n_hits * sizeof(HgHit), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
             hipMemcpyAsync(ctx->aux.data(), out.d_aux, out.n_hits * sizeof(HgHitAux), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
             hipStreamSynchronize(ctx->stream) != hipSuccess) {
@@ -907,6 +932,10 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
   (void)hipStreamSynchronize(ctx->copy_stream);  // a copy issued ahead may still be in flight
   ring.flush();
   if (pieces_scanned) *pieces_scanned = line_base;
+  if (counts && rc == 0 && !counts->copy_totals(fc->n_lines.data(), fc->n_reports.data())) {  // n_bins x 16 bytes, once
+    rc = HYPERSCANNER_SCAN;
+    healthy = false;
+  }
   if (trace)
     std::fprintf(stderr, "[hypergrep_amd] %s: %.1f MiB in %.4f s; reader filling slots %.4f s; consumer: waiting for data %.4f s, window tuning + scanner %.4f s (%s), copy + scan %.4f s, delivering %llu hits %.4f s\n",
                  file_name, bytes_in / 1048576.0, now() - t_call, t_read, t_wait_slot, t_setup, db->tuned ? "tuned windows" : "static windows", t_scan,
@@ -930,13 +959,23 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
 // With parts (hg_hyperscan_files_parts) each pack is one scan_packed_parts: the per-file parts stage runs behind the segment
 // stage, and a file's batches hold one Result per part of each line it keeps (the bytes from the pack's host copy), as
 // scan_file delivers a chunk's.  Files of the per-file route take scan_file with parts.
+//
+// With `fcs` (hg_hyperscan_files_counts; on_event is NULL then) the counts stage runs behind every pack's segment stage with
+// per-segment matrices, which are all that leaves the GPU beside the per-file arrays; a pack is closed early where one more
+// file would take the matrices past the stage's limit of cells.  Files of the per-file route take scan_file with counts.
+struct FilesCounts {
+  uint32_t *ids;
+  unsigned int max_ids, *n_ids;
+  uint64_t *file_lines, *file_reports;  // n_files rows of max_ids values
+};
 static int files_impl(const char *const *file_names, unsigned int n_files, const char *const *patterns, const unsigned int *pattern_flags,
                       const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hg_files_event on_event, void *context,
                       const int buffer_size, int buffer_count, unsigned long long max_match_count, int invert, hg_file_summary_t *summaries, uint32_t before,
-                      uint32_t after, bool parts = false) {
+                      uint32_t after, bool parts = false, const FilesCounts *fcs = nullptr) {
   if (!on_event) before = after = 0;  // summaries only: they are those of the call without context
   const bool with_context = before || after;
   if (!summaries || (!file_names && n_files) || buffer_count < 1 || buffer_size < 1) return HYPERSCANNER_STATE_MEM;
+  if (fcs && fcs->n_ids) *fcs->n_ids = 0;
   if (max_match_count > 0 && max_match_count < static_cast<unsigned long long>(buffer_count)) buffer_count = static_cast<int>(max_match_count);
   for (unsigned int i = 0; i < n_files; i++) summaries[i] = hg_file_summary_t{0, 0, 0};
   std::string err;
@@ -952,6 +991,14 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
     }
     if (!on_event) parts = false;  // summaries only: they are those of the call without parts
   }
+  const size_t n_bins = db->report_ids.size(), n_cols = fcs ? std::min<size_t>(n_bins, fcs->max_ids) : 0;
+  if (fcs) {
+    *fcs->n_ids = static_cast<unsigned int>(n_bins);
+    std::copy(db->report_ids.begin(), db->report_ids.begin() + n_cols, fcs->ids);
+    std::fill(fcs->file_lines, fcs->file_lines + static_cast<size_t>(n_files) * fcs->max_ids, uint64_t{0});
+    std::fill(fcs->file_reports, fcs->file_reports + static_cast<size_t>(n_files) * fcs->max_ids, uint64_t{0});
+  }
+  std::vector<uint32_t> seg_lines, seg_reports;  // the pack's matrices
   // one file through the per-file route: its events carry its index, its distinct lines are counted on the way
   auto single = [&](unsigned int f) {
     uint64_t selected = 0, last = ~0ull, pieces = 0;
@@ -963,7 +1010,13 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
         }
       if (on_event) on_event(f, r, n, context);
     };
-    const int rc = scan_file(file_names[f], patterns, pattern_flags, pattern_ids, ext, elements, ev, buffer_size, buffer_count, max_match_count, invert != 0, before, after, &pieces, parts);
+    FileCounts fc;
+    const int rc = scan_file(file_names[f], patterns, pattern_flags, pattern_ids, ext, elements, ev, buffer_size, buffer_count, max_match_count, invert != 0, before, after, &pieces, parts,
+                             fcs ? &fc : nullptr);
+    if (fcs && fc.n_lines.size() >= n_cols) {  // (nothing was delivered, so `selected` stays 0: the row says what was selected)
+      std::copy(fc.n_lines.begin(), fc.n_lines.begin() + n_cols, fcs->file_lines + static_cast<size_t>(f) * fcs->max_ids);
+      std::copy(fc.n_reports.begin(), fc.n_reports.begin() + n_cols, fcs->file_reports + static_cast<size_t>(f) * fcs->max_ids);
+    }
     summaries[f] = hg_file_summary_t{rc, pieces, selected};
   };
   const size_t cap = chunk_bytes();
@@ -1061,6 +1114,17 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
             hipStreamSynchronize(ctx->stream) != hipSuccess)
           src = HG_ERR_HIP;
       }
+      if (src == HG_OK && fcs && n_bins) {  // the counts stage behind the segment stage; the two matrices come back
+        HgCounts counts(ctx->device, *db);
+        HgCountsOutput co{};
+        const size_t cells = n_seg * n_bins;
+        seg_lines.resize(cells);
+        seg_reports.resize(cells);
+        src = counts.run(HgCountsInput{HgCountsList{out.d_hits, seg.d_record_segment, out.n_hits}, static_cast<uint32_t>(n_seg), HG_COUNTS_F_PER_SEGMENT}, ctx->stream, &co, &err);
+        if (src == HG_OK && (hipMemcpy(seg_lines.data(), co.d_seg_lines, cells * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+                             hipMemcpy(seg_reports.data(), co.d_seg_reports, cells * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess))
+          src = HG_ERR_HIP;
+      }
       if (src != HG_OK) {
         std::fprintf(stderr, "ERROR: Unable to scan buffer. Exiting. (%s)\n", ctx->sc ? ctx->sc->last_error().c_str() : "copy");
         fail_pack(HYPERSCANNER_SCAN);
@@ -1072,6 +1136,11 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
         for (size_t s = 0; s < n_seg; s++) {
           cur_file = seg_file[s];
           summaries[cur_file] = hg_file_summary_t{0, n_lines[s], n_selected[s]};
+          if (fcs)
+            for (size_t b = 0; b < n_cols; b++) {
+              fcs->file_lines[static_cast<size_t>(cur_file) * fcs->max_ids + b] = seg_lines[s * n_bins + b];
+              fcs->file_reports[static_cast<size_t>(cur_file) * fcs->max_ids + b] = seg_reports[s * n_bins + b];
+            }
           if (!on_event) continue;
           const uint8_t *base = host + seg_start[s];  // the records are file-relative
           if (parts) {  // every part of each kept line, in order, in place of its reports (as scan_file)
@@ -1135,7 +1204,7 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
       else summaries[f].rc = HYPERSCANNER_SCAN;
       continue;
     }
-    if (fill + size + 2 > cap) flush_pack();
+    if (fill + size + 2 > cap || (fcs && (seg_file.size() + 1) * n_bins > HG_COUNTS_MAX_CELLS)) flush_pack();
     if (!healthy) {
       summaries[f].rc = HYPERSCANNER_SCAN;
       continue;
@@ -1192,6 +1261,30 @@ extern "C" int hg_hyperscan_files_parts(const char *const *file_names, unsigned 
                                         void *context, const int buffer_size, int buffer_count, unsigned long long max_match_count,
                                         hg_file_summary_t *summaries) {
   return files_impl(file_names, n_files, patterns, pattern_flags, pattern_ids, ext, elements, on_event, context, buffer_size, buffer_count, max_match_count, 0, summaries, 0, 0, true);
+}
+
+extern "C" int hg_hyperscan_files_counts(const char *const *file_names, unsigned int n_files, const char *const *patterns, const unsigned int *pattern_flags,
+                                         const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, const int buffer_size,
+                                         hg_file_summary_t *summaries, uint32_t *ids, unsigned int max_ids, unsigned int *n_ids, uint64_t *file_lines,
+                                         uint64_t *file_reports) {
+  if (!n_ids || (max_ids && (!ids || (n_files && (!file_lines || !file_reports))))) return HYPERSCANNER_STATE_MEM;
+  const FilesCounts fcs{ids, max_ids, n_ids, file_lines, file_reports};
+  return files_impl(file_names, n_files, patterns, pattern_flags, pattern_ids, ext, elements, nullptr, nullptr, buffer_size, 1, 0, 0, summaries, 0, 0, false, &fcs);
+}
+
+extern "C" int hg_hyperscan_counts(char *file_name, const char *const *patterns, const unsigned int *pattern_flags, const unsigned int *pattern_ids,
+                                   const hs_expr_ext_t *const *ext, const unsigned int elements, const int buffer_size, hg_id_count_t *counts,
+                                   unsigned int max_counts, unsigned int *n_counts, uint64_t *n_lines) {
+  if (!n_counts || (max_counts && !counts)) return HYPERSCANNER_STATE_MEM;
+  *n_counts = 0;
+  if (n_lines) *n_lines = 0;
+  FileCounts fc;
+  uint64_t pieces = 0;
+  const int rc = scan_file(file_name, patterns, pattern_flags, pattern_ids, ext, elements, [](hyperscanner_result_t *, int) {}, buffer_size, 1, 0, false, 0, 0, &pieces, false, &fc);
+  *n_counts = static_cast<unsigned int>(fc.ids.size());
+  for (size_t b = 0; b < fc.ids.size() && b < max_counts; b++) counts[b] = hg_id_count_t{fc.ids[b], 0, fc.n_lines[b], fc.n_reports[b]};
+  if (n_lines) *n_lines = pieces;
+  return rc;
 }
 
 extern "C" int hg_hyperscan_ext(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,

@@ -24,6 +24,10 @@ HG_CONTEXT_TAIL = 1  # hg_context_t.flags
 HG_LINES_CONTEXT, HG_LINES_TERMINATE, HG_LINES_NUMBER, HG_LINES_SEPARATOR = 1, 2, 4, 8
 HG_LINE_MATCH, HG_LINE_CONTEXT, HG_LINE_TAIL = 0, 1, 2
 HG_GATHER_TILE = 16384
+# Scanner.count (hg_count_records): the flags, the bins a workgroup counts in LDS, and the records one workgroup takes
+HG_COUNTS_ACCUMULATE, HG_COUNTS_PER_SEGMENT = 1, 2
+HG_COUNTS_LDS_BINS = 4096
+HG_COUNTS_RUN = 16384
 
 
 class HgHit(ctypes.Structure):
@@ -78,6 +82,12 @@ class HgLinesResult(ctypes.Structure):
     _fields_ = [("n_entries", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("d_bytes", ctypes.c_void_p), ("d_entry_off", ctypes.c_void_p),
                 ("d_line_number", ctypes.c_void_p), ("d_kind", ctypes.c_void_p), ("d_segment", ctypes.c_void_p), ("d_first_entry", ctypes.c_void_p),
                 ("gather_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class HgCountsResult(ctypes.Structure):
+    _fields_ = [("n_bins", ctypes.c_uint32), ("n_seg", ctypes.c_uint32), ("n_records", ctypes.c_uint64), ("d_ids", ctypes.c_void_p),
+                ("d_n_lines", ctypes.c_void_p), ("d_n_reports", ctypes.c_void_p), ("d_seg_lines", ctypes.c_void_p), ("d_seg_reports", ctypes.c_void_p),
+                ("counts_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class HgFinalizeInfo(ctypes.Structure):
@@ -156,6 +166,12 @@ def lib() -> ctypes.CDLL:
             l.hg_copy_lines.argtypes = [ctypes.c_void_p, p8, ctypes.c_uint64, p64, p64, p32, p32, ctypes.c_uint64]
             l.hg_copy_lines_first.argtypes = [ctypes.c_void_p, p64]
             l.hg_copy_lines_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        if hasattr(l, "hg_count_records"):  # (absent from a build before the counts stage)
+            p32, p64 = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+            l.hg_count_records.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(HgCountsResult)]
+            l.hg_copy_counts.argtypes = [ctypes.c_void_p, p32, p64, p64, ctypes.c_uint32]
+            l.hg_copy_segment_counts.argtypes = [ctypes.c_void_p, p32, p32, ctypes.c_uint32, ctypes.c_uint32]
+            l.hg_db_report_ids.argtypes = [ctypes.c_void_p, p32, ctypes.c_uint32, p32]
         l.hg_copy_hits.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
         l.hg_copy_hits_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hit_starts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
@@ -209,6 +225,17 @@ class Database:
         lib().hg_db_info(self._h, ctypes.byref(out))
         return {n: getattr(out, n) for n, _ in HgDbInfo._fields_}
 
+    def report_ids(self):
+        """The bins of Scanner.count(): the distinct report ids of the set, ascending, as a uint32 numpy array (needs no GPU)."""
+        import numpy as np
+
+        n = ctypes.c_uint32()
+        if lib().hg_db_report_ids(self._h, None, 0, ctypes.byref(n)) != 0:
+            raise ValueError("hg_db_report_ids failed")
+        out = np.zeros(n.value, dtype=np.uint32)
+        lib().hg_db_report_ids(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n.value, ctypes.byref(n))
+        return out
+
     def __del__(self):
         if getattr(self, "_h", None) and lib is not None:  # (module globals are gone at interpreter shutdown)
             lib().hg_db_release(self._h)
@@ -244,6 +271,14 @@ class GatherStats:
     gather_us: int  # the gather stage alone, microseconds
 
 
+@dataclass
+class CountStats:
+    n_bins: int  # distinct report ids of the database
+    n_records: int  # records this call counted
+    counts_us: int  # the counts stage alone, microseconds
+    n_seg: int = 0  # rows of segment_counts() (0 without per_segment)
+
+
 class Scanner:
     """Database + workspace resident on one GPU."""
 
@@ -261,6 +296,7 @@ class Scanner:
         self._last_seg = None  # (HgSegmentResult, n_seg) of the last scan, if it had segments
         self._last_segment_parts = False  # the last scan was one with segment_parts
         self._last_lines = None  # HgLinesResult of the last gather, None after a scan
+        self._last_counts = None  # HgCountsResult of the last count
         self._seg_arena = None
 
     def _place_segments(self, starts, ends):
@@ -483,6 +519,56 @@ class Scanner:
         if rc != 0:
             raise DeviceError(f"hg_copy_lines_device failed ({rc})")
         return n
+
+    def count(self, accumulate: bool = False, per_segment: bool = False, stream: int = 0) -> CountStats:
+        """Counts per report id (hg_count_records) of the last scan's records (hits(), or the surviving records of a scan with
+        segments; context and parts are ignored), computed on the GPU: for every distinct report id of the database the
+        records with it and the distinct (file, line) among them.  accumulate: add to the totals already on the scanner (the
+        buffers of a chained scan); per_segment: after a scan with segments, also the per-file matrices of segment_counts().
+        counts(), counts_arrays() and segment_counts() give the result; hits(), lines() ... are unchanged by it.  DeviceError
+        with the reason when there is nothing to count: no scan yet, an inverted scan, per_segment without segments."""
+        res = HgCountsResult()
+        self._last_counts = None
+        flags = (HG_COUNTS_ACCUMULATE if accumulate else 0) | (HG_COUNTS_PER_SEGMENT if per_segment else 0)
+        rc = lib().hg_count_records(self._h, flags, ctypes.c_void_p(stream), ctypes.byref(res))
+        if rc != 0:
+            raise DeviceError(f"hg_count_records failed ({rc}): {lib().hg_scanner_error(self._h).decode(errors='replace')}")
+        self._last_counts = res
+        return CountStats(res.n_bins, res.n_records, res.counts_us, res.n_seg)
+
+    def counts_arrays(self):
+        """The last count as numpy arrays (ids uint32 ascending, n_lines uint64, n_reports uint64), one value per bin."""
+        import numpy as np
+
+        c = self._last_counts
+        if c is None:
+            raise ValueError("no count on this scanner")
+        ids, n_lines, n_reports = np.zeros(c.n_bins, dtype=np.uint32), np.zeros(c.n_bins, dtype=np.uint64), np.zeros(c.n_bins, dtype=np.uint64)
+        p64 = ctypes.POINTER(ctypes.c_uint64)
+        rc = lib().hg_copy_counts(self._h, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n_lines.ctypes.data_as(p64), n_reports.ctypes.data_as(p64), c.n_bins)
+        if rc != 0:
+            raise DeviceError(f"hg_copy_counts failed ({rc})")
+        return ids, n_lines, n_reports
+
+    def counts(self):
+        """The last count as {id: (n_lines, n_reports)}, every bin of the database (zeroes included)."""
+        ids, n_lines, n_reports = self.counts_arrays()
+        return {int(i): (int(l), int(r)) for i, l, r in zip(ids, n_lines, n_reports)}
+
+    def segment_counts(self):
+        """The per-file matrices of the last count(per_segment=True): (lines, reports), uint32 numpy arrays of shape
+        (n_seg, n_bins); the columns are the bins of counts_arrays()."""
+        import numpy as np
+
+        c = self._last_counts
+        if c is None or not c.d_seg_lines:
+            raise ValueError("no count with per_segment since the last scan")
+        lines, reports = np.zeros((c.n_seg, c.n_bins), dtype=np.uint32), np.zeros((c.n_seg, c.n_bins), dtype=np.uint32)
+        p32 = ctypes.POINTER(ctypes.c_uint32)
+        rc = lib().hg_copy_segment_counts(self._h, lines.ctypes.data_as(p32), reports.ctypes.data_as(p32), 0, c.n_seg)
+        if rc != 0:
+            raise DeviceError(f"hg_copy_segment_counts failed ({rc}): {lib().hg_scanner_error(self._h).decode(errors='replace')}")
+        return lines, reports
 
     def context(self, limit: int | None = None):
         """Last scan's context records as a list of (line_number, HG_ID_CONTEXT | HG_ID_CONTEXT_TAIL, 0, start, len), in line

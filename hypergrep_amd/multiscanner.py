@@ -249,6 +249,33 @@ def parallel_grep(  # pylint: disable=too-many-arguments,too-many-locals
     return 2 if replay.errored else (0 if replay.matched else 1)
 
 
+def pattern_counts(files: list, patterns: list[str], shown: list[str] | None = None, ignore_case: bool = False, with_file_name: bool = False,
+                   no_messages: bool = False) -> int:
+    """--pattern-counts: for every file one line "[file:]count:pattern" per pattern that matched, in pattern order, `count`
+    being the file's matching lines for that pattern (what grep -c -e pattern prints).  The counts are taken on the GPU
+    (hypergrep_amd.count_files; count for one file): the patterns get the ids 0..n-1 and no line leaves the device.
+    shown: the patterns as the user wrote them (default: as compiled).  Returns grep's exit code."""
+    shown = shown if shown is not None else patterns
+    flags = hypergrep_amd.utils.HS_FLAG_DOTALL | hypergrep_amd.utils.HS_FLAG_MULTILINE | hypergrep_amd.utils.HS_FLAG_SINGLEMATCH
+    flags |= hypergrep_amd.utils.HS_FLAG_CASELESS if ignore_case else 0
+    kwargs = {"flags": [flags] * len(patterns), "ids": list(range(len(patterns)))}
+    outcomes = [hypergrep_amd.count(files[0], patterns, **kwargs)] if len(files) == 1 else hypergrep_amd.count_files(files, patterns, **kwargs)
+    matched = errored = False
+    for name, (counts, return_code) in zip(files, outcomes):
+        if return_code:
+            errored = True
+            if not no_messages:
+                problem = "No such file or directory" if not os.path.exists(name) else ("is a directory" if os.path.isdir(name) else f"scan failed ({return_code})")
+                print(f"hyperscanner: {name}: {problem}")
+            continue
+        for index, pattern in enumerate(shown):
+            lines = counts.get(index, (0, 0))[0]
+            if lines:
+                matched = True
+                print(f"{name}:{lines}:{pattern}" if with_file_name else f"{lines}:{pattern}")
+    return 2 if errored else (0 if matched else 1)
+
+
 def print_results(results: list, file_name: str, with_file_name: bool = False, with_line_number: bool = False) -> None:
     """Print (line number, line) results with the requested prefixes; lines keep their own newline."""
     head = f"{file_name}:" if with_file_name else ""
@@ -418,8 +445,18 @@ def parse_args(args: list = None) -> argparse.Namespace:
     own.add_argument("--gnu-parts", dest="gnu_parts", action="store_true", default=argparse.SUPPRESS,
                      help="With -o: print the matched parts of ALL patterns, leftmost-longest, computed on the GPU (GNU grep's -o\n"
                           "output for several patterns and alternations).  Without -o it has no effect.")
+    # (no attribute unless given, like -v)
+    own.add_argument("--pattern-counts", dest="pattern_counts", action="store_true", default=argparse.SUPPRESS,
+                     help="For every file print one line [file:]count:pattern per pattern that matched, count being the matching\n"
+                          "lines, counted on the GPU.  Not combined with -v, -o, -c, -l, -L, -q, -A / -B / -C or -m.")
     parser.set_defaults(parser=parser)
-    return parser.parse_intermixed_args(args=args)
+    parsed = parser.parse_intermixed_args(args=args)
+    if getattr(parsed, "pattern_counts", False):
+        others = (getattr(parsed, "invert_match", False) or parsed.only_matching or parsed.count or parsed.files_with_matches or parsed.files_without_match or parsed.quiet or
+                  parsed.max_count or any(hasattr(parsed, name) for name in ("after_context", "before_context", "context")))
+        if others:
+            parser.error("--pattern-counts is not combined with -v, -o, -c, -l, -L, -q, -A, -B, -C or -m")  # (exit code 2)
+    return parsed
 
 
 def main() -> None:
@@ -430,6 +467,7 @@ def main() -> None:
         if not patterns:
             args.parser.print_usage()
             raise SystemExit(2)
+        patterns_as_written = list(patterns)
         if args.regexp == "bre":
             patterns = to_basic_regular_expressions(patterns)
     except ValueError as error:
@@ -452,6 +490,8 @@ def main() -> None:
         with_file_name = True
     else:
         with_file_name = recursive or len(files) > 1
+    if getattr(args, "pattern_counts", False):
+        raise SystemExit(pattern_counts(files, patterns, patterns_as_written, args.ignore_case, with_file_name, args.no_messages))
     raise SystemExit(
         parallel_grep(
             files=files,

@@ -315,6 +315,79 @@ def scan_files(  # pylint: disable=too-many-arguments
     return [(summaries[i].rc, summaries[i].n_lines, summaries[i].n_selected) for i in range(len(names))]
 
 
+class IdCount(ctypes.Structure):
+    """hg_id_count_t: a report id with the matching lines and the reports of that id."""
+
+    _fields_ = [("id", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("n_lines", ctypes.c_uint64), ("n_reports", ctypes.c_uint64)]
+
+
+def _run_native(native_call: Callable) -> bool:
+    """The native call on a daemon thread, so that Ctrl-C reaches Python; False when it was interrupted."""
+    worker = threading.Thread(target=native_call, daemon=True)
+    worker.start()
+    try:
+        worker.join(timeout=_JOIN_TIMEOUT_S)
+    except KeyboardInterrupt:
+        return False
+    return True
+
+
+def count(file: str, patterns: list[str], flags: list[int] = (), ids: list[int] = (), ext=None, buffer_size: int = 262140) -> tuple[dict, int]:
+    """Which patterns fired in a plain / gzip / zstd text file, and how often (hg_hyperscan_counts): ({id: (matching lines,
+    reports)}, return code) with one entry per distinct report id, zeroes included.  The counts are taken on the GPU behind
+    every chunk's scan; no hit record and no line leaves it.  There is no max_match_count: counts describe the whole file."""
+    c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags, ids=ids)
+    c_ext = None if ext is None else ext_array(ext, len(c_patterns))
+    max_counts = len(set(c_ids))
+    rows = (IdCount * max_counts)()
+    n_counts, n_lines = ctypes.c_uint(), ctypes.c_uint64()
+    engine = _get_hyperscanner_lib()
+    engine.hg_hyperscan_counts.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
+                                           ctypes.POINTER(ctypes.POINTER(ExprExt)), ctypes.c_uint, ctypes.c_int, ctypes.POINTER(IdCount), ctypes.c_uint,
+                                           ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint64)]
+    outcome = [0]
+
+    def native_call() -> None:
+        outcome[0] = engine.hg_hyperscan_counts(os.fspath(file).encode(), c_patterns, c_flags, c_ids, c_ext, len(c_patterns), buffer_size, rows, max_counts,
+                                                ctypes.byref(n_counts), ctypes.byref(n_lines))
+
+    if not _run_native(native_call):
+        return {}, _RC_INTERRUPTED
+    return {rows[b].id: (rows[b].n_lines, rows[b].n_reports) for b in range(min(n_counts.value, max_counts))}, outcome[0]
+
+
+def count_files(files: Sequence[str], patterns: list[str], flags: list[int] = (), ids: list[int] = (), ext=None, buffer_size: int = 262140) -> list[tuple[dict, int]]:
+    """count() for many files in ONE native call (hg_hyperscan_files_counts): small files are packed into one buffer and share
+    one GPU scan, with the per-file counts taken behind it.  One ({id: (matching lines, reports)}, return code) per file, what
+    count() gives for it alone; a missing or unreadable file has return code 6 and zero counts."""
+    names = [os.fspath(name) for name in files]
+    c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags, ids=ids)
+    c_ext = None if ext is None else ext_array(ext, len(c_patterns))
+    c_names = (ctypes.c_char_p * max(len(names), 1))(*[name.encode() for name in names])
+    summaries = (FileSummary * max(len(names), 1))()
+    max_ids = len(set(c_ids))
+    c_report_ids = (ctypes.c_uint32 * max_ids)()
+    n_ids = ctypes.c_uint()
+    file_lines, file_reports = (ctypes.c_uint64 * max(len(names) * max_ids, 1))(), (ctypes.c_uint64 * max(len(names) * max_ids, 1))()
+    engine = _get_hyperscanner_lib()
+    engine.hg_hyperscan_files_counts.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint),
+                                                 ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.POINTER(ExprExt)), ctypes.c_uint, ctypes.c_int,
+                                                 ctypes.POINTER(FileSummary), ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint, ctypes.POINTER(ctypes.c_uint),
+                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    outcome = [0]
+
+    def native_call() -> None:
+        outcome[0] = engine.hg_hyperscan_files_counts(c_names, len(names), c_patterns, c_flags, c_ids, c_ext, len(c_patterns), buffer_size, summaries, c_report_ids,
+                                                      max_ids, ctypes.byref(n_ids), file_lines, file_reports)
+
+    if not _run_native(native_call):
+        return [({}, _RC_INTERRUPTED)] * len(names)
+    if outcome[0]:  # a failure of the whole call (the expressions do not compile): every file reports it, as count() would
+        return [({}, outcome[0])] * len(names)
+    n = min(n_ids.value, max_ids)
+    return [({c_report_ids[b]: (file_lines[f * max_ids + b], file_reports[f * max_ids + b]) for b in range(n)}, summaries[f].rc) for f in range(len(names))]
+
+
 class _GrepSink:
     """on_match for grep(): counts, keeps whole lines, or keeps the matched parts (`re.finditer` of the pattern whose
     id the hit carries — with grep()'s all-zero ids that is the first pattern, as in the reference)."""

@@ -267,6 +267,33 @@ int hg_hyperscan_files_parts(const char *const *file_names, unsigned int n_files
                              void *context, const int buffer_size, int buffer_count, unsigned long long max_match_count,
                              hg_file_summary_t *summaries);
 
+/* Counts per report id for files: which expressions fired, on how many lines and how often, without one callback row per
+ * report.  hg_hyperscan_counts takes hg_hyperscan_ext's arguments, reader, chunking, decompression and database cache, and
+ * runs the counts stage (hg_count_records below, with HG_COUNTS_ACCUMULATE) behind every chunk; no record is downloaded, and
+ * n_bins x 24 bytes come back once at the end.  There is no max_match_count: counts describe the whole file.  counts[b]: the
+ * b-th distinct report id of the expressions, ascending, with the file's matching lines and reports of that id; *n_counts:
+ * the number of distinct ids, whatever max_counts is (a smaller max_counts fills what fits); *n_lines: the file's line
+ * pieces.  Return codes are hg_hyperscan_ext's.
+ * hg_hyperscan_files_counts takes hg_hyperscan_files' packing and runs the stage with HG_COUNTS_PER_SEGMENT behind every pack.
+ * ids receives the distinct report ids (min(max_ids, *n_ids) of them); file_lines and file_reports are n_files rows of max_ids
+ * values each, row f holding file f's counts in its first min(max_ids, *n_ids) places.  Files of the per-file route (gzip,
+ * zstd, larger than a pack, every file when buffer_size < 2) go through hg_hyperscan_counts' code inside the call; a file
+ * that cannot be opened sets its own rc and has a zero row.  The summaries are those of hg_hyperscan_files, but for n_selected
+ * of a file of the per-file route, which is 0: nothing is delivered to count it from. */
+typedef struct hg_id_count {
+    uint32_t id, reserved;
+    uint64_t n_lines, n_reports;
+} hg_id_count_t; /* sizeof 24 */
+int hg_hyperscan_counts(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                        const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements,
+                        const int buffer_size, hg_id_count_t *counts, unsigned int max_counts, unsigned int *n_counts,
+                        uint64_t *n_lines);
+int hg_hyperscan_files_counts(const char *const *file_names, unsigned int n_files, const char *const *patterns,
+                              const unsigned int *pattern_flags, const unsigned int *pattern_ids,
+                              const hs_expr_ext_t *const *ext, const unsigned int elements, const int buffer_size,
+                              hg_file_summary_t *summaries, uint32_t *ids, unsigned int max_ids, unsigned int *n_ids,
+                              uint64_t *file_lines, uint64_t *file_reports);
+
 /* call site hyperscanner.c:136 */
 int hs_compile_multi(const char *const *expressions, const unsigned int *flags, const unsigned int *ids,
                      unsigned int elements, unsigned int mode, const hs_platform_info_t *platform,
@@ -785,6 +812,50 @@ int hg_copy_lines(hg_scanner_t *scanner, uint8_t *bytes, uint64_t max_bytes, uin
 int hg_copy_lines_first(hg_scanner_t *scanner, uint64_t *first_entry);
 /* The bytes (the first max_bytes of them) into a DEVICE buffer, asynchronously on `stream`. */
 int hg_copy_lines_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes, void *stream);
+
+/* Counts per report id (hg_count_records): which expressions fired, and on how many lines, without moving the record list.
+ * Bins.  A bin is a distinct report id of the database, in ascending id order (hg_db_report_ids; n_bins <= n_patterns).
+ * Expressions that share an id share a bin; the id of a combination is a bin; the id of a QUIET expression is a bin that
+ * always stays 0, because QUIET reports are never delivered.
+ * Definition.  Take the records of the last scan on the scanner: the final hits, or the surviving records of a scan with
+ * segments (context lists and parts are ignored).  For bin b with id v, n_reports[b] is the number of records with id == v and
+ * n_lines[b] the number of distinct (segment, line_number) among them.  By the records' order, (segment, line_number, id,
+ * to), a record counts as a new line for its bin iff it is record 0 or differs from the record before it in segment,
+ * line_number or id.
+ * HG_COUNTS_ACCUMULATE adds to the totals already on the scanner instead of zeroing them first: buffers of one text that are
+ * cut at piece boundaries never share a line piece, so the sums of a chained scan are the counts of the whole text.  The first
+ * call after hg_scanner_create starts from zero either way.  HG_COUNTS_PER_SEGMENT, only after a scan with segments, also
+ * fills two row-major n_seg x n_bins uint32_t matrices, lines and reports per file (a pack is at most 256 MiB, so 32 bits
+ * suffice); they are never accumulated, each call overwrites them; n_seg * n_bins above 2^28 cells is HG_ERR_ARG.
+ * HG_ERR_ARG, with nothing launched and the reason in hg_scanner_error: no successful scan on this scanner yet; the last scan
+ * was inverted (its records carry HG_ID_INVERT and no expression); unknown flag bits; HG_COUNTS_PER_SEGMENT after a scan
+ * without segments; result == NULL.
+ * Zero records is a success with all-zero counts.  The stage leaves the scan's own results and a previous gather untouched,
+ * and every hg_copy_* works after it as before.  All sizes are known before the launch; the call blocks once, at the end.
+ * counts_us: the stage in microseconds (HIP events).
+ * The stage is one kernel (hypergrep_amd/csrc/hg_counts.hip): a workgroup per run of records counts in LDS up to
+ * HG_COUNTS_LDS_BINS bins (in memory above), a wave that agrees on one bin adds once, and integer atomics make the result
+ * exact whatever the order.  Only the 16-byte hit records are read. */
+#define HG_COUNTS_ACCUMULATE 1u
+#define HG_COUNTS_PER_SEGMENT 2u
+#define HG_COUNTS_LDS_BINS 4096u /* up to this many bins a workgroup counts in LDS */
+typedef struct hg_counts_result { /* sizeof 64 */
+    uint32_t n_bins, n_seg;       /* n_seg 0 without HG_COUNTS_PER_SEGMENT */
+    uint64_t n_records;           /* records this call counted */
+    const uint32_t *d_ids;        /* DEVICE, n_bins ascending; valid until the next scan or count */
+    const uint64_t *d_n_lines, *d_n_reports;     /* n_bins totals (accumulated with the flag) */
+    const uint32_t *d_seg_lines, *d_seg_reports; /* n_seg x n_bins, NULL without the flag */
+    uint32_t counts_us, reserved;
+} hg_counts_result_t;
+int hg_count_records(hg_scanner_t *scanner, uint32_t flags, void *stream, hg_counts_result_t *result);
+/* The bins and totals of the last count (the first min(n_bins, max_bins) of them; any pointer may be NULL) to host memory.
+ * HG_ERR_ARG without a count on this scanner. */
+int hg_copy_counts(hg_scanner_t *scanner, uint32_t *ids, uint64_t *n_lines, uint64_t *n_reports, uint32_t max_bins);
+/* Rows [first_seg, first_seg + n) of the last count's matrices (n x n_bins values each; either pointer may be NULL).
+ * HG_ERR_ARG unless the last count had HG_COUNTS_PER_SEGMENT and no scan followed it, or when the rows are out of range. */
+int hg_copy_segment_counts(hg_scanner_t *scanner, uint32_t *seg_lines, uint32_t *seg_reports, uint32_t first_seg, uint32_t n);
+/* host only, needs no GPU: the bins of a compiled database (the first min(max, *n_bins) ids; ids may be NULL) */
+int hg_db_report_ids(const hg_database_t *db, uint32_t *ids, uint32_t max, uint32_t *n_bins);
 
 /* Copy the last scan's first `max` hits (and aux records, if aux != NULL) to host memory. */
 int hg_copy_hits(hg_scanner_t *scanner, hg_hit_t *hits, hg_hit_aux_t *aux, uint64_t max);

@@ -335,8 +335,10 @@ bool ensure_buffers(Ctx *c, size_t cap, int slots) {
     }
     c->d_cap = cap;
   }
-  // + 32: the kernels may read the text up to its size rounded up to 16 bytes, and the verify pass's byte-aligned
-  // discriminator load up to 3 bytes further (hg_verify_kernel)
+  // + 32: slack.  The kernels read the text up to its size rounded up to 16 bytes and no further (include/hypergrep_amd.h,
+  // hg_scan_device): the verify pass's aligned discriminator dword ends before the size rounded up to 4, its byte-aligned
+  // windows are read byte by byte inside the text (verify_body).  What lies behind a batch is the previous, longer batch;
+  // no result depends on it (tests/test_text_bounds_gpu.py).
   for (int i = 0; i < (slots > 1 ? Ctx::kDevBufs : 1); i++)
     if (!c->d_text[i] && hgmem::dev_alloc(&c->d_text[i], c->d_cap + 32, "d_text") != hipSuccess) return false;
   return true;

@@ -496,6 +496,11 @@ const char *hg_scanner_error(const hg_scanner_t *scanner);
 
 /* Scan `nbytes` of text resident in HBM at d_text (16-byte aligned; must be readable up to nbytes
  * rounded up to 16).  Lines are numbered from line_base.  `stream` is a hipStream_t (NULL = default).
+ * The text is the bytes [d_text, d_text + nbytes) and nothing else.  The CONTENT of any byte outside them never influences a
+ * result of this call or of a call built on it (invert, context, parts, segments, gather, counts): the up to 15 bytes of the
+ * round-up may hold anything, a continuation of the text included, and d_text may point into the middle of a larger
+ * allocation.  Only the stated round-up must be readable, and nothing before d_text is read.  (tests/test_text_bounds_gpu.py
+ * scans windows of a larger text whose neighbouring bytes would complete a match, add a line or change a `\b` / `$`.)
  * Blocks until the results are ready.  No size limit besides HBM: a buffer with more than 2^28 reports (or more
  * pipeline chunks than one pass has) is scanned in segments whose ordered hits are put one after the other. */
 int hg_scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, int buffer_size,

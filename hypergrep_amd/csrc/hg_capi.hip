@@ -39,6 +39,11 @@ struct hg_scanner {
   bool last_invert;
   HgCounts *counts;
   hg_counts_result_t last_counts;
+  // what hg_gather_parts needs beside them: whether the last scan was one with parts (zero parts leave last_parts empty); the
+  // stage's own buffers (made by the first parts gather), and the last parts gather's result (zeroes after a scan)
+  bool last_with_parts = false;
+  HgPartLines *partlines = nullptr;
+  hg_part_lines_result_t last_part_lines = {};
 };
 
 static_assert(HG_ID_CONTEXT == HG_CTX_ID_CONTEXT && HG_ID_CONTEXT_TAIL == HG_CTX_ID_TAIL, "the context records carry the ids the header names");
@@ -51,6 +56,10 @@ static_assert(HG_LINES_CONTEXT == HG_GATHER_CONTEXT && HG_LINES_TERMINATE == HG_
 static_assert(HG_COUNTS_ACCUMULATE == HG_COUNTS_F_ACCUMULATE && HG_COUNTS_PER_SEGMENT == HG_COUNTS_F_PER_SEGMENT && HG_COUNTS_LDS_BINS == HG_COUNTS_LDS_MAX &&
                   sizeof(hg_counts_result_t) == 64,
               "the counts stage's flags and limit are the header's");
+static_assert(HG_PARTS_NUMBER == HG_PARTLINES_NUMBER && HG_PARTS_BYTE_OFFSET == HG_PARTLINES_BYTE_OFFSET && HG_PARTS_TERMINATE == HG_PARTLINES_TERMINATE &&
+                  HG_PARTS_LINE == HG_PARTLINES_LINE && HG_PART_FIRST == HG_PARTLINES_FIRST && HG_PART_LAST == HG_PARTLINES_LAST &&
+                  HG_PARTS_MARK_MAX == HG_PARTLINES_MARK_MAX && sizeof(hg_part_lines_params_t) == 56 && sizeof(hg_part_lines_result_t) == 80,
+              "the parts gather's flags, kinds and limit are the header's");
 
 static void put_err(char *err, size_t errlen, const std::string &msg) {
   if (err && errlen) std::snprintf(err, errlen, "%s", msg.c_str());
@@ -125,6 +134,7 @@ void hg_scanner_destroy(hg_scanner_t *scanner) {
   if (!scanner) return;
   delete scanner->gather;
   delete scanner->counts;
+  delete scanner->partlines;
   delete scanner->sc;
   delete scanner;
 }
@@ -140,6 +150,8 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
   HgPartsOutput pt{};
   scanner->scanned = false;
   scanner->last_lines = hg_lines_result_t{};
+  scanner->last_part_lines = hg_part_lines_result_t{};
+  scanner->last_with_parts = false;
   scanner->last_counts.n_seg = 0;  // (the totals stay: HG_COUNTS_ACCUMULATE adds the next scan's)
   scanner->last_counts.d_seg_lines = scanner->last_counts.d_seg_reports = nullptr;
   scanner->last_parts = hg_parts_result_t{};
@@ -205,6 +217,7 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
   scanner->d_from = o.d_from;
   scanner->scanned = true;
   scanner->last_invert = invert;
+  scanner->last_with_parts = parts_result != nullptr;
   scanner->last_text = d_text;
   scanner->last_nbytes = nbytes;
   scanner->last_seg_start = segments ? segments->d_seg_start : nullptr;
@@ -324,6 +337,83 @@ int hg_copy_lines_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes,
   if (!scanner || !d_dst) return HG_ERR_ARG;
   const hg_lines_result_t &g = scanner->last_lines;
   if (!g.d_entry_off) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_lines_device: no gather since the last scan");
+  const uint64_t nb = std::min(g.n_bytes, max_bytes);
+  if (!nb) return HG_OK;
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  return hipMemcpyAsync(d_dst, g.d_bytes, nb, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)) == hipSuccess ? HG_OK : HG_ERR_HIP;
+}
+
+int hg_gather_parts(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, const hg_part_lines_params_t *params, void *stream, hg_part_lines_result_t *result) {
+  if (!scanner) return HG_ERR_ARG;
+  if (result) *result = hg_part_lines_result_t{};
+  const bool seg = scanner->last_seg.d_first_record != nullptr;
+  const char *why = !result                                                                    ? "hg_gather_parts: result is NULL"
+                    : !params                                                                  ? "hg_gather_parts: params is NULL"
+                    : !scanner->scanned                                                        ? "hg_gather_parts: no successful scan to gather the parts of"
+                    : (d_text != scanner->last_text || nbytes != scanner->last_nbytes)         ? "hg_gather_parts: d_text and nbytes are not those of the last scan"
+                    : !scanner->last_with_parts                                                ? "hg_gather_parts: the last scan was not one with parts (hg_scan_device_parts, hg_scan_device_segments_parts)"
+                    : (params->flags & ~(HG_PARTS_NUMBER | HG_PARTS_BYTE_OFFSET | HG_PARTS_TERMINATE | HG_PARTS_LINE)) ? "hg_gather_parts: unknown flag bits"
+                    : (params->mark_on_len > HG_PARTS_MARK_MAX || params->mark_off_len > HG_PARTS_MARK_MAX) ? "hg_gather_parts: a mark of more than 16 bytes"
+                    : (seg && params->byte_base)                                               ? "hg_gather_parts: byte_base must be 0 after a scan with segments (the starts are file-relative)"
+                                                                                               : nullptr;
+  if (why) return scanner->sc->set_error(HG_ERR_ARG, why);
+  scanner->last_part_lines = hg_part_lines_result_t{};
+  if (!scanner->partlines) scanner->partlines = new HgPartLines(scanner->sc->device());
+  HgPartLinesInput in{};
+  in.text = static_cast<const uint8_t *>(d_text);
+  in.recs = HgGatherList{reinterpret_cast<const HgHit *>(scanner->last.d_hits), reinterpret_cast<const HgHitAux *>(scanner->last.d_aux),
+                         seg ? scanner->last_seg.d_record_segment : nullptr, scanner->last.n_hits};
+  in.parts = reinterpret_cast<const HgPart *>(scanner->last_parts.d_parts);
+  in.part_pattern = scanner->last_parts.d_part_pattern;
+  in.n_parts = scanner->last_parts.n_parts;
+  if (seg) {
+    in.part_seg = scanner->last_segparts.d_part_segment;
+    in.seg_start = scanner->last_seg_start;
+    in.first_part = scanner->last_segparts.d_first_part;
+    in.n_seg = scanner->last_n_seg;
+  }
+  in.flags = params->flags;
+  in.byte_base = params->byte_base;
+  in.marks = hg_partlines_marks(params->mark_on, params->mark_on_len, params->mark_off, params->mark_off_len);
+  HgPartLinesOutput o{};
+  std::string err;
+  const int rc = scanner->partlines->run(in, static_cast<hipStream_t>(stream), &o, &err);
+  if (rc != HG_OK) return scanner->sc->set_error(rc, err);
+  scanner->last_part_lines = hg_part_lines_result_t{o.n_entries, o.n_bytes, o.d_bytes, o.d_entry_off, o.d_line_number, o.d_kind, o.d_pattern, o.d_segment, o.d_first_entry,
+                                                    static_cast<uint32_t>(o.ms_gather * 1000.0f + 0.5f), 0};
+  *result = scanner->last_part_lines;
+  return HG_OK;
+}
+
+int hg_copy_part_lines(hg_scanner_t *scanner, uint8_t *bytes, uint64_t max_bytes, uint64_t *entry_off, uint64_t *line_number, uint32_t *kind, uint32_t *pattern,
+                       uint32_t *segment, uint64_t max_entries) {
+  if (!scanner) return HG_ERR_ARG;
+  const hg_part_lines_result_t &g = scanner->last_part_lines;
+  if (!g.d_entry_off) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_part_lines: no parts gather since the last scan");
+  if (segment && !g.d_segment) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_part_lines: the last scan had no segments");
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  const uint64_t nb = std::min(g.n_bytes, max_bytes), ne = std::min(g.n_entries, max_entries);
+  if (bytes && nb && hipMemcpy(bytes, g.d_bytes, nb, hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (entry_off && hipMemcpy(entry_off, g.d_entry_off, (ne + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (line_number && ne && hipMemcpy(line_number, g.d_line_number, ne * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (kind && ne && hipMemcpy(kind, g.d_kind, ne * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (pattern && ne && hipMemcpy(pattern, g.d_pattern, ne * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (segment && ne && hipMemcpy(segment, g.d_segment, ne * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
+}
+
+int hg_copy_part_lines_first(hg_scanner_t *scanner, uint64_t *first_entry) {
+  if (!scanner || !first_entry) return HG_ERR_ARG;
+  const hg_part_lines_result_t &g = scanner->last_part_lines;
+  if (!g.d_first_entry) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_part_lines_first: no parts gather after a scan with segments");
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  return hipMemcpy(first_entry, g.d_first_entry, (scanner->last_n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) == hipSuccess ? HG_OK : HG_ERR_HIP;
+}
+
+int hg_copy_part_lines_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes, void *stream) {
+  if (!scanner || !d_dst) return HG_ERR_ARG;
+  const hg_part_lines_result_t &g = scanner->last_part_lines;
+  if (!g.d_entry_off) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_part_lines_device: no parts gather since the last scan");
   const uint64_t nb = std::min(g.n_bytes, max_bytes);
   if (!nb) return HG_OK;
   if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;

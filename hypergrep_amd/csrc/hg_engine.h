@@ -16,6 +16,7 @@
 #include "hg_parts.h"
 #include "hg_segparts.h"
 #include "hg_gather.h"
+#include "hg_partlines.h"
 #include "hg_counts.h"
 #include "hg_mem.h"
 #include "hg_post.h"
@@ -306,6 +307,52 @@ class HgGather {
   DevBuf<HgGatherEntry> entries_{"gather entries", 0};
   DevBuf<uint8_t> temp_{"gather temp", 0}, bytes_{"gather bytes", 16};
   hgmem::Buf<uint64_t, hgmem::Space::Host> totals_{"gather totals", 0};  // pinned: {entries, bytes}
+};
+
+// The parts gather (hg_partlines.hip) over the parts a scan left, one step per launch on `stream`: the entries (fields, size,
+// per-entry arrays), the first entry of every output span of HG_GATHER_TILE bytes, and the copy pass over those spans.
+enum class HgPartLinesStep { Entry, Span, Copy };
+hipError_t hg_partlines_launch(const HgPartLinesArgs &a, HgPartLinesStep step, hipStream_t stream);
+// What a parts gather works on (the last scan's records and parts, as hg_capi.hip remembers them) and what it leaves
+// (hg_part_lines_result_t).
+struct HgPartLinesInput {
+  const uint8_t *text;
+  HgGatherList recs;
+  const HgPart *parts;
+  const uint32_t *part_pattern, *part_seg;  // part_seg nullptr without segments
+  uint64_t n_parts;
+  const uint64_t *seg_start, *first_part;   // nullptr without segments
+  uint64_t n_seg;
+  uint32_t flags;
+  uint64_t byte_base;
+  HgPartLinesMarks marks;
+};
+struct HgPartLinesOutput {
+  uint64_t n_entries, n_bytes;
+  const uint8_t *d_bytes;  // device arrays, valid until the next parts gather on this object
+  const uint64_t *d_entry_off, *d_line_number;
+  const uint32_t *d_kind, *d_pattern, *d_segment;
+  const uint64_t *d_first_entry;
+  float ms_gather;  // the stage: entries, scan, the host sync that sizes the output, spans, copy
+};
+// The stage's buffers and launch sequence.  It owns its scratch (hgmem::Buf: freed with the object, every allocation logged)
+// and touches nothing of the scanner's, of HgGather's or of HgCounts'.
+class HgPartLines {
+ public:
+  explicit HgPartLines(int device) : device_(device) {}
+  ~HgPartLines();
+  int run(const HgPartLinesInput &in, hipStream_t stream, HgPartLinesOutput *out, std::string *err);
+
+ private:
+  template <typename T>
+  using DevBuf = hgmem::Buf<T, hgmem::Space::Dev>;
+  int device_;
+  hipEvent_t ev_[2] = {nullptr, nullptr};
+  DevBuf<uint64_t> size_{"partlines size", 0}, off_{"partlines off", 0}, line_{"partlines line", 0}, first_{"partlines first", 0}, span_{"partlines span", 0};
+  DevBuf<uint32_t> kind_{"partlines kind", 0}, pattern_{"partlines pattern", 0}, seg_{"partlines seg", 0};
+  DevBuf<HgPartLinesEntry> entries_{"partlines entries", 0};
+  DevBuf<uint8_t> temp_{"partlines temp", 0}, bytes_{"partlines bytes", 16};
+  hgmem::Buf<uint64_t, hgmem::Space::Host> totals_{"partlines totals", 0};  // pinned: {bytes}
 };
 
 // The counts stage (hg_counts.hip) over the record list a scan left: one launch on `stream` (nothing for an empty list).

@@ -1833,6 +1833,98 @@ int HgGather::run(const HgGatherInput &in, hipStream_t stream, HgGatherOutput *o
   return HG_OK;
 }
 
+// ---------------------------------------------------------------- parts gather (hg_gather_parts): buffers and launch sequence
+HgPartLines::~HgPartLines() {
+  (void)hipSetDevice(device_);  // (the buffers are freed behind this body)
+  for (hipEvent_t e : ev_)
+    if (e) (void)hipEventDestroy(e);
+}
+
+#define HG_PARTLINES_TRY(expr, what)                                                      \
+  do {                                                                                    \
+    const hipError_t e_ = (expr);                                                         \
+    if (e_ != hipSuccess) {                                                               \
+      *err = std::string("parts gather: ") + (what) + ": " + hipGetErrorString(e_);       \
+      return HG_ERR_HIP;                                                                  \
+    }                                                                                     \
+  } while (0)
+
+int HgPartLines::run(const HgPartLinesInput &in, hipStream_t stream, HgPartLinesOutput *out, std::string *err) {
+  *out = HgPartLinesOutput{};
+  HG_PARTLINES_TRY(hipSetDevice(device_), "hipSetDevice");
+  for (hipEvent_t &e : ev_)
+    if (!e) HG_PARTLINES_TRY(hipEventCreate(&e), "event");
+  const uint64_t n = in.n_parts, cap = n + 1;
+  size_t tb = 0;
+  HG_PARTLINES_TRY(rocprim::exclusive_scan(nullptr, tb, static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), uint64_t{0}, cap, rocprim::plus<uint64_t>(), stream),
+                   "scan size");
+  tb = std::max<size_t>(tb, 16);
+  const size_t grow = cap + cap / 4;
+  const bool ok = size_.reserve(cap, grow) && off_.reserve(cap, grow) && line_.reserve(cap, grow) && kind_.reserve(cap, grow) && pattern_.reserve(cap, grow) &&
+                  (!in.seg_start || (seg_.reserve(cap, grow) && first_.reserve(in.n_seg + 1, in.n_seg + 1))) && entries_.reserve(cap, grow) && temp_.reserve(tb, tb + tb / 4) &&
+                  totals_.reserve(1, 1);
+  if (!ok) {
+    *err = "parts gather: out of memory";
+    return HG_ERR_NOMEM;
+  }
+  HgPartLinesArgs a{};
+  a.text = HgGatherText{in.text};
+  a.recs = in.recs;
+  a.parts = in.parts;
+  a.part_pattern = in.part_pattern;
+  a.part_seg = in.seg_start ? in.part_seg : nullptr;
+  a.n_parts = n;
+  a.seg_start = in.seg_start;
+  a.flags = in.flags;
+  a.byte_base = in.byte_base;
+  a.marks = in.marks;
+  a.size = size_.get();
+  a.entries = entries_.get();
+  a.line_number = line_.get();
+  a.kind = kind_.get();
+  a.pattern = pattern_.get();
+  a.segment = in.seg_start ? seg_.get() : nullptr;
+  a.off = off_.get();
+  HG_PARTLINES_TRY(hipEventRecord(ev_[0], stream), "event");
+  HG_PARTLINES_TRY(hg_partlines_launch(a, HgPartLinesStep::Entry, stream), "launch (entries)");
+  // an entry per part: the segments' first entries are their first parts
+  if (in.seg_start) HG_PARTLINES_TRY(hipMemcpyAsync(first_.get(), in.first_part, (in.n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream), "copy (first_entry)");
+  size_t t = temp_.cap();
+  HG_PARTLINES_TRY(rocprim::exclusive_scan(temp_.get(), t, size_.get(), off_.get(), uint64_t{0}, cap, rocprim::plus<uint64_t>(), stream), "scan (sizes)");
+  uint64_t *totals = totals_.get();
+  HG_PARTLINES_TRY(hipMemcpyAsync(totals, off_.get() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "copy count");
+  HG_PARTLINES_TRY(hipStreamSynchronize(stream), "stream sync");
+  a.n_entries = n;
+  a.n_bytes = totals[0];
+  const uint64_t padded = (a.n_bytes + 15) & ~static_cast<uint64_t>(15);
+  if (!bytes_.reserve(std::max<uint64_t>(padded, 16), std::max<uint64_t>(padded + padded / 8, 16))) {
+    *err = "parts gather: out of memory for " + std::to_string(a.n_bytes) + " bytes of parts";
+    return HG_ERR_NOMEM;
+  }
+  a.out = bytes_.get();
+  const uint64_t n_spans = (a.n_bytes + HG_GATHER_TILE - 1) / HG_GATHER_TILE;
+  if (!span_.reserve(n_spans + 1, n_spans + n_spans / 8 + 1)) {
+    *err = "parts gather: out of memory";
+    return HG_ERR_NOMEM;
+  }
+  a.span = span_.get();
+  HG_PARTLINES_TRY(hg_partlines_launch(a, HgPartLinesStep::Span, stream), "launch (spans)");
+  HG_PARTLINES_TRY(hg_partlines_launch(a, HgPartLinesStep::Copy, stream), "launch (copy)");
+  HG_PARTLINES_TRY(hipEventRecord(ev_[1], stream), "event");
+  HG_PARTLINES_TRY(hipStreamSynchronize(stream), "stream sync");
+  HG_PARTLINES_TRY(hipEventElapsedTime(&out->ms_gather, ev_[0], ev_[1]), "event time");
+  out->n_entries = a.n_entries;
+  out->n_bytes = a.n_bytes;
+  out->d_bytes = bytes_.get();
+  out->d_entry_off = off_.get();
+  out->d_line_number = line_.get();
+  out->d_kind = kind_.get();
+  out->d_pattern = pattern_.get();
+  out->d_segment = a.segment;
+  out->d_first_entry = in.seg_start ? first_.get() : nullptr;
+  return HG_OK;
+}
+
 // ---------------------------------------------------------------- counts stage (hg_count_records): buffers and launch sequence
 HgCounts::~HgCounts() {
   (void)hipSetDevice(device_);  // (the buffers are freed behind this body)

@@ -28,6 +28,10 @@ HG_GATHER_TILE = 16384
 HG_COUNTS_ACCUMULATE, HG_COUNTS_PER_SEGMENT = 1, 2
 HG_COUNTS_LDS_BINS = 4096
 HG_COUNTS_RUN = 16384
+# Scanner.gather_parts (hg_gather_parts): the flags, the bits of an entry's kind, and the longest marker
+HG_PARTS_NUMBER, HG_PARTS_BYTE_OFFSET, HG_PARTS_TERMINATE, HG_PARTS_LINE = 1, 2, 4, 8
+HG_PART_FIRST, HG_PART_LAST = 1, 2
+HG_PARTS_MARK_MAX = 16
 
 
 class HgHit(ctypes.Structure):
@@ -82,6 +86,17 @@ class HgLinesResult(ctypes.Structure):
     _fields_ = [("n_entries", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("d_bytes", ctypes.c_void_p), ("d_entry_off", ctypes.c_void_p),
                 ("d_line_number", ctypes.c_void_p), ("d_kind", ctypes.c_void_p), ("d_segment", ctypes.c_void_p), ("d_first_entry", ctypes.c_void_p),
                 ("gather_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class HgPartLinesParams(ctypes.Structure):  # sizeof 56
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("byte_base", ctypes.c_uint64), ("mark_on_len", ctypes.c_uint32),
+                ("mark_off_len", ctypes.c_uint32), ("mark_on", ctypes.c_uint8 * 16), ("mark_off", ctypes.c_uint8 * 16)]
+
+
+class HgPartLinesResult(ctypes.Structure):  # sizeof 80
+    _fields_ = [("n_entries", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("d_bytes", ctypes.c_void_p), ("d_entry_off", ctypes.c_void_p),
+                ("d_line_number", ctypes.c_void_p), ("d_kind", ctypes.c_void_p), ("d_pattern", ctypes.c_void_p), ("d_segment", ctypes.c_void_p),
+                ("d_first_entry", ctypes.c_void_p), ("gather_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class HgCountsResult(ctypes.Structure):
@@ -172,6 +187,13 @@ def lib() -> ctypes.CDLL:
             l.hg_copy_counts.argtypes = [ctypes.c_void_p, p32, p64, p64, ctypes.c_uint32]
             l.hg_copy_segment_counts.argtypes = [ctypes.c_void_p, p32, p32, ctypes.c_uint32, ctypes.c_uint32]
             l.hg_db_report_ids.argtypes = [ctypes.c_void_p, p32, ctypes.c_uint32, p32]
+        if hasattr(l, "hg_gather_parts"):  # (absent from a build before the parts gather)
+            p8, p32, p64 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+            l.hg_gather_parts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(HgPartLinesParams), ctypes.c_void_p,
+                                          ctypes.POINTER(HgPartLinesResult)]
+            l.hg_copy_part_lines.argtypes = [ctypes.c_void_p, p8, ctypes.c_uint64, p64, p64, p32, p32, p32, ctypes.c_uint64]
+            l.hg_copy_part_lines_first.argtypes = [ctypes.c_void_p, p64]
+            l.hg_copy_part_lines_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hits.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
         l.hg_copy_hits_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hit_starts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
@@ -272,6 +294,13 @@ class GatherStats:
 
 
 @dataclass
+class PartLinesStats:
+    n_entries: int  # one per part
+    n_bytes: int  # bytes of all entries
+    gather_us: int  # the parts gather alone, microseconds
+
+
+@dataclass
 class CountStats:
     n_bins: int  # distinct report ids of the database
     n_records: int  # records this call counted
@@ -297,6 +326,7 @@ class Scanner:
         self._last_segment_parts = False  # the last scan was one with segment_parts
         self._last_lines = None  # HgLinesResult of the last gather, None after a scan
         self._last_counts = None  # HgCountsResult of the last count
+        self._last_part_lines = None  # (HgPartLinesResult, whole_line) of the last parts gather, None after a scan
         self._seg_arena = None
 
     def _place_segments(self, starts, ends):
@@ -347,6 +377,7 @@ class Scanner:
         cres = HgContextResult()
         sres = HgSegmentResult()
         self._last_lines = None
+        self._last_part_lines = None
         self._last_seg = None
         self._last_segment_parts = False
         if segments is not None:
@@ -518,6 +549,85 @@ class Scanner:
         rc = lib().hg_copy_lines_device(self._h, ctypes.c_void_p(d_dst), n, ctypes.c_void_p(stream))
         if rc != 0:
             raise DeviceError(f"hg_copy_lines_device failed ({rc})")
+        return n
+
+    def gather_parts(self, d_text: int, nbytes: int, number: bool = False, byte_offset: bool = False, terminate: bool = False, whole_line: bool = False,
+                     mark: tuple[bytes, bytes] = (b"", b""), byte_base: int = 0, stream: int = 0) -> PartLinesStats:
+        """The matched parts themselves (hg_gather_parts): after scan(parts=True) or scan(segment_parts=True), the bytes of every
+        part, one entry per part in the parts' order, gathered on the GPU into one device buffer.  d_text and nbytes must be
+        the last scan's.  number: the 1-based line number and ':' in front; byte_offset: the byte offset (byte_base + the part's
+        offset in the text; file-relative after a scan with segments, where byte_base must be 0) and ':' in front; terminate:
+        every entry ends in a newline (grep -o -n -b).  whole_line: the whole matching line instead, its parts between the two
+        byte strings of `mark` (at most 16 bytes each; grep --color), number and byte_offset (the line's) once per line.
+        part_lines(), part_lines_arrays() and copy_part_lines_to() give the result; hits(), parts(), lines(), counts() ... are
+        unchanged by it.  ValueError with the reason when there are no parts to gather: no scan yet, a scan without parts,
+        d_text / nbytes not the last scan's, a mark too long, byte_base after segments."""
+        flags = (HG_PARTS_NUMBER if number else 0) | (HG_PARTS_BYTE_OFFSET if byte_offset else 0) | (HG_PARTS_TERMINATE if terminate else 0) | (HG_PARTS_LINE if whole_line else 0)
+        return self._gather_parts(d_text, nbytes, flags, mark, byte_base, stream)
+
+    def _gather_parts(self, d_text: int, nbytes: int, flags: int, mark=(b"", b""), byte_base: int = 0, stream: int = 0, mark_lens=None) -> PartLinesStats:
+        on, off = bytes(mark[0]), bytes(mark[1])
+        params = HgPartLinesParams(flags=flags, byte_base=byte_base, mark_on_len=len(on), mark_off_len=len(off))
+        if mark_lens is not None:  # (the tests: lengths the bytes do not have)
+            params.mark_on_len, params.mark_off_len = mark_lens
+        ctypes.memmove(params.mark_on, on, min(len(on), 16))
+        ctypes.memmove(params.mark_off, off, min(len(off), 16))
+        res = HgPartLinesResult()
+        self._last_part_lines = None
+        rc = lib().hg_gather_parts(self._h, ctypes.c_void_p(d_text), nbytes, ctypes.byref(params), ctypes.c_void_p(stream), ctypes.byref(res))
+        if rc == -1:  # HG_ERR_ARG: nothing was launched
+            raise ValueError(lib().hg_scanner_error(self._h).decode(errors="replace"))
+        if rc != 0:
+            raise DeviceError(f"hg_gather_parts failed ({rc}): {lib().hg_scanner_error(self._h).decode(errors='replace')}")
+        self._last_part_lines = (res, bool(flags & HG_PARTS_LINE))
+        return PartLinesStats(res.n_entries, res.n_bytes, res.gather_us)
+
+    def part_lines_arrays(self):
+        """The last parts gather as a dict: bytes (the blob), and numpy arrays entry_off (uint64, n + 1: entry j is
+        bytes[entry_off[j]:entry_off[j + 1]]), line_number (uint64), kind (uint32, HG_PART_FIRST | HG_PART_LAST), pattern
+        (uint32, the expression index), and after a scan with segments segment (uint32) and first_entry (uint64, files + 1),
+        else None.  ValueError without a parts gather since the last scan."""
+        import numpy as np
+
+        if self._last_part_lines is None:
+            raise ValueError("no parts gather since the last scan")
+        g = self._last_part_lines[0]
+        n = g.n_entries
+        blob = np.zeros(max(g.n_bytes, 1), dtype=np.uint8)
+        out = {"entry_off": np.zeros(n + 1, dtype=np.uint64), "line_number": np.zeros(n, dtype=np.uint64), "kind": np.zeros(n, dtype=np.uint32),
+               "pattern": np.zeros(n, dtype=np.uint32), "segment": np.zeros(n, dtype=np.uint32) if g.d_segment else None, "first_entry": None}
+        p8, p32, p64 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+        rc = lib().hg_copy_part_lines(self._h, blob.ctypes.data_as(p8), g.n_bytes, out["entry_off"].ctypes.data_as(p64), out["line_number"].ctypes.data_as(p64),
+                                      out["kind"].ctypes.data_as(p32), out["pattern"].ctypes.data_as(p32), out["segment"].ctypes.data_as(p32) if g.d_segment else None, n)
+        if rc != 0:
+            raise DeviceError(f"hg_copy_part_lines failed ({rc})")
+        if g.d_first_entry:
+            _, n_seg = self._last_seg
+            out["first_entry"] = np.zeros(n_seg + 1, dtype=np.uint64)
+            rc = lib().hg_copy_part_lines_first(self._h, out["first_entry"].ctypes.data_as(p64))
+            if rc != 0:
+                raise DeviceError(f"hg_copy_part_lines_first failed ({rc})")
+        out["bytes"] = blob[:g.n_bytes].tobytes()
+        return out
+
+    def part_lines(self):
+        """The last parts gather as a list of bytes, in order: one per part, or with whole_line one per line (the entries of
+        a line joined)."""
+        a = self.part_lines_arrays()
+        off = a["entry_off"].tolist()
+        if not self._last_part_lines[1]:
+            return [a["bytes"][off[j]:off[j + 1]] for j in range(len(off) - 1)]
+        firsts = [j for j, k in enumerate(a["kind"].tolist()) if k & HG_PART_FIRST] + [len(off) - 1]
+        return [a["bytes"][off[lo]:off[hi]] for lo, hi in zip(firsts, firsts[1:])]
+
+    def copy_part_lines_to(self, d_dst: int, max_bytes: int, stream: int = 0) -> int:
+        """Async device-to-device copy of the last parts gather's bytes (the first max_bytes of them); returns the number copied."""
+        if self._last_part_lines is None:
+            raise ValueError("no parts gather since the last scan")
+        n = min(max_bytes, self._last_part_lines[0].n_bytes)
+        rc = lib().hg_copy_part_lines_device(self._h, ctypes.c_void_p(d_dst), n, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise DeviceError(f"hg_copy_part_lines_device failed ({rc})")
         return n
 
     def count(self, accumulate: bool = False, per_segment: bool = False, stream: int = 0) -> CountStats:

@@ -758,7 +758,7 @@ int hg_copy_segment_parts(hg_scanner_t *scanner, uint32_t *part_segment, uint64_
  * stage runs after a scan, on that scan's records; it scans nothing and changes nothing about scanning.
  * Entries.  An entry is a distinct (segment, line_number) among the last scan's final records: the hits (several reports on
  * one line give one entry), the selected pieces of an inverted scan, or the surviving records of a scan with segments.  Every
- * hg_scan_device* call is accepted as the last scan; after a scan with parts the hits are used, parts are not gathered.
+ * hg_scan_device* call is accepted as the last scan; after a scan with parts the hits are used, parts are not gathered (hg_gather_parts below gathers them).
  * Entries come in the records' order.
  * Entry j is the bytes d_bytes[d_entry_off[j], d_entry_off[j + 1]) = [separator][number prefix] body [terminator]:
  *   body        exactly the piece's scanned bytes text[start, start + len) (hg_hit_aux_t); after a scan with segments `start`
@@ -817,6 +817,82 @@ int hg_copy_lines(hg_scanner_t *scanner, uint8_t *bytes, uint64_t max_bytes, uin
 int hg_copy_lines_first(hg_scanner_t *scanner, uint64_t *first_entry);
 /* The bytes (the first max_bytes of them) into a DEVICE buffer, asynchronously on `stream`. */
 int hg_copy_lines_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes, void *stream);
+
+/* The matched parts themselves (grep -o -n -b, grep --color): the bytes of every part the last scan with parts on this scanner
+ * left a record for, gathered on the GPU into one compact, ordered, optionally print-ready DEVICE buffer that goes to the host
+ * or to another GPU in a single transfer.  The stage runs after hg_scan_device_parts or hg_scan_device_segments_parts, on that
+ * scan's records; it scans nothing and changes nothing about scanning or about any other stage.
+ * Entries.  One entry per part, in the parts' order.  Part q belongs to the piece (segment, line_number); S is the offset of
+ * the piece's first scanned byte: hg_hit_aux_t.start of the piece's record, plus seg_start[segment] after a scan with segments
+ * (the sum in 64 bits; the segments' d_seg_start array must still be valid when the stage runs); len is that record's len.
+ * prev_to is the `to` of the previous part of the same piece, 0 if there is none.
+ * Entry q is the bytes d_bytes[d_entry_off[q], d_entry_off[q + 1]):
+ *   parts mode (default)       [number][offset] [mark_on] text[S+from, S+to) [mark_off] [terminator]
+ *   line mode (HG_PARTS_LINE)  [number][offset] text[S+prev_to, S+from) [mark_on] text[S+from, S+to) [mark_off]
+ *                              [ text[S+to, S+len) [terminator] ]
+ *                              number and offset on the first part of a piece only, the trailing text and the terminator on
+ *                              the last part of a piece only: the entries of a piece, joined, are the whole line with its
+ *                              parts marked.
+ *   number      with HG_PARTS_NUMBER, the decimal line_number + 1 followed by ':' (grep -n);
+ *   offset      with HG_PARTS_BYTE_OFFSET, a 64-bit decimal followed by ':' (grep -b): in parts mode byte_base +
+ *               hg_hit_aux_t.start + from, in line mode byte_base + hg_hit_aux_t.start.  After a scan with segments `start` is
+ *               file-relative already and byte_base must be 0;
+ *   terminator  with HG_PARTS_TERMINATE, one '\n' where the last text byte the entry emitted is not '\n': text[S+to-1] in
+ *               parts mode, text[S+len-1] (on the last part only) in line mode;
+ *   mark_on, mark_off   0 to HG_PARTS_MARK_MAX bytes each, copied by value when the call is made (grep --color's escapes).
+ * The per-entry arrays: d_line_number as in the parts; d_kind, bit 0 HG_PART_FIRST and bit 1 HG_PART_LAST of its piece (both
+ * modes); d_pattern the expression index (as d_part_pattern); after a scan with segments d_segment and d_first_entry (n_seg + 1:
+ * file s owns the entries [first_entry[s], first_entry[s + 1])), both NULL otherwise.  Zero parts is a success with n_entries =
+ * n_bytes = 0 and entry_off[0] = 0.
+ * Identities: with flags 0 and no marks n_entries = n_parts and n_bytes is the sum of to - from; HG_PARTS_LINE alone gives the
+ * bytes hg_gather_lines gives with flags 0 on the same scan.
+ * HG_ERR_ARG, with nothing launched and the reason in hg_scanner_error: no successful scan on this scanner yet (or the last
+ * one failed); d_text or nbytes differ from the last scan's; the last scan was not one with parts; unknown flag bits; a mark
+ * length above HG_PARTS_MARK_MAX; byte_base != 0 after a scan with segments; params == NULL or result == NULL.
+ * Lifetime.  The result stays valid until the next scan or hg_gather_parts on this scanner.  The stage has buffers of its own:
+ * the scan's results, a previous hg_gather_lines and a previous hg_count_records stay as they are.  gather_us: the stage in
+ * microseconds (HIP events; the host synchronisation that sizes the output included).
+ * The stage runs on the GPU (hypergrep_amd/csrc/hg_partlines.hip): an entry pass, a lane per part (a lower bound into the
+ * records, first / last from the neighbouring parts, the fields and the 64-bit size); an exclusive scan of the sizes; and a
+ * copy pass divided by OUTPUT bytes, HG_GATHER_TILE per workgroup, which finds its entries by binary search and writes whole
+ * aligned 16-byte words.  The text is read inside the pieces that have parts only (whole aligned dwords: never past nbytes
+ * rounded up to 4). */
+#define HG_PARTS_NUMBER 1u      /* the decimal line_number + 1 and ':' in front (line mode: of a piece's first part) */
+#define HG_PARTS_BYTE_OFFSET 2u /* the decimal byte offset and ':' in front (line mode: of a piece's first part) */
+#define HG_PARTS_TERMINATE 4u   /* a '\n' behind an entry (line mode: a piece's last) whose last text byte is not one */
+#define HG_PARTS_LINE 8u        /* line mode: the whole line, its parts between the marks */
+#define HG_PART_FIRST 1u
+#define HG_PART_LAST 2u
+#define HG_PARTS_MARK_MAX 16
+typedef struct hg_part_lines_params { /* sizeof 56 */
+    uint32_t flags;                   /* HG_PARTS_* */
+    uint32_t reserved;
+    uint64_t byte_base;               /* added to the offset prefix: the offset of d_text in a larger text */
+    uint32_t mark_on_len, mark_off_len;
+    uint8_t mark_on[16], mark_off[16];
+} hg_part_lines_params_t;
+typedef struct hg_part_lines_result { /* sizeof 80 */
+    uint64_t n_entries, n_bytes;
+    const uint8_t *d_bytes;        /* DEVICE, valid until the next scan or hg_gather_parts on this scanner */
+    const uint64_t *d_entry_off;   /* n_entries + 1 */
+    const uint64_t *d_line_number; /* as in the parts (file-relative after a scan with segments) */
+    const uint32_t *d_kind;        /* HG_PART_FIRST | HG_PART_LAST */
+    const uint32_t *d_pattern;     /* expression index of each entry's part */
+    const uint32_t *d_segment;     /* NULL unless the last scan had segments */
+    const uint64_t *d_first_entry; /* n_seg + 1, NULL unless segments */
+    uint32_t gather_us, reserved;
+} hg_part_lines_result_t;
+int hg_gather_parts(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, const hg_part_lines_params_t *params, void *stream,
+                    hg_part_lines_result_t *result);
+/* Copy the last parts gather's first max_bytes bytes and the per-entry arrays of its first max_entries entries to host memory
+ * (any pointer may be NULL; entry_off receives min(n_entries, max_entries) + 1 values).  HG_ERR_ARG without a parts gather
+ * since the last scan, and for `segment` after a scan without segments. */
+int hg_copy_part_lines(hg_scanner_t *scanner, uint8_t *bytes, uint64_t max_bytes, uint64_t *entry_off, uint64_t *line_number, uint32_t *kind,
+                       uint32_t *pattern, uint32_t *segment, uint64_t max_entries);
+/* first_entry (n_seg + 1 values) of the last parts gather; HG_ERR_ARG unless it followed a scan with segments. */
+int hg_copy_part_lines_first(hg_scanner_t *scanner, uint64_t *first_entry);
+/* The bytes (the first max_bytes of them) into a DEVICE buffer, asynchronously on `stream`. */
+int hg_copy_part_lines_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes, void *stream);
 
 /* Counts per report id (hg_count_records): which expressions fired, and on how many lines, without moving the record list.
  * Bins.  A bin is a distinct report id of the database, in ascending id order (hg_db_report_ids; n_bins <= n_patterns).

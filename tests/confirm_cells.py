@@ -1,5 +1,7 @@
 """The confirm routines of the literal-anchored tier as test cells (hypergrep_amd/csrc/hg_confirm_dev.h, hg_kernels.hip,
-hg_huge.hip), the texts that drive each cell through the window and piece geometry, and the reference.  Test infrastructure:
+hg_huge.hip), the texts that drive each cell through the window and piece geometry, and the reference.  The huge-automaton
+kernel has four cells, one per routine of hg_huge.hip (huge: huge_run_reg<1>, huge_reg2, huge_reg4, huge_lds: huge_run on
+staged tables and on tables in L2); the routines' own word, slab and exception geometry is in huge_cells.py.  Test infrastructure:
 imported by test_confirm_cells.py, test_confirm_cells_gpu.py and gpu_cases.py.
 
 A cell is a small set of expressions the compiler must place in one confirm routine (mode 0-4) with one class of lead (the
@@ -154,6 +156,29 @@ CELLS = [
         Expr(r"[0-9]{0,3}needle_hb_2.{0,1050}fin\b", 14, b"needle_hb_2", ((b"", b"fin"), (b"123", b" fin"), (b"7", fill(1050, 5) + b"fin")),
              ((b"", b"needle_hb_2", b"fine"), (b"", b"needle_hb_2", fill(1051, 5) + b"fin")), lead="lt16"),
     ), nw="huge", excluded={"q_sweep": NO_Q, "multi/far_start": "the leads are bounded"}),
+    # the same shape with longer repeats: the other routines of hg_huge.hip under the confirm caller (the routine of each
+    # expression is asserted through hugesim_py: HUGE_ROUTINES)
+    Cell("huge_reg2", 4, (
+        Expr("needle_hc_3.{0,2100}end_i", 14, b"needle_hc_3", ((b"", b"end_i"), (b"", b"abc end_i"), (b"", fill(2100, 3) + b"end_i")),
+             ((b"", b"needle_hc_3", fill(2101, 3) + b"end_i"), (b"", b"needle_hc_3", b"abc end_")), lead="zero"),
+        Expr(r"[0-9]{0,3}needle_hd_4.{0,2050}fim\b", 14, b"needle_hd_4", ((b"", b"fim"), (b"123", b" fim"), (b"7", fill(2050, 5) + b"fim")),
+             ((b"", b"needle_hd_4", b"fime"), (b"", b"needle_hd_4", fill(2051, 5) + b"fim")), lead="lt16"),
+    ), nw="huge", excluded={"q_sweep": NO_Q, "multi/far_start": "the leads are bounded"}),
+    Cell("huge_reg4", 4, (
+        Expr("needle_he_5.{0,4200}end_j", 14, b"needle_he_5", ((b"", b"end_j"), (b"", b"abc end_j"), (b"", fill(4200, 3) + b"end_j")),
+             ((b"", b"needle_he_5", fill(4201, 3) + b"end_j"), (b"", b"needle_he_5", b"abc end_")), lead="zero"),
+        Expr(r"[0-9]{0,3}needle_hf_6.{0,4150}fio\b", 14, b"needle_hf_6", ((b"", b"fio"), (b"123", b" fio"), (b"7", fill(4150, 5) + b"fio")),
+             ((b"", b"needle_hf_6", b"fioe"), (b"", b"needle_hf_6", fill(61, 5) + b"fi")), lead="lt16"),
+    ), nw="huge", excluded={"q_sweep": NO_Q, "multi/far_start": "the leads are bounded"}),
+    # above 256 words: huge_run, on staged tables (the first) and on tables in L2 (the second: conditions and twelve byte classes
+    # outgrow the staging area).  Only the first carries a sample as long as its repeat, the near miss one byte past the bound:
+    # the text limit (huge_cells.py holds the repeat bounds of both routines from both sides)
+    Cell("huge_lds", 4, (
+        Expr("needle_hg_7.{0,8300}end_k", 14, b"needle_hg_7", ((b"", b"end_k"), (b"", b"abc end_k"), (b"", fill(1500, 3) + b"end_k")),
+             ((b"", b"needle_hg_7", fill(8301, 3) + b"end_k"), (b"", b"needle_hg_7", b"abc end_")), lead="zero"),
+        Expr(r"[0-9]{0,3}needle_hh_8.{0,8250}fiq\b", 14, b"needle_hh_8", ((b"", b"fiq"), (b"123", b" fiq"), (b"7", fill(50, 5) + b"fiq")),
+             ((b"", b"needle_hh_8", b"fiqe"), (b"", b"needle_hh_8", fill(60, 5) + b"fi")), lead="lt16"),
+    ), nw="huge", excluded={"q_sweep": NO_Q, "multi/far_start": "the leads are bounded"}),
     Cell("mixed_shared_ids", None, (
         Expr("needle_ma_1", 14, b"needle_ma_1", ((b"", b""),)),
         Expr("needle_mb_2[0-9]{1,3}x", 14, b"needle_mb_2", ((b"", b"5x"), (b"", b"123x")), ((b"", b"needle_mb_2", b"1234x"),)),
@@ -162,6 +187,8 @@ CELLS = [
     ), modes=(0, 1, 2, 3), excluded={"q_sweep": "covered by the cells of the single routines", "multi/far_start": "the leads are bounded"}),
 ]
 BY_NAME = {c.name: c for c in CELLS}
+# the huge cells: the routine of hg_huge.hip each expression runs in (hugesim_py.placement)
+HUGE_ROUTINES = {"huge": ("reg1", "reg1"), "huge_reg2": ("reg2", "reg2"), "huge_reg4": ("reg4", "reg4"), "huge_lds": ("lds_staged", "lds_l2")}
 # every cell plants each of these at least once, unless its `excluded` names the tag with the reason
 REQUIRED_TAGS = (
     "align/hit", "align/miss",

@@ -33,6 +33,12 @@ def test_placement(cell):
         assert {e.lead for e in cell.exprs} >= {"lt16", "unbounded"}
     if cell.modes:
         assert sorted(p["mode"] for p in info) == [0, 1, 2, 3]
+    if cell.nw == "huge":  # which routine of hg_huge.hip runs each expression
+        import hugesim_py
+
+        pl = hugesim_py.placement(cell.patterns, cell.flags, cell.ids(False))
+        assert tuple(pl["exprs"][i]["routine"] for i in range(len(cell.exprs))) == cc.HUGE_ROUTINES[cell.name], pl["exprs"]
+        assert [pl["exprs"][i]["ctxfree"] for i in range(len(cell.exprs))] == [True, False]
 
 
 def test_excluded_classes_name_known_tags():

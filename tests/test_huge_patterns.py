@@ -1,6 +1,9 @@
 """Expressions beyond 1024 automaton positions: the compiler accepts what the oracle (and Hyperscan: bounded repeats up to
 32767) accepts, and the sparse tables + the host mirror of the wave-cooperative routine (hg_core.h hg_huge_scan_slice)
-reproduce the oracle's reports.  The GPU side of the same cases: test_gpu_parity.py::test_huge_patterns_*."""
+reproduce the oracle's reports.  The GPU side of the same cases: test_gpu_parity.py::test_huge_patterns_*.  These sets sit on
+shuffled random text, and which routine of hg_huge.hip a set lands in follows from its repeat count; the routines themselves
+(huge_run_reg<1 / 2 / 4>, huge_run on staged tables and on tables in L2) are named, placed and driven through their word, slab,
+exception and caller geometry by huge_cells.py (test_huge_cells.py, test_huge_cells_gpu.py)."""
 from __future__ import annotations
 
 import pytest

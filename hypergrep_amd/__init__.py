@@ -18,6 +18,7 @@ from hypergrep_amd.utils import (  # the reference package re-exports exactly th
     configure_libraries,
     count,
     count_files,
+    count_values,
     grep,
     grep_files,
     prepare_patterns,
@@ -35,5 +36,7 @@ __all__ = [
     "grep_files", "scan_files",
     # counts per report id, taken on the GPU
     "count", "count_files",
+    # distinct matched parts and their counts, grouped on the GPU
+    "count_values",
 ]
 __version__ = "0.1.0"

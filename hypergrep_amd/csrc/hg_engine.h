@@ -17,6 +17,7 @@
 #include "hg_segparts.h"
 #include "hg_gather.h"
 #include "hg_partlines.h"
+#include "hg_values.h"
 #include "hg_counts.h"
 #include "hg_mem.h"
 #include "hg_post.h"
@@ -353,6 +354,53 @@ class HgPartLines {
   DevBuf<HgPartLinesEntry> entries_{"partlines entries", 0};
   DevBuf<uint8_t> temp_{"partlines temp", 0}, bytes_{"partlines bytes", 16};
   hgmem::Buf<uint64_t, hgmem::Space::Host> totals_{"partlines totals", 0};  // pinned: {bytes}
+};
+
+// The values stage (hg_values.hip) over the parts a scan left, one step per launch on `stream`: value and hash per part, the
+// long parts (a wave each), the table probes, the occupied marks, the (first, count) pairs, and the per-value arrays.  The values'
+// bytes are then copied by the gather stage's span and copy pass (hg_gather_launch) over entries that are nothing but a body.
+enum class HgValuesStep { Hash, Long, Insert, Mark, Compact, Derive };
+hipError_t hg_values_launch(const HgValuesArgs &a, HgValuesStep step, hipStream_t stream);
+// What a value count works on (the last scan's records and parts, as hg_capi.hip remembers them) and what it leaves
+// (hg_values_result_t).
+struct HgValuesInput {
+  const uint8_t *text;
+  HgGatherList recs;
+  const HgPart *parts;
+  const uint32_t *part_pattern, *part_seg;  // part_seg nullptr without segments
+  uint64_t n_parts;
+  const uint64_t *seg_start;                // nullptr without segments
+  uint32_t flags, hash_bits, table_log2;    // hash_bits 1 .. 64, 2^table_log2 > n_parts (the caller has checked both)
+};
+struct HgValuesOutput {
+  uint64_t n_values, n_parts, n_bytes;
+  const uint8_t *d_bytes;  // device arrays, valid until the next value count on this object
+  const uint64_t *d_off, *d_count, *d_first, *d_line_number;
+  const uint32_t *d_pattern, *d_segment;
+  uint32_t table_log2;
+  float ms_values;  // the stage: everything between the first memset and the copy pass, its two host synchronisations included
+};
+// The stage's buffers and launch sequence.  It owns its scratch (hgmem::Buf: freed with the object, every allocation logged)
+// and touches nothing of the scanner's, of HgGather's, of HgPartLines' or of HgCounts'.
+class HgValues {
+ public:
+  explicit HgValues(int device) : device_(device) {}
+  ~HgValues();
+  int run(const HgValuesInput &in, hipStream_t stream, HgValuesOutput *out, std::string *err);
+
+ private:
+  template <typename T>
+  using DevBuf = hgmem::Buf<T, hgmem::Space::Dev>;
+  int device_;
+  hipEvent_t ev_[2] = {nullptr, nullptr};
+  DevBuf<uint64_t> src_{"values src", 0}, hash_{"values hash", 0}, long_{"values long", 0}, pos_{"values pos", 0}, pair_first_{"values pair first", 0},
+      pair_count_{"values pair count", 0}, first_{"values first", 0}, count_{"values count", 0}, size_{"values size", 0}, off_{"values off", 0}, line_{"values line", 0},
+      span_{"values span", 0};
+  DevBuf<unsigned long long> slot_{"values slot", 0}, slot_count_{"values slot count", 0}, slot_first_{"values slot first", 0}, counters_{"values counters", 0};
+  DevBuf<uint32_t> len_{"values len", 0}, pattern_{"values pattern", 0}, seg_{"values seg", 0};
+  DevBuf<HgGatherEntry> entries_{"values entries", 0};
+  DevBuf<uint8_t> temp_{"values temp", 0}, bytes_{"values bytes", 16};
+  hgmem::Buf<uint64_t, hgmem::Space::Host> totals_{"values totals", 0};  // pinned: the counters, then {bytes}
 };
 
 // The counts stage (hg_counts.hip) over the record list a scan left: one launch on `stream` (nothing for an empty list).

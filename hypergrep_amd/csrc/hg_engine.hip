@@ -1925,6 +1925,151 @@ int HgPartLines::run(const HgPartLinesInput &in, hipStream_t stream, HgPartLines
   return HG_OK;
 }
 
+// ---------------------------------------------------------------- values stage (hg_count_values): buffers and launch sequence
+HgValues::~HgValues() {
+  (void)hipSetDevice(device_);  // (the buffers are freed behind this body)
+  for (hipEvent_t e : ev_)
+    if (e) (void)hipEventDestroy(e);
+}
+
+#define HG_VALUES_TRY(expr, what)                                                   \
+  do {                                                                              \
+    const hipError_t e_ = (expr);                                                   \
+    if (e_ != hipSuccess) {                                                         \
+      *err = std::string("values stage: ") + (what) + ": " + hipGetErrorString(e_); \
+      return HG_ERR_HIP;                                                            \
+    }                                                                               \
+  } while (0)
+
+int HgValues::run(const HgValuesInput &in, hipStream_t stream, HgValuesOutput *out, std::string *err) {
+  *out = HgValuesOutput{};
+  HG_VALUES_TRY(hipSetDevice(device_), "hipSetDevice");
+  for (hipEvent_t &e : ev_)
+    if (!e) HG_VALUES_TRY(hipEventCreate(&e), "event");
+  const uint64_t n = in.n_parts, cap = uint64_t{1} << in.table_log2, np = n + 1;
+  // per part and per slot now; per value once their number is known
+  size_t tb = 0;
+  HG_VALUES_TRY(rocprim::exclusive_scan(nullptr, tb, static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), uint64_t{0}, cap, rocprim::plus<uint64_t>(), stream),
+                "scan size");
+  tb = std::max<size_t>(tb, 16);
+  const size_t grow = np + np / 4;
+  const bool ok = src_.reserve(np, grow) && hash_.reserve(np, grow) && long_.reserve(np, grow) && len_.reserve(np, grow) && pair_first_.reserve(np, grow) &&
+                  pair_count_.reserve(np, grow) && slot_.reserve(cap, cap) && slot_count_.reserve(cap, cap) && slot_first_.reserve(cap, cap) && pos_.reserve(cap, cap) &&
+                  counters_.reserve(HG_VALUES_COUNTERS, HG_VALUES_COUNTERS) && temp_.reserve(tb, tb + tb / 4) && totals_.reserve(HG_VALUES_COUNTERS + 1, HG_VALUES_COUNTERS + 1);
+  if (!ok) {
+    *err = "values stage: out of memory (" + std::to_string(n) + " parts, a table of 2^" + std::to_string(in.table_log2) + " slots)";
+    return HG_ERR_NOMEM;
+  }
+  HgValuesArgs a{};
+  a.text = HgGatherText{in.text};
+  a.recs = in.recs;
+  a.parts = in.parts;
+  a.part_pattern = in.part_pattern;
+  a.part_seg = in.seg_start ? in.part_seg : nullptr;
+  a.n_parts = n;
+  a.seg_start = in.seg_start;
+  a.flags = in.flags;
+  a.hash_bits = in.hash_bits;
+  a.table_log2 = in.table_log2;
+  a.src = src_.get();
+  a.len = len_.get();
+  a.hash = hash_.get();
+  a.long_list = long_.get();
+  a.counters = counters_.get();
+  a.slot = slot_.get();
+  a.count = slot_count_.get();
+  a.first = slot_first_.get();
+  a.pos = pos_.get();
+  a.pair_first = pair_first_.get();
+  a.pair_count = pair_count_.get();
+  uint64_t *totals = totals_.get();
+  HG_VALUES_TRY(hipEventRecord(ev_[0], stream), "event");
+  HG_VALUES_TRY(hipMemsetAsync(counters_.get(), 0, HG_VALUES_COUNTERS * sizeof(unsigned long long), stream), "memset");
+  if (n) {
+    HG_VALUES_TRY(hipMemsetAsync(slot_.get(), 0xFF, cap * sizeof(unsigned long long), stream), "memset");  // HG_VALUES_EMPTY
+    HG_VALUES_TRY(hipMemsetAsync(slot_first_.get(), 0xFF, cap * sizeof(unsigned long long), stream), "memset");
+    HG_VALUES_TRY(hipMemsetAsync(slot_count_.get(), 0, cap * sizeof(unsigned long long), stream), "memset");
+    HG_VALUES_TRY(hg_values_launch(a, HgValuesStep::Hash, stream), "launch (hash)");
+    HG_VALUES_TRY(hg_values_launch(a, HgValuesStep::Long, stream), "launch (long parts)");
+    HG_VALUES_TRY(hg_values_launch(a, HgValuesStep::Insert, stream), "launch (insert)");
+    HG_VALUES_TRY(hg_values_launch(a, HgValuesStep::Mark, stream), "launch (mark)");
+    size_t t = temp_.cap();
+    HG_VALUES_TRY(rocprim::exclusive_scan(temp_.get(), t, pos_.get(), pos_.get(), uint64_t{0}, cap, rocprim::plus<uint64_t>(), stream), "scan (marks)");
+    HG_VALUES_TRY(hg_values_launch(a, HgValuesStep::Compact, stream), "launch (compact)");
+  }
+  HG_VALUES_TRY(hipMemcpyAsync(totals, counters_.get(), HG_VALUES_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "copy counters");
+  HG_VALUES_TRY(hipStreamSynchronize(stream), "stream sync");
+  if (totals[HG_VALUES_OVERFLOW] || totals[HG_VALUES_N_VALUES] > n) {
+    *err = "values stage: a probe went round the whole table of 2^" + std::to_string(in.table_log2) + " slots";
+    return HG_ERR_NOMEM;
+  }
+  a.n_values = totals[HG_VALUES_N_VALUES];
+  {
+    const uint64_t nv = a.n_values + 1, nv_grow = nv + nv / 4;
+    size_t t_sort = 0, t_size = 0;
+    HG_VALUES_TRY(rocprim::radix_sort_pairs(nullptr, t_sort, static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr),
+                                            static_cast<uint64_t *>(nullptr), nv, 0, 64, stream),
+                  "sort size");
+    HG_VALUES_TRY(rocprim::exclusive_scan(nullptr, t_size, static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), uint64_t{0}, nv, rocprim::plus<uint64_t>(), stream),
+                  "scan size");
+    const size_t tv = std::max<size_t>(std::max(t_sort, t_size), 16);
+    if (!first_.reserve(nv, nv_grow) || !count_.reserve(nv, nv_grow) || !size_.reserve(nv, nv_grow) || !off_.reserve(nv, nv_grow) || !line_.reserve(nv, nv_grow) ||
+        !pattern_.reserve(nv, nv_grow) || (in.seg_start && !seg_.reserve(nv, nv_grow)) || !entries_.reserve(nv, nv_grow) || !temp_.reserve(tv, tv + tv / 4)) {
+      *err = "values stage: out of memory for " + std::to_string(a.n_values) + " values";
+      return HG_ERR_NOMEM;
+    }
+  }
+  a.v_first = first_.get();
+  a.size = size_.get();
+  a.entries = entries_.get();
+  a.pattern = pattern_.get();
+  a.segment = in.seg_start ? seg_.get() : nullptr;
+  a.line_number = line_.get();
+  if (a.n_values) {
+    size_t t = temp_.cap();
+    uint32_t bits = 1;
+    while (bits < 64 && (n >> bits)) bits++;  // first < n_parts
+    HG_VALUES_TRY(rocprim::radix_sort_pairs(temp_.get(), t, pair_first_.get(), first_.get(), pair_count_.get(), count_.get(), a.n_values, 0, bits, stream), "sort (first)");
+  }
+  HG_VALUES_TRY(hg_values_launch(a, HgValuesStep::Derive, stream), "launch (derive)");
+  {
+    size_t t = temp_.cap();
+    HG_VALUES_TRY(rocprim::exclusive_scan(temp_.get(), t, size_.get(), off_.get(), uint64_t{0}, a.n_values + 1, rocprim::plus<uint64_t>(), stream), "scan (lengths)");
+  }
+  HG_VALUES_TRY(hipMemcpyAsync(totals + HG_VALUES_COUNTERS, off_.get() + a.n_values, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "copy count");
+  HG_VALUES_TRY(hipStreamSynchronize(stream), "stream sync");
+  HgGatherArgs g{};
+  g.text = a.text;
+  g.entries = entries_.get();
+  g.off = off_.get();
+  g.n_entries = a.n_values;
+  g.n_bytes = totals[HG_VALUES_COUNTERS];
+  const uint64_t padded = (g.n_bytes + 15) & ~static_cast<uint64_t>(15), n_spans = (g.n_bytes + HG_GATHER_TILE - 1) / HG_GATHER_TILE;
+  if (!bytes_.reserve(std::max<uint64_t>(padded, 16), std::max<uint64_t>(padded + padded / 8, 16)) || !span_.reserve(n_spans + 1, n_spans + n_spans / 8 + 1)) {
+    *err = "values stage: out of memory for " + std::to_string(g.n_bytes) + " bytes of values";
+    return HG_ERR_NOMEM;
+  }
+  g.span = span_.get();
+  g.out = bytes_.get();
+  HG_VALUES_TRY(hg_gather_launch(g, HgGatherStep::Span, stream), "launch (spans)");  // (nothing without bytes)
+  HG_VALUES_TRY(hg_gather_launch(g, HgGatherStep::Copy, stream), "launch (copy)");
+  HG_VALUES_TRY(hipEventRecord(ev_[1], stream), "event");
+  HG_VALUES_TRY(hipStreamSynchronize(stream), "stream sync");
+  HG_VALUES_TRY(hipEventElapsedTime(&out->ms_values, ev_[0], ev_[1]), "event time");
+  out->n_values = a.n_values;
+  out->n_parts = n;
+  out->n_bytes = g.n_bytes;
+  out->d_bytes = bytes_.get();
+  out->d_off = off_.get();
+  out->d_count = count_.get();
+  out->d_first = first_.get();
+  out->d_line_number = line_.get();
+  out->d_pattern = pattern_.get();
+  out->d_segment = a.segment;
+  out->table_log2 = in.table_log2;
+  return HG_OK;
+}
+
 // ---------------------------------------------------------------- counts stage (hg_count_records): buffers and launch sequence
 HgCounts::~HgCounts() {
   (void)hipSetDevice(device_);  // (the buffers are freed behind this body)

@@ -593,10 +593,34 @@ struct FileCounts {
   std::vector<uint32_t> ids;
   std::vector<uint64_t> n_lines, n_reports;
 };
+// With `fv` (hg_hyperscan_values) nothing is delivered either: every chunk is scanned with the parts stage, the values stage runs
+// behind it, and only the chunk's distinct values come back (bytes, offsets, counts, expressions), to be merged here by key.  No
+// part record and no line is downloaded.  The rows keep the order in which their keys first occurred in the file.
+struct FileValues {
+  hg_values_params_t params;
+  std::map<std::string, size_t> index;  // key ([expression index, 4 bytes] value bytes) -> row
+  std::vector<std::string> value;
+  std::vector<uint32_t> pattern;
+  std::vector<uint64_t> count;
+  void add(const uint8_t *bytes, uint64_t len, uint32_t pat, uint64_t n) {
+    std::string key;
+    if (params.flags & HG_VALUES_BY_PATTERN) key.assign(reinterpret_cast<const char *>(&pat), 4);
+    key.append(reinterpret_cast<const char *>(bytes), len);
+    const auto it = index.find(key);
+    if (it != index.end()) {
+      count[it->second] += n;
+      return;
+    }
+    index.emplace(std::move(key), value.size());
+    value.emplace_back(reinterpret_cast<const char *>(bytes), len);
+    pattern.push_back(pat);
+    count.push_back(n);
+  }
+};
 static int scan_file(const char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
                      const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, FileEvent on_event,
                      const int buffer_size, int buffer_count, unsigned long long max_match_count, const bool invert, const uint32_t before = 0,
-                     const uint32_t after = 0, uint64_t *pieces_scanned = nullptr, const bool parts = false, FileCounts *fc = nullptr) {
+                     const uint32_t after = 0, uint64_t *pieces_scanned = nullptr, const bool parts = false, FileCounts *fc = nullptr, FileValues *fv = nullptr) {
   if (max_match_count > 0 && max_match_count < static_cast<unsigned long long>(buffer_count)) buffer_count = static_cast<int>(max_match_count);
   if (buffer_count < 1 || buffer_size < 1 || !on_event) return HYPERSCANNER_STATE_MEM;
   Ring ring;
@@ -615,6 +639,10 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
     }
   }
   std::unique_ptr<HgCounts> counts;  // (made with the scanner; its buffers are its own)
+  std::unique_ptr<HgValues> values;  // (likewise)
+  std::vector<uint8_t> v_bytes;      // a chunk's distinct values
+  std::vector<uint64_t> v_off, v_count;
+  std::vector<uint32_t> v_pattern;
   if (fc) {
     fc->ids = db->report_ids;
     fc->n_lines.assign(fc->ids.size(), 0);
@@ -770,6 +798,7 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
         break;
       }
       if (fc) counts = std::make_unique<HgCounts>(ctx->device, *db);
+      if (fv) values = std::make_unique<HgValues>(ctx->device);
       t_setup = now() - t0;
     }
     if (cut) {
@@ -810,7 +839,39 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
           break;
         }
       }
-      const uint64_t n_rows = counts ? 0 : out.n_hits;
+      if (values) {  // the chunk's parts are grouped where they lie: only the distinct values come back
+        const uint32_t log2 = fv->params.table_log2 ? fv->params.table_log2 : hg_values_default_log2(pout.n_parts);
+        HgValuesOutput vo{};
+        if (log2 > HG_VALUES_MAX_TABLE_LOG2 || (uint64_t{1} << log2) <= pout.n_parts) {
+          std::fprintf(stderr, "ERROR: Unable to scan buffer. Exiting. (a chunk has %llu parts: more than a table of 2^%u slots serves)\n",
+                       static_cast<unsigned long long>(pout.n_parts), log2);
+          rc = HYPERSCANNER_SCAN;
+          break;
+        }
+        const HgValuesInput vin{d_text, HgGatherList{out.d_hits, out.d_aux, nullptr, out.n_hits}, pout.d_parts, pout.d_pattern, nullptr, pout.n_parts, nullptr, fv->params.flags,
+                                fv->params.hash_bits ? fv->params.hash_bits : 64u, log2};
+        bool ok = values->run(vin, ctx->stream, &vo, &err) == HG_OK;
+        if (ok) {
+          v_bytes.resize(vo.n_bytes);
+          v_off.resize(vo.n_values + 1);
+          v_count.resize(vo.n_values);
+          v_pattern.resize(vo.n_values);
+          ok = (!vo.n_bytes || hipMemcpyAsync(v_bytes.data(), vo.d_bytes, vo.n_bytes, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess) &&
+               hipMemcpyAsync(v_off.data(), vo.d_off, (vo.n_values + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+               (!vo.n_values || (hipMemcpyAsync(v_count.data(), vo.d_count, vo.n_values * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+                                 hipMemcpyAsync(v_pattern.data(), vo.d_pattern, vo.n_values * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess)) &&
+               hipStreamSynchronize(ctx->stream) == hipSuccess;
+          if (!ok) err = "copying the values";
+        }
+        if (!ok) {
+          std::fprintf(stderr, "ERROR: Unable to scan buffer. Exiting. (%s)\n", err.c_str());
+          rc = HYPERSCANNER_SCAN;
+          healthy = false;
+          break;
+        }
+        for (uint64_t j = 0; j < vo.n_values; j++) fv->add(v_bytes.data() + v_off[j], v_off[j + 1] - v_off[j], v_pattern[j], v_count[j]);
+      }
+      const uint64_t n_rows = counts || values ? 0 : out.n_hits;
       ctx->hits.resize(n_rows);
       ctx->aux.resize(n_rows);
       if (n_rows) {
@@ -833,9 +894,10 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
           break;
         }
       }
-      part_recs.resize(pout.n_parts);
-      part_pattern.resize(pout.n_parts);
-      if (pout.n_parts) {
+      const uint64_t n_part_rows = values ? 0 : pout.n_parts;
+      part_recs.resize(n_part_rows);
+      part_pattern.resize(n_part_rows);
+      if (n_part_rows) {
         if (hipMemcpyAsync(part_recs.data(), pout.d_parts, pout.n_parts * sizeof(HgPart), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
             hipMemcpyAsync(part_pattern.data(), pout.d_pattern, pout.n_parts * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
             hipStreamSynchronize(ctx->stream) != hipSuccess) {
@@ -1287,6 +1349,25 @@ extern "C" int hg_hyperscan_counts(char *file_name, const char *const *patterns,
   for (size_t b = 0; b < fc.ids.size() && b < max_counts; b++) counts[b] = hg_id_count_t{fc.ids[b], 0, fc.n_lines[b], fc.n_reports[b]};
   if (n_lines) *n_lines = pieces;
   return rc;
+}
+
+extern "C" int hg_hyperscan_values(char *file_name, const char *const *patterns, const unsigned int *pattern_flags, const unsigned int *pattern_ids,
+                                   const hs_expr_ext_t *const *ext, const unsigned int elements, const int buffer_size, const hg_values_params_t *params,
+                                   hg_values_event on_values, void *context) {
+  if (!on_values) return HYPERSCANNER_STATE_MEM;
+  FileValues fv;
+  fv.params = params ? *params : hg_values_params_t{0, 0, 0, 0};
+  if ((fv.params.flags & ~HG_VALUES_BY_PATTERN) || fv.params.hash_bits > 64 || fv.params.table_log2 > HG_VALUES_MAX_TABLE_LOG2) return HYPERSCANNER_STATE_MEM;
+  const int rc = scan_file(file_name, patterns, pattern_flags, pattern_ids, ext, elements, [](hyperscanner_result_t *, int) {}, buffer_size, 1, 0, false, 0, 0, nullptr, true, nullptr, &fv);
+  if (rc) return rc;
+  std::vector<uint8_t> bytes;
+  std::vector<uint64_t> off(1, 0);
+  for (const std::string &v : fv.value) {
+    bytes.insert(bytes.end(), v.begin(), v.end());
+    off.push_back(bytes.size());
+  }
+  on_values(context, bytes.data(), off.data(), fv.count.data(), fv.pattern.data(), fv.value.size());
+  return 0;
 }
 
 extern "C" int hg_hyperscan_ext(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,

@@ -99,6 +99,19 @@ class HgPartLinesResult(ctypes.Structure):  # sizeof 80
                 ("d_first_entry", ctypes.c_void_p), ("gather_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+HG_VALUES_BY_PATTERN = 1
+
+
+class HgValuesParams(ctypes.Structure):  # sizeof 16
+    _fields_ = [("flags", ctypes.c_uint32), ("hash_bits", ctypes.c_uint32), ("table_log2", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class HgValuesResult(ctypes.Structure):  # sizeof 88
+    _fields_ = [("n_values", ctypes.c_uint64), ("n_parts", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("d_bytes", ctypes.c_void_p), ("d_off", ctypes.c_void_p),
+                ("d_count", ctypes.c_void_p), ("d_first", ctypes.c_void_p), ("d_pattern", ctypes.c_void_p), ("d_line_number", ctypes.c_void_p),
+                ("d_segment", ctypes.c_void_p), ("table_log2", ctypes.c_uint32), ("values_us", ctypes.c_uint32)]
+
+
 class HgCountsResult(ctypes.Structure):
     _fields_ = [("n_bins", ctypes.c_uint32), ("n_seg", ctypes.c_uint32), ("n_records", ctypes.c_uint64), ("d_ids", ctypes.c_void_p),
                 ("d_n_lines", ctypes.c_void_p), ("d_n_reports", ctypes.c_void_p), ("d_seg_lines", ctypes.c_void_p), ("d_seg_reports", ctypes.c_void_p),
@@ -194,6 +207,11 @@ def lib() -> ctypes.CDLL:
             l.hg_copy_part_lines.argtypes = [ctypes.c_void_p, p8, ctypes.c_uint64, p64, p64, p32, p32, p32, ctypes.c_uint64]
             l.hg_copy_part_lines_first.argtypes = [ctypes.c_void_p, p64]
             l.hg_copy_part_lines_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        if hasattr(l, "hg_count_values"):  # (absent from a build before the values stage)
+            p8, p32, p64 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+            l.hg_count_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(HgValuesParams), ctypes.c_void_p, ctypes.POINTER(HgValuesResult)]
+            l.hg_copy_values.argtypes = [ctypes.c_void_p, p8, ctypes.c_uint64, p64, p64, p64, p32, p64, p32, ctypes.c_uint64]
+            l.hg_copy_values_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hits.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
         l.hg_copy_hits_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hit_starts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
@@ -301,6 +319,14 @@ class PartLinesStats:
 
 
 @dataclass
+class ValueStats:
+    n_values: int  # distinct values (groups)
+    n_parts: int  # parts of the scan
+    n_bytes: int  # bytes of all distinct values
+    values_us: int  # the values stage alone, microseconds
+
+
+@dataclass
 class CountStats:
     n_bins: int  # distinct report ids of the database
     n_records: int  # records this call counted
@@ -327,6 +353,7 @@ class Scanner:
         self._last_lines = None  # HgLinesResult of the last gather, None after a scan
         self._last_counts = None  # HgCountsResult of the last count
         self._last_part_lines = None  # (HgPartLinesResult, whole_line) of the last parts gather, None after a scan
+        self._last_values = None  # HgValuesResult of the last value count, None after a scan
         self._seg_arena = None
 
     def _place_segments(self, starts, ends):
@@ -378,6 +405,7 @@ class Scanner:
         sres = HgSegmentResult()
         self._last_lines = None
         self._last_part_lines = None
+        self._last_values = None
         self._last_seg = None
         self._last_segment_parts = False
         if segments is not None:
@@ -628,6 +656,67 @@ class Scanner:
         rc = lib().hg_copy_part_lines_device(self._h, ctypes.c_void_p(d_dst), n, ctypes.c_void_p(stream))
         if rc != 0:
             raise DeviceError(f"hg_copy_part_lines_device failed ({rc})")
+        return n
+
+    def count_values(self, d_text: int, nbytes: int, by_pattern: bool = False, stream: int = 0, hash_bits: int = 0, table_log2: int = 0) -> ValueStats:
+        """Distinct matched parts and how often each occurs (hg_count_values; grep -o | sort | uniq -c): after scan(parts=True) or
+        scan(segment_parts=True), the parts grouped by their bytes on the GPU (by_pattern: by expression index and bytes).
+        d_text and nbytes must be the last scan's.  Groups come in the order of their first part; files are never part of the
+        key.  hash_bits (1 .. 64, 0: 64) and table_log2 (0: from the number of parts; else 2 ** table_log2 must exceed it) are
+        knobs for tests: fewer hash bits or a nearly full table give the same result, slower.  values(), values_arrays() and
+        copy_values_to() give the result; hits(), parts(), part_lines(), counts() ... are unchanged by it.  ValueError with
+        the reason when nothing was launched: no scan yet, a scan without parts, d_text / nbytes not the last scan's, a knob
+        out of range."""
+        params = HgValuesParams(flags=HG_VALUES_BY_PATTERN if by_pattern else 0, hash_bits=hash_bits, table_log2=table_log2)
+        return self._count_values(d_text, nbytes, params, stream)
+
+    def _count_values(self, d_text: int, nbytes: int, params, stream: int = 0) -> ValueStats:
+        res = HgValuesResult()
+        self._last_values = None
+        rc = lib().hg_count_values(self._h, ctypes.c_void_p(d_text), nbytes, ctypes.byref(params) if params is not None else None, ctypes.c_void_p(stream), ctypes.byref(res))
+        if rc == -1:  # HG_ERR_ARG: nothing was launched
+            raise ValueError(lib().hg_scanner_error(self._h).decode(errors="replace"))
+        if rc != 0:
+            raise DeviceError(f"hg_count_values failed ({rc}): {lib().hg_scanner_error(self._h).decode(errors='replace')}")
+        self._last_values = res
+        return ValueStats(res.n_values, res.n_parts, res.n_bytes, res.values_us)
+
+    def values_arrays(self):
+        """The last value count as a dict: bytes (the blob), and numpy arrays off (uint64, n + 1: value j is
+        bytes[off[j]:off[j + 1]]), count (uint64), first (uint64, the smallest part index, ascending), pattern (uint32),
+        line_number (uint64) and, after a scan with segments, segment (uint32), else None.  ValueError without a value count
+        since the last scan."""
+        import numpy as np
+
+        g = self._last_values
+        if g is None:
+            raise ValueError("no value count since the last scan")
+        n = g.n_values
+        blob = np.zeros(max(g.n_bytes, 1), dtype=np.uint8)
+        out = {"off": np.zeros(n + 1, dtype=np.uint64), "count": np.zeros(n, dtype=np.uint64), "first": np.zeros(n, dtype=np.uint64), "pattern": np.zeros(n, dtype=np.uint32),
+               "line_number": np.zeros(n, dtype=np.uint64), "segment": np.zeros(n, dtype=np.uint32) if g.d_segment else None}
+        p8, p32, p64 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+        rc = lib().hg_copy_values(self._h, blob.ctypes.data_as(p8), g.n_bytes, out["off"].ctypes.data_as(p64), out["count"].ctypes.data_as(p64), out["first"].ctypes.data_as(p64),
+                                  out["pattern"].ctypes.data_as(p32), out["line_number"].ctypes.data_as(p64), out["segment"].ctypes.data_as(p32) if g.d_segment else None, n)
+        if rc != 0:
+            raise DeviceError(f"hg_copy_values failed ({rc})")
+        out["bytes"] = blob[:g.n_bytes].tobytes()
+        return out
+
+    def values(self):
+        """The last value count as a list of (value_bytes, count, pattern, line_number), in the order of the values' first parts."""
+        a = self.values_arrays()
+        off = a["off"].tolist()
+        return [(a["bytes"][off[j]:off[j + 1]], int(c), int(p), int(l)) for j, (c, p, l) in enumerate(zip(a["count"], a["pattern"], a["line_number"]))]
+
+    def copy_values_to(self, d_dst: int, max_bytes: int, stream: int = 0) -> int:
+        """Async device-to-device copy of the last value count's bytes (the first max_bytes of them); returns the number copied."""
+        if self._last_values is None:
+            raise ValueError("no value count since the last scan")
+        n = min(max_bytes, self._last_values.n_bytes)
+        rc = lib().hg_copy_values_device(self._h, ctypes.c_void_p(d_dst), n, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise DeviceError(f"hg_copy_values_device failed ({rc})")
         return n
 
     def count(self, accumulate: bool = False, per_segment: bool = False, stream: int = 0) -> CountStats:

@@ -276,6 +276,30 @@ def pattern_counts(files: list, patterns: list[str], shown: list[str] | None = N
     return 2 if errored else (0 if matched else 1)
 
 
+def value_counts(files: list, patterns: list[str], ignore_case: bool = False, with_file_name: bool = False, no_messages: bool = False) -> int:
+    """--value-counts: for every file, one after another, one line "[file:]count:value" per distinct matched part (what grep -o
+    prints), by count descending, then value ascending: grep -o | sort | uniq -c | sort -rn.  The parts are grouped on the GPU
+    (hypergrep_amd.count_values); only the distinct values leave the device.  Returns grep's exit code."""
+    flags = hypergrep_amd.utils.HS_FLAG_DOTALL | hypergrep_amd.utils.HS_FLAG_MULTILINE | hypergrep_amd.utils.HS_FLAG_SINGLEMATCH
+    flags |= hypergrep_amd.utils.HS_FLAG_CASELESS if ignore_case else 0
+    matched = errored = False
+    for name in files:
+        rows, return_code = hypergrep_amd.count_values(name, patterns, flags=[flags] * len(patterns), ids=list(range(len(patterns))))
+        if return_code:
+            errored = True
+            if not no_messages:
+                problem = "No such file or directory" if not os.path.exists(name) else ("is a directory" if os.path.isdir(name) else f"scan failed ({return_code})")
+                print(f"hyperscanner: {name}: {problem}")
+            continue
+        head = f"{name}:".encode() if with_file_name else b""
+        sys.stdout.flush()
+        for value, count in rows:
+            matched = True
+            sys.stdout.buffer.write(head + str(count).encode() + b":" + value + b"\n")  # (the value as it was counted, byte for byte)
+        sys.stdout.buffer.flush()
+    return 2 if errored else (0 if matched else 1)
+
+
 def print_results(results: list, file_name: str, with_file_name: bool = False, with_line_number: bool = False) -> None:
     """Print (line number, line) results with the requested prefixes; lines keep their own newline."""
     head = f"{file_name}:" if with_file_name else ""
@@ -449,8 +473,17 @@ def parse_args(args: list = None) -> argparse.Namespace:
     own.add_argument("--pattern-counts", dest="pattern_counts", action="store_true", default=argparse.SUPPRESS,
                      help="For every file print one line [file:]count:pattern per pattern that matched, count being the matching\n"
                           "lines, counted on the GPU.  Not combined with -v, -o, -c, -l, -L, -q, -A / -B / -C or -m.")
+    # (no attribute unless given, like -v)
+    own.add_argument("--value-counts", dest="value_counts", action="store_true", default=argparse.SUPPRESS,
+                     help="For every file print one line [file:]count:value per distinct matched part (grep -o | sort | uniq -c |\n"
+                          "sort -rn), grouped on the GPU; a value is printed byte for byte as it was counted.  Not combined with --pattern-counts, -v, -o, -c, -l, -L, -q, -A / -B / -C or -m.")
     parser.set_defaults(parser=parser)
     parsed = parser.parse_intermixed_args(args=args)
+    if getattr(parsed, "value_counts", False):
+        others = (getattr(parsed, "pattern_counts", False) or getattr(parsed, "invert_match", False) or parsed.only_matching or parsed.count or parsed.files_with_matches or
+                  parsed.files_without_match or parsed.quiet or parsed.max_count or any(hasattr(parsed, name) for name in ("after_context", "before_context", "context")))
+        if others:
+            parser.error("--value-counts is not combined with --pattern-counts, -v, -o, -c, -l, -L, -q, -A, -B, -C or -m")  # (exit code 2)
     if getattr(parsed, "pattern_counts", False):
         others = (getattr(parsed, "invert_match", False) or parsed.only_matching or parsed.count or parsed.files_with_matches or parsed.files_without_match or parsed.quiet or
                   parsed.max_count or any(hasattr(parsed, name) for name in ("after_context", "before_context", "context")))
@@ -490,6 +523,8 @@ def main() -> None:
         with_file_name = True
     else:
         with_file_name = recursive or len(files) > 1
+    if getattr(args, "value_counts", False):
+        raise SystemExit(value_counts(files, patterns, args.ignore_case, with_file_name, args.no_messages))
     if getattr(args, "pattern_counts", False):
         raise SystemExit(pattern_counts(files, patterns, patterns_as_written, args.ignore_case, with_file_name, args.no_messages))
     raise SystemExit(

@@ -356,6 +356,46 @@ def count(file: str, patterns: list[str], flags: list[int] = (), ids: list[int] 
     return {rows[b].id: (rows[b].n_lines, rows[b].n_reports) for b in range(min(n_counts.value, max_counts))}, outcome[0]
 
 
+class ValuesParams(ctypes.Structure):
+    """hg_values_params_t (include/hypergrep_amd.h)."""
+
+    _fields_ = [("flags", ctypes.c_uint32), ("hash_bits", ctypes.c_uint32), ("table_log2", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+_VALUES_EVENT = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                 ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64)
+
+
+def count_values(file: str, patterns: list[str], flags: list[int] = (), ids: list[int] = (), by_pattern: bool = False, buffer_size: int = 262140) -> tuple[list, int]:
+    """The distinct matched parts of a plain / gzip / zstd text file and how often each occurs (hg_hyperscan_values; grep -o |
+    sort | uniq -c | sort -rn): (rows, return code).  The rows are (value bytes, count), with by_pattern (value bytes, pattern
+    index, count) and the pattern index part of the key; sorted by count descending, then value ascending.  The parts are
+    grouped on the GPU behind every chunk's scan; only each chunk's distinct values come back, and the chunks are merged here."""
+    c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags, ids=ids)
+    params = ValuesParams(flags=1 if by_pattern else 0)
+    rows: list = []
+
+    def on_values(_context, data, off, counts, pattern, n_values) -> None:
+        blob = ctypes.string_at(data, off[n_values]) if n_values else b""
+        for j in range(n_values):
+            value = blob[off[j]:off[j + 1]]
+            rows.append((value, pattern[j], counts[j]) if by_pattern else (value, counts[j]))
+
+    callback = _VALUES_EVENT(on_values)
+    engine = _get_hyperscanner_lib()
+    engine.hg_hyperscan_values.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
+                                           ctypes.POINTER(ctypes.POINTER(ExprExt)), ctypes.c_uint, ctypes.c_int, ctypes.POINTER(ValuesParams), _VALUES_EVENT, ctypes.c_void_p]
+    outcome = [0]
+
+    def native_call() -> None:
+        outcome[0] = engine.hg_hyperscan_values(os.fspath(file).encode(), c_patterns, c_flags, c_ids, None, len(c_patterns), buffer_size, ctypes.byref(params), callback, None)
+
+    if not _run_native(native_call):
+        return [], _RC_INTERRUPTED
+    rows.sort(key=(lambda r: (-r[2], r[0], r[1])) if by_pattern else (lambda r: (-r[1], r[0])))
+    return rows, outcome[0]
+
+
 def count_files(files: Sequence[str], patterns: list[str], flags: list[int] = (), ids: list[int] = (), ext=None, buffer_size: int = 262140) -> list[tuple[dict, int]]:
     """count() for many files in ONE native call (hg_hyperscan_files_counts): small files are packed into one buffer and share
     one GPU scan, with the per-file counts taken behind it.  One ({id: (matching lines, reports)}, return code) per file, what

@@ -894,6 +894,81 @@ int hg_copy_part_lines_first(hg_scanner_t *scanner, uint64_t *first_entry);
 /* The bytes (the first max_bytes of them) into a DEVICE buffer, asynchronously on `stream`. */
 int hg_copy_part_lines_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes, void *stream);
 
+/* Distinct matched parts and how often each occurs (grep -o | sort | uniq -c): the parts of the last scan with parts on this
+ * scanner, grouped by their bytes on the GPU, so that only the distinct values go to the host.  The stage runs after
+ * hg_scan_device_parts or hg_scan_device_segments_parts, on that scan's records; it scans nothing and changes nothing about
+ * scanning or about any other stage.
+ * Value.  The value of part q is text[S + from, S + to), S as for hg_gather_parts: hg_hit_aux_t.start of the record of the
+ * part's piece, plus seg_start[segment] after a scan with segments (the segments' d_seg_start array must still be valid).  A
+ * part whose piece has no record is not counted (the parts stage never leaves one).
+ * Key.  The value's bytes; with HG_VALUES_BY_PATTERN the pair (expression index d_part_pattern[q], bytes).  The segment is
+ * never part of the key: after a scan of many files equal values in different files are one group.
+ * Per group: count, the number of parts with the key; first, the smallest part index with it; pattern, line_number and
+ * segment those of part `first` (without HG_VALUES_BY_PATTERN the pattern is that of the first part only).  Groups are ordered
+ * by ascending first; d_bytes holds the values joined in that order, value j being d_bytes[d_off[j], d_off[j + 1]).  Every
+ * output is a function of the input alone: two runs give identical arrays.  Zero parts is a success with n_values = 0 and
+ * off[0] = 0.
+ * params (NULL: all defaults).  hash_bits: 0 means 64; 1 .. 64 cut the hash to that many low bits before any use, which makes
+ * distinct keys collide (a knob for tests and experiments: the result is the same, only slower).  table_log2: 0 means the
+ * smallest power of two that is at least 2 * n_parts and at least 2^10; an explicit value must satisfy 2^table_log2 > n_parts
+ * and be at most 40 (a nearly full table: long probes, same result).
+ * HG_ERR_ARG, with nothing launched and the reason in hg_scanner_error: no successful scan on this scanner yet (or the last
+ * one failed); d_text or nbytes differ from the last scan's; the last scan was not one with parts; unknown flag bits;
+ * hash_bits above 64; table_log2 too small or above 40; scanner == NULL or result == NULL.  HG_ERR_NOMEM when the buffers do
+ * not fit (a part costs 44 bytes, a slot 32, a value 72 plus its bytes).
+ * Lifetime.  The result stays valid until the next scan or hg_count_values on this scanner.  The stage has buffers of its
+ * own: the scan's results, a previous hg_gather_lines, hg_gather_parts and hg_count_records stay as they are.  values_us: the
+ * stage in microseconds (HIP events; its two host synchronisations included).
+ * The stage runs on the GPU (hypergrep_amd/csrc/hg_values.hip): a hash pass (a lane per part, a wavefront per part longer
+ * than 256 bytes), an insert pass into an open-addressing table of 64-bit slots claimed by compare-and-swap, with integer
+ * atomics for count and first, a compaction and a sort by first, and the gathers' copy pass divided by output bytes.  Text is
+ * read inside the parts only (whole aligned dwords: never past nbytes rounded up to 4).
+ * Not offered: values per file, case folding, accumulation across scans on the device, and anything for the databases the
+ * parts stage refuses. */
+#define HG_VALUES_BY_PATTERN 1u /* the expression index is part of the key */
+typedef struct hg_values_params { /* sizeof 16 */
+    uint32_t flags;               /* HG_VALUES_* */
+    uint32_t hash_bits;           /* 0: 64 */
+    uint32_t table_log2;          /* 0: from n_parts */
+    uint32_t reserved;
+} hg_values_params_t;
+typedef struct hg_values_result { /* sizeof 88 */
+    uint64_t n_values, n_parts, n_bytes;
+    const uint8_t *d_bytes;        /* DEVICE, valid until the next scan or hg_count_values on this scanner */
+    const uint64_t *d_off;         /* n_values + 1 */
+    const uint64_t *d_count;       /* parts per value */
+    const uint64_t *d_first;       /* the smallest part index per value, ascending */
+    const uint32_t *d_pattern;     /* expression index of part `first` */
+    const uint64_t *d_line_number; /* line_number of part `first` */
+    const uint32_t *d_segment;     /* segment of part `first`; NULL unless the last scan had segments */
+    uint32_t table_log2, values_us; /* the table the stage used */
+} hg_values_result_t;
+int hg_count_values(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, const hg_values_params_t *params, void *stream,
+                    hg_values_result_t *result);
+/* Copy the last value count's first max_bytes bytes and the per-value arrays of its first max_values values to host memory
+ * (any pointer may be NULL; off receives min(n_values, max_values) + 1 values).  HG_ERR_ARG without a value count since the
+ * last scan (a refused or failed hg_count_values leaves none: the count before it is gone), and for `segment` after a scan
+ * without segments. */
+int hg_copy_values(hg_scanner_t *scanner, uint8_t *bytes, uint64_t max_bytes, uint64_t *off, uint64_t *count, uint64_t *first,
+                   uint32_t *pattern, uint64_t *line_number, uint32_t *segment, uint64_t max_values);
+/* The bytes (the first max_bytes of them) into a DEVICE buffer, asynchronously on `stream`. */
+int hg_copy_values_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes, void *stream);
+/* The same for a file: hg_hyperscan_counts' arguments, reader, chunking (256 MiB chunks cut at piece boundaries),
+ * decompression and database cache, with the parts stage and the values stage behind every chunk's scan.  Only each chunk's
+ * distinct values are downloaded (bytes, offsets, counts, expression indices) and merged on the host by key; no part record
+ * and no line leaves the GPU.  There is no max_match_count: the counts describe the whole file.  params as for
+ * hg_count_values (NULL: defaults; an explicit table_log2 must serve every chunk's parts).  On success on_values is called
+ * once, with the merged groups in the order in which their keys first occur in the file: value j is bytes[off[j], off[j + 1]),
+ * pattern[j] the expression index of its first part (part of the key with HG_VALUES_BY_PATTERN).  The pointers are valid
+ * during the call only.  Return codes are hg_hyperscan_ext's: a set that does not compile or that the parts stage refuses
+ * (HYPERSCANNER_DB) and a file that cannot be opened are answered before any device resource is taken; bad params or
+ * on_values == NULL give the code of a bad buffer_count. */
+typedef void (*hg_values_event)(void *context, const uint8_t *bytes, const uint64_t *off, const uint64_t *count, const uint32_t *pattern,
+                                uint64_t n_values);
+int hg_hyperscan_values(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                        const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements,
+                        const int buffer_size, const hg_values_params_t *params, hg_values_event on_values, void *context);
+
 /* Counts per report id (hg_count_records): which expressions fired, and on how many lines, without moving the record list.
  * Bins.  A bin is a distinct report id of the database, in ascending id order (hg_db_report_ids; n_bins <= n_patterns).
  * Expressions that share an id share a bin; the id of a combination is a bin; the id of a QUIET expression is a bin that

@@ -19,6 +19,7 @@ from hypergrep_amd.utils import (  # the reference package re-exports exactly th
     count,
     count_files,
     count_values,
+    count_values_files,
     grep,
     grep_files,
     prepare_patterns,
@@ -38,5 +39,7 @@ __all__ = [
     "count", "count_files",
     # distinct matched parts and their counts, grouped on the GPU
     "count_values",
+    # ... for many files in one native call, ranked by count and cut to the most frequent of every file on the GPU
+    "count_values_files",
 ]
 __version__ = "0.1.0"

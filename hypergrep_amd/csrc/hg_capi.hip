@@ -47,6 +47,9 @@ struct hg_scanner {
   // the values stage's own buffers (made by the first hg_count_values) and its last result (zeroes after a scan)
   HgValues *values = nullptr;
   hg_values_result_t last_values = {};
+  // the rank stage's own buffers (made by the first hg_rank_values) and its last result (zeroes after a scan)
+  HgRank *rank = nullptr;
+  hg_rank_result_t last_rank = {};
 };
 
 static_assert(HG_ID_CONTEXT == HG_CTX_ID_CONTEXT && HG_ID_CONTEXT_TAIL == HG_CTX_ID_TAIL, "the context records carry the ids the header names");
@@ -64,6 +67,8 @@ static_assert(HG_PARTS_NUMBER == HG_PARTLINES_NUMBER && HG_PARTS_BYTE_OFFSET == 
                   HG_PARTS_MARK_MAX == HG_PARTLINES_MARK_MAX && sizeof(hg_part_lines_params_t) == 56 && sizeof(hg_part_lines_result_t) == 80,
               "the parts gather's flags, kinds and limit are the header's");
 static_assert(HG_VALUES_BY_PATTERN == HG_VALUES_F_BY_PATTERN && sizeof(hg_values_params_t) == 16 && sizeof(hg_values_result_t) == 88, "the values stage's flag is the header's");
+static_assert(HG_RANK_BY_PATTERN == HG_RANK_F_BY_PATTERN && HG_RANK_PER_SEGMENT == HG_RANK_F_PER_SEGMENT && sizeof(hg_rank_params_t) == 24 && sizeof(hg_rank_result_t) == 128,
+              "the rank stage's flags are the header's");
 
 static void put_err(char *err, size_t errlen, const std::string &msg) {
   if (err && errlen) std::snprintf(err, errlen, "%s", msg.c_str());
@@ -140,6 +145,7 @@ void hg_scanner_destroy(hg_scanner_t *scanner) {
   delete scanner->counts;
   delete scanner->partlines;
   delete scanner->values;
+  delete scanner->rank;
   delete scanner->sc;
   delete scanner;
 }
@@ -157,6 +163,7 @@ static int scan_device(hg_scanner_t *scanner, const void *d_text, uint64_t nbyte
   scanner->last_lines = hg_lines_result_t{};
   scanner->last_part_lines = hg_part_lines_result_t{};
   scanner->last_values = hg_values_result_t{};
+  scanner->last_rank = hg_rank_result_t{};
   scanner->last_with_parts = false;
   scanner->last_counts.n_seg = 0;  // (the totals stay: HG_COUNTS_ACCUMULATE adds the next scan's)
   scanner->last_counts.d_seg_lines = scanner->last_counts.d_seg_reports = nullptr;
@@ -491,6 +498,92 @@ int hg_copy_values_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes
   if (!scanner || !d_dst) return HG_ERR_ARG;
   const hg_values_result_t &g = scanner->last_values;
   if (!g.d_off) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_values_device: no value count since the last scan");
+  const uint64_t nb = std::min(g.n_bytes, max_bytes);
+  if (!nb) return HG_OK;
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  return hipMemcpyAsync(d_dst, g.d_bytes, nb, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)) == hipSuccess ? HG_OK : HG_ERR_HIP;
+}
+
+int hg_rank_values(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, const hg_rank_params_t *params, void *stream, hg_rank_result_t *result) {
+  if (!scanner) return HG_ERR_ARG;
+  if (result) *result = hg_rank_result_t{};
+  scanner->last_rank = hg_rank_result_t{};  // (a refused call leaves no earlier ranking behind for hg_copy_ranked_values)
+  const hg_rank_params_t p = params ? *params : hg_rank_params_t{0, 0, 0, 0, 0};
+  const bool seg = scanner->last_seg.d_first_record != nullptr;
+  const uint64_t n_parts = scanner->last_with_parts ? scanner->last_parts.n_parts : 0;
+  const char *why = !result                                                            ? "hg_rank_values: result is NULL"
+                    : !scanner->scanned                                                ? "hg_rank_values: no successful scan to rank the values of"
+                    : (d_text != scanner->last_text || nbytes != scanner->last_nbytes) ? "hg_rank_values: d_text and nbytes are not those of the last scan"
+                    : !scanner->last_with_parts                                        ? "hg_rank_values: the last scan was not one with parts (hg_scan_device_parts, hg_scan_device_segments_parts)"
+                    : (p.flags & ~(HG_RANK_BY_PATTERN | HG_RANK_PER_SEGMENT))          ? "hg_rank_values: unknown flag bits"
+                    : ((p.flags & HG_RANK_PER_SEGMENT) && !seg)                        ? "hg_rank_values: HG_RANK_PER_SEGMENT after a scan without segments"
+                    : p.hash_bits > 64                                                 ? "hg_rank_values: hash_bits above 64"
+                    : p.table_log2 > HG_VALUES_MAX_TABLE_LOG2                          ? "hg_rank_values: table_log2 above 40"
+                    : (p.table_log2 && (uint64_t{1} << p.table_log2) <= n_parts)       ? "hg_rank_values: 2^table_log2 must exceed the number of parts"
+                    : (!p.table_log2 && hg_values_default_log2(n_parts) > HG_VALUES_MAX_TABLE_LOG2) ? "hg_rank_values: more parts than a table of 2^40 slots serves"
+                                                                                       : nullptr;
+  if (why) return scanner->sc->set_error(HG_ERR_ARG, why);
+  if (!scanner->rank) scanner->rank = new HgRank(scanner->sc->device());
+  HgRankInput in{};
+  in.values.text = static_cast<const uint8_t *>(d_text);
+  in.values.recs = HgGatherList{reinterpret_cast<const HgHit *>(scanner->last.d_hits), reinterpret_cast<const HgHitAux *>(scanner->last.d_aux),
+                                seg ? scanner->last_seg.d_record_segment : nullptr, scanner->last.n_hits};
+  in.values.parts = reinterpret_cast<const HgPart *>(scanner->last_parts.d_parts);
+  in.values.part_pattern = scanner->last_parts.d_part_pattern;
+  in.values.n_parts = n_parts;
+  if (seg) {
+    in.values.part_seg = scanner->last_segparts.d_part_segment;
+    in.values.seg_start = scanner->last_seg_start;
+  }
+  in.values.flags = p.flags;
+  in.values.hash_bits = p.hash_bits ? p.hash_bits : 64;
+  in.values.table_log2 = p.table_log2 ? p.table_log2 : hg_values_default_log2(n_parts);
+  in.n_seg = seg ? scanner->last_n_seg : 0;
+  in.top = p.top;
+  HgRankOutput o{};
+  std::string err;
+  const int rc = scanner->rank->run(in, static_cast<hipStream_t>(stream), &o, &err);
+  if (rc != HG_OK) return scanner->sc->set_error(rc, err);
+  scanner->last_rank = hg_rank_result_t{o.n_values, o.n_distinct, o.n_parts, o.n_bytes, o.d_bytes, o.d_off, o.d_count, o.d_first, o.d_pattern, o.d_line_number, o.d_segment,
+                                        o.d_first_value, o.d_seg_distinct, o.d_seg_parts, o.n_seg, o.table_log2, static_cast<uint32_t>(o.ms_rank * 1000.0f + 0.5f), 0};
+  *result = scanner->last_rank;
+  return HG_OK;
+}
+
+int hg_copy_ranked_values(hg_scanner_t *scanner, uint8_t *bytes, uint64_t max_bytes, uint64_t *off, uint64_t *count, uint64_t *first, uint32_t *pattern, uint64_t *line_number,
+                          uint32_t *segment, uint64_t max_values) {
+  if (!scanner) return HG_ERR_ARG;
+  const hg_rank_result_t &g = scanner->last_rank;
+  if (!g.d_off) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_ranked_values: no ranking since the last scan");
+  if (segment && !g.d_segment) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_ranked_values: the last scan had no segments");
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  const uint64_t nb = std::min(g.n_bytes, max_bytes), nv = std::min(g.n_values, max_values);
+  if (bytes && nb && hipMemcpy(bytes, g.d_bytes, nb, hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (off && hipMemcpy(off, g.d_off, (nv + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (count && nv && hipMemcpy(count, g.d_count, nv * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (first && nv && hipMemcpy(first, g.d_first, nv * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (pattern && nv && hipMemcpy(pattern, g.d_pattern, nv * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (line_number && nv && hipMemcpy(line_number, g.d_line_number, nv * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (segment && nv && hipMemcpy(segment, g.d_segment, nv * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
+}
+
+int hg_copy_ranked_segments(hg_scanner_t *scanner, uint64_t *first_value, uint64_t *seg_distinct, uint64_t *seg_parts) {
+  if (!scanner) return HG_ERR_ARG;
+  const hg_rank_result_t &g = scanner->last_rank;
+  if (!g.d_first_value) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_ranked_segments: no ranking with HG_RANK_PER_SEGMENT since the last scan");
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  const uint64_t ns = g.n_seg;
+  if (first_value && hipMemcpy(first_value, g.d_first_value, (ns + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (seg_distinct && ns && hipMemcpy(seg_distinct, g.d_seg_distinct, ns * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (seg_parts && ns && hipMemcpy(seg_parts, g.d_seg_parts, ns * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
+}
+
+int hg_copy_ranked_values_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes, void *stream) {
+  if (!scanner || !d_dst) return HG_ERR_ARG;
+  const hg_rank_result_t &g = scanner->last_rank;
+  if (!g.d_off) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_ranked_values_device: no ranking since the last scan");
   const uint64_t nb = std::min(g.n_bytes, max_bytes);
   if (!nb) return HG_OK;
   if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;

@@ -17,6 +17,7 @@
 #include "hg_segparts.h"
 #include "hg_gather.h"
 #include "hg_partlines.h"
+#include "hg_rank.h"
 #include "hg_values.h"
 #include "hg_counts.h"
 #include "hg_mem.h"
@@ -372,6 +373,13 @@ struct HgValuesInput {
   const uint64_t *seg_start;                // nullptr without segments
   uint32_t flags, hash_bits, table_log2;    // hash_bits 1 .. 64, 2^table_log2 > n_parts (the caller has checked both)
 };
+// What HgValues::group leaves: the groups as (first, count) pairs sorted by first, and the kernels' arguments they were made with
+// (the hash pass's src and len per part among them).
+struct HgValuesGroups {
+  HgValuesArgs args;
+  uint64_t n_values;
+  const uint64_t *d_first, *d_count;
+};
 struct HgValuesOutput {
   uint64_t n_values, n_parts, n_bytes;
   const uint8_t *d_bytes;  // device arrays, valid until the next value count on this object
@@ -387,12 +395,16 @@ class HgValues {
   explicit HgValues(int device) : device_(device) {}
   ~HgValues();
   int run(const HgValuesInput &in, hipStream_t stream, HgValuesOutput *out, std::string *err);
+  // The first half of run, for the rank stage: everything through the sort by first (one host synchronisation); in.flags may
+  // carry HG_VALUES_F_BY_SEGMENT.  The arrays are valid until the next group or run on this object.
+  int group(const HgValuesInput &in, hipStream_t stream, HgValuesGroups *groups, std::string *err);
 
  private:
   template <typename T>
   using DevBuf = hgmem::Buf<T, hgmem::Space::Dev>;
   int device_;
   hipEvent_t ev_[2] = {nullptr, nullptr};
+  DevBuf<uint64_t> key_{"values key", 0};  // (HG_VALUES_F_BY_SEGMENT only)
   DevBuf<uint64_t> src_{"values src", 0}, hash_{"values hash", 0}, long_{"values long", 0}, pos_{"values pos", 0}, pair_first_{"values pair first", 0},
       pair_count_{"values pair count", 0}, first_{"values first", 0}, count_{"values count", 0}, size_{"values size", 0}, off_{"values off", 0}, line_{"values line", 0},
       span_{"values span", 0};
@@ -401,6 +413,51 @@ class HgValues {
   DevBuf<HgGatherEntry> entries_{"values entries", 0};
   DevBuf<uint8_t> temp_{"values temp", 0}, bytes_{"values bytes", 16};
   hgmem::Buf<uint64_t, hgmem::Space::Host> totals_{"values totals", 0};  // pinned: the counters, then {bytes}
+};
+
+// The rank stage (hg_rank.hip) behind the values stage's groups, one step per launch on `stream`: the groups' segments as sort keys,
+// their counts in the final order, the segments' bounds and cuts, and the kept rows.
+enum class HgRankStep { Keys, Counts, Bounds, Place };
+hipError_t hg_rank_launch(const HgRankArgs &a, HgRankStep step, hipStream_t stream);
+// HgValuesStep::Hash, Long and Insert with the segment in the key (a.key != nullptr): hg_rank.hip's instantiations.
+hipError_t hg_rank_group_launch(const HgValuesArgs &a, HgValuesStep step, hipStream_t stream);
+// What a ranking works on (HgValuesInput with HG_RANK_F_* as flags, the scan's segments and the cut) and what it leaves
+// (hg_rank_result_t).
+struct HgRankInput {
+  HgValuesInput values;
+  uint32_t n_seg;  // the scan's segments (0 without)
+  uint64_t top;
+};
+struct HgRankOutput {
+  uint64_t n_values, n_distinct, n_parts, n_bytes;
+  const uint8_t *d_bytes;  // device arrays, valid until the next ranking on this object
+  const uint64_t *d_off, *d_count, *d_first, *d_line_number;
+  const uint32_t *d_pattern, *d_segment;
+  const uint64_t *d_first_value, *d_seg_distinct, *d_seg_parts;  // nullptr without HG_RANK_F_PER_SEGMENT
+  uint32_t n_seg, table_log2;
+  float ms_rank;  // the stage: from the first memset to the copy pass, its host synchronisations included
+};
+// The stage's buffers and launch sequence.  It owns its scratch and a values stage of its own (hgmem::Buf: freed with the
+// object, every allocation logged) and touches nothing of the scanner's or of any other stage, hg_count_values' HgValues included.
+class HgRank {
+ public:
+  explicit HgRank(int device) : device_(device), groups_(device) {}
+  ~HgRank();
+  int run(const HgRankInput &in, hipStream_t stream, HgRankOutput *out, std::string *err);
+
+ private:
+  template <typename T>
+  using DevBuf = hgmem::Buf<T, hgmem::Space::Dev>;
+  int device_;
+  HgValues groups_;
+  hipEvent_t ev_[2] = {nullptr, nullptr};
+  DevBuf<uint64_t> g_first_{"rank group first", 0}, g_count_{"rank group count", 0}, key_idx_{"rank key idx", 0}, s_idx_{"rank sorted idx", 0}, s_count_{"rank sorted count", 0},
+      cum_{"rank cum", 0}, first_group_{"rank first group", 0}, seg_distinct_{"rank seg distinct", 0}, seg_parts_{"rank seg parts", 0}, kept_{"rank kept", 0},
+      first_value_{"rank first value", 0}, first_{"rank first", 0}, count_{"rank count", 0}, size_{"rank size", 0}, off_{"rank off", 0}, line_{"rank line", 0}, span_{"rank span", 0};
+  DevBuf<uint32_t> key_seg_{"rank key seg", 0}, s_seg_{"rank sorted seg", 0}, pattern_{"rank pattern", 0}, seg_{"rank seg", 0};
+  DevBuf<HgGatherEntry> entries_{"rank entries", 0};
+  DevBuf<uint8_t> temp_{"rank temp", 0}, bytes_{"rank bytes", 16};
+  hgmem::Buf<uint64_t, hgmem::Space::Host> totals_{"rank totals", 0};  // pinned: {rows, bytes}
 };
 
 // The counts stage (hg_counts.hip) over the record list a scan left: one launch on `stream` (nothing for an empty list).

@@ -1941,8 +1941,8 @@ HgValues::~HgValues() {
     }                                                                               \
   } while (0)
 
-int HgValues::run(const HgValuesInput &in, hipStream_t stream, HgValuesOutput *out, std::string *err) {
-  *out = HgValuesOutput{};
+int HgValues::group(const HgValuesInput &in, hipStream_t stream, HgValuesGroups *groups, std::string *err) {
+  *groups = HgValuesGroups{};
   HG_VALUES_TRY(hipSetDevice(device_), "hipSetDevice");
   for (hipEvent_t &e : ev_)
     if (!e) HG_VALUES_TRY(hipEventCreate(&e), "event");
@@ -1956,7 +1956,8 @@ int HgValues::run(const HgValuesInput &in, hipStream_t stream, HgValuesOutput *o
   const bool ok = src_.reserve(np, grow) && hash_.reserve(np, grow) && long_.reserve(np, grow) && len_.reserve(np, grow) && pair_first_.reserve(np, grow) &&
                   pair_count_.reserve(np, grow) && slot_.reserve(cap, cap) && slot_count_.reserve(cap, cap) && slot_first_.reserve(cap, cap) && pos_.reserve(cap, cap) &&
                   counters_.reserve(HG_VALUES_COUNTERS, HG_VALUES_COUNTERS) && temp_.reserve(tb, tb + tb / 4) && totals_.reserve(HG_VALUES_COUNTERS + 1, HG_VALUES_COUNTERS + 1);
-  if (!ok) {
+  const bool by_seg = (in.flags & HG_VALUES_F_BY_SEGMENT) != 0;  // (the rank stage's: the segment in the key)
+  if (!ok || (by_seg && !key_.reserve(np, grow))) {
     *err = "values stage: out of memory (" + std::to_string(n) + " parts, a table of 2^" + std::to_string(in.table_log2) + " slots)";
     return HG_ERR_NOMEM;
   }
@@ -1982,6 +1983,7 @@ int HgValues::run(const HgValuesInput &in, hipStream_t stream, HgValuesOutput *o
   a.pos = pos_.get();
   a.pair_first = pair_first_.get();
   a.pair_count = pair_count_.get();
+  a.key = by_seg ? key_.get() : nullptr;
   uint64_t *totals = totals_.get();
   HG_VALUES_TRY(hipEventRecord(ev_[0], stream), "event");
   HG_VALUES_TRY(hipMemsetAsync(counters_.get(), 0, HG_VALUES_COUNTERS * sizeof(unsigned long long), stream), "memset");
@@ -1989,9 +1991,10 @@ int HgValues::run(const HgValuesInput &in, hipStream_t stream, HgValuesOutput *o
     HG_VALUES_TRY(hipMemsetAsync(slot_.get(), 0xFF, cap * sizeof(unsigned long long), stream), "memset");  // HG_VALUES_EMPTY
     HG_VALUES_TRY(hipMemsetAsync(slot_first_.get(), 0xFF, cap * sizeof(unsigned long long), stream), "memset");
     HG_VALUES_TRY(hipMemsetAsync(slot_count_.get(), 0, cap * sizeof(unsigned long long), stream), "memset");
-    HG_VALUES_TRY(hg_values_launch(a, HgValuesStep::Hash, stream), "launch (hash)");
-    HG_VALUES_TRY(hg_values_launch(a, HgValuesStep::Long, stream), "launch (long parts)");
-    HG_VALUES_TRY(hg_values_launch(a, HgValuesStep::Insert, stream), "launch (insert)");
+    const auto launch = by_seg ? hg_rank_group_launch : hg_values_launch;
+    HG_VALUES_TRY(launch(a, HgValuesStep::Hash, stream), "launch (hash)");
+    HG_VALUES_TRY(launch(a, HgValuesStep::Long, stream), "launch (long parts)");
+    HG_VALUES_TRY(launch(a, HgValuesStep::Insert, stream), "launch (insert)");
     HG_VALUES_TRY(hg_values_launch(a, HgValuesStep::Mark, stream), "launch (mark)");
     size_t t = temp_.cap();
     HG_VALUES_TRY(rocprim::exclusive_scan(temp_.get(), t, pos_.get(), pos_.get(), uint64_t{0}, cap, rocprim::plus<uint64_t>(), stream), "scan (marks)");
@@ -2013,24 +2016,46 @@ int HgValues::run(const HgValuesInput &in, hipStream_t stream, HgValuesOutput *o
     HG_VALUES_TRY(rocprim::exclusive_scan(nullptr, t_size, static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), uint64_t{0}, nv, rocprim::plus<uint64_t>(), stream),
                   "scan size");
     const size_t tv = std::max<size_t>(std::max(t_sort, t_size), 16);
-    if (!first_.reserve(nv, nv_grow) || !count_.reserve(nv, nv_grow) || !size_.reserve(nv, nv_grow) || !off_.reserve(nv, nv_grow) || !line_.reserve(nv, nv_grow) ||
-        !pattern_.reserve(nv, nv_grow) || (in.seg_start && !seg_.reserve(nv, nv_grow)) || !entries_.reserve(nv, nv_grow) || !temp_.reserve(tv, tv + tv / 4)) {
+    if (!first_.reserve(nv, nv_grow) || !count_.reserve(nv, nv_grow) || !temp_.reserve(tv, tv + tv / 4)) {
       *err = "values stage: out of memory for " + std::to_string(a.n_values) + " values";
       return HG_ERR_NOMEM;
     }
   }
   a.v_first = first_.get();
-  a.size = size_.get();
-  a.entries = entries_.get();
-  a.pattern = pattern_.get();
-  a.segment = in.seg_start ? seg_.get() : nullptr;
-  a.line_number = line_.get();
   if (a.n_values) {
     size_t t = temp_.cap();
     uint32_t bits = 1;
     while (bits < 64 && (n >> bits)) bits++;  // first < n_parts
     HG_VALUES_TRY(rocprim::radix_sort_pairs(temp_.get(), t, pair_first_.get(), first_.get(), pair_count_.get(), count_.get(), a.n_values, 0, bits, stream), "sort (first)");
   }
+  groups->args = a;
+  groups->n_values = a.n_values;
+  groups->d_first = first_.get();
+  groups->d_count = count_.get();
+  return HG_OK;
+}
+
+int HgValues::run(const HgValuesInput &in, hipStream_t stream, HgValuesOutput *out, std::string *err) {
+  *out = HgValuesOutput{};
+  HgValuesGroups groups{};
+  const int rc = group(in, stream, &groups, err);
+  if (rc != HG_OK) return rc;
+  HgValuesArgs a = groups.args;
+  const uint64_t n = in.n_parts;
+  uint64_t *totals = totals_.get();
+  {
+    const uint64_t nv = a.n_values + 1, nv_grow = nv + nv / 4;
+    if (!size_.reserve(nv, nv_grow) || !off_.reserve(nv, nv_grow) || !line_.reserve(nv, nv_grow) || !pattern_.reserve(nv, nv_grow) || (in.seg_start && !seg_.reserve(nv, nv_grow)) ||
+        !entries_.reserve(nv, nv_grow)) {
+      *err = "values stage: out of memory for " + std::to_string(a.n_values) + " values";
+      return HG_ERR_NOMEM;
+    }
+  }
+  a.size = size_.get();
+  a.entries = entries_.get();
+  a.pattern = pattern_.get();
+  a.segment = in.seg_start ? seg_.get() : nullptr;
+  a.line_number = line_.get();
   HG_VALUES_TRY(hg_values_launch(a, HgValuesStep::Derive, stream), "launch (derive)");
   {
     size_t t = temp_.cap();
@@ -2067,6 +2092,166 @@ int HgValues::run(const HgValuesInput &in, hipStream_t stream, HgValuesOutput *o
   out->d_pattern = pattern_.get();
   out->d_segment = a.segment;
   out->table_log2 = in.table_log2;
+  return HG_OK;
+}
+
+// ---------------------------------------------------------------- rank stage (hg_rank_values): buffers and launch sequence
+HgRank::~HgRank() {
+  (void)hipSetDevice(device_);  // (the buffers are freed behind this body)
+  for (hipEvent_t e : ev_)
+    if (e) (void)hipEventDestroy(e);
+}
+
+#define HG_RANK_TRY(expr, what)                                                   \
+  do {                                                                            \
+    const hipError_t e_ = (expr);                                                 \
+    if (e_ != hipSuccess) {                                                       \
+      *err = std::string("rank stage: ") + (what) + ": " + hipGetErrorString(e_); \
+      return HG_ERR_HIP;                                                          \
+    }                                                                             \
+  } while (0)
+
+int HgRank::run(const HgRankInput &in, hipStream_t stream, HgRankOutput *out, std::string *err) {
+  *out = HgRankOutput{};
+  HG_RANK_TRY(hipSetDevice(device_), "hipSetDevice");
+  for (hipEvent_t &e : ev_)
+    if (!e) HG_RANK_TRY(hipEventCreate(&e), "event");
+  HG_RANK_TRY(hipEventRecord(ev_[0], stream), "event");
+  // the groups, sorted by first: the values stage's passes with the segment in the key (one host synchronisation)
+  HgValuesGroups groups{};
+  const int rc = groups_.group(in.values, stream, &groups, err);
+  if (rc != HG_OK) return rc;
+  const bool per_seg = (in.values.flags & HG_RANK_F_PER_SEGMENT) != 0;
+  const uint64_t ng = groups.n_values, np = ng + 1, np_grow = np + np / 4, n_parts = in.values.n_parts;
+  const uint32_t n_seg = per_seg ? in.n_seg : 1u;
+  const uint64_t ns = static_cast<uint64_t>(n_seg) + 1;
+  uint32_t bits = 1, seg_bits = 1;
+  while (bits < 64 && (n_parts >> bits)) bits++;            // count <= n_parts
+  while (seg_bits < 32 && (n_seg >> seg_bits)) seg_bits++;  // segment < n_seg
+  size_t t_count = 0, t_seg = 0, t_scan = 0, t_scan_seg = 0;
+  HG_RANK_TRY(rocprim::radix_sort_pairs_desc(nullptr, t_count, static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr),
+                                             static_cast<uint64_t *>(nullptr), std::max<uint64_t>(ng, 1), 0, bits, stream),
+              "sort size");
+  HG_RANK_TRY(rocprim::radix_sort_pairs(nullptr, t_seg, static_cast<uint32_t *>(nullptr), static_cast<uint32_t *>(nullptr), static_cast<uint64_t *>(nullptr),
+                                        static_cast<uint64_t *>(nullptr), std::max<uint64_t>(ng, 1), 0, seg_bits, stream),
+              "sort size");
+  HG_RANK_TRY(rocprim::exclusive_scan(nullptr, t_scan, static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), uint64_t{0}, np, rocprim::plus<uint64_t>(), stream),
+              "scan size");
+  HG_RANK_TRY(rocprim::exclusive_scan(nullptr, t_scan_seg, static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), uint64_t{0}, ns, rocprim::plus<uint64_t>(), stream),
+              "scan size");
+  const size_t tb = std::max<size_t>(std::max(std::max(t_count, t_seg), std::max(t_scan, t_scan_seg)), 16);
+  const bool ok = g_first_.reserve(np, np_grow) && g_count_.reserve(np, np_grow) && s_count_.reserve(np, np_grow) && cum_.reserve(np, np_grow) && first_.reserve(np, np_grow) &&
+                  count_.reserve(np, np_grow) && size_.reserve(np, np_grow) && off_.reserve(np, np_grow) && line_.reserve(np, np_grow) && pattern_.reserve(np, np_grow) &&
+                  entries_.reserve(np, np_grow) && (!in.values.seg_start || seg_.reserve(np, np_grow)) &&
+                  (!per_seg || (key_idx_.reserve(np, np_grow) && s_idx_.reserve(np, np_grow) && key_seg_.reserve(np, np_grow) && s_seg_.reserve(np, np_grow))) &&
+                  first_group_.reserve(ns, ns + ns / 4) && seg_distinct_.reserve(ns, ns + ns / 4) && seg_parts_.reserve(ns, ns + ns / 4) && kept_.reserve(ns, ns + ns / 4) &&
+                  first_value_.reserve(ns, ns + ns / 4) && temp_.reserve(tb, tb + tb / 4) && totals_.reserve(2, 2);
+  if (!ok) {
+    *err = "rank stage: out of memory (" + std::to_string(ng) + " distinct values, " + std::to_string(n_seg) + " segments)";
+    return HG_ERR_NOMEM;
+  }
+  HgRankArgs a{};
+  a.parts = groups.args.parts;
+  a.part_pattern = groups.args.part_pattern;
+  a.part_seg = groups.args.part_seg;
+  a.n_parts = n_parts;
+  a.src = groups.args.src;
+  a.len = groups.args.len;
+  a.flags = in.values.flags;
+  a.n_seg = n_seg;
+  a.top = in.top;
+  a.n_groups = ng;
+  a.g_first = g_first_.get();
+  a.g_count = g_count_.get();
+  a.s_count = s_count_.get();
+  a.cum = cum_.get();
+  a.first_group = first_group_.get();
+  a.seg_distinct = seg_distinct_.get();
+  a.seg_parts = seg_parts_.get();
+  a.kept = kept_.get();
+  a.first_value = first_value_.get();
+  a.out_first = first_.get();
+  a.out_count = count_.get();
+  a.size = size_.get();
+  a.entries = entries_.get();
+  a.pattern = pattern_.get();
+  a.segment = in.values.seg_start ? seg_.get() : nullptr;
+  a.line_number = line_.get();
+  if (ng) {
+    size_t t = temp_.cap();
+    HG_RANK_TRY(rocprim::radix_sort_pairs_desc(temp_.get(), t, groups.d_count, g_count_.get(), groups.d_first, g_first_.get(), ng, 0, bits, stream), "sort (count)");
+  }
+  if (per_seg) {
+    a.key_seg = key_seg_.get();
+    a.key_idx = key_idx_.get();
+    HG_RANK_TRY(hg_rank_launch(a, HgRankStep::Keys, stream), "launch (keys)");
+    if (ng) {
+      size_t t = temp_.cap();
+      HG_RANK_TRY(rocprim::radix_sort_pairs(temp_.get(), t, key_seg_.get(), s_seg_.get(), key_idx_.get(), s_idx_.get(), ng, 0, seg_bits, stream), "sort (segment)");
+    }
+    a.s_seg = s_seg_.get();
+    a.s_idx = s_idx_.get();
+  }
+  HG_RANK_TRY(hg_rank_launch(a, HgRankStep::Counts, stream), "launch (counts)");
+  {
+    size_t t = temp_.cap();
+    HG_RANK_TRY(rocprim::exclusive_scan(temp_.get(), t, s_count_.get(), cum_.get(), uint64_t{0}, np, rocprim::plus<uint64_t>(), stream), "scan (counts)");
+  }
+  HG_RANK_TRY(hg_rank_launch(a, HgRankStep::Bounds, stream), "launch (bounds)");
+  {
+    size_t t = temp_.cap();
+    HG_RANK_TRY(rocprim::exclusive_scan(temp_.get(), t, kept_.get(), first_value_.get(), uint64_t{0}, ns, rocprim::plus<uint64_t>(), stream), "scan (kept)");
+  }
+  HG_RANK_TRY(hipMemsetAsync(size_.get(), 0, np * sizeof(uint64_t), stream), "memset");
+  HG_RANK_TRY(hg_rank_launch(a, HgRankStep::Place, stream), "launch (place)");
+  {
+    size_t t = temp_.cap();
+    HG_RANK_TRY(rocprim::exclusive_scan(temp_.get(), t, size_.get(), off_.get(), uint64_t{0}, np, rocprim::plus<uint64_t>(), stream), "scan (lengths)");
+  }
+  uint64_t *totals = totals_.get();
+  HG_RANK_TRY(hipMemcpyAsync(totals, first_value_.get() + n_seg, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "copy rows");
+  HG_RANK_TRY(hipMemcpyAsync(totals + 1, off_.get() + ng, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "copy bytes");
+  HG_RANK_TRY(hipStreamSynchronize(stream), "stream sync");
+  if (totals[0] > ng) {
+    *err = "rank stage: more rows than distinct values";
+    return HG_ERR_HIP;
+  }
+  HgGatherArgs g{};
+  g.text = groups.args.text;
+  g.entries = entries_.get();
+  g.off = off_.get();
+  g.n_entries = totals[0];
+  g.n_bytes = totals[1];
+  const uint64_t padded = (g.n_bytes + 15) & ~static_cast<uint64_t>(15), n_spans = (g.n_bytes + HG_GATHER_TILE - 1) / HG_GATHER_TILE;
+  if (!bytes_.reserve(std::max<uint64_t>(padded, 16), std::max<uint64_t>(padded + padded / 8, 16)) || !span_.reserve(n_spans + 1, n_spans + n_spans / 8 + 1)) {
+    *err = "rank stage: out of memory for " + std::to_string(g.n_bytes) + " bytes of values";
+    return HG_ERR_NOMEM;
+  }
+  g.span = span_.get();
+  g.out = bytes_.get();
+  HG_RANK_TRY(hg_gather_launch(g, HgGatherStep::Span, stream), "launch (spans)");  // (nothing without bytes)
+  HG_RANK_TRY(hg_gather_launch(g, HgGatherStep::Copy, stream), "launch (copy)");
+  HG_RANK_TRY(hipEventRecord(ev_[1], stream), "event");
+  HG_RANK_TRY(hipStreamSynchronize(stream), "stream sync");
+  HG_RANK_TRY(hipEventElapsedTime(&out->ms_rank, ev_[0], ev_[1]), "event time");
+  out->n_values = totals[0];
+  out->n_distinct = ng;
+  out->n_parts = n_parts;
+  out->n_bytes = g.n_bytes;
+  out->d_bytes = bytes_.get();
+  out->d_off = off_.get();
+  out->d_count = count_.get();
+  out->d_first = first_.get();
+  out->d_line_number = line_.get();
+  out->d_pattern = pattern_.get();
+  out->d_segment = a.segment;
+  if (per_seg) {
+    out->d_first_value = first_value_.get();
+    out->d_seg_distinct = seg_distinct_.get();
+    out->d_seg_parts = seg_parts_.get();
+  }
+  out->n_seg = per_seg ? n_seg : 0;
+  out->table_log2 = in.values.table_log2;
   return HG_OK;
 }
 

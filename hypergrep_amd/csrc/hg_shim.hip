@@ -1027,15 +1027,27 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
 // With `fcs` (hg_hyperscan_files_counts; on_event is NULL then) the counts stage runs behind every pack's segment stage with
 // per-segment matrices, which are all that leaves the GPU beside the per-file arrays; a pack is closed early where one more
 // file would take the matrices past the stage's limit of cells.  Files of the per-file route take scan_file with counts.
+//
+// With `fvs` (hg_hyperscan_files_values; on_event is NULL then) every pack is scanned with parts and the rank stage runs behind
+// it with HG_RANK_PER_SEGMENT and the caller's cut: only the kept rows (bytes, offsets, counts, expressions) and three numbers
+// per file leave the GPU, no part record and no line.  on_file is called once per file, in file order, so a file that cannot be
+// opened closes the pack before it.  Files of the per-file route take scan_file with values (hg_hyperscan_values' chunk merge)
+// and are ordered and cut here by the same rule: count descending, then first occurrence in the file.
 struct FilesCounts {
   uint32_t *ids;
   unsigned int max_ids, *n_ids;
   uint64_t *file_lines, *file_reports;  // n_files rows of max_ids values
 };
+struct FilesValues {
+  hg_rank_params_t params;
+  hg_file_values_event on_file;
+  void *context;
+  void none(unsigned int f) const { on_file(context, f, nullptr, nullptr, nullptr, nullptr, 0, 0, 0); }
+};
 static int files_impl(const char *const *file_names, unsigned int n_files, const char *const *patterns, const unsigned int *pattern_flags,
                       const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, hg_files_event on_event, void *context,
                       const int buffer_size, int buffer_count, unsigned long long max_match_count, int invert, hg_file_summary_t *summaries, uint32_t before,
-                      uint32_t after, bool parts = false, const FilesCounts *fcs = nullptr) {
+                      uint32_t after, bool parts = false, const FilesCounts *fcs = nullptr, const FilesValues *fvs = nullptr) {
   if (!on_event) before = after = 0;  // summaries only: they are those of the call without context
   const bool with_context = before || after;
   if (!summaries || (!file_names && n_files) || buffer_count < 1 || buffer_size < 1) return HYPERSCANNER_STATE_MEM;
@@ -1053,7 +1065,7 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
       std::fprintf(stderr, "ERROR: Unable to create database. Exiting. (%s)\n", why);
       return HYPERSCANNER_DB;
     }
-    if (!on_event) parts = false;  // summaries only: they are those of the call without parts
+    if (!on_event && !fvs) parts = false;  // summaries only: they are those of the call without parts
   }
   const size_t n_bins = db->report_ids.size(), n_cols = fcs ? std::min<size_t>(n_bins, fcs->max_ids) : 0;
   if (fcs) {
@@ -1063,6 +1075,11 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
     std::fill(fcs->file_reports, fcs->file_reports + static_cast<size_t>(n_files) * fcs->max_ids, uint64_t{0});
   }
   std::vector<uint32_t> seg_lines, seg_reports;  // the pack's matrices
+  std::unique_ptr<HgRank> rank;  // (hg_hyperscan_files_values: made with the first pack, on its device; its buffers are its own)
+  int rank_device = -1;
+  std::vector<uint8_t> r_bytes;  // a pack's kept rows and per-file arrays
+  std::vector<uint64_t> r_off, r_count, r_first_value, r_distinct, r_parts;
+  std::vector<uint32_t> r_pattern;
   // one file through the per-file route: its events carry its index, its distinct lines are counted on the way
   auto single = [&](unsigned int f) {
     uint64_t selected = 0, last = ~0ull, pieces = 0;
@@ -1075,8 +1092,30 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
       if (on_event) on_event(f, r, n, context);
     };
     FileCounts fc;
+    FileValues fv;
+    if (fvs) fv.params = hg_values_params_t{fvs->params.flags & HG_VALUES_BY_PATTERN, fvs->params.hash_bits, fvs->params.table_log2, 0};
     const int rc = scan_file(file_names[f], patterns, pattern_flags, pattern_ids, ext, elements, ev, buffer_size, buffer_count, max_match_count, invert != 0, before, after, &pieces, parts,
-                             fcs ? &fc : nullptr);
+                             fcs ? &fc : nullptr, fvs ? &fv : nullptr);
+    if (fvs && rc) fvs->none(f);
+    if (fvs && !rc) {  // the merged rows come in the order of their first occurrence: a stable sort by count, then the cut
+      std::vector<size_t> order(fv.value.size());
+      for (size_t j = 0; j < order.size(); j++) order[j] = j;
+      std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return fv.count[x] > fv.count[y]; });
+      uint64_t n_parts = 0;
+      for (uint64_t c : fv.count) n_parts += c;
+      const size_t kept = fvs->params.top && fvs->params.top < order.size() ? static_cast<size_t>(fvs->params.top) : order.size();
+      std::vector<uint8_t> bytes;
+      std::vector<uint64_t> off(1, 0), count(kept);
+      std::vector<uint32_t> pattern(kept);
+      for (size_t j = 0; j < kept; j++) {
+        const std::string &v = fv.value[order[j]];
+        bytes.insert(bytes.end(), v.begin(), v.end());
+        off.push_back(bytes.size());
+        count[j] = fv.count[order[j]];
+        pattern[j] = fv.pattern[order[j]];
+      }
+      fvs->on_file(fvs->context, f, bytes.data(), off.data(), count.data(), pattern.data(), kept, order.size(), n_parts);
+    }
     if (fcs && fc.n_lines.size() >= n_cols) {  // (nothing was delivered, so `selected` stays 0: the row says what was selected)
       std::copy(fc.n_lines.begin(), fc.n_lines.begin() + n_cols, fcs->file_lines + static_cast<size_t>(f) * fcs->max_ids);
       std::copy(fc.n_reports.begin(), fc.n_reports.begin() + n_cols, fcs->file_reports + static_cast<size_t>(f) * fcs->max_ids);
@@ -1112,7 +1151,10 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
   if (on_event && !ring.init(buffer_count, std::max(buffer_size, 2), [&](hyperscanner_result_t *r, int n) { on_event(cur_file, r, n, context); }))
     return HYPERSCANNER_COMPILE_MEM;
   auto fail_pack = [&](int rc) {
-    for (unsigned int f : seg_file) summaries[f].rc = rc;
+    for (unsigned int f : seg_file) {
+      summaries[f].rc = rc;
+      if (fvs) fvs->none(f);
+    }
     healthy = false;
   };
   // scan the pack and deliver its files
@@ -1159,9 +1201,9 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
            hipMemcpyAsync(first_ctx.data(), sx.d_first_context, (n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
         src = HG_ERR_HIP;  // (the synchronisation below waits for these copies too)
       first_part.assign(n_seg + 1, 0);
-      part_recs.resize(src == HG_OK ? pout.n_parts : 0);
+      part_recs.resize(src == HG_OK && !fvs ? pout.n_parts : 0);  // (with fvs no part record comes back)
       part_pattern.resize(part_recs.size());
-      if (src == HG_OK && parts &&
+      if (src == HG_OK && parts && !fvs &&
           ((pout.n_parts && (hipMemcpyAsync(part_recs.data(), pout.d_parts, pout.n_parts * sizeof(HgPart), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
                              hipMemcpyAsync(part_pattern.data(), pout.d_pattern, pout.n_parts * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) ||
            hipMemcpyAsync(first_part.data(), spo.d_first_part, (n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
@@ -1189,6 +1231,46 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
                              hipMemcpy(seg_reports.data(), co.d_seg_reports, cells * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess))
           src = HG_ERR_HIP;
       }
+      HgRankOutput ro{};
+      if (src == HG_OK && fvs) {  // the rank stage behind the parts stage, per file; the kept rows and the per-file arrays come back
+        const uint32_t log2 = fvs->params.table_log2 ? fvs->params.table_log2 : hg_values_default_log2(pout.n_parts);
+        if (log2 > HG_VALUES_MAX_TABLE_LOG2 || (uint64_t{1} << log2) <= pout.n_parts) {
+          err = "a pack has " + std::to_string(pout.n_parts) + " parts: more than a table of 2^" + std::to_string(log2) + " slots serves";
+          src = HG_ERR_ARG;
+        } else {
+          if (!rank || rank_device != ctx->device) {
+            rank = std::make_unique<HgRank>(ctx->device);
+            rank_device = ctx->device;
+          }
+          HgRankInput rin{};
+          rin.values = HgValuesInput{ctx->d_text[0], HgGatherList{out.d_hits, out.d_aux, seg.d_record_segment, out.n_hits}, pout.d_parts, pout.d_pattern, spo.d_part_segment, pout.n_parts,
+                                     d_segs, (fvs->params.flags & HG_RANK_F_BY_PATTERN) | HG_RANK_F_PER_SEGMENT, fvs->params.hash_bits ? fvs->params.hash_bits : 64u, log2};
+          rin.n_seg = static_cast<uint32_t>(n_seg);
+          rin.top = fvs->params.top;
+          src = rank->run(rin, ctx->stream, &ro, &err);
+        }
+        if (src == HG_OK) {
+          r_bytes.resize(ro.n_bytes);
+          r_off.resize(ro.n_values + 1);
+          r_count.resize(ro.n_values);
+          r_pattern.resize(ro.n_values);
+          r_first_value.resize(n_seg + 1);
+          r_distinct.resize(n_seg);
+          r_parts.resize(n_seg);
+          if ((ro.n_bytes && hipMemcpyAsync(r_bytes.data(), ro.d_bytes, ro.n_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
+              hipMemcpyAsync(r_off.data(), ro.d_off, (ro.n_values + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+              (ro.n_values && (hipMemcpyAsync(r_count.data(), ro.d_count, ro.n_values * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                               hipMemcpyAsync(r_pattern.data(), ro.d_pattern, ro.n_values * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) ||
+              hipMemcpyAsync(r_first_value.data(), ro.d_first_value, (n_seg + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+              hipMemcpyAsync(r_distinct.data(), ro.d_seg_distinct, n_seg * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+              hipMemcpyAsync(r_parts.data(), ro.d_seg_parts, n_seg * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+              hipStreamSynchronize(ctx->stream) != hipSuccess) {
+            err = "copying the ranked values";
+            src = HG_ERR_HIP;
+          }
+        }
+        if (src != HG_OK) ctx->sc->set_error(src, err);
+      }
       if (src != HG_OK) {
         std::fprintf(stderr, "ERROR: Unable to scan buffer. Exiting. (%s)\n", ctx->sc ? ctx->sc->last_error().c_str() : "copy");
         fail_pack(HYPERSCANNER_SCAN);
@@ -1205,6 +1287,10 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
               fcs->file_lines[static_cast<size_t>(cur_file) * fcs->max_ids + b] = seg_lines[s * n_bins + b];
               fcs->file_reports[static_cast<size_t>(cur_file) * fcs->max_ids + b] = seg_reports[s * n_bins + b];
             }
+          if (fvs) {  // the file's rows of the pack's ranking (off[0] is where its first value lies among the pack's bytes)
+            const uint64_t lo = r_first_value[s], n = r_first_value[s + 1] - lo;
+            fvs->on_file(fvs->context, cur_file, r_bytes.data(), r_off.data() + lo, r_count.data() + lo, r_pattern.data() + lo, n, r_distinct[s], r_parts[s]);
+          }
           if (!on_event) continue;
           const uint8_t *base = host + seg_start[s];  // the records are file-relative
           if (parts) {  // every part of each kept line, in order, in place of its reports (as scan_file)
@@ -1246,11 +1332,14 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
   for (unsigned int f = 0; f < n_files; f++) {
     if (!healthy) {  // a device error ended the packs: the rest is not scanned
       summaries[f].rc = HYPERSCANNER_SCAN;
+      if (fvs) fvs->none(f);
       continue;
     }
     Reader in;
     if (!file_names[f] || !in.open(file_names[f])) {
+      if (fvs) flush_pack();  // (its callback comes in its place in the order)
       summaries[f].rc = HYPERSCANNER_GZ_OPEN;
+      if (fvs) fvs->none(f);
       continue;
     }
     const size_t size = in.size_hint();
@@ -1265,12 +1354,16 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
         ctx = nullptr;
       }
       if (healthy) single(f);
-      else summaries[f].rc = HYPERSCANNER_SCAN;
+      else {
+        summaries[f].rc = HYPERSCANNER_SCAN;
+        if (fvs) fvs->none(f);
+      }
       continue;
     }
     if (fill + size + 2 > cap || (fcs && (seg_file.size() + 1) * n_bins > HG_COUNTS_MAX_CELLS)) flush_pack();
     if (!healthy) {
       summaries[f].rc = HYPERSCANNER_SCAN;
+      if (fvs) fvs->none(f);
       continue;
     }
     if (!ctx) {
@@ -1278,7 +1371,10 @@ static int files_impl(const char *const *file_names, unsigned int n_files, const
       if (!ctx || hipSetDevice(ctx->device) != hipSuccess || !ensure_buffers(ctx, cap, 1)) {
         std::fprintf(stderr, "ERROR: Unable to allocate scratch space. Exiting. (%s)\n", err.c_str());
         if (ctx) healthy = false;
-        for (unsigned int g = f; g < n_files; g++) summaries[g].rc = HYPERSCANNER_SCRATCH;
+        for (unsigned int g = f; g < n_files; g++) {
+          summaries[g].rc = HYPERSCANNER_SCRATCH;
+          if (fvs) fvs->none(g);
+        }
         return 0;
       }
     }
@@ -1334,6 +1430,15 @@ extern "C" int hg_hyperscan_files_counts(const char *const *file_names, unsigned
   if (!n_ids || (max_ids && (!ids || (n_files && (!file_lines || !file_reports))))) return HYPERSCANNER_STATE_MEM;
   const FilesCounts fcs{ids, max_ids, n_ids, file_lines, file_reports};
   return files_impl(file_names, n_files, patterns, pattern_flags, pattern_ids, ext, elements, nullptr, nullptr, buffer_size, 1, 0, 0, summaries, 0, 0, false, &fcs);
+}
+
+extern "C" int hg_hyperscan_files_values(const char *const *file_names, unsigned int n_files, const char *const *patterns, const unsigned int *pattern_flags,
+                                         const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements, const int buffer_size,
+                                         const hg_rank_params_t *params, hg_file_values_event on_file, void *context, hg_file_summary_t *summaries) {
+  if (!on_file) return HYPERSCANNER_STATE_MEM;
+  FilesValues fvs{params ? *params : hg_rank_params_t{0, 0, 0, 0, 0}, on_file, context};
+  if ((fvs.params.flags & ~HG_RANK_BY_PATTERN) || fvs.params.hash_bits > 64 || fvs.params.table_log2 > HG_VALUES_MAX_TABLE_LOG2) return HYPERSCANNER_STATE_MEM;
+  return files_impl(file_names, n_files, patterns, pattern_flags, pattern_ids, ext, elements, nullptr, nullptr, buffer_size, 1, 0, 0, summaries, 0, 0, true, nullptr, &fvs);
 }
 
 extern "C" int hg_hyperscan_counts(char *file_name, const char *const *patterns, const unsigned int *pattern_flags, const unsigned int *pattern_ids,

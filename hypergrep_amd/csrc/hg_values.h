@@ -7,7 +7,13 @@
 //    (hg_gather_lower_bound over the final records, hg_gather_seg; hg_partlines.h, PIECE), S = seg_start[segment] + aux.start, and the
 //    value is text[S + from, S + to).  A part whose piece has no record has no value (len 0: a part is never empty) and is not
 //    counted.  hg_values_locate is the one place that decides this.
-//  - KEY.  The value's bytes; with HG_VALUES_F_BY_PATTERN the pair (part_pattern[q], bytes).  The segment is never in the key.
+//  - KEY.  The value's bytes; with HG_VALUES_F_BY_PATTERN the pair (part_pattern[q], bytes).  hg_count_values never has the
+//    segment in the key.  The rank stage (hg_rank.h) has it with HG_VALUES_F_BY_SEGMENT, a flag no public call of this stage
+//    passes on: its own instantiations of the hash, long and insert pass (the SEG template argument, false by default) keep a
+//    key word per part, hg_values_key_word = (segment + 1) << 32 | expression step, hash it with one more Horner step
+//    (segment + 1) behind the expression's and compare it in hg_values_candidate in place of the expression.  The
+//    instantiations without it use the registers they used before the bodies became templates (the same SGPRs, VGPRs and
+//    occupancy; the instruction streams differ a little) and were measured against the earlier library.
 //  - HASH.  64 bits, a Horner form in 64-bit arithmetic: h = SEED, then h = h * P + v for v = len, then the expression index + 1
 //    (0 when not keyed by it), then byte + 1 for every byte, a final mix (hg_values_finish) and the cut to the low hash_bits
 //    bits.  hg_values_hash_bytes is that definition, a byte at a time; hg_values_hash_dwords reads whole aligned dwords and
@@ -29,6 +35,7 @@
 #include "hg_parts.h"
 
 constexpr uint32_t HG_VALUES_F_BY_PATTERN = 1u;  // HG_VALUES_BY_PATTERN of the C ABI
+constexpr uint32_t HG_VALUES_F_BY_SEGMENT = 2u;  // internal (hg_rank_values with HG_RANK_PER_SEGMENT): hg_count_values refuses the bit
 #ifndef HG_VALUES_LANE_MAX
 #define HG_VALUES_LANE_MAX 256u  // a part of at most this many bytes is hashed and compared by one lane, a longer one by a wavefront
 #endif
@@ -70,11 +77,20 @@ struct HgValuesArgs {
   HgGatherEntry *entries;             // what the copy pass reads: {src, line, len, form 0}
   uint32_t *pattern, *segment;        // (segment nullptr without segments)
   uint64_t *line_number;
+  // the SEG instantiations only (nullptr otherwise): per part its key word, written by their hash pass
+  uint64_t *key;
 };
 
 HG_HD uint64_t hg_values_step(uint64_t h, uint64_t v) { return h * HG_VALUES_P + v; }
 HG_HD uint64_t hg_values_init(uint32_t len, uint32_t flags, uint32_t pattern) {
   return hg_values_step(hg_values_step(HG_VALUES_SEED, len), (flags & HG_VALUES_F_BY_PATTERN) ? static_cast<uint64_t>(pattern) + 1 : 0);
+}
+// The key word of a part in the SEG instantiations and the Horner value its hash starts from.
+HG_HD uint64_t hg_values_key_word(uint32_t flags, uint32_t pattern, uint32_t segment) {
+  return ((static_cast<uint64_t>(segment) + 1) << 32) | ((flags & HG_VALUES_F_BY_PATTERN) ? pattern + 1u : 0u);
+}
+HG_HD uint64_t hg_values_init_key(uint32_t len, uint64_t key) {
+  return hg_values_step(hg_values_step(hg_values_step(HG_VALUES_SEED, len), key & 0xFFFFFFFFull), key >> 32);
 }
 HG_HD uint64_t hg_values_step_dword(uint64_t h, uint32_t w) {  // four byte steps
   h = hg_values_step(h, (w & 0xFFu) + 1);
@@ -130,22 +146,34 @@ HG_HD uint64_t hg_values_run_dwords(const Text &text, uint64_t h, uint64_t s, ui
   return hg_values_run_bytes(text, h, s + 4 * full, n - 4 * full);
 }
 template <typename Text>
+HG_HD uint64_t hg_values_hash_bytes_from(const Text &text, uint64_t h0, uint64_t s, uint32_t len, uint32_t hash_bits) {  // (h0: hg_values_init or hg_values_init_key)
+  return hg_values_finish(hg_values_run_bytes(text, h0, s, len), hash_bits);
+}
+template <typename Text>
+HG_HD uint64_t hg_values_hash_dwords_from(const Text &text, uint64_t h0, uint64_t s, uint32_t len, uint32_t hash_bits) {
+  return hg_values_finish(hg_values_run_dwords(text, h0, s, len), hash_bits);
+}
+template <typename Text>
 HG_HD uint64_t hg_values_hash_bytes(const Text &text, uint64_t s, uint32_t len, uint32_t flags, uint32_t pattern, uint32_t hash_bits) {
-  return hg_values_finish(hg_values_run_bytes(text, hg_values_init(len, flags, pattern), s, len), hash_bits);
+  return hg_values_hash_bytes_from(text, hg_values_init(len, flags, pattern), s, len, hash_bits);
 }
 template <typename Text>
 HG_HD uint64_t hg_values_hash_dwords(const Text &text, uint64_t s, uint32_t len, uint32_t flags, uint32_t pattern, uint32_t hash_bits) {
-  return hg_values_finish(hg_values_run_dwords(text, hg_values_init(len, flags, pattern), s, len), hash_bits);
+  return hg_values_hash_dwords_from(text, hg_values_init(len, flags, pattern), s, len, hash_bits);
 }
 // Lane l's share of the whole rounds of a long value: the sum over the 64 lanes is the Horner value after len / 256 * 256 bytes.
 // hg_values_hash_wave_end turns that sum into the hash (the bytes behind the whole rounds, the mix and the cut).
 template <typename Text>
-HG_HD uint64_t hg_values_hash_wave_lane(const Text &text, uint64_t s, uint32_t len, uint32_t flags, uint32_t pattern, uint32_t lane) {
-  uint64_t acc = lane == HG_VALUES_WAVE - 1 ? hg_values_init(len, flags, pattern) : 0;
+HG_HD uint64_t hg_values_hash_wave_lane_from(const Text &text, uint64_t h0, uint64_t s, uint32_t len, uint32_t lane) {
+  uint64_t acc = lane == HG_VALUES_WAVE - 1 ? h0 : 0;
   const uint32_t rounds = len / HG_VALUES_ROUND;
   for (uint32_t r = 0; r < rounds; r++)
     acc = acc * HG_VALUES_P_ROUND + hg_values_step_dword(0, hg_values_word(text, s + static_cast<uint64_t>(r) * HG_VALUES_ROUND + 4 * lane));
   return acc * hg_values_pow(HG_VALUES_P, 4 * (HG_VALUES_WAVE - 1 - lane));
+}
+template <typename Text>
+HG_HD uint64_t hg_values_hash_wave_lane(const Text &text, uint64_t s, uint32_t len, uint32_t flags, uint32_t pattern, uint32_t lane) {
+  return hg_values_hash_wave_lane_from(text, hg_values_init(len, flags, pattern), s, len, lane);
 }
 template <typename Text>
 HG_HD uint64_t hg_values_hash_wave_end(const Text &text, uint64_t sum, uint64_t s, uint32_t len, uint32_t hash_bits) {
@@ -191,16 +219,18 @@ HG_HD uint64_t hg_values_tag(uint64_t h) { return h >> HG_VALUES_REP_BITS; }
 HG_HD uint64_t hg_values_slot_word(uint64_t h, uint64_t q) { return (hg_values_tag(h) << HG_VALUES_REP_BITS) | q; }
 HG_HD uint64_t hg_values_home(uint64_t h, uint32_t table_log2) { return h & ((uint64_t{1} << table_log2) - 1); }
 // Can the occupied slot word w be the group of part q (hash h), by everything but the bytes?  *rep: its representative.
+template <bool SEG = false>
 HG_HD bool hg_values_candidate(const HgValuesArgs &a, uint64_t w, uint64_t q, uint64_t h, uint64_t *rep) {
   *rep = w & HG_VALUES_REP_MASK;
   if ((w >> HG_VALUES_REP_BITS) != hg_values_tag(h) || *rep >= a.n_parts) return false;
   if (a.len[*rep] != a.len[q]) return false;
+  if (SEG) return a.key[*rep] == a.key[q];
   return !(a.flags & HG_VALUES_F_BY_PATTERN) || a.part_pattern[*rep] == a.part_pattern[q];
 }
 
 // The probe of part q (a lane's): the slot of its group, claimed if it is new, or HG_VALUES_NO_SLOT after a whole round of the
 // table.  Table: load(slot) and claim(slot, word), which returns what the slot held (HG_VALUES_EMPTY: the claim holds).
-template <typename Text, typename Table>
+template <bool SEG = false, typename Text, typename Table>
 HG_HD uint64_t hg_values_insert(const HgValuesArgs &a, const Text &text, const Table &t, uint64_t q) {
   const uint64_t h = a.hash[q], cap = uint64_t{1} << a.table_log2, mine = hg_values_slot_word(h, q);
   uint64_t s = hg_values_home(h, a.table_log2);
@@ -211,7 +241,7 @@ HG_HD uint64_t hg_values_insert(const HgValuesArgs &a, const Text &text, const T
       if (w == HG_VALUES_EMPTY) return s;
     }
     uint64_t rep;
-    if (hg_values_candidate(a, w, q, h, &rep) && hg_values_equal(text, a.src[rep], a.src[q], a.len[q])) return s;
+    if (hg_values_candidate<SEG>(a, w, q, h, &rep) && hg_values_equal(text, a.src[rep], a.src[q], a.len[q])) return s;
   }
   return HG_VALUES_NO_SLOT;
 }

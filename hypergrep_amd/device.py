@@ -112,6 +112,21 @@ class HgValuesResult(ctypes.Structure):  # sizeof 88
                 ("d_segment", ctypes.c_void_p), ("table_log2", ctypes.c_uint32), ("values_us", ctypes.c_uint32)]
 
 
+HG_RANK_BY_PATTERN = 1
+HG_RANK_PER_SEGMENT = 2
+
+
+class HgRankParams(ctypes.Structure):  # sizeof 24
+    _fields_ = [("flags", ctypes.c_uint32), ("hash_bits", ctypes.c_uint32), ("table_log2", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("top", ctypes.c_uint64)]
+
+
+class HgRankResult(ctypes.Structure):  # sizeof 128
+    _fields_ = [("n_values", ctypes.c_uint64), ("n_distinct", ctypes.c_uint64), ("n_parts", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("d_bytes", ctypes.c_void_p),
+                ("d_off", ctypes.c_void_p), ("d_count", ctypes.c_void_p), ("d_first", ctypes.c_void_p), ("d_pattern", ctypes.c_void_p), ("d_line_number", ctypes.c_void_p),
+                ("d_segment", ctypes.c_void_p), ("d_first_value", ctypes.c_void_p), ("d_seg_distinct", ctypes.c_void_p), ("d_seg_parts", ctypes.c_void_p),
+                ("n_seg", ctypes.c_uint32), ("table_log2", ctypes.c_uint32), ("rank_us", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class HgCountsResult(ctypes.Structure):
     _fields_ = [("n_bins", ctypes.c_uint32), ("n_seg", ctypes.c_uint32), ("n_records", ctypes.c_uint64), ("d_ids", ctypes.c_void_p),
                 ("d_n_lines", ctypes.c_void_p), ("d_n_reports", ctypes.c_void_p), ("d_seg_lines", ctypes.c_void_p), ("d_seg_reports", ctypes.c_void_p),
@@ -212,6 +227,12 @@ def lib() -> ctypes.CDLL:
             l.hg_count_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(HgValuesParams), ctypes.c_void_p, ctypes.POINTER(HgValuesResult)]
             l.hg_copy_values.argtypes = [ctypes.c_void_p, p8, ctypes.c_uint64, p64, p64, p64, p32, p64, p32, ctypes.c_uint64]
             l.hg_copy_values_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        if hasattr(l, "hg_rank_values"):  # (absent from a build before the rank stage)
+            p8, p32, p64 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+            l.hg_rank_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(HgRankParams), ctypes.c_void_p, ctypes.POINTER(HgRankResult)]
+            l.hg_copy_ranked_values.argtypes = [ctypes.c_void_p, p8, ctypes.c_uint64, p64, p64, p64, p32, p64, p32, ctypes.c_uint64]
+            l.hg_copy_ranked_segments.argtypes = [ctypes.c_void_p, p64, p64, p64]
+            l.hg_copy_ranked_values_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hits.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
         l.hg_copy_hits_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hit_starts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
@@ -327,6 +348,15 @@ class ValueStats:
 
 
 @dataclass
+class RankStats:
+    n_values: int  # kept rows
+    n_distinct: int  # groups before the cut
+    n_parts: int  # parts of the scan
+    n_bytes: int  # bytes of the kept rows' values
+    rank_us: int  # the rank stage alone, microseconds
+
+
+@dataclass
 class CountStats:
     n_bins: int  # distinct report ids of the database
     n_records: int  # records this call counted
@@ -354,6 +384,7 @@ class Scanner:
         self._last_counts = None  # HgCountsResult of the last count
         self._last_part_lines = None  # (HgPartLinesResult, whole_line) of the last parts gather, None after a scan
         self._last_values = None  # HgValuesResult of the last value count, None after a scan
+        self._last_rank = None  # HgRankResult of the last ranking, None after a scan
         self._seg_arena = None
 
     def _place_segments(self, starts, ends):
@@ -406,6 +437,7 @@ class Scanner:
         self._last_lines = None
         self._last_part_lines = None
         self._last_values = None
+        self._last_rank = None
         self._last_seg = None
         self._last_segment_parts = False
         if segments is not None:
@@ -717,6 +749,91 @@ class Scanner:
         rc = lib().hg_copy_values_device(self._h, ctypes.c_void_p(d_dst), n, ctypes.c_void_p(stream))
         if rc != 0:
             raise DeviceError(f"hg_copy_values_device failed ({rc})")
+        return n
+
+    def rank_values(self, d_text: int, nbytes: int, top: int = 0, per_segment: bool = False, by_pattern: bool = False, stream: int = 0, hash_bits: int = 0,
+                    table_log2: int = 0) -> RankStats:
+        """The matched values ranked by count and cut to the `top` most frequent on the GPU (hg_rank_values; grep -o | sort | uniq -c |
+        sort -rn | head): after scan(parts=True) or scan(segment_parts=True), the parts grouped by their bytes (by_pattern: by
+        expression index and bytes; per_segment: additionally by file, so that equal values in two files are two groups),
+        ordered by segment (per_segment only), descending count, then first occurrence, and cut to the first `top` groups of the
+        scan, or of every file with per_segment (top=0: no cut).  Only the kept rows' bytes are gathered.  d_text and nbytes
+        must be the last scan's; hash_bits and table_log2 are count_values()' knobs.  ranked_values(), ranked_values_arrays(),
+        ranked_segments() and copy_ranked_values_to() give the result; hits(), parts(), values(), counts(), lines() ... are
+        unchanged by it.  ValueError with the reason when nothing was launched: what count_values() refuses, or per_segment
+        after a scan without segments."""
+        if top < 0:
+            raise ValueError("top must not be negative")
+        params = HgRankParams(flags=(HG_RANK_BY_PATTERN if by_pattern else 0) | (HG_RANK_PER_SEGMENT if per_segment else 0), hash_bits=hash_bits, table_log2=table_log2, top=top)
+        return self._rank_values(d_text, nbytes, params, stream)
+
+    def _rank_values(self, d_text: int, nbytes: int, params, stream: int = 0) -> RankStats:
+        res = HgRankResult()
+        self._last_rank = None
+        rc = lib().hg_rank_values(self._h, ctypes.c_void_p(d_text), nbytes, ctypes.byref(params) if params is not None else None, ctypes.c_void_p(stream), ctypes.byref(res))
+        if rc == -1:  # HG_ERR_ARG: nothing was launched
+            raise ValueError(lib().hg_scanner_error(self._h).decode(errors="replace"))
+        if rc != 0:
+            raise DeviceError(f"hg_rank_values failed ({rc}): {lib().hg_scanner_error(self._h).decode(errors='replace')}")
+        self._last_rank = res
+        return RankStats(res.n_values, res.n_distinct, res.n_parts, res.n_bytes, res.rank_us)
+
+    def ranked_values_arrays(self):
+        """The last ranking as a dict: bytes (the blob), and numpy arrays off (uint64, n + 1: row j is bytes[off[j]:off[j + 1]]),
+        count (uint64), first (uint64, the smallest part index), pattern (uint32), line_number (uint64) and, after a scan with
+        segments, segment (uint32), else None.  ValueError without a ranking since the last scan."""
+        import numpy as np
+
+        g = self._last_rank
+        if g is None:
+            raise ValueError("no ranking since the last scan")
+        n = g.n_values
+        blob = np.zeros(max(g.n_bytes, 1), dtype=np.uint8)
+        out = {"off": np.zeros(n + 1, dtype=np.uint64), "count": np.zeros(n, dtype=np.uint64), "first": np.zeros(n, dtype=np.uint64), "pattern": np.zeros(n, dtype=np.uint32),
+               "line_number": np.zeros(n, dtype=np.uint64), "segment": np.zeros(n, dtype=np.uint32) if g.d_segment else None}
+        p8, p32, p64 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+        rc = lib().hg_copy_ranked_values(self._h, blob.ctypes.data_as(p8), g.n_bytes, out["off"].ctypes.data_as(p64), out["count"].ctypes.data_as(p64),
+                                         out["first"].ctypes.data_as(p64), out["pattern"].ctypes.data_as(p32), out["line_number"].ctypes.data_as(p64),
+                                         out["segment"].ctypes.data_as(p32) if g.d_segment else None, n)
+        if rc != 0:
+            raise DeviceError(f"hg_copy_ranked_values failed ({rc})")
+        out["bytes"] = blob[:g.n_bytes].tobytes()
+        return out
+
+    def ranked_values(self):
+        """The last ranking as a list of (value_bytes, count, pattern, line_number), with the segment as a fifth element after a
+        scan with segments, in the ranking's order."""
+        a = self.ranked_values_arrays()
+        off = a["off"].tolist()
+        rows = [(a["bytes"][off[j]:off[j + 1]], int(c), int(p), int(l)) for j, (c, p, l) in enumerate(zip(a["count"], a["pattern"], a["line_number"]))]
+        if a["segment"] is not None:
+            rows = [r + (int(s),) for r, s in zip(rows, a["segment"])]
+        return rows
+
+    def ranked_segments(self):
+        """The per-file arrays of the last ranking with per_segment=True as a dict of numpy uint64 arrays: first_value (n_seg + 1:
+        file s owns rows first_value[s] .. first_value[s + 1]), seg_distinct and seg_parts (n_seg: the file's distinct values
+        and its counted parts before the cut).  ValueError otherwise."""
+        import numpy as np
+
+        g = self._last_rank
+        if g is None or not g.d_first_value:
+            raise ValueError("no ranking with per_segment=True since the last scan")
+        out = {"first_value": np.zeros(g.n_seg + 1, dtype=np.uint64), "seg_distinct": np.zeros(g.n_seg, dtype=np.uint64), "seg_parts": np.zeros(g.n_seg, dtype=np.uint64)}
+        p64 = ctypes.POINTER(ctypes.c_uint64)
+        rc = lib().hg_copy_ranked_segments(self._h, out["first_value"].ctypes.data_as(p64), out["seg_distinct"].ctypes.data_as(p64), out["seg_parts"].ctypes.data_as(p64))
+        if rc != 0:
+            raise DeviceError(f"hg_copy_ranked_segments failed ({rc})")
+        return out
+
+    def copy_ranked_values_to(self, d_dst: int, max_bytes: int, stream: int = 0) -> int:
+        """Async device-to-device copy of the last ranking's bytes (the first max_bytes of them); returns the number copied."""
+        if self._last_rank is None:
+            raise ValueError("no ranking since the last scan")
+        n = min(max_bytes, self._last_rank.n_bytes)
+        rc = lib().hg_copy_ranked_values_device(self._h, ctypes.c_void_p(d_dst), n, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise DeviceError(f"hg_copy_ranked_values_device failed ({rc})")
         return n
 
     def count(self, accumulate: bool = False, per_segment: bool = False, stream: int = 0) -> CountStats:

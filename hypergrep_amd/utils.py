@@ -396,6 +396,66 @@ def count_values(file: str, patterns: list[str], flags: list[int] = (), ids: lis
     return rows, outcome[0]
 
 
+class RankParams(ctypes.Structure):
+    """hg_rank_params_t (include/hypergrep_amd.h)."""
+
+    _fields_ = [("flags", ctypes.c_uint32), ("hash_bits", ctypes.c_uint32), ("table_log2", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("top", ctypes.c_uint64)]
+
+
+_FILE_VALUES_EVENT = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                      ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64)
+
+
+def count_values_files(files: Sequence[str], patterns: list[str], flags: list[int] = (), ids: list[int] = (), by_pattern: bool = False, top: int = 0,
+                       buffer_size: int = 262140, totals: list | None = None) -> list[tuple[list, int]]:
+    """count_values() for many files in ONE native call (hg_hyperscan_files_values): small files are packed into one buffer and
+    share one GPU scan, with the values grouped per file, ordered by count and cut to the `top` most frequent of every file on
+    the GPU behind it (top=0: all of them).  One (rows, return code) per file, the rows shaped and sorted as count_values()
+    gives them (count descending, then value); the cut keeps the most frequent values, a tie at the cut going to the value
+    that occurs first in the file.  With top=0 it equals [count_values(f, ...) for f in files]; a missing or unreadable file
+    has return code 6 and no rows.  totals: a list that receives one (distinct values, counted parts) per file, both before
+    the cut."""
+    if top < 0:
+        raise ValueError("top must not be negative")
+    names = [os.fspath(name) for name in files]
+    c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags, ids=ids)
+    params = RankParams(flags=1 if by_pattern else 0, top=top)
+    rows: list = [[] for _ in names]
+    seen: list = [(0, 0)] * len(names)
+
+    def on_file(_context, index, data, off, counts, pattern, n_values, n_distinct, n_parts) -> None:
+        seen[index] = (n_distinct, n_parts)
+        if not n_values:
+            return
+        base = off[0]
+        blob = ctypes.string_at(ctypes.addressof(data.contents) + base, off[n_values] - base)
+        for j in range(n_values):
+            value = blob[off[j] - base:off[j + 1] - base]
+            rows[index].append((value, pattern[j], counts[j]) if by_pattern else (value, counts[j]))
+
+    callback = _FILE_VALUES_EVENT(on_file)
+    c_names = (ctypes.c_char_p * max(len(names), 1))(*[name.encode() for name in names])
+    summaries = (FileSummary * max(len(names), 1))()
+    engine = _get_hyperscanner_lib()
+    engine.hg_hyperscan_files_values.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint),
+                                                 ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.POINTER(ExprExt)), ctypes.c_uint, ctypes.c_int, ctypes.POINTER(RankParams),
+                                                 _FILE_VALUES_EVENT, ctypes.c_void_p, ctypes.POINTER(FileSummary)]
+    outcome = [0]
+
+    def native_call() -> None:
+        outcome[0] = engine.hg_hyperscan_files_values(c_names, len(names), c_patterns, c_flags, c_ids, None, len(c_patterns), buffer_size, ctypes.byref(params), callback, None,
+                                                      summaries)
+
+    if not _run_native(native_call):
+        return [([], _RC_INTERRUPTED)] * len(names)
+    if totals is not None:
+        totals[:] = seen
+    if outcome[0]:  # a failure of the whole call (the expressions do not compile): every file reports it, as count_values() would
+        return [([], outcome[0])] * len(names)
+    order = (lambda r: (-r[2], r[0], r[1])) if by_pattern else (lambda r: (-r[1], r[0]))
+    return [(sorted(rows[i], key=order) if not summaries[i].rc else [], summaries[i].rc) for i in range(len(names))]
+
+
 def count_files(files: Sequence[str], patterns: list[str], flags: list[int] = (), ids: list[int] = (), ext=None, buffer_size: int = 262140) -> list[tuple[dict, int]]:
     """count() for many files in ONE native call (hg_hyperscan_files_counts): small files are packed into one buffer and share
     one GPU scan, with the per-file counts taken behind it.  One ({id: (matching lines, reports)}, return code) per file, what

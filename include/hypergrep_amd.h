@@ -923,8 +923,8 @@ int hg_copy_part_lines_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_b
  * than 256 bytes), an insert pass into an open-addressing table of 64-bit slots claimed by compare-and-swap, with integer
  * atomics for count and first, a compaction and a sort by first, and the gathers' copy pass divided by output bytes.  Text is
  * read inside the parts only (whole aligned dwords: never past nbytes rounded up to 4).
- * Not offered: values per file, case folding, accumulation across scans on the device, and anything for the databases the
- * parts stage refuses. */
+ * Not offered: case folding, accumulation across scans on the device, and anything for the databases the parts stage
+ * refuses.  Values per file, an order by count and a cut to the most frequent are hg_rank_values' (below). */
 #define HG_VALUES_BY_PATTERN 1u /* the expression index is part of the key */
 typedef struct hg_values_params { /* sizeof 16 */
     uint32_t flags;               /* HG_VALUES_* */
@@ -968,6 +968,95 @@ typedef void (*hg_values_event)(void *context, const uint8_t *bytes, const uint6
 int hg_hyperscan_values(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
                         const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements,
                         const int buffer_size, const hg_values_params_t *params, hg_values_event on_values, void *context);
+
+/* The matched values ranked by count, per file if asked, and cut to the most frequent on the GPU (grep -o | sort | uniq -c |
+ * sort -rn | head): the distinct values of the last scan with parts on this scanner, ordered by count, of which only the kept
+ * rows' bytes are gathered and go to the host.  The stage runs after hg_scan_device_parts or hg_scan_device_segments_parts,
+ * on that scan's records, as hg_count_values does; it scans nothing and changes nothing about scanning or any other stage.
+ * Value.  As for hg_count_values.  A part whose piece has no record is not counted.
+ * Key.  The value's bytes; with HG_RANK_BY_PATTERN the pair (expression index, bytes); with HG_RANK_PER_SEGMENT additionally
+ * the part's segment, so that equal values in two files are two groups.
+ * Per group: count, the number of parts with the key; first, the smallest part index with it; pattern, line_number and
+ * segment those of part `first`.
+ * Order.  Ascending segment (only with HG_RANK_PER_SEGMENT), then descending count, then ascending first.  first is unique,
+ * so the order is total and every output is a function of the input alone: two runs give identical arrays.
+ * Cut.  top == 0 keeps every group.  Otherwise the first `top` groups of the whole scan are kept, or the first `top` of every
+ * segment with HG_RANK_PER_SEGMENT; a tie in count at the cut is decided by first (the smaller stays).
+ * Result.  The kept groups in that order, n_values of them: d_bytes holds their values joined, row j being
+ * d_bytes[d_off[j], d_off[j + 1]); d_count, d_first, d_pattern, d_line_number per row, d_segment too unless the last scan had
+ * no segments (NULL then).  With HG_RANK_PER_SEGMENT also d_first_value (n_seg + 1: segment s owns the rows
+ * [first_value[s], first_value[s + 1]); a file without parts owns an empty range), d_seg_distinct (n_seg: the segment's
+ * distinct values before the cut) and d_seg_parts (n_seg: the sum of the segment's groups' counts before the cut, so that a
+ * share can be computed from a cut result); all three NULL, and n_seg 0, without the flag.  n_distinct is the number of
+ * groups before the cut, n_parts the scan's parts, n_bytes the kept rows' bytes.  Zero parts is a success with n_values = 0.
+ * params (NULL: all defaults).  hash_bits and table_log2 mean what they mean in hg_values_params_t.
+ * HG_ERR_ARG, with nothing launched and the reason in hg_scanner_error: everything hg_count_values refuses (no successful
+ * scan, another text, a scan without parts, hash_bits above 64, table_log2 too small or above 40, scanner == NULL or
+ * result == NULL); unknown flag bits; HG_RANK_PER_SEGMENT after a scan without segments.  HG_ERR_NOMEM when the buffers do
+ * not fit (a part costs 44 bytes, a slot 32, a group 120, a segment 40, plus the kept rows' bytes; HG_RANK_PER_SEGMENT adds 8
+ * bytes a part and 24 a group).
+ * Lifetime.  The stage has buffers of its own.  The result stays valid until the next scan or hg_rank_values on this scanner;
+ * a refused or failed call leaves no earlier ranking behind.  The scan's results and any earlier hg_count_values,
+ * hg_gather_lines, hg_gather_parts or hg_count_records stay as they are.  rank_us: the stage in microseconds (HIP events; its
+ * host synchronisations included).
+ * The stage runs on the GPU: the values stage's hash, insert and compaction passes with the segment as a third key component
+ * (hypergrep_amd/csrc/hg_values.hip), two stable radix sorts, and the kernels of hypergrep_amd/csrc/hg_rank.hip (a lane per
+ * group or per segment; no atomics, no text reads), then the gathers' copy pass over the kept rows.
+ * Not offered: case folding, accumulation across scans on the device, a tie-break by value bytes, ranking across GPUs. */
+#define HG_RANK_BY_PATTERN 1u  /* the expression index is part of the key */
+#define HG_RANK_PER_SEGMENT 2u /* the segment is part of the key; order and cut are per segment */
+typedef struct hg_rank_params { /* sizeof 24 */
+    uint32_t flags;             /* HG_RANK_* */
+    uint32_t hash_bits;         /* 0: 64 */
+    uint32_t table_log2;        /* 0: from n_parts */
+    uint32_t reserved;
+    uint64_t top;               /* 0: no cut */
+} hg_rank_params_t;
+typedef struct hg_rank_result { /* sizeof 128 */
+    uint64_t n_values, n_distinct, n_parts, n_bytes;
+    const uint8_t *d_bytes;         /* DEVICE, valid until the next scan or hg_rank_values on this scanner */
+    const uint64_t *d_off;          /* n_values + 1 */
+    const uint64_t *d_count;        /* parts per row */
+    const uint64_t *d_first;        /* the smallest part index per row */
+    const uint32_t *d_pattern;      /* expression index of part `first` */
+    const uint64_t *d_line_number;  /* line_number of part `first` */
+    const uint32_t *d_segment;      /* segment of part `first`; NULL unless the last scan had segments */
+    const uint64_t *d_first_value;  /* n_seg + 1; NULL without HG_RANK_PER_SEGMENT, as the next two */
+    const uint64_t *d_seg_distinct; /* n_seg */
+    const uint64_t *d_seg_parts;    /* n_seg */
+    uint32_t n_seg, table_log2, rank_us, reserved;
+} hg_rank_result_t;
+int hg_rank_values(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, const hg_rank_params_t *params, void *stream,
+                   hg_rank_result_t *result);
+/* Copy the last ranking's first max_bytes bytes and the per-row arrays of its first max_values rows to host memory (any
+ * pointer may be NULL; off receives min(n_values, max_values) + 1 values).  HG_ERR_ARG without a ranking since the last scan,
+ * and for `segment` after a scan without segments. */
+int hg_copy_ranked_values(hg_scanner_t *scanner, uint8_t *bytes, uint64_t max_bytes, uint64_t *off, uint64_t *count, uint64_t *first,
+                          uint32_t *pattern, uint64_t *line_number, uint32_t *segment, uint64_t max_values);
+/* first_value (n_seg + 1 values), seg_distinct and seg_parts (n_seg each) of the last ranking (any pointer may be NULL);
+ * HG_ERR_ARG unless it was one with HG_RANK_PER_SEGMENT. */
+int hg_copy_ranked_segments(hg_scanner_t *scanner, uint64_t *first_value, uint64_t *seg_distinct, uint64_t *seg_parts);
+/* The bytes (the first max_bytes of them) into a DEVICE buffer, asynchronously on `stream`. */
+int hg_copy_ranked_values_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes, void *stream);
+/* The same for many files in one call: hg_hyperscan_files_parts' arguments, reader and packing (small plain files share one
+ * buffer and one GPU scan), with the parts stage and the rank stage behind every pack's scan, the latter with
+ * HG_RANK_PER_SEGMENT and params->top (params->flags may carry HG_RANK_BY_PATTERN only; NULL: defaults).  Only the kept rows
+ * are downloaded (bytes, offsets, counts, expression indices) and three numbers per file; no part record and no line leaves the
+ * GPU.  on_file is called once per file, in file order: row j of the file is bytes[off[j], off[j + 1]) (off[0] need not be 0),
+ * with count[j] and pattern[j]; n_values rows are kept of the file's n_distinct values, n_parts is the sum of the counts of all
+ * of them (before the cut).  A file without parts and a file that cannot be opened are called too, with zero rows; the latter
+ * has its own rc in `summaries`.  The pointers are valid during the call only.  Files of the per-file route (gzip, zstd, larger
+ * than a pack, every file when buffer_size < 2) go through hg_hyperscan_values' chunk merge inside the call, and the host
+ * applies the same order (count descending, then first occurrence in the file) and the same cut: a file's rows do not depend
+ * on the route it took.  summaries as for hg_hyperscan_files_parts (n_selected is 0 for a file of the per-file route).  Return
+ * codes and early refusals are hg_hyperscan_files_parts' and hg_hyperscan_values': bad params or on_file == NULL give the code
+ * of a bad buffer_count. */
+typedef void (*hg_file_values_event)(void *context, unsigned int file_index, const uint8_t *bytes, const uint64_t *off, const uint64_t *count,
+                                     const uint32_t *pattern, uint64_t n_values, uint64_t n_distinct, uint64_t n_parts);
+int hg_hyperscan_files_values(const char *const *file_names, unsigned int n_files, const char *const *patterns,
+                              const unsigned int *pattern_flags, const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext,
+                              const unsigned int elements, const int buffer_size, const hg_rank_params_t *params,
+                              hg_file_values_event on_file, void *context, hg_file_summary_t *summaries);
 
 /* Counts per report id (hg_count_records): which expressions fired, and on how many lines, without moving the record list.
  * Bins.  A bin is a distinct report id of the database, in ascending id order (hg_db_report_ids; n_bins <= n_patterns).

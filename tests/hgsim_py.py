@@ -80,6 +80,55 @@ class Db:
         return {"violations": bad, "filter_log2": out[0], "wide": out[1], "crowded_slots": out[2], "byte_windows": out[3], "shared_windows": out[4], "table_first": out[5],
                 "window_bytes": out[6]}
 
+    WINDOW_FIELDS = ("factor", "off", "value", "table", "probes", "way", "delta", "select", "bucket", "len", "pattern", "casebits")
+    TABLE_STATES = ("absent", "owner", "shared", "other")
+
+    def windows(self) -> list:
+        """Placement of every window of every literal (hostsim.cpp::hgsim_windows): where the verify pass finds it."""
+        fn = lib().hgsim_windows
+        fn.restype = ctypes.c_uint32
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32]
+        n = fn(self.h, None, 0)
+        out = (ctypes.c_uint32 * (12 * max(n, 1)))()
+        fn(self.h, out, n)
+        rows = []
+        for i in range(n):
+            r = dict(zip(self.WINDOW_FIELDS, out[12 * i:12 * i + 12]))
+            r["table"] = self.TABLE_STATES[r["table"]]
+            r["delta"] = r["delta"] - 256 if r["delta"] >= 128 else r["delta"]
+            rows.append(r)
+        return rows
+
+    VERIFY3_FIELDS = ("positions", "table_first", "buckets_only", "brute_force", "differing", "table_ends", "bucket_value_mismatch", "largest_bucket", "negative_at",
+                      "select_outside", "byte_compare_tail", "before_text", "mask_tail", "first_differing")
+
+    def verify3(self, data: bytes) -> dict:
+        """The verify pass at every probe position of `data`, by the table-first routine, by the buckets-only path and by brute
+        force (hostsim.cpp::hgsim_verify3)."""
+        fn = lib().hgsim_verify3
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+        fn.restype = None
+        buf = ctypes.create_string_buffer(data, (len(data) + 15 & ~15) + 16)  # readable up to the size rounded up to 16
+        out = (ctypes.c_uint64 * 14)()
+        fn(self.h, buf, len(data), out)
+        return dict(zip(self.VERIFY3_FIELDS, out))
+
+    CANDIDATE_FIELDS = ("candidates", "table_ends", "zero_pairs", "value_mismatch", "select_before", "select_behind", "negative_at", "verified")
+
+    def candidates(self, data: bytes, cap: int = 1 << 20):
+        """(counts, [(pos, class bits)]) of the positions of `data` the filter lets through: what the device's verify pass sees
+        (hostsim.cpp::hgsim_candidates; class bits in the order of CANDIDATE_FIELDS[1:])."""
+        fn = lib().hgsim_candidates
+        fn.restype = ctypes.c_uint64
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint8),
+                       ctypes.c_uint64]
+        buf = ctypes.create_string_buffer(data, (len(data) + 15 & ~15) + 16)
+        out = (ctypes.c_uint64 * 8)()
+        pos = (ctypes.c_uint64 * cap)()
+        cls = (ctypes.c_uint8 * cap)()
+        n = min(fn(self.h, buf, len(data), out, pos, cls, cap), cap)
+        return dict(zip(self.CANDIDATE_FIELDS, out)), [(pos[i], cls[i]) for i in range(n)]
+
     def tune(self, sample: bytes) -> int:
         lib().hgsim_tune.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         return lib().hgsim_tune(self.h, sample, len(sample))

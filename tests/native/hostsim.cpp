@@ -327,4 +327,263 @@ long hgsim_scan(void *h, const uint8_t *data, uint64_t nbytes, int buffer_size, 
   return static_cast<long>(kept.size());
 }
 void hgsim_free_hits(SimHit *p) { free(p); }
+
+// ---- verify pass: placement read-out and the buckets-only path (tests/verify_cells.py) ----------------------------------------
+// One record of 12 words per window of every literal, in the order of db->windows:
+//   0 factor index, 1 offset of the window in the literal, 2 value (folded), 3 table state (0 absent, 1 this window is the direct
+//   owner, 2 shared), 4 buckets probed before the value's (0: its home bucket), 5 way in that bucket, 6 discriminator delta
+//   (int8 as a byte), 7 discriminator byte-select bits, 8 size of the discriminated bucket this window lies in (found with the
+//   literal itself as the text), 9 literal length, 10 pattern index, 11 the literal's case bits.
+// Returns the number of windows (records beyond cap are not written).
+uint32_t hgsim_windows(void *h, uint32_t *out, uint32_t cap) {
+  HgDb *db = static_cast<HgDb *>(h);
+  const HgDbView v = view_of(db);
+  if (!db->nreal_factors) return 0;
+  uint32_t n = 0;
+  for (const HgWindow &w : db->windows) {
+    if (n < cap) {
+      uint32_t *r = out + static_cast<size_t>(n) * 12;
+      const HgFactor &f = db->factors[w.factor_off >> 8];
+      const uint32_t off = w.factor_off & 0xff;
+      r[0] = w.factor_off >> 8;
+      r[1] = off;
+      r[2] = w.value;
+      r[3] = 0, r[4] = 0, r[5] = 0;
+      uint32_t probes = 0;
+      for (uint32_t b = hg_wtab_bucket(w.value, db->wtab_mask);; b = (b + 1u) & db->wtab_mask, probes++) {
+        const HgWinBucket &e = db->wtab[b];
+        bool stop = false;
+        for (uint32_t k = 0; k < HG_WTAB_WAYS && !stop; k++) {
+          if (e.factor_off[k] == HG_WTAB_EMPTY) stop = true;
+          else if (e.value[k] == w.value) {
+            r[3] = e.factor_off[k] == HG_WTAB_SHARED ? 2u : (e.factor_off[k] == w.factor_off ? 1u : 3u);
+            r[4] = probes;
+            r[5] = k;
+            stop = true;
+          }
+        }
+        if (stop) break;
+      }
+      const uint32_t d = db->disc[hg_hash_window(w.value)];
+      r[6] = d & 0xFFu;
+      r[7] = d >> 8;
+      std::vector<uint8_t> text(f.lit, f.lit + f.len);
+      if (f.len < db->window_bytes) text.push_back(static_cast<uint8_t>(w.value >> 24));
+      uint32_t j0, j1;
+      hg_disc_range(v, text.data(), text.size(), off, w.value, &j0, &j1);
+      r[8] = j1 - j0;
+      r[9] = f.len;
+      r[10] = f.pattern;
+      r[11] = f.casebits;
+    }
+    n++;
+  }
+  return n;
+}
+
+// The literal compare of the verify kernel (literal_occurs in hg_kernels.hip) restated: dwords under hg_factor_mask_dword while
+// 16 / 32 bytes from fs are readable, bytes in the buffer's last 16 / 32.
+static bool sim_literal_occurs(const HgFactor &f, const uint8_t *text, uint64_t fs, uint64_t readable) {
+  const uint32_t len = f.len, cb = f.casebits;
+  uint32_t diff = 0;
+  if (fs + (len > 16 ? 32u : 16u) <= readable) {
+    for (uint32_t j = 0; j < (len > 16 ? 8u : 4u); j++) {
+      uint32_t x, l;
+      std::memcpy(&x, text + fs + 4 * j, 4);
+      std::memcpy(&l, f.lit + 4 * j, 4);
+      diff |= (x ^ l) & hg_factor_mask_dword(cb, len, j);
+    }
+  } else {
+    for (uint32_t b = 0; b < len; b++) diff |= (text[fs + b] ^ f.lit[b]) & (((cb >> b) & 1u) ? 0xDFu : 0xFFu);
+  }
+  return diff == 0;
+}
+
+// The verify pass over EVERY probe position of a text, three ways:
+//   A  hg_verify_window: the direct table first (what the host replay and the block-mode kernel run);
+//   B  the buckets-only path, what the verify kernel does for a set without wtab_first: the discriminated bucket of every
+//      position, the value compare inside it, the kernel's position checks and its literal compare (sim_literal_occurs);
+//   C  brute force: every window of every literal against the text's dword, every literal byte by byte, no table.
+// `text` must be readable up to nbytes rounded up to 16.  Each answer is the multiset of (pattern, literal start) per position;
+// out[0] positions, out[1..3] emits of A, B, C, out[4] positions where the three differ, out[5] positions the table ends
+// (value absent), out[6] positions whose bucket is not empty but holds no window of the value, out[7] the largest bucket met,
+// out[8] positions with a negative discriminator address (at < 0) whose selected bytes lie inside the text, out[9] positions
+// whose selected bytes lie outside the text, out[10] positions verified through a byte compare at the buffer's end,
+// out[11] windows whose literal would start before the text (pos < off), out[12] occurrences with another byte behind the
+// literal than its record holds there, inside a compared dword (the tail mask decides), out[13] the first differing position.
+void hgsim_verify3(void *h, const uint8_t *text, uint64_t nbytes, uint64_t *out) {
+  HgDb *db = static_cast<HgDb *>(h);
+  const HgDbView v = view_of(db);
+  for (int i = 0; i < 14; i++) out[i] = 0;
+  out[13] = ~0ull;
+  if (!db->nreal_factors) return;
+  const uint32_t step = db->dense ? db->dense : 4;
+  const uint64_t readable = (nbytes + 15) & ~15ull;
+  typedef std::vector<std::pair<uint32_t, uint64_t>> Answer;
+  for (uint64_t pos = 0; pos < nbytes; pos += step) {
+    uint32_t w = 0;
+    std::memcpy(&w, text + pos, nbytes - pos < 4 ? nbytes - pos : 4);
+    const uint32_t folded = (w | v.fold_mask) & v.window_mask;
+    Answer a, b, c;
+    hg_verify_window(v, text, nbytes, pos, w, [&](uint32_t pattern, uint64_t fs, uint32_t) { a.push_back({pattern, fs}); });
+    if (hg_wtab_find(v.wtab, v.wtab_mask, folded) == HG_WTAB_EMPTY) out[5]++;
+    {  // B
+      const uint32_t hh = hg_hash_window(folded), d = v.disc[hh], sel = d >> 8;
+      uint32_t key = 0, j0 = 0, cnt = 0;
+      bool inside = true;
+      if (sel) {
+        const int64_t at = static_cast<int64_t>(pos) + static_cast<int8_t>(d & 0xFFu);
+        const uint32_t lo = hg_ctz(sel), hi = 31u - hg_clz32(sel);
+        inside = at + static_cast<int64_t>(lo) >= 0 && static_cast<uint64_t>(at + hi) < nbytes;
+        if (!inside) out[9]++;
+        if (inside && at < 0) out[8]++;
+        if (inside) {
+          uint32_t x = 0;
+          if (at >= 0 && (at & 3) == 0) std::memcpy(&x, text + at, 4);  // (ends before the size rounded up to 4)
+          else
+            for (uint32_t q = lo; q <= hi; q++) x |= static_cast<uint32_t>(text[at + static_cast<int64_t>(q)]) << (8u * q);
+          key = (x | v.fold_mask) & hg_disc_bytes(sel);
+        }
+      }
+      if (inside) {
+        const uint32_t h2 = hg_disc_bucket(hh, key);
+        j0 = v.bucket_off2[h2];
+        cnt = v.bucket_off2[h2 + 1] - j0;
+      }
+      if (cnt > out[7]) out[7] = cnt;
+      bool value_seen = false;
+      for (uint32_t t = 0; t < cnt; t++) {
+        const HgWindow win = v.windows2[j0 + t];
+        if (win.value != folded) continue;
+        value_seen = true;
+        const uint32_t off = win.factor_off & 0xffu;
+        const HgFactor &f = v.factors[win.factor_off >> 8];
+        if (pos < off) { out[11]++; continue; }
+        if (pos - off + f.len > nbytes) continue;
+        const uint64_t fs = pos - off;
+        if (fs + (f.len > 16 ? 32u : 16u) > readable) out[10]++;
+        if (sim_literal_occurs(f, text, fs, readable)) b.push_back({f.pattern, fs});
+      }
+      if (cnt && !value_seen) out[6]++;
+    }
+    for (const HgWindow &win : db->windows) {  // C
+      if (win.value != folded) continue;
+      const uint32_t off = win.factor_off & 0xffu;
+      const HgFactor &f = db->factors[win.factor_off >> 8];
+      if (pos < off || pos - off + f.len > nbytes) continue;
+      bool same = true;
+      for (uint32_t q = 0; q < f.len && same; q++) {
+        const uint8_t x = text[pos - off + q], l = f.lit[q];
+        same = ((f.casebits >> q) & 1u) ? ((x | 0x20) == (l | 0x20)) : (x == l);
+      }
+      if (!same) continue;
+      c.push_back({f.pattern, pos - off});
+      // the byte behind the literal differs from the record's byte there, in a dword the compare loads: the tail mask decides
+      const uint64_t fs = pos - off;
+      if (f.len < HG_FACTOR_MAX && (f.len & 3u) && fs + (f.len > 16 ? 32u : 16u) <= readable && text[fs + f.len] != f.lit[f.len]) out[12]++;
+    }
+    std::sort(a.begin(), a.end());
+    std::sort(b.begin(), b.end());
+    std::sort(c.begin(), c.end());
+    out[0]++;
+    out[1] += a.size();
+    out[2] += b.size();
+    out[3] += c.size();
+    if (a != b || a != c) {
+      out[4]++;
+      if (out[13] == ~0ull) out[13] = pos;
+    }
+  }
+}
+
+// The stream pass's filter at one probe position, as hgsim_scan applies it (both levels): does `pos` become a candidate?
+static bool sim_filter_pass(HgDb *db, const HgDbView &v, const uint8_t *data, uint64_t nbytes, uint64_t pos, uint32_t w) {
+  const uint32_t folded = (w | v.fold_mask) & db->window_mask, byte_mask = ((1u << db->filter_log2) - 1u) << 2;
+  auto dword_at = [&](int64_t p) -> uint32_t {
+    uint32_t x = 0;
+    for (int b = 0; b < 4; b++)
+      if (p + b >= 0 && static_cast<uint64_t>(p + b) < nbytes) x |= static_cast<uint32_t>(data[p + b]) << (8 * b);
+    return x;
+  };
+  const uint32_t key0 = hg_hash_window(folded);
+  uint32_t sla = hg_slot(folded, db->weights_a, byte_mask) >> 2, slb = hg_slot(folded, db->weights_b, byte_mask) >> 2;
+  if (db->filter_wide) {
+    const uint32_t a = hg_dot4(folded, db->weights_a), b = hg_dot4(folded, db->weights_b);
+    sla = hg_slot_wide(a, b, byte_mask) >> 2, slb = hg_slot_wide(b, a, byte_mask) >> 2;
+  }
+  bool ha = hg_slot_match(db->filter[sla], key0), hb = false;
+  if (db->filter_wide) {
+    const uint32_t fp = key0 & 0xFFFFu, ta = db->filter[sla], tb = db->filter[slb];
+    ha = (ta & 0xFFFFu) == fp || (ta >> 16) == fp;
+    hb = (tb & 0xFFFFu) == fp || (tb >> 16) == fp;
+  }
+  if (!ha && !hb) return false;
+  if (db->filter_wide) return true;
+  const uint32_t pf = dword_at(static_cast<int64_t>(pos) - 4) | v.fold_mask, nf = dword_at(static_cast<int64_t>(pos) + db->window_bytes) | v.fold_mask;
+  const bool edge_prev = !db->dense && (pos % 1024) == 0, edge_next = !db->dense && (pos % 1024) == 1020;
+  auto pass = [&](uint32_t sl) {
+    return hg_slot_pass(db->ext[sl], folded, pf, nf, edge_prev ? 0u : 0xFFFFFFFFu, edge_next ? (HG_WINDOW_BYTES == 4 ? 0u : 0xFFu) : 0xFFFFFFFFu);
+  };
+  return (ha && pass(sla)) || (hb && pass(slb));
+}
+
+// What the verify pass meets at the CANDIDATES of a text (the positions the filter lets through: what the device kernel sees),
+// and per candidate its class.  cls[i] for the i-th candidate at pos[i] (up to cap): bit 0 the direct table holds no such
+// value, bit 1 the discriminated bucket is empty or skipped (zero pairs on the buckets-only path), bit 2 the bucket is not
+// empty and holds no window of the value, bit 3 a selected discriminator byte lies before the text (at + lo < 0), bit 4 one
+// lies at or behind nbytes, bit 5 at < 0 with every selected byte inside, bit 6 some literal verifies here.
+// out[0] candidates, out[1..7] candidates with each bit.  Returns the number of candidates.
+uint64_t hgsim_candidates(void *h, const uint8_t *text, uint64_t nbytes, uint64_t *out, uint64_t *pos_out, uint8_t *cls_out, uint64_t cap) {
+  HgDb *db = static_cast<HgDb *>(h);
+  const HgDbView v = view_of(db);
+  for (int i = 0; i < 8; i++) out[i] = 0;
+  if (!db->nreal_factors) return 0;
+  const uint32_t step = db->dense ? db->dense : 4;
+  uint64_t n = 0;
+  for (uint64_t pos = 0; pos < nbytes; pos += step) {
+    uint32_t w = 0;
+    std::memcpy(&w, text + pos, nbytes - pos < 4 ? nbytes - pos : 4);
+    if (!sim_filter_pass(db, v, text, nbytes, pos, w)) continue;
+    const uint32_t folded = (w | v.fold_mask) & v.window_mask;
+    uint8_t cls = 0;
+    if (hg_wtab_find(v.wtab, v.wtab_mask, folded) == HG_WTAB_EMPTY) cls |= 1;
+    const uint32_t hh = hg_hash_window(folded), d = v.disc[hh], sel = d >> 8;
+    uint32_t key = 0, cnt = 0, j0 = 0;
+    bool inside = true;
+    if (sel) {
+      const int64_t at = static_cast<int64_t>(pos) + static_cast<int8_t>(d & 0xFFu);
+      const uint32_t lo = hg_ctz(sel), hi = 31u - hg_clz32(sel);
+      if (at + static_cast<int64_t>(lo) < 0) cls |= 8;
+      if (static_cast<uint64_t>(at + hi) >= nbytes && at + static_cast<int64_t>(hi) >= 0) cls |= 16;
+      inside = !(cls & 24);
+      if (inside && at < 0) cls |= 32;
+      if (inside) {
+        uint32_t x = 0;
+        for (uint32_t q = lo; q <= hi; q++) x |= static_cast<uint32_t>(text[at + static_cast<int64_t>(q)]) << (8u * q);
+        key = (x | v.fold_mask) & hg_disc_bytes(sel);
+      }
+    }
+    if (inside) {
+      const uint32_t h2 = hg_disc_bucket(hh, key);
+      j0 = v.bucket_off2[h2];
+      cnt = v.bucket_off2[h2 + 1] - j0;
+    }
+    bool seen = false;
+    for (uint32_t t = 0; t < cnt; t++) seen = seen || v.windows2[j0 + t].value == folded;
+    if (cnt == 0) cls |= 2;
+    if (cnt && !seen) cls |= 4;
+    bool any = false;
+    hg_verify_window(v, text, nbytes, pos, w, [&](uint32_t, uint64_t, uint32_t) { any = true; });
+    if (any) cls |= 64;
+    out[0]++;
+    for (int b = 0; b < 7; b++)
+      if (cls >> b & 1) out[1 + b]++;
+    if (n < cap) {
+      pos_out[n] = pos;
+      cls_out[n] = cls;
+    }
+    n++;
+  }
+  return n;
+}
 }

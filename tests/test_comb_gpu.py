@@ -13,6 +13,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import chunk_texts
 import comb_ref
 import oracle_py
 
@@ -94,9 +95,17 @@ def reference(text, pats, flags, ids, bs):
     return comb_ref.apply_to_hits(cs, hits)
 
 
-def check(arena, text, pats, flags, ids, bs=262140):
-    got, patterns, _, _ = gpu_scan(arena, text, pats, flags, ids, bs)
-    want = reference(text, pats, flags, ids, bs)
+def reference_by_distinct_lines(text, pats, flags, ids, bs):
+    """The same reference with the oracle run once per DISTINCT line (texts of chunk_texts: every line shorter than the scan
+    buffer, long runs of repeated lines)."""
+    mini, which, starts = chunk_texts.distinct(text)
+    return chunk_texts.expand(reference(mini, pats, flags, ids, bs), mini, which, starts)
+
+
+def check(arena, text, pats, flags, ids, bs=262140, min_launches=0, ref=reference):
+    got, patterns, _, st = gpu_scan(arena, text, pats, flags, ids, bs)
+    assert st.stream_launches >= min_launches
+    want = ref(text, pats, flags, ids, bs)
     assert got == want, next(((g, w) for g, w in zip(got, want) if g != w), (len(got), len(want)))
     for (_, rid, _, _, _), p in zip(got, patterns):  # each hit names an expression with its id
         assert ids[p] == rid
@@ -171,12 +180,29 @@ def test_several_pipeline_chunks_and_segments(arena, monkeypatch):
     sc = device.Scanner(device.Database(pats, flags=flags, ids=ids), 0)
     raw = sc.scan(arena.place(text), len(text), buffer_size=1000).n_raw_hits
     assert raw > 4000
-    for env in ({"HG_CHUNK_TILES": "4"}, {"HG_HIT_LIMIT": str(raw * 3 // 4)}, {"HG_HIT_LIMIT": str(raw // 2)}):
+    for env in ({"HG_HIT_LIMIT": str(raw * 3 // 4)}, {"HG_HIT_LIMIT": str(raw // 2)}):
         with monkeypatch.context() as m:
             for k, v in env.items():
                 m.setenv(k, v)
             n, c = check(arena, text, pats, flags, ids, 1000)
             assert c > 1000, (env, n, c)
+    # three pipeline chunks of 1024 tiles (the engine honours no smaller one) on more than 2048 tiles: lines of make_text around
+    # the two cuts, a few repeated lines between them; the oracle runs once per distinct line
+    parts = [[ln + b"\n" for ln in make_text(rng, 1200).rstrip(b"\n").split(b"\n")] for _ in range(4)]
+    parts[2].append(b"user=abcd_12 status=503 " + b"q" * 300 + b" ERROR 42 failed; timeout=120ms\n")  # the line across the second cut
+    every = b"user=abcd_12 status=503; ERROR 42 failed; connection reset; timeout=120ms " + b"q " * 200
+    fillers = [b"lorem ipsum dolor " * 45 + b"\n", every + b"\n", b"0 " * 400 + b"\n", b"ERROR 42 failed " + b"q " * 300 + b"a1b2c3d4e5f6" * 8 + b"x\n",
+               b"connection reset; " + b"- " * 200 + b"timeout=120ms\n"]
+    big_text = chunk_texts.build(parts, fillers)
+    big = device.GuardedArena(chunk_texts.SIZE + 64)
+    try:
+        with monkeypatch.context() as m:
+            for k, v in chunk_texts.CHUNK_ENV.items():
+                m.setenv(k, v)
+            n, c = check(big, big_text, pats, flags, ids, 1000, min_launches=2, ref=reference_by_distinct_lines)
+            assert c > 1000, (n, c)
+    finally:
+        big.free()
 
 
 def test_hit_heavy_long_lines(arena):

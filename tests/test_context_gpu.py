@@ -10,6 +10,7 @@ import random
 
 import pytest
 
+import chunk_texts
 import context_ref
 import huge_cases
 import invert_ref
@@ -73,7 +74,7 @@ def re_matching(text, pats, flags, ids, need, bs, line_base):
     return lines, len(pcs)
 
 
-def check(arena, text, pats, flags=None, ids=None, bs=262140, line_base=0, need=None, by_re=False, invert=False, calls=((2, 3, 0, False),)):
+def check(arena, text, pats, flags=None, ids=None, bs=262140, line_base=0, need=None, by_re=False, invert=False, calls=((2, 3, 0, False),), min_launches=0):
     """One scanner, one text: for every (before, after, carry_after, tail) of `calls`, the scan with context leaves the hits of
     the scan without, and context() equals the reference.  Returns [(n_context, n_tail)] per call and the piece count."""
     from hypergrep_amd import device
@@ -97,6 +98,7 @@ def check(arena, text, pats, flags=None, ids=None, bs=262140, line_base=0, need=
         where = (pats, bs, len(text), line_base, before, after, carry, tail, invert)
         st = sc.scan(ptr, len(text), buffer_size=bs, line_base=line_base, invert=invert, context=(before, after), carry_after=carry, tail=tail)
         assert sc.hits() == plain_hits, where  # hits() is identical to the scan without context
+        assert plain.stream_launches >= min_launches and st.stream_launches >= min_launches, where
         assert (st.n_hits, st.n_lines, st.n_candidates, st.n_raw_hits) == (plain.n_hits, plain.n_lines, plain.n_candidates, plain.n_raw_hits), where
         got = sc.context()
         want, owed, n_tail = context_ref.expected(text, bs, matching, before, after, line_base, carry, tail)
@@ -222,6 +224,14 @@ def test_chaining_identity_on_the_device(arena):
         assert base == n and sorted(rows) == whole, cut
 
 
+def chunked_text(rng: random.Random) -> bytes:
+    """More than 2048 tiles (chunk_texts): lines of log_text around the two cuts, a few repeated lines between them."""
+    parts = [log_text(rng, 40000, share=0.3).splitlines(keepends=True) for _ in range(4)]
+    parts[2].append(b"abc zz needle-in-hay " + b"q" * 300 + b" ERROR 42 failed\n")  # the line across the second cut
+    fillers = [b"lorem ipsum dolor " * 45 + b"\n", b"zz - needle-in-hay " + b"quiet " * 100 + b"\n", b"12x " * 200 + b"\n", b"user=q " * 120 + b"\n", b"- " * 300 + b"\n"]
+    return chunk_texts.build(parts, fillers)
+
+
 def test_pipeline_chunks_and_segmented_scans(arena, monkeypatch):
     """A buffer the engine scans in several pipeline chunks, or in segments whose hits are put one after the other: the
     context stage runs once over the whole buffer's tile states and the concatenated hits."""
@@ -232,12 +242,23 @@ def test_pipeline_chunks_and_segmented_scans(arena, monkeypatch):
     sc = device.Scanner(device.Database(LITERALS + ["abc"], flags=[6] * 3, ids=[0, 1, 2]), 0)
     raw = sc.scan(arena.place(text), len(text), buffer_size=1000).n_raw_hits
     assert raw > 4000
-    for env in ({"HG_CHUNK_TILES": "4"}, {"HG_HIT_LIMIT": str(raw * 3 // 4)}, {"HG_HIT_LIMIT": str(raw * 11 // 20)}):  # (segments are 16 tiles at least)
+    for env in ({"HG_HIT_LIMIT": str(raw * 3 // 4)}, {"HG_HIT_LIMIT": str(raw * 11 // 20)}):  # (segments are 16 tiles at least)
         with monkeypatch.context() as m:
             for k, v in env.items():
                 m.setenv(k, v)
             counts, n = check(arena, text, LITERALS + ["abc"], [6] * 3, bs=1000, calls=[(1, 1, 0, True)])
             assert 500 < counts[0][0] < n, env
+    # three pipeline chunks of 1024 tiles (the engine honours no smaller one): the matching lines by the `re` brute force, once
+    # per distinct line
+    big = device.GuardedArena(chunk_texts.SIZE + 64)
+    try:
+        with monkeypatch.context() as m:
+            for k, v in chunk_texts.CHUNK_ENV.items():
+                m.setenv(k, v)
+            counts, n = check(big, chunked_text(rng), LITERALS + ["abc"], [6] * 3, bs=1000, by_re=True, calls=[(1, 1, 0, True)], min_launches=2)
+            assert 500 < counts[0][0] < n
+    finally:
+        big.free()
 
 
 def test_inverted_scan_with_context(arena):

@@ -12,6 +12,7 @@ import re
 
 import pytest
 
+import chunk_texts
 import huge_cases
 import invert_ref
 import oracle_py
@@ -69,7 +70,7 @@ def re_matching(text, pats, flags, ids, need, bs, line_base):
     return lines, len(pcs)
 
 
-def check(arena, text, pats, flags=None, ids=None, bs=262140, line_base=0, need=None, by_re=False):
+def check(arena, text, pats, flags=None, ids=None, bs=262140, line_base=0, need=None, by_re=False, min_launches=0):
     """The inverted scan equals the reference and complements the normal scan.  Returns (selected, pieces)."""
     from hypergrep_amd import device
 
@@ -80,6 +81,7 @@ def check(arena, text, pats, flags=None, ids=None, bs=262140, line_base=0, need=
     normal = sc.scan(ptr, len(text), buffer_size=bs, line_base=line_base)
     normal_lines = {h[0] for h in sc.hits()}
     inverted = sc.scan(ptr, len(text), buffer_size=bs, line_base=line_base, invert=True)
+    assert normal.stream_launches >= min_launches and inverted.stream_launches >= min_launches
     got = sc.hits()
     starts = sc.hit_starts()
     if by_re:
@@ -141,6 +143,14 @@ def test_every_line_matches_and_no_line_matches(arena):
     assert check(arena, text, LITERALS, bs=10)[0] > 0  # pieces of 9 bytes: most hold no match
 
 
+def chunked_text(rng: random.Random) -> bytes:
+    """More than 2048 tiles (chunk_texts): lines of log_text around the two cuts, a few repeated lines between them."""
+    parts = [log_text(rng, 40000).splitlines(keepends=True) for _ in range(4)]
+    parts[2].append(b"abc zz needle-in-hay " + b"q" * 300 + b" ERROR 42 failed\n")  # the line across the second cut
+    fillers = [b"lorem ipsum dolor " * 45 + b"\n", b"zz - needle-in-hay " + b"quiet " * 100 + b"\n", b"12x " * 200 + b"\n"]
+    return chunk_texts.build(parts, fillers)
+
+
 def test_pipeline_chunks_and_segmented_scans(arena, monkeypatch):
     """A buffer the engine scans in several pipeline chunks, or in segments whose hits are put one after the other: the invert
     stage runs once over the whole buffer's tile states and the concatenated hits."""
@@ -151,12 +161,23 @@ def test_pipeline_chunks_and_segmented_scans(arena, monkeypatch):
     sc = device.Scanner(device.Database(LITERALS + ["abc"], flags=[6] * 3, ids=[0, 1, 2]), 0)
     raw = sc.scan(arena.place(text), len(text), buffer_size=1000).n_raw_hits
     assert raw > 4000
-    for env in ({"HG_CHUNK_TILES": "4"}, {"HG_HIT_LIMIT": str(raw * 3 // 4)}, {"HG_HIT_LIMIT": str(raw * 11 // 20)}):  # (segments are 16 tiles at least)
+    for env in ({"HG_HIT_LIMIT": str(raw * 3 // 4)}, {"HG_HIT_LIMIT": str(raw * 11 // 20)}):  # (segments are 16 tiles at least)
         with monkeypatch.context() as m:
             for k, v in env.items():
                 m.setenv(k, v)
             selected, n = check(arena, text, LITERALS + ["abc"], [6] * 3, bs=1000)
             assert 1000 < selected < n, env
+    # three pipeline chunks of 1024 tiles (the engine honours no smaller one): the matching lines by the `re` brute force, once
+    # per distinct line
+    big = device.GuardedArena(chunk_texts.SIZE + 64)
+    try:
+        with monkeypatch.context() as m:
+            for k, v in chunk_texts.CHUNK_ENV.items():
+                m.setenv(k, v)
+            selected, n = check(big, chunked_text(rng), LITERALS + ["abc"], [6] * 3, bs=1000, by_re=True, min_launches=2)
+            assert 1000 < selected < n
+    finally:
+        big.free()
 
 
 def test_quiet_combination_and_min_length(arena):

@@ -12,6 +12,7 @@ import tempfile
 
 import pytest
 
+import chunk_texts
 import somsim_py
 from minlensim_py import COMBINATION, QUIET, SINGLE, SOM, expected_piece, exts_for
 
@@ -181,8 +182,8 @@ def test_combinations_and_quiet_see_surviving_reports_only(arena):
 
 
 def test_many_lines_pipeline_chunks_and_segments(arena, monkeypatch):
-    # small pipeline chunks (several stream launches), and a report limit below the text's reports: the scan is split into
-    # segments, each of which filters its own raw reports before its finalize
+    # a report limit below the text's reports: the scan is split into segments, each of which filters its own raw reports
+    # before its finalize; and three pipeline chunks (several stream launches)
     from hypergrep_amd import device
 
     rng = random.Random(14)
@@ -195,13 +196,35 @@ def test_many_lines_pipeline_chunks_and_segments(arena, monkeypatch):
     raw = sc.scan(arena.place(text), len(text), buffer_size=1000).n_raw_hits
     want = expected(text, pats, flags, ids, need, 1000)
     assert raw > len(want) > 4000
-    for env in ({"HG_CHUNK_TILES": "4"}, {"HG_HIT_LIMIT": str(raw * 3 // 4)}, {"HG_HIT_LIMIT": str(raw // 3)}):
+    for env in ({"HG_HIT_LIMIT": str(raw * 3 // 4)}, {"HG_HIT_LIMIT": str(raw // 3)}):
         with monkeypatch.context() as m:
             for k, v in env.items():
                 m.setenv(k, v)
             got, stats = gpu_hits(arena, text, pats, flags, ids, need, 1000)
             assert got == want, env
             assert stats.n_raw_hits >= raw  # (segments overlap: a piece's reports may be counted by two passes before they are dropped)
+    # chunks of 1024 tiles (the engine honours no smaller one) on more than 2048 tiles: lines of the pool around the two cuts, a
+    # few repeated lines between them
+    pool = line_pool(rng, ["anchored", "byte_windows", "always_on_1w", "always_on_2w"], 60)
+    parts = [[ln + b"\n" for ln in make_text(rng, pool, 1500).rstrip(b"\n").split(b"\n")] for _ in range(4)]
+    parts[2].append(b"abc12345 ERROR 4 failed " + b"q" * 300 + b" user=abcdefgh_12 status=599 timeout=12345ms\n")  # the line across the second cut
+    fillers = [b"lorem ipsum dolor " * 45 + b"\n", b"zz needle-in-hay abc1 abc12345 " + b"lorem " * 140 + b"\n", b"- " * 300 + b"\n",
+               b"ERROR 1234 failed; 12345x " + b"q " * 300 + b"timeout=123ms\n"]
+    big_text = chunk_texts.build(parts, fillers)
+    big = device.GuardedArena(chunk_texts.SIZE + 64)
+    try:
+        raw = gpu_hits(big, big_text, pats, flags, ids, need, 1000)[1].n_raw_hits
+        want = expected(big_text, pats, flags, ids, need, 1000)
+        assert raw > len(want) > 4000
+        with monkeypatch.context() as m:
+            for k, v in chunk_texts.CHUNK_ENV.items():
+                m.setenv(k, v)
+            got, stats = gpu_hits(big, big_text, pats, flags, ids, need, 1000)
+            assert stats.stream_launches >= 2
+            assert got == want
+            assert stats.n_raw_hits >= raw
+    finally:
+        big.free()
 
 
 # ---- Face A

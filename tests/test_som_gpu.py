@@ -11,6 +11,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import chunk_texts
 import somsim_py
 from somsim_py import SOM, start_by_brute_force
 
@@ -59,13 +60,14 @@ def scan_with_starts(arena, text, pats, flags, ids, bs):
 
     db = device.Database(pats, flags=flags, ids=ids)
     sc = device.Scanner(db, 0)
-    sc.scan(arena.place(text), len(text), buffer_size=bs)
-    return sc.hits_array(), sc.hit_starts()
+    stats = sc.scan(arena.place(text), len(text), buffer_size=bs)
+    return sc.hits_array(), sc.hit_starts(), stats
 
 
-def check_set(arena, text, pats, flags, ids, bs, brute=True):
-    got, starts = scan_with_starts(arena, text, pats, flags, ids, bs)
-    plain, plain_starts = scan_with_starts(arena, text, pats, [f & ~SOM for f in flags], ids, bs)
+def check_set(arena, text, pats, flags, ids, bs, brute=True, min_launches=0):
+    got, starts, stats = scan_with_starts(arena, text, pats, flags, ids, bs)
+    plain, plain_starts, plain_stats = scan_with_starts(arena, text, pats, [f & ~SOM for f in flags], ids, bs)
+    assert stats.stream_launches >= min_launches and plain_stats.stream_launches >= min_launches
     assert np.array_equal(got, plain), "the flag changed the reports"
     assert not plain_starts.any(), "a database without SOM reports from = 0"
     assert len(starts) == len(got)
@@ -79,7 +81,7 @@ def check_set(arena, text, pats, flags, ids, bs, brute=True):
         if rid not in som_ids:
             assert frm == 0
             continue
-        key = (start, ln)
+        key = line  # (each distinct piece goes through the host routine once)
         if key not in piece_cache:
             piece_cache[key] = {(r[0], r[1]): r[2] for r in host.piece(line)}
         assert frm == piece_cache[key][(rid, to)], (line, rid, to, frm)
@@ -112,8 +114,8 @@ def test_shared_ids_and_mixed_som(arena):
 
 
 def test_several_pipeline_chunks_and_segments(arena, monkeypatch):
-    # small pipeline chunks (several stream launches), and a report limit below the text's reports (the scan is split into
-    # segments whose hits, and starts, are put one after the other)
+    # a report limit below the text's reports (the scan is split into segments whose hits, and starts, are put one after the
+    # other), and three pipeline chunks (several stream launches)
     from hypergrep_amd import device
 
     rng = random.Random(8)
@@ -125,11 +127,24 @@ def test_several_pipeline_chunks_and_segments(arena, monkeypatch):
     sc = device.Scanner(device.Database(pats, flags=flags, ids=ids), 0)
     raw = sc.scan(arena.place(text), len(text), buffer_size=1000).n_raw_hits
     assert raw > 4000
-    for env in ({"HG_CHUNK_TILES": "4"}, {"HG_HIT_LIMIT": str(raw * 3 // 4)}):
+    with monkeypatch.context() as m:
+        m.setenv("HG_HIT_LIMIT", str(raw * 3 // 4))
+        assert check_set(arena, text, pats, flags, ids, 1000, brute=False) > 4000
+    # chunks of 1024 tiles (the engine honours no smaller one) on more than 2048 tiles: lines of make_text around the two cuts,
+    # a few repeated lines between them
+    parts = [[ln + b"\n" for ln in make_text(rng, 1200).rstrip(b"\n").split(b"\n")] for _ in range(4)]
+    parts[2].append(b"user=abcd_12 status=503 " + b"q" * 300 + b" ERROR 42 failed; timeout=120ms\n")  # the line across the second cut
+    fillers = [b"lorem ipsum dolor " * 45 + b"\n", b"zz user=abcd_12 status=503 " + b"- " * 200 + b"ERROR 42 failed\n", b"0 " * 400 + b"\n",
+               b"connection reset " + b"a1b2c3d4e5f6" * 8 + b"x " + b"q " * 250 + b"timeout=120ms\n"]
+    big_text = chunk_texts.build(parts, fillers)
+    big = device.GuardedArena(chunk_texts.SIZE + 64)
+    try:
         with monkeypatch.context() as m:
-            for k, v in env.items():
+            for k, v in chunk_texts.CHUNK_ENV.items():
                 m.setenv(k, v)
-            assert check_set(arena, text, pats, flags, ids, 1000, brute=False) > 4000
+            assert check_set(big, big_text, pats, flags, ids, 1000, brute=False, min_launches=2) > 4000
+    finally:
+        big.free()
 
 
 def test_large_synthetic_buffer_sampled(arena):

@@ -37,6 +37,10 @@ def lib() -> ctypes.CDLL:
         _lib.flowsim_free.argtypes = [ctypes.c_void_p]
         _lib.flowsim_hold.restype = ctypes.c_uint32
         _lib.flowsim_hold.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+        _lib.flowsim_group_span.restype = ctypes.c_uint32
+        _lib.flowsim_group_span.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+        _lib.flowsim_words.restype = ctypes.c_uint32
+        _lib.flowsim_words.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
         _lib.flowsim_block.restype = ctypes.c_long
         _lib.flowsim_block.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]
         _lib.flowsim_deliver.restype = ctypes.c_long
@@ -62,6 +66,13 @@ class Db:
 
     def hold(self, i: int) -> bool:
         return bool(lib().flowsim_hold(self.h, i))
+
+    def group_span(self, g: int) -> int:
+        """Words of tables of hg_flow_scan_kernel's group g (`hi - lo`: staged in LDS up to HG_BLOCK_SMALL_POOL words)."""
+        return lib().flowsim_group_span(self.h, g)
+
+    def words(self, i: int) -> int:
+        return lib().flowsim_words(self.h, i)
 
     def block(self, data: bytes):
         """{(expression, end)} of hg_nfa_scan over data."""

@@ -35,6 +35,18 @@ uint32_t flowsim_hold(void *h, uint32_t i) {
   return hg_flow_hold_flags(db.pool.data(), db.patterns.data(), static_cast<uint32_t>(db.patterns.size()))[i] ? 1u : 0u;
 }
 
+// Words of automaton tables of group g (expressions [g * HG_FLOW_PPW, ...)) by hg_flow_scan_kernel's formula: the kernel stages
+// the group in LDS when this is at most HG_BLOCK_SMALL_POOL (flowsim_pool_words), else reads the tables from HBM.
+uint32_t flowsim_group_span(void *h, uint32_t g) {
+  const HgDb &db = *static_cast<HgDb *>(h);
+  const uint32_t np = static_cast<uint32_t>(db.patterns.size());
+  const uint32_t first = g * HG_FLOW_PPW, last = std::min(first + HG_FLOW_PPW, np);
+  if (first >= last) return 0;
+  const HgPattern &pl = db.patterns[last - 1];
+  return pl.acc_off + 20u * pl.nw - db.patterns[first].reach_off;
+}
+uint32_t flowsim_words(void *h, uint32_t i) { return static_cast<HgDb *>(h)->patterns[i].nw; }
+
 // Raw ends of every expression over data[0, len) as one block: out[2 k] = expression, out[2 k + 1] = end.
 long flowsim_block(void *h, const uint8_t *data, uint32_t len, uint32_t *out, size_t cap) {
   const HgDb &db = *static_cast<HgDb *>(h);

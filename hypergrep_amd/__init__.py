@@ -20,6 +20,7 @@ from hypergrep_amd.utils import (  # the reference package re-exports exactly th
     count_files,
     count_values,
     count_values_files,
+    count_values_top,
     grep,
     grep_files,
     prepare_patterns,
@@ -41,5 +42,7 @@ __all__ = [
     "count_values",
     # ... for many files in one native call, ranked by count and cut to the most frequent of every file on the GPU
     "count_values_files",
+    # ... for one file of any number of chunks, accumulated in a value store on the GPU and cut to the most frequent there
+    "count_values_top",
 ]
 __version__ = "0.1.0"

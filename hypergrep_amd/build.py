@@ -29,9 +29,9 @@ if os.environ.get("HG_BUILD_OUT"):
     OBJ = LIB + ".obj"
     LIBHS_NAME = os.path.basename(LIB) + ".libhs.so.5"
 
-HIP_SOURCES = ["hg_stream.hip", "hg_kernels.hip", "hg_always_on.hip", "hg_huge.hip", "hg_som.hip", "hg_comb.hip", "hg_invert.hip", "hg_context.hip", "hg_parts.hip", "hg_segments.hip", "hg_segctx.hip", "hg_segparts.hip", "hg_gather.hip", "hg_partlines.hip", "hg_values.hip", "hg_rank.hip", "hg_counts.hip", "hg_flows.hip", "hg_batch.hip", "hg_engine.hip", "hg_capi.hip", "hg_shim.hip", "hg_hsface.hip"]
+HIP_SOURCES = ["hg_stream.hip", "hg_kernels.hip", "hg_always_on.hip", "hg_huge.hip", "hg_som.hip", "hg_comb.hip", "hg_invert.hip", "hg_context.hip", "hg_parts.hip", "hg_segments.hip", "hg_segctx.hip", "hg_segparts.hip", "hg_gather.hip", "hg_partlines.hip", "hg_values.hip", "hg_rank.hip", "hg_valstore.hip", "hg_counts.hip", "hg_flows.hip", "hg_batch.hip", "hg_engine.hip", "hg_capi.hip", "hg_shim.hip", "hg_hsface.hip"]
 CXX_SOURCES = ["hg_compile.cpp"]
-HEADERS = ["hg_mem.h", "hg_db.h", "hg_core.h", "hg_post.h", "hg_engine.h", "hg_compile.h", "hg_synth.h", "hg_confirm_dev.h", "hg_sink_dev.h", "hg_tables_dev.h", "hg_som.h", "hg_comb.h", "hg_invert.h", "hg_context.h", "hg_parts.h", "hg_parts_dev.h", "hg_segments.h", "hg_segctx.h", "hg_segparts.h", "hg_gather.h", "hg_partlines.h", "hg_values.h", "hg_values_dev.h", "hg_rank.h", "hg_counts.h", "hg_wave_dev.h", "hg_flows.h", "hg_flow_rules.h", "hg_batch.h", "hg_batch_launch.h"]
+HEADERS = ["hg_mem.h", "hg_db.h", "hg_core.h", "hg_post.h", "hg_engine.h", "hg_compile.h", "hg_synth.h", "hg_confirm_dev.h", "hg_sink_dev.h", "hg_tables_dev.h", "hg_som.h", "hg_comb.h", "hg_invert.h", "hg_context.h", "hg_parts.h", "hg_parts_dev.h", "hg_segments.h", "hg_segctx.h", "hg_segparts.h", "hg_gather.h", "hg_partlines.h", "hg_values.h", "hg_values_dev.h", "hg_rank.h", "hg_valstore.h", "hg_counts.h", "hg_wave_dev.h", "hg_flows.h", "hg_flow_rules.h", "hg_batch.h", "hg_batch_launch.h"]
 
 
 def _hipcc() -> str:
@@ -56,6 +56,8 @@ STAGE_SOURCES = ("hg_partlines.hip",)
 VALUES_SOURCES = ("hg_values.hip",)
 # ... and that one as well: lib/kernel_resources_rank.json
 RANK_SOURCES = ("hg_rank.hip",)
+# ... and that one: lib/kernel_resources_valstore.json
+VALSTORE_SOURCES = ("hg_valstore.hip",)
 
 
 def _compile_kernels(cmd: list[str], table_path: str) -> None:
@@ -183,6 +185,27 @@ def _merge_rank_resources() -> None:
             raise RuntimeError(f"{kernel} uses {', '.join(used)}: the rank stage's lanes keep a group or a segment in registers")
 
 
+def _merge_valstore_resources() -> None:
+    """lib/kernel_resources_valstore.json = the tables of VALSTORE_SOURCES; refuse scratch, spills or a dynamic stack in the value store."""
+    import json
+
+    table = {}
+    for src in VALSTORE_SOURCES:
+        path = os.path.join(OBJ, src + ".resources.json")
+        if os.path.exists(path):
+            with open(path, encoding="utf-8") as f:
+                table.update(json.load(f))
+    with open(os.path.join(LIB_DIR, "kernel_resources_valstore.json"), "w", encoding="utf-8") as f:
+        json.dump(table, f, indent=1, sort_keys=True)
+    for kernel, res in table.items():
+        used = [f"{res[key]} {what}" for key, what in (("ScratchSize [bytes/lane]", "bytes of scratch per lane"), ("VGPRs Spill", "spilled VGPRs"), ("SGPRs Spill", "spilled SGPRs"))
+                if res.get(key, 0) > 0]
+        if res.get("Dynamic Stack") not in (None, 0, "False"):
+            used.append("a dynamic stack")
+        if "hg_valstore_" in kernel and used:
+            raise RuntimeError(f"{kernel} uses {', '.join(used)}: the value store probes and compares in registers")
+
+
 def build(verbose: bool = False, force: bool = False) -> str:
     from concurrent.futures import ThreadPoolExecutor
 
@@ -208,7 +231,7 @@ def build(verbose: bool = False, force: bool = False) -> str:
 
     def run(job) -> None:
         src, cmd = job
-        if src in KERNEL_SOURCES or src in STAGE_SOURCES or src in VALUES_SOURCES or src in RANK_SOURCES:
+        if src in KERNEL_SOURCES or src in STAGE_SOURCES or src in VALUES_SOURCES or src in RANK_SOURCES or src in VALSTORE_SOURCES:
             _compile_kernels(cmd, os.path.join(OBJ, src + ".resources.json"))
         else:
             subprocess.check_call(cmd)
@@ -220,6 +243,7 @@ def build(verbose: bool = False, force: bool = False) -> str:
     _merge_stage_resources()
     _merge_values_resources()
     _merge_rank_resources()
+    _merge_valstore_resources()
     if force or _stale(LIB, objs + [os.path.join(CSRC, "exports.map")]):
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-o", LIB] + objs + ["-lz", "-ldl", "-Wl,-Bsymbolic", "-Wl,-soname,libhyperscanner.so",
                                                                                 "-Wl,--version-script=" + os.path.join(CSRC, "exports.map")]

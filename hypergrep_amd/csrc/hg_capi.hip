@@ -50,6 +50,10 @@ struct hg_scanner {
   // the rank stage's own buffers (made by the first hg_rank_values) and its last result (zeroes after a scan)
   HgRank *rank = nullptr;
   hg_rank_result_t last_rank = {};
+  // the value store (made by the first hg_accumulate_values; it survives scans) and its last ranking (zeroes after an accumulate
+  // or a reset)
+  HgValueStore *store = nullptr;
+  hg_acc_rank_result_t last_acc_rank = {};
 };
 
 static_assert(HG_ID_CONTEXT == HG_CTX_ID_CONTEXT && HG_ID_CONTEXT_TAIL == HG_CTX_ID_TAIL, "the context records carry the ids the header names");
@@ -69,6 +73,8 @@ static_assert(HG_PARTS_NUMBER == HG_PARTLINES_NUMBER && HG_PARTS_BYTE_OFFSET == 
 static_assert(HG_VALUES_BY_PATTERN == HG_VALUES_F_BY_PATTERN && sizeof(hg_values_params_t) == 16 && sizeof(hg_values_result_t) == 88, "the values stage's flag is the header's");
 static_assert(HG_RANK_BY_PATTERN == HG_RANK_F_BY_PATTERN && HG_RANK_PER_SEGMENT == HG_RANK_F_PER_SEGMENT && sizeof(hg_rank_params_t) == 24 && sizeof(hg_rank_result_t) == 128,
               "the rank stage's flags are the header's");
+static_assert(HG_ACC_BY_PATTERN == HG_VALSTORE_F_BY_PATTERN && sizeof(hg_acc_params_t) == 16 && sizeof(hg_acc_result_t) == 56 && sizeof(hg_acc_rank_result_t) == 88,
+              "the value store's flag is the header's");
 
 static void put_err(char *err, size_t errlen, const std::string &msg) {
   if (err && errlen) std::snprintf(err, errlen, "%s", msg.c_str());
@@ -146,6 +152,7 @@ void hg_scanner_destroy(hg_scanner_t *scanner) {
   delete scanner->partlines;
   delete scanner->values;
   delete scanner->rank;
+  delete scanner->store;
   delete scanner->sc;
   delete scanner;
 }
@@ -588,6 +595,112 @@ int hg_copy_ranked_values_device(hg_scanner_t *scanner, void *d_dst, uint64_t ma
   if (!nb) return HG_OK;
   if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
   return hipMemcpyAsync(d_dst, g.d_bytes, nb, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)) == hipSuccess ? HG_OK : HG_ERR_HIP;
+}
+
+int hg_accumulate_values(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, const hg_acc_params_t *params, void *stream, hg_acc_result_t *result) {
+  if (!scanner) return HG_ERR_ARG;
+  if (result) *result = hg_acc_result_t{};
+  const hg_acc_params_t p = params ? *params : hg_acc_params_t{0, 0, 0, 0};
+  const bool seg = scanner->last_seg.d_first_record != nullptr, reset = (p.flags & HG_ACC_RESET) != 0;
+  const uint64_t n_parts = scanner->last_with_parts ? scanner->last_parts.n_parts : 0;
+  const uint32_t hash_bits = p.hash_bits ? p.hash_bits : 64;
+  const char *why = !result                                                            ? "hg_accumulate_values: result is NULL"
+                    : !scanner->scanned                                                ? "hg_accumulate_values: no successful scan to accumulate the values of"
+                    : (d_text != scanner->last_text || nbytes != scanner->last_nbytes) ? "hg_accumulate_values: d_text and nbytes are not those of the last scan"
+                    : !scanner->last_with_parts                                        ? "hg_accumulate_values: the last scan was not one with parts (hg_scan_device_parts, hg_scan_device_segments_parts)"
+                    : (p.flags & ~(HG_ACC_BY_PATTERN | HG_ACC_RESET))                  ? "hg_accumulate_values: unknown flag bits"
+                    : p.hash_bits > 64                                                 ? "hg_accumulate_values: hash_bits above 64"
+                    : p.table_log2 > HG_VALUES_MAX_TABLE_LOG2                          ? "hg_accumulate_values: table_log2 above 40"
+                    : (p.table_log2 && (uint64_t{1} << p.table_log2) <= n_parts)       ? "hg_accumulate_values: 2^table_log2 must exceed the number of parts"
+                    : (!p.table_log2 && hg_values_default_log2(n_parts) > HG_VALUES_MAX_TABLE_LOG2) ? "hg_accumulate_values: more parts than a table of 2^40 slots serves"
+                    : p.store_log2 > HG_VALUES_MAX_TABLE_LOG2                          ? "hg_accumulate_values: store_log2 above 40"
+                                                                                       : nullptr;
+  if (why) return scanner->sc->set_error(HG_ERR_ARG, why);
+  if (scanner->store) {
+    if (const char *differs = scanner->store->mismatch(p.flags & HG_ACC_BY_PATTERN, hash_bits, reset)) return scanner->sc->set_error(HG_ERR_ARG, std::string("hg_accumulate_values: ") + differs);
+  } else {
+    scanner->store = new HgValueStore(scanner->sc->device());
+  }
+  HgValStoreInput in{};
+  in.values.text = static_cast<const uint8_t *>(d_text);
+  in.values.recs = HgGatherList{reinterpret_cast<const HgHit *>(scanner->last.d_hits), reinterpret_cast<const HgHitAux *>(scanner->last.d_aux),
+                                seg ? scanner->last_seg.d_record_segment : nullptr, scanner->last.n_hits};
+  in.values.parts = reinterpret_cast<const HgPart *>(scanner->last_parts.d_parts);
+  in.values.part_pattern = scanner->last_parts.d_part_pattern;
+  in.values.n_parts = n_parts;
+  if (seg) {
+    in.values.part_seg = scanner->last_segparts.d_part_segment;
+    in.values.seg_start = scanner->last_seg_start;
+  }
+  in.values.flags = p.flags & HG_ACC_BY_PATTERN;
+  in.values.hash_bits = hash_bits;
+  in.values.table_log2 = p.table_log2 ? p.table_log2 : hg_values_default_log2(n_parts);
+  in.store_log2 = p.store_log2;
+  in.reset = reset;
+  HgValStoreOutput o{};
+  std::string err;
+  const int rc = scanner->store->accumulate(in, static_cast<hipStream_t>(stream), &o, &err);
+  if (rc != HG_OK) {  // (the store is as it was, and so is its last ranking; after a HIP error it may be empty)
+    if (!scanner->store->began()) scanner->last_acc_rank = hg_acc_rank_result_t{};
+    return scanner->sc->set_error(rc, err);
+  }
+  scanner->last_acc_rank = hg_acc_rank_result_t{};
+  *result = hg_acc_result_t{o.n_distinct, o.n_added, o.n_groups, o.n_parts, o.n_parts_total, o.n_bytes, o.store_log2, static_cast<uint32_t>(o.ms_acc * 1000.0f + 0.5f)};
+  return HG_OK;
+}
+
+int hg_rank_accumulated(hg_scanner_t *scanner, uint64_t top, uint32_t flags, void *stream, hg_acc_rank_result_t *result) {
+  if (!scanner) return HG_ERR_ARG;
+  if (result) *result = hg_acc_rank_result_t{};
+  const char *why = !result                                        ? "hg_rank_accumulated: result is NULL"
+                    : (flags & ~HG_ACC_ORDER_FIRST)                ? "hg_rank_accumulated: unknown flag bits"
+                    : (!scanner->store || !scanner->store->began()) ? "hg_rank_accumulated: no accumulation since the last reset"
+                                                                   : nullptr;
+  if (why) return scanner->sc->set_error(HG_ERR_ARG, why);
+  scanner->last_acc_rank = hg_acc_rank_result_t{};
+  HgValRankOutput o{};
+  std::string err;
+  const int rc = scanner->store->rank(top, (flags & HG_ACC_ORDER_FIRST) != 0, static_cast<hipStream_t>(stream), &o, &err);
+  if (rc != HG_OK) return scanner->sc->set_error(rc, err);
+  scanner->last_acc_rank = hg_acc_rank_result_t{o.n_values, o.n_distinct, o.n_parts, o.n_bytes, o.d_bytes, o.d_off, o.d_count, o.d_first, o.d_pattern, o.d_line_number,
+                                                o.store_log2, static_cast<uint32_t>(o.ms_rank * 1000.0f + 0.5f)};
+  *result = scanner->last_acc_rank;
+  return HG_OK;
+}
+
+int hg_copy_accumulated(hg_scanner_t *scanner, uint8_t *bytes, uint64_t max_bytes, uint64_t *off, uint64_t *count, uint64_t *first, uint32_t *pattern, uint64_t *line_number,
+                        uint64_t max_values) {
+  if (!scanner) return HG_ERR_ARG;
+  if (!scanner->store || !scanner->store->began()) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_accumulated: no accumulation since the last reset");
+  const hg_acc_rank_result_t &g = scanner->last_acc_rank;
+  if (!g.d_off) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_accumulated: no ranking since the last accumulation");
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  const uint64_t nb = std::min(g.n_bytes, max_bytes), nv = std::min(g.n_values, max_values);
+  if (bytes && nb && hipMemcpy(bytes, g.d_bytes, nb, hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (off && hipMemcpy(off, g.d_off, (nv + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (count && nv && hipMemcpy(count, g.d_count, nv * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (first && nv && hipMemcpy(first, g.d_first, nv * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (pattern && nv && hipMemcpy(pattern, g.d_pattern, nv * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  if (line_number && nv && hipMemcpy(line_number, g.d_line_number, nv * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return HG_ERR_HIP;
+  return HG_OK;
+}
+
+int hg_copy_accumulated_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes, void *stream) {
+  if (!scanner || !d_dst) return HG_ERR_ARG;
+  if (!scanner->store || !scanner->store->began()) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_accumulated_device: no accumulation since the last reset");
+  const hg_acc_rank_result_t &g = scanner->last_acc_rank;
+  if (!g.d_off) return scanner->sc->set_error(HG_ERR_ARG, "hg_copy_accumulated_device: no ranking since the last accumulation");
+  const uint64_t nb = std::min(g.n_bytes, max_bytes);
+  if (!nb) return HG_OK;
+  if (hipSetDevice(scanner->sc->device()) != hipSuccess) return HG_ERR_HIP;
+  return hipMemcpyAsync(d_dst, g.d_bytes, nb, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)) == hipSuccess ? HG_OK : HG_ERR_HIP;
+}
+
+int hg_reset_accumulated(hg_scanner_t *scanner) {
+  if (!scanner) return HG_ERR_ARG;
+  if (scanner->store) scanner->store->reset();
+  scanner->last_acc_rank = hg_acc_rank_result_t{};
+  return HG_OK;
 }
 
 int hg_db_report_ids(const hg_database_t *db, uint32_t *ids, uint32_t max, uint32_t *n_bins) {

@@ -19,6 +19,7 @@
 #include "hg_partlines.h"
 #include "hg_rank.h"
 #include "hg_values.h"
+#include "hg_valstore.h"
 #include "hg_counts.h"
 #include "hg_mem.h"
 #include "hg_post.h"
@@ -458,6 +459,77 @@ class HgRank {
   DevBuf<HgGatherEntry> entries_{"rank entries", 0};
   DevBuf<uint8_t> temp_{"rank temp", 0}, bytes_{"rank bytes", 16};
   hgmem::Buf<uint64_t, hgmem::Space::Host> totals_{"rank totals", 0};  // pinned: {rows, bytes}
+};
+
+// The value store (hg_valstore.hip) behind the values stage's groups, one step per launch on `stream`: the groups' lookup (a lane
+// each, a wave for the long ones), the new groups' sizes, the table's rehash when it changes size, and the apply pass; a
+// ranking's place pass.
+enum class HgValStoreStep { Lookup, Long, Size, Rehash, Apply };
+hipError_t hg_valstore_launch(const HgValStoreArgs &a, HgValStoreStep step, hipStream_t stream);
+hipError_t hg_valstore_place_launch(const HgValRankArgs &a, hipStream_t stream);
+// What an accumulation works on (HgValuesInput with HG_VALSTORE_F_* as flags: the call's parts; hash_bits and table_log2 govern
+// the per-call grouping) and what it and a ranking leave (hg_acc_result_t, hg_acc_rank_result_t).
+struct HgValStoreInput {
+  HgValuesInput values;
+  uint32_t store_log2;  // 0: the table grows on its own
+  bool reset;           // empty the store first
+};
+struct HgValStoreOutput {
+  uint64_t n_distinct, n_added, n_groups, n_parts, n_parts_total, n_bytes;
+  uint32_t store_log2;
+  float ms_acc;  // the call: from the grouping's first memset to the copy pass, its host synchronisations included
+};
+struct HgValRankOutput {
+  uint64_t n_values, n_distinct, n_parts, n_bytes;
+  const uint8_t *d_bytes;  // device arrays, valid until the next accumulate, rank or reset on this object
+  const uint64_t *d_off, *d_count, *d_first, *d_line_number;
+  const uint32_t *d_pattern;
+  uint32_t store_log2;
+  float ms_rank;
+};
+// The store's buffers and launch sequences.  It owns the table, the per-value rows, the byte arena, its scratch and a values
+// stage of its own (hgmem::Buf: freed with the object, every allocation logged), survives scans and touches nothing of the
+// scanner's or of any other stage.  A call that is refused or runs out of memory leaves the store as it was: the rows and the
+// arena grow into fresh buffers that keep their contents (hgmem::Buf::grow), a table of another size is built aside and
+// swapped in, and the host's view of the store changes on success only.
+class HgValueStore {
+ public:
+  explicit HgValueStore(int device) : device_(device), groups_(device) {}
+  ~HgValueStore();
+  // Why a call with these flags and hash_bits cannot join the store as it is (nullptr: it can).
+  const char *mismatch(uint32_t flags, uint32_t hash_bits, bool reset) const;
+  int accumulate(const HgValStoreInput &in, hipStream_t stream, HgValStoreOutput *out, std::string *err);
+  int rank(uint64_t top, bool order_first, hipStream_t stream, HgValRankOutput *out, std::string *err);
+  void reset() { began_ = false, n_values_ = n_parts_ = tail_ = n_bytes_ = 0, log2_ = 0; }
+  bool began() const { return began_; }
+  int device() const { return device_; }
+
+ private:
+  template <typename T>
+  using DevBuf = hgmem::Buf<T, hgmem::Space::Dev>;
+  int device_;
+  HgValues groups_;
+  hipEvent_t ev_[2] = {nullptr, nullptr};
+  // the store: what the host knows of it, the table, the rows, the arena
+  bool began_ = false;
+  uint32_t flags_ = 0, hash_bits_ = 0, log2_ = 0;
+  uint64_t n_values_ = 0, n_parts_ = 0, tail_ = 0, n_bytes_ = 0;  // (tail_: arena bytes in use; n_bytes_: the values' own)
+  DevBuf<unsigned long long> slot_{"valstore slot", 0}, slot_new_{"valstore slot new", 0}, counters_{"valstore counters", 0};
+  DevBuf<uint64_t> v_off_{"valstore off", 0}, v_count_{"valstore count", 0}, v_first_{"valstore first", 0}, v_line_{"valstore line", 0}, v_hash_{"valstore hash", 0};
+  DevBuf<uint32_t> v_len_{"valstore len", 0}, v_pattern_{"valstore pattern", 0};
+  DevBuf<uint8_t> arena_{"valstore arena", 16};
+  // a call's scratch
+  DevBuf<uint64_t> match_{"valstore match", 0}, long_{"valstore long", 0}, new_flag_{"valstore new flag", 0}, new_len_{"valstore new len", 0}, new_idx_{"valstore new idx", 0},
+      new_off_{"valstore new off", 0}, ent_off_{"valstore entry off", 0}, span_{"valstore span", 0};
+  DevBuf<HgGatherEntry> entries_{"valstore entries", 0};
+  DevBuf<uint8_t> temp_{"valstore temp", 0};
+  hgmem::Buf<uint64_t, hgmem::Space::Host> totals_{"valstore totals", 0};  // pinned: {new values, new bytes, counters}; a ranking's {bytes}
+  // a ranking's
+  DevBuf<uint64_t> r_keys_{"valstore rank keys", 0}, r_order_{"valstore rank order", 0}, r_count_{"valstore rank count", 0}, r_first_{"valstore rank first", 0},
+      r_line_{"valstore rank line", 0}, r_size_{"valstore rank size", 0}, r_off_{"valstore rank off", 0}, r_span_{"valstore rank span", 0};
+  DevBuf<uint32_t> r_pattern_{"valstore rank pattern", 0};
+  DevBuf<HgGatherEntry> r_entries_{"valstore rank entries", 0};
+  DevBuf<uint8_t> r_bytes_{"valstore rank bytes", 16};
 };
 
 // The counts stage (hg_counts.hip) over the record list a scan left: one launch on `stream` (nothing for an empty list).

@@ -2255,6 +2255,277 @@ int HgRank::run(const HgRankInput &in, hipStream_t stream, HgRankOutput *out, st
   return HG_OK;
 }
 
+// ---------------------------------------------------------------- value store (hg_accumulate_values, hg_rank_accumulated)
+HgValueStore::~HgValueStore() {
+  (void)hipSetDevice(device_);  // (the buffers are freed behind this body)
+  for (hipEvent_t e : ev_)
+    if (e) (void)hipEventDestroy(e);
+}
+
+#define HG_VALSTORE_TRY(expr, what)                                                \
+  do {                                                                             \
+    const hipError_t e_ = (expr);                                                  \
+    if (e_ != hipSuccess) {                                                        \
+      *err = std::string("value store: ") + (what) + ": " + hipGetErrorString(e_); \
+      return HG_ERR_HIP;                                                           \
+    }                                                                              \
+  } while (0)
+
+const char *HgValueStore::mismatch(uint32_t flags, uint32_t hash_bits, bool reset) const {
+  if (!began_ || reset) return nullptr;
+  if (flags != flags_) return "HG_ACC_BY_PATTERN differs from the call that began the store (HG_ACC_RESET begins another)";
+  if (hash_bits != hash_bits_) return "hash_bits differs from the call that began the store (HG_ACC_RESET begins another)";
+  return nullptr;
+}
+
+int HgValueStore::accumulate(const HgValStoreInput &in, hipStream_t stream, HgValStoreOutput *out, std::string *err) {
+  *out = HgValStoreOutput{};
+  HG_VALSTORE_TRY(hipSetDevice(device_), "hipSetDevice");
+  for (hipEvent_t &e : ev_)
+    if (!e) HG_VALSTORE_TRY(hipEventCreate(&e), "event");
+  HG_VALSTORE_TRY(hipEventRecord(ev_[0], stream), "event");
+  // the store this call joins: with reset an empty one, which replaces the old one on success only
+  const bool fresh = in.reset || !began_;
+  const uint64_t n_old = fresh ? 0 : n_values_, parts_before = fresh ? 0 : n_parts_, bytes_before = fresh ? 0 : n_bytes_;
+  const uint64_t tail16 = fresh ? 0 : (tail_ + 15) & ~static_cast<uint64_t>(15);
+  const uint32_t log2_old = fresh ? 0 : log2_;
+  // 1. the call's groups, sorted by first (one host synchronisation)
+  HgValuesGroups groups{};
+  const int rc = groups_.group(in.values, stream, &groups, err);
+  if (rc != HG_OK) return rc;
+  const uint64_t ng = groups.n_values, np = ng + 1, np_grow = np + np / 4;
+  size_t tb = 0;
+  HG_VALSTORE_TRY(rocprim::exclusive_scan(nullptr, tb, static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), uint64_t{0}, np, rocprim::plus<uint64_t>(), stream), "scan size");
+  tb = std::max<size_t>(tb, 16);
+  if (!match_.reserve(np, np_grow) || !long_.reserve(np, np_grow) || !new_flag_.reserve(np, np_grow) || !new_len_.reserve(np, np_grow) || !new_idx_.reserve(np, np_grow) ||
+      !new_off_.reserve(np, np_grow) || !counters_.reserve(HG_VALSTORE_COUNTERS, HG_VALSTORE_COUNTERS) || !temp_.reserve(tb, tb + tb / 4) || !totals_.reserve(4, 4)) {
+    *err = "value store: out of memory (" + std::to_string(ng) + " groups)";
+    return HG_ERR_NOMEM;
+  }
+  HgValStoreArgs a{};
+  a.text = groups.args.text;
+  a.arena = HgGatherText{arena_.get()};
+  a.parts = groups.args.parts;
+  a.part_pattern = groups.args.part_pattern;
+  a.n_parts = in.values.n_parts;
+  a.src = groups.args.src;
+  a.len = groups.args.len;
+  a.hash = groups.args.hash;
+  a.g_first = groups.d_first;
+  a.g_count = groups.d_count;
+  a.n_groups = ng;
+  a.flags = in.values.flags;
+  a.store_log2 = log2_old;
+  a.slot = slot_.get();
+  a.n_values = n_old;
+  a.v_off = v_off_.get();
+  a.v_count = v_count_.get();
+  a.v_first = v_first_.get();
+  a.v_line = v_line_.get();
+  a.v_hash = v_hash_.get();
+  a.v_len = v_len_.get();
+  a.v_pattern = v_pattern_.get();
+  a.parts_before = parts_before;
+  a.arena_tail = tail16;
+  a.match = match_.get();
+  a.long_list = long_.get();
+  a.counters = counters_.get();
+  a.new_flag = new_flag_.get();
+  a.new_len = new_len_.get();
+  a.new_idx = new_idx_.get();
+  a.new_off = new_off_.get();
+  // 2. lookup (read-only) and 3. the sizes: one host synchronisation reads the two totals
+  uint64_t *totals = totals_.get();
+  HG_VALSTORE_TRY(hipMemsetAsync(counters_.get(), 0, HG_VALSTORE_COUNTERS * sizeof(unsigned long long), stream), "memset");
+  HG_VALSTORE_TRY(hg_valstore_launch(a, HgValStoreStep::Lookup, stream), "launch (lookup)");
+  HG_VALSTORE_TRY(hg_valstore_launch(a, HgValStoreStep::Long, stream), "launch (long groups)");
+  HG_VALSTORE_TRY(hg_valstore_launch(a, HgValStoreStep::Size, stream), "launch (size)");
+  {
+    size_t t = temp_.cap();
+    HG_VALSTORE_TRY(rocprim::exclusive_scan(temp_.get(), t, new_flag_.get(), new_idx_.get(), uint64_t{0}, np, rocprim::plus<uint64_t>(), stream), "scan (new values)");
+    t = temp_.cap();
+    HG_VALSTORE_TRY(rocprim::exclusive_scan(temp_.get(), t, new_len_.get(), new_off_.get(), uint64_t{0}, np, rocprim::plus<uint64_t>(), stream), "scan (new bytes)");
+  }
+  HG_VALSTORE_TRY(hipMemcpyAsync(totals, new_idx_.get() + ng, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "copy count");
+  HG_VALSTORE_TRY(hipMemcpyAsync(totals + 1, new_off_.get() + ng, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "copy bytes");
+  HG_VALSTORE_TRY(hipMemcpyAsync(totals + 2, counters_.get(), HG_VALSTORE_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "copy counters");
+  HG_VALSTORE_TRY(hipStreamSynchronize(stream), "stream sync");
+  const uint64_t n_new = totals[0], new_bytes = totals[1], n_after = n_old + n_new;
+  if (totals[2 + HG_VALSTORE_OVERFLOW] || n_new > ng) {
+    *err = "value store: a probe went round the whole table of 2^" + std::to_string(log2_old) + " slots";
+    return HG_ERR_NOMEM;
+  }
+  // the table the store has after the call
+  uint32_t log2_new = in.store_log2 ? in.store_log2 : std::max(log2_old, hg_valstore_default_log2(n_after));
+  if (log2_new > HG_VALUES_MAX_TABLE_LOG2 || (uint64_t{1} << log2_new) <= n_after) {
+    *err = "value store: " + std::to_string(n_after) + " distinct values do not fit a table of 2^" + std::to_string(std::min(log2_new, HG_VALUES_MAX_TABLE_LOG2)) + " slots with one to spare";
+    return HG_ERR_NOMEM;
+  }
+  // every buffer the rest of the call writes, now: the rows and the arena keep their contents, the table is built aside
+  const uint64_t cap_new = uint64_t{1} << log2_new, nv = std::max<uint64_t>(n_after, 1), nv_grow = nv + nv / 2;
+  const uint64_t padded = (new_bytes + 15) & ~static_cast<uint64_t>(15), arena_need = std::max<uint64_t>(tail16 + padded, 16), arena_grow = arena_need + arena_need / 2;
+  // (with reset the old store is kept too, until the call can no longer run out of memory)
+  const uint64_t n_spans = (new_bytes + HG_GATHER_TILE - 1) / HG_GATHER_TILE, keep_rows = began_ ? n_values_ : 0, keep_arena = began_ ? tail_ : 0;
+  const uint64_t keep_slots = began_ && log2_ ? uint64_t{1} << log2_ : 0;
+  const bool rebuild = !fresh && n_old && log2_new != log2_old;
+  const bool ok = v_off_.grow(nv, nv_grow, keep_rows, stream) && v_count_.grow(nv, nv_grow, keep_rows, stream) && v_first_.grow(nv, nv_grow, keep_rows, stream) &&
+                  v_line_.grow(nv, nv_grow, keep_rows, stream) && v_hash_.grow(nv, nv_grow, keep_rows, stream) && v_len_.grow(nv, nv_grow, keep_rows, stream) &&
+                  v_pattern_.grow(nv, nv_grow, keep_rows, stream) && arena_.grow(arena_need, arena_grow, keep_arena, stream) && entries_.reserve(n_new + 1, n_new + n_new / 4 + 1) &&
+                  ent_off_.reserve(n_new + 1, n_new + n_new / 4 + 1) && span_.reserve(n_spans + 1, n_spans + n_spans / 8 + 1) &&
+                  (rebuild ? slot_new_.reserve(cap_new, cap_new) : slot_.grow(cap_new, cap_new, keep_slots, stream));
+  if (!ok) {
+    *err = "value store: out of memory (" + std::to_string(n_after) + " distinct values, " + std::to_string(tail16 + new_bytes) + " bytes, a table of 2^" + std::to_string(log2_new) + " slots)";
+    return HG_ERR_NOMEM;
+  }
+  a.arena = HgGatherText{arena_.get()};
+  a.v_off = v_off_.get();
+  a.v_count = v_count_.get();
+  a.v_first = v_first_.get();
+  a.v_line = v_line_.get();
+  a.v_hash = v_hash_.get();
+  a.v_len = v_len_.get();
+  a.v_pattern = v_pattern_.get();
+  a.max_values = n_after;
+  a.entries = entries_.get();
+  a.ent_off = ent_off_.get();
+  // from here on the store changes, and what is left can only fail with a HIP error: the store is emptied then
+  const auto finish = [&]() -> int {
+    if (rebuild) {  // the stored values into a table of the new size, which then is the store's
+      a.slot_new = slot_new_.get();
+      a.new_log2 = log2_new;
+      HG_VALSTORE_TRY(hipMemsetAsync(slot_new_.get(), 0xFF, cap_new * sizeof(unsigned long long), stream), "memset");  // HG_VALUES_EMPTY
+      HG_VALSTORE_TRY(hg_valstore_launch(a, HgValStoreStep::Rehash, stream), "launch (rehash)");
+      HG_VALSTORE_TRY(hipStreamSynchronize(stream), "stream sync");  // (nothing queued reads the old table when it changes hands)
+      slot_.swap(slot_new_);
+    } else if (!n_old) {
+      HG_VALSTORE_TRY(hipMemsetAsync(slot_.get(), 0xFF, cap_new * sizeof(unsigned long long), stream), "memset");
+    }
+    a.slot = slot_.get();
+    a.store_log2 = log2_new;
+    began_ = true, flags_ = in.values.flags, hash_bits_ = in.values.hash_bits, log2_ = log2_new;
+    n_values_ = n_after, n_parts_ = parts_before + in.values.n_parts, tail_ = tail16 + new_bytes, n_bytes_ = bytes_before + new_bytes;
+    // 4. apply and 5. the new values' bytes, from the text to the arena's tail
+    HG_VALSTORE_TRY(hg_valstore_launch(a, HgValStoreStep::Apply, stream), "launch (apply)");
+    HgGatherArgs g{};
+    g.text = a.text;
+    g.entries = entries_.get();
+    g.off = ent_off_.get();
+    g.n_entries = n_new;
+    g.n_bytes = new_bytes;
+    g.span = span_.get();
+    g.out = arena_.get() + tail16;
+    HG_VALSTORE_TRY(hg_gather_launch(g, HgGatherStep::Span, stream), "launch (spans)");  // (nothing without bytes)
+    HG_VALSTORE_TRY(hg_gather_launch(g, HgGatherStep::Copy, stream), "launch (copy)");
+    HG_VALSTORE_TRY(hipMemcpyAsync(totals + 2, counters_.get(), HG_VALSTORE_COUNTERS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "copy counters");
+    HG_VALSTORE_TRY(hipEventRecord(ev_[1], stream), "event");
+    HG_VALSTORE_TRY(hipStreamSynchronize(stream), "stream sync");
+    HG_VALSTORE_TRY(hipEventElapsedTime(&out->ms_acc, ev_[0], ev_[1]), "event time");
+    if (totals[2 + HG_VALSTORE_OVERFLOW]) {  // (a table with a slot to spare has room for every claim)
+      *err = "value store: a claim went round the whole table of 2^" + std::to_string(log2_new) + " slots";
+      return HG_ERR_HIP;
+    }
+    return HG_OK;
+  };
+  if (const int rc_finish = finish()) {
+    reset();
+    *err += "; the store is emptied";
+    return rc_finish;
+  }
+  out->n_distinct = n_after;
+  out->n_added = n_new;
+  out->n_groups = ng;
+  out->n_parts = in.values.n_parts;
+  out->n_parts_total = n_parts_;
+  out->n_bytes = n_bytes_;
+  out->store_log2 = log2_new;
+  return HG_OK;
+}
+
+int HgValueStore::rank(uint64_t top, bool order_first, hipStream_t stream, HgValRankOutput *out, std::string *err) {
+  *out = HgValRankOutput{};
+  HG_VALSTORE_TRY(hipSetDevice(device_), "hipSetDevice");
+  for (hipEvent_t &e : ev_)
+    if (!e) HG_VALSTORE_TRY(hipEventCreate(&e), "event");
+  HG_VALSTORE_TRY(hipEventRecord(ev_[0], stream), "event");
+  const uint64_t n = n_values_, rows = (top && top < n) ? top : n, np = rows + 1, np_grow = np + np / 4, nn = std::max<uint64_t>(n, 1);
+  uint32_t bits = 1;
+  while (bits < 64 && (n_parts_ >> bits)) bits++;  // count <= the accumulated parts
+  size_t t_sort = 0, t_scan = 0;
+  HG_VALSTORE_TRY(rocprim::radix_sort_pairs_desc(nullptr, t_sort, static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), rocprim::counting_iterator<uint64_t>(0),
+                                                 static_cast<uint64_t *>(nullptr), nn, 0, bits, stream),
+                  "sort size");
+  HG_VALSTORE_TRY(rocprim::exclusive_scan(nullptr, t_scan, static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr), uint64_t{0}, np, rocprim::plus<uint64_t>(), stream), "scan size");
+  const size_t tb = std::max<size_t>(std::max(t_sort, t_scan), 16);
+  if ((!order_first && (!r_keys_.reserve(nn, nn + nn / 4) || !r_order_.reserve(nn, nn + nn / 4))) || !r_count_.reserve(np, np_grow) || !r_first_.reserve(np, np_grow) ||
+      !r_line_.reserve(np, np_grow) || !r_size_.reserve(np, np_grow) || !r_off_.reserve(np, np_grow) || !r_pattern_.reserve(np, np_grow) || !r_entries_.reserve(np, np_grow) ||
+      !temp_.reserve(tb, tb + tb / 4) || !totals_.reserve(4, 4)) {
+    *err = "value store: out of memory (ranking " + std::to_string(n) + " distinct values)";
+    return HG_ERR_NOMEM;
+  }
+  if (!order_first && n) {  // stable: ties stay in index order, which is the order of first
+    size_t t = temp_.cap();
+    HG_VALSTORE_TRY(rocprim::radix_sort_pairs_desc(temp_.get(), t, v_count_.get(), r_keys_.get(), rocprim::counting_iterator<uint64_t>(0), r_order_.get(), n, 0, bits, stream), "sort (count)");
+  }
+  HgValRankArgs a{};
+  a.n_values = n;
+  a.n_rows = rows;
+  a.order = order_first ? nullptr : r_order_.get();
+  a.v_off = v_off_.get();
+  a.v_count = v_count_.get();
+  a.v_first = v_first_.get();
+  a.v_line = v_line_.get();
+  a.v_len = v_len_.get();
+  a.v_pattern = v_pattern_.get();
+  a.out_count = r_count_.get();
+  a.out_first = r_first_.get();
+  a.out_line = r_line_.get();
+  a.out_pattern = r_pattern_.get();
+  a.size = r_size_.get();
+  a.entries = r_entries_.get();
+  HG_VALSTORE_TRY(hg_valstore_place_launch(a, stream), "launch (place)");
+  {
+    size_t t = temp_.cap();
+    HG_VALSTORE_TRY(rocprim::exclusive_scan(temp_.get(), t, r_size_.get(), r_off_.get(), uint64_t{0}, np, rocprim::plus<uint64_t>(), stream), "scan (lengths)");
+  }
+  uint64_t *totals = totals_.get();
+  HG_VALSTORE_TRY(hipMemcpyAsync(totals, r_off_.get() + rows, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "copy bytes");
+  HG_VALSTORE_TRY(hipStreamSynchronize(stream), "stream sync");
+  HgGatherArgs g{};
+  g.text = HgGatherText{arena_.get()};
+  g.entries = r_entries_.get();
+  g.off = r_off_.get();
+  g.n_entries = rows;
+  g.n_bytes = totals[0];
+  const uint64_t padded = (g.n_bytes + 15) & ~static_cast<uint64_t>(15), n_spans = (g.n_bytes + HG_GATHER_TILE - 1) / HG_GATHER_TILE;
+  if (g.n_bytes > n_bytes_) {
+    *err = "value store: more bytes in the kept rows than in the store";
+    return HG_ERR_HIP;
+  }
+  if (!r_bytes_.reserve(std::max<uint64_t>(padded, 16), std::max<uint64_t>(padded + padded / 8, 16)) || !r_span_.reserve(n_spans + 1, n_spans + n_spans / 8 + 1)) {
+    *err = "value store: out of memory for " + std::to_string(g.n_bytes) + " bytes of values";
+    return HG_ERR_NOMEM;
+  }
+  g.span = r_span_.get();
+  g.out = r_bytes_.get();
+  HG_VALSTORE_TRY(hg_gather_launch(g, HgGatherStep::Span, stream), "launch (spans)");  // (nothing without bytes)
+  HG_VALSTORE_TRY(hg_gather_launch(g, HgGatherStep::Copy, stream), "launch (copy)");
+  HG_VALSTORE_TRY(hipEventRecord(ev_[1], stream), "event");
+  HG_VALSTORE_TRY(hipStreamSynchronize(stream), "stream sync");
+  HG_VALSTORE_TRY(hipEventElapsedTime(&out->ms_rank, ev_[0], ev_[1]), "event time");
+  out->n_values = rows;
+  out->n_distinct = n;
+  out->n_parts = n_parts_;
+  out->n_bytes = g.n_bytes;
+  out->d_bytes = r_bytes_.get();
+  out->d_off = r_off_.get();
+  out->d_count = r_count_.get();
+  out->d_first = r_first_.get();
+  out->d_line_number = r_line_.get();
+  out->d_pattern = r_pattern_.get();
+  out->store_log2 = log2_;
+  return HG_OK;
+}
+
 // ---------------------------------------------------------------- counts stage (hg_count_records): buffers and launch sequence
 HgCounts::~HgCounts() {
   (void)hipSetDevice(device_);  // (the buffers are freed behind this body)

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
+#include <utility>
 
 namespace hgmem {
 
@@ -85,6 +86,28 @@ class Buf {
     }
     cap_ = new_cap;
     return true;
+  }
+  // Room for `need` elements with the first `keep` (<= cap()) kept: nothing to do if there is.  Else a fresh allocation of
+  // new_cap (>= need) elements plus the slack takes those elements (a copy on `stream`, waited for: work queued on the stream
+  // may still read the old one) and is swapped in, and the old one is freed.  false, with the buffer as it was, if that fails.
+  bool grow(size_t need, size_t new_cap, size_t keep, hipStream_t stream) {
+    if (cap_ >= need) return true;
+    assert(new_cap >= need && keep <= cap_);
+    T *fresh = nullptr;
+    const size_t bytes = new_cap * sizeof(T) + slack_;
+    if ((S == Space::Dev ? dev_alloc(&fresh, bytes, name_) : host_alloc(&fresh, bytes, name_)) != hipSuccess) return false;
+    if (log_file()) note("grow  %s  %-14s %p -> %p  keeps %zu\n", S == Space::Dev ? "dev " : "host", name_, static_cast<void *>(p_), static_cast<void *>(fresh), keep * sizeof(T));
+    if ((keep && hipMemcpyAsync(fresh, p_, keep * sizeof(T), hipMemcpyDefault, stream) != hipSuccess) || hipStreamSynchronize(stream) != hipSuccess) {
+      S == Space::Dev ? dev_free(fresh, name_) : host_free(fresh, name_);
+      return false;
+    }
+    release();
+    p_ = fresh, cap_ = new_cap;
+    return true;
+  }
+  void swap(Buf &other) {  // (both of one element type and space; the log names stay with the objects)
+    std::swap(p_, other.p_);
+    std::swap(cap_, other.cap_);
   }
 
  private:

@@ -596,8 +596,14 @@ struct FileCounts {
 // With `fv` (hg_hyperscan_values) nothing is delivered either: every chunk is scanned with the parts stage, the values stage runs
 // behind it, and only the chunk's distinct values come back (bytes, offsets, counts, expressions), to be merged here by key.  No
 // part record and no line is downloaded.  The rows keep the order in which their keys first occurred in the file.
+// With fv->on_device (hg_hyperscan_values_top) not even those: a value store accumulates every chunk's parts on the device, one
+// ranking at the end cuts it to `top` rows, and only those come back, in the ranking's order, with the totals before the cut.
 struct FileValues {
   hg_values_params_t params;
+  bool on_device = false;
+  uint64_t top = 0, n_distinct = 0, n_parts = 0;
+  std::vector<uint8_t> top_bytes;
+  std::vector<uint64_t> top_off;
   std::map<std::string, size_t> index;  // key ([expression index, 4 bytes] value bytes) -> row
   std::vector<std::string> value;
   std::vector<uint32_t> pattern;
@@ -640,6 +646,7 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
   }
   std::unique_ptr<HgCounts> counts;  // (made with the scanner; its buffers are its own)
   std::unique_ptr<HgValues> values;  // (likewise)
+  std::unique_ptr<HgValueStore> store;  // (likewise: the file's value store, hg_hyperscan_values_top)
   std::vector<uint8_t> v_bytes;      // a chunk's distinct values
   std::vector<uint64_t> v_off, v_count;
   std::vector<uint32_t> v_pattern;
@@ -798,7 +805,8 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
         break;
       }
       if (fc) counts = std::make_unique<HgCounts>(ctx->device, *db);
-      if (fv) values = std::make_unique<HgValues>(ctx->device);
+      if (fv && fv->on_device) store = std::make_unique<HgValueStore>(ctx->device);
+      else if (fv) values = std::make_unique<HgValues>(ctx->device);
       t_setup = now() - t0;
     }
     if (cut) {
@@ -839,6 +847,25 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
           break;
         }
       }
+      if (store) {  // the chunk's parts join the file's store where they lie: nothing comes back
+        const uint32_t log2 = fv->params.table_log2 ? fv->params.table_log2 : hg_values_default_log2(pout.n_parts);
+        if (log2 > HG_VALUES_MAX_TABLE_LOG2 || (uint64_t{1} << log2) <= pout.n_parts) {
+          std::fprintf(stderr, "ERROR: Unable to scan buffer. Exiting. (a chunk has %llu parts: more than a table of 2^%u slots serves)\n",
+                       static_cast<unsigned long long>(pout.n_parts), log2);
+          rc = HYPERSCANNER_SCAN;
+          break;
+        }
+        HgValStoreInput vin{};
+        vin.values = HgValuesInput{d_text, HgGatherList{out.d_hits, out.d_aux, nullptr, out.n_hits}, pout.d_parts, pout.d_pattern, nullptr, pout.n_parts, nullptr, fv->params.flags,
+                                   fv->params.hash_bits ? fv->params.hash_bits : 64u, log2};
+        HgValStoreOutput so{};
+        if (store->accumulate(vin, ctx->stream, &so, &err) != HG_OK) {
+          std::fprintf(stderr, "ERROR: Unable to scan buffer. Exiting. (%s)\n", err.c_str());
+          rc = HYPERSCANNER_SCAN;
+          healthy = false;
+          break;
+        }
+      }
       if (values) {  // the chunk's parts are grouped where they lie: only the distinct values come back
         const uint32_t log2 = fv->params.table_log2 ? fv->params.table_log2 : hg_values_default_log2(pout.n_parts);
         HgValuesOutput vo{};
@@ -871,7 +898,7 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
         }
         for (uint64_t j = 0; j < vo.n_values; j++) fv->add(v_bytes.data() + v_off[j], v_off[j + 1] - v_off[j], v_pattern[j], v_count[j]);
       }
-      const uint64_t n_rows = counts || values ? 0 : out.n_hits;
+      const uint64_t n_rows = counts || values || store ? 0 : out.n_hits;
       ctx->hits.resize(n_rows);
       ctx->aux.resize(n_rows);
       if (n_rows) {
@@ -999,6 +1026,29 @@ static int scan_file(const char *file_name, const char *const *patterns, const u
   if (counts && rc == 0 && !counts->copy_totals(fc->n_lines.data(), fc->n_reports.data())) {  // n_bins x 16 bytes, once
     rc = HYPERSCANNER_SCAN;
     healthy = false;
+  }
+  if (store && rc == 0 && store->began()) {  // one ranking, and the kept rows once
+    HgValRankOutput ro{};
+    bool ok = store->rank(fv->top, false, ctx->stream, &ro, &err) == HG_OK;
+    if (ok) {
+      fv->n_distinct = ro.n_distinct;
+      fv->n_parts = ro.n_parts;
+      fv->top_bytes.resize(ro.n_bytes);
+      fv->top_off.resize(ro.n_values + 1);
+      fv->count.resize(ro.n_values);
+      fv->pattern.resize(ro.n_values);
+      ok = (!ro.n_bytes || hipMemcpyAsync(fv->top_bytes.data(), ro.d_bytes, ro.n_bytes, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess) &&
+           hipMemcpyAsync(fv->top_off.data(), ro.d_off, (ro.n_values + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+           (!ro.n_values || (hipMemcpyAsync(fv->count.data(), ro.d_count, ro.n_values * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+                             hipMemcpyAsync(fv->pattern.data(), ro.d_pattern, ro.n_values * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess)) &&
+           hipStreamSynchronize(ctx->stream) == hipSuccess;
+      if (!ok) err = "copying the values";
+    }
+    if (!ok) {
+      std::fprintf(stderr, "ERROR: Unable to scan buffer. Exiting. (%s)\n", err.c_str());
+      rc = HYPERSCANNER_SCAN;
+      healthy = false;
+    }
   }
   if (trace)
     std::fprintf(stderr, "[hypergrep_amd] %s: %.1f MiB in %.4f s; reader filling slots %.4f s; consumer: waiting for data %.4f s, window tuning + scanner %.4f s (%s), copy + scan %.4f s, delivering %llu hits %.4f s\n",
@@ -1472,6 +1522,26 @@ extern "C" int hg_hyperscan_values(char *file_name, const char *const *patterns,
     off.push_back(bytes.size());
   }
   on_values(context, bytes.data(), off.data(), fv.count.data(), fv.pattern.data(), fv.value.size());
+  return 0;
+}
+
+extern "C" int hg_hyperscan_values_top(char *file_name, const char *const *patterns, const unsigned int *pattern_flags, const unsigned int *pattern_ids,
+                                       const hs_expr_ext_t *const *ext, const unsigned int elements, const int buffer_size, const hg_values_params_t *params, uint64_t top,
+                                       hg_values_event on_values, void *context, uint64_t *n_distinct, uint64_t *n_parts) {
+  if (n_distinct) *n_distinct = 0;
+  if (n_parts) *n_parts = 0;
+  if (!on_values) return HYPERSCANNER_STATE_MEM;
+  FileValues fv;
+  fv.params = params ? *params : hg_values_params_t{0, 0, 0, 0};
+  fv.on_device = true;
+  fv.top = top;
+  if ((fv.params.flags & ~HG_VALUES_BY_PATTERN) || fv.params.hash_bits > 64 || fv.params.table_log2 > HG_VALUES_MAX_TABLE_LOG2) return HYPERSCANNER_STATE_MEM;
+  const int rc = scan_file(file_name, patterns, pattern_flags, pattern_ids, ext, elements, [](hyperscanner_result_t *, int) {}, buffer_size, 1, 0, false, 0, 0, nullptr, true, nullptr, &fv);
+  if (rc) return rc;
+  if (fv.top_off.empty()) fv.top_off.assign(1, 0);
+  if (n_distinct) *n_distinct = fv.n_distinct;
+  if (n_parts) *n_parts = fv.n_parts;
+  on_values(context, fv.top_bytes.data(), fv.top_off.data(), fv.count.data(), fv.pattern.data(), fv.count.size());
   return 0;
 }
 

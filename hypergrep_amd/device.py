@@ -114,6 +114,24 @@ class HgValuesResult(ctypes.Structure):  # sizeof 88
 
 HG_RANK_BY_PATTERN = 1
 HG_RANK_PER_SEGMENT = 2
+HG_ACC_BY_PATTERN = 1
+HG_ACC_RESET = 2
+HG_ACC_ORDER_FIRST = 1
+
+
+class HgAccParams(ctypes.Structure):  # sizeof 16
+    _fields_ = [("flags", ctypes.c_uint32), ("hash_bits", ctypes.c_uint32), ("table_log2", ctypes.c_uint32), ("store_log2", ctypes.c_uint32)]
+
+
+class HgAccResult(ctypes.Structure):  # sizeof 56
+    _fields_ = [("n_distinct", ctypes.c_uint64), ("n_added", ctypes.c_uint64), ("n_groups", ctypes.c_uint64), ("n_parts", ctypes.c_uint64), ("n_parts_total", ctypes.c_uint64),
+                ("n_bytes", ctypes.c_uint64), ("store_log2", ctypes.c_uint32), ("acc_us", ctypes.c_uint32)]
+
+
+class HgAccRankResult(ctypes.Structure):  # sizeof 88
+    _fields_ = [("n_values", ctypes.c_uint64), ("n_distinct", ctypes.c_uint64), ("n_parts", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("d_bytes", ctypes.c_void_p),
+                ("d_off", ctypes.c_void_p), ("d_count", ctypes.c_void_p), ("d_first", ctypes.c_void_p), ("d_pattern", ctypes.c_void_p), ("d_line_number", ctypes.c_void_p),
+                ("store_log2", ctypes.c_uint32), ("rank_us", ctypes.c_uint32)]
 
 
 class HgRankParams(ctypes.Structure):  # sizeof 24
@@ -233,6 +251,13 @@ def lib() -> ctypes.CDLL:
             l.hg_copy_ranked_values.argtypes = [ctypes.c_void_p, p8, ctypes.c_uint64, p64, p64, p64, p32, p64, p32, ctypes.c_uint64]
             l.hg_copy_ranked_segments.argtypes = [ctypes.c_void_p, p64, p64, p64]
             l.hg_copy_ranked_values_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        if hasattr(l, "hg_accumulate_values"):  # (absent from a build before the value store)
+            p8, p32, p64 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+            l.hg_accumulate_values.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(HgAccParams), ctypes.c_void_p, ctypes.POINTER(HgAccResult)]
+            l.hg_rank_accumulated.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(HgAccRankResult)]
+            l.hg_copy_accumulated.argtypes = [ctypes.c_void_p, p8, ctypes.c_uint64, p64, p64, p64, p32, p64, ctypes.c_uint64]
+            l.hg_copy_accumulated_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+            l.hg_reset_accumulated.argtypes = [ctypes.c_void_p]
         l.hg_copy_hits.argtypes = [ctypes.c_void_p, ctypes.POINTER(HgHit), ctypes.POINTER(HgHitAux), ctypes.c_uint64]
         l.hg_copy_hits_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         l.hg_copy_hit_starts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
@@ -357,6 +382,27 @@ class RankStats:
 
 
 @dataclass
+class AccStats:
+    n_distinct: int  # distinct values in the store after the call
+    n_added: int  # of them new with this call
+    n_groups: int  # this call's groups
+    n_parts: int  # this call's parts
+    n_parts_total: int  # parts accumulated since the last reset
+    n_bytes: int  # bytes of the store's values
+    store_log2: int  # the store's table
+    acc_us: int  # the call alone, microseconds
+
+
+@dataclass
+class AccRankStats:
+    n_values: int  # kept rows
+    n_distinct: int  # groups before the cut
+    n_parts: int  # parts accumulated since the last reset
+    n_bytes: int  # bytes of the kept rows' values
+    rank_us: int  # the ranking alone, microseconds
+
+
+@dataclass
 class CountStats:
     n_bins: int  # distinct report ids of the database
     n_records: int  # records this call counted
@@ -385,6 +431,7 @@ class Scanner:
         self._last_part_lines = None  # (HgPartLinesResult, whole_line) of the last parts gather, None after a scan
         self._last_values = None  # HgValuesResult of the last value count, None after a scan
         self._last_rank = None  # HgRankResult of the last ranking, None after a scan
+        self._last_acc_rank = None  # HgAccRankResult of the value store's last ranking, None after an accumulate or a reset (scans leave it)
         self._seg_arena = None
 
     def _place_segments(self, starts, ends):
@@ -835,6 +882,93 @@ class Scanner:
         if rc != 0:
             raise DeviceError(f"hg_copy_ranked_values_device failed ({rc})")
         return n
+
+    def accumulate_values(self, d_text: int, nbytes: int, by_pattern: bool = False, reset: bool = False, stream: int = 0, hash_bits: int = 0, table_log2: int = 0,
+                          store_log2: int = 0) -> AccStats:
+        """Add the matched parts of the last scan with parts to the scanner's value store (hg_accumulate_values): a device-resident
+        table of distinct values that survives scans, so that a text that arrives in many buffers (scanned in order, line_base
+        chained) is grouped as the whole text would be.  by_pattern: the expression index is part of the key; reset: empty the
+        store first.  by_pattern and hash_bits are fixed when a store begins.  hash_bits and table_log2 are count_values()' knobs
+        for the call's own grouping; store_log2 fixes the store's table size (0: it grows on its own), for tests.
+        rank_accumulated() orders and cuts the store; hits(), parts(), values(), ranked_values() ... are unchanged by it.
+        ValueError with the reason when nothing was launched (what count_values() refuses; a changed by_pattern or hash_bits
+        without reset); a DeviceError (-2: out of memory, an explicit store_log2 too small) leaves the store as it was."""
+        params = HgAccParams(flags=(HG_ACC_BY_PATTERN if by_pattern else 0) | (HG_ACC_RESET if reset else 0), hash_bits=hash_bits, table_log2=table_log2, store_log2=store_log2)
+        return self._accumulate_values(d_text, nbytes, params, stream)
+
+    def _accumulate_values(self, d_text: int, nbytes: int, params, stream: int = 0) -> AccStats:
+        res = HgAccResult()
+        rc = lib().hg_accumulate_values(self._h, ctypes.c_void_p(d_text), nbytes, ctypes.byref(params) if params is not None else None, ctypes.c_void_p(stream), ctypes.byref(res))
+        if rc == -1:  # HG_ERR_ARG: nothing was launched
+            raise ValueError(lib().hg_scanner_error(self._h).decode(errors="replace"))
+        if rc != 0:
+            err = DeviceError(f"hg_accumulate_values failed ({rc}): {lib().hg_scanner_error(self._h).decode(errors='replace')}")
+            err.rc = rc
+            raise err
+        self._last_acc_rank = None
+        return AccStats(res.n_distinct, res.n_added, res.n_groups, res.n_parts, res.n_parts_total, res.n_bytes, res.store_log2, res.acc_us)
+
+    def rank_accumulated(self, top: int = 0, order_first: bool = False, stream: int = 0) -> AccRankStats:
+        """Order the value store by descending count, then first occurrence (order_first: by first occurrence only) and keep the
+        first `top` groups (0: all) on the GPU (hg_rank_accumulated); only the kept rows' bytes are gathered.
+        accumulated_values(), accumulated_values_arrays() and copy_accumulated_to() give the result, which stays valid until the
+        next accumulate_values(), rank_accumulated() or reset_accumulated().  ValueError without an accumulation since the
+        last reset."""
+        if top < 0:
+            raise ValueError("top must not be negative")
+        res = HgAccRankResult()
+        self._last_acc_rank = None
+        rc = lib().hg_rank_accumulated(self._h, top, HG_ACC_ORDER_FIRST if order_first else 0, ctypes.c_void_p(stream), ctypes.byref(res))
+        if rc == -1:
+            raise ValueError(lib().hg_scanner_error(self._h).decode(errors="replace"))
+        if rc != 0:
+            raise DeviceError(f"hg_rank_accumulated failed ({rc}): {lib().hg_scanner_error(self._h).decode(errors='replace')}")
+        self._last_acc_rank = res
+        return AccRankStats(res.n_values, res.n_distinct, res.n_parts, res.n_bytes, res.rank_us)
+
+    def accumulated_values_arrays(self):
+        """The value store's last ranking as a dict: bytes (the blob), and numpy arrays off (uint64, n + 1: row j is
+        bytes[off[j]:off[j + 1]]), count (uint64), first (uint64, the smallest ordinal: the parts of the earlier calls plus the
+        part's index in its call), pattern (uint32) and line_number (uint64).  ValueError without a ranking since the last
+        accumulate_values() or reset_accumulated()."""
+        import numpy as np
+
+        g = self._last_acc_rank
+        if g is None:
+            raise ValueError("no ranking of the value store since the last accumulation")
+        n = g.n_values
+        blob = np.zeros(max(g.n_bytes, 1), dtype=np.uint8)
+        out = {"off": np.zeros(n + 1, dtype=np.uint64), "count": np.zeros(n, dtype=np.uint64), "first": np.zeros(n, dtype=np.uint64), "pattern": np.zeros(n, dtype=np.uint32),
+               "line_number": np.zeros(n, dtype=np.uint64)}
+        p8, p32, p64 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+        rc = lib().hg_copy_accumulated(self._h, blob.ctypes.data_as(p8), g.n_bytes, out["off"].ctypes.data_as(p64), out["count"].ctypes.data_as(p64),
+                                       out["first"].ctypes.data_as(p64), out["pattern"].ctypes.data_as(p32), out["line_number"].ctypes.data_as(p64), n)
+        if rc != 0:
+            raise DeviceError(f"hg_copy_accumulated failed ({rc})")
+        out["bytes"] = blob[:g.n_bytes].tobytes()
+        return out
+
+    def accumulated_values(self):
+        """The value store's last ranking as a list of (value_bytes, count, pattern, line_number), in the ranking's order."""
+        a = self.accumulated_values_arrays()
+        off = a["off"].tolist()
+        return [(a["bytes"][off[j]:off[j + 1]], int(c), int(p), int(l)) for j, (c, p, l) in enumerate(zip(a["count"], a["pattern"], a["line_number"]))]
+
+    def copy_accumulated_to(self, d_dst: int, max_bytes: int, stream: int = 0) -> int:
+        """Async device-to-device copy of the last ranking's bytes (the first max_bytes of them); returns the number copied."""
+        if self._last_acc_rank is None:
+            raise ValueError("no ranking of the value store since the last accumulation")
+        n = min(max_bytes, self._last_acc_rank.n_bytes)
+        rc = lib().hg_copy_accumulated_device(self._h, ctypes.c_void_p(d_dst), n, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise DeviceError(f"hg_copy_accumulated_device failed ({rc})")
+        return n
+
+    def reset_accumulated(self) -> None:
+        """Empty the value store (hg_reset_accumulated)."""
+        self._last_acc_rank = None
+        if lib().hg_reset_accumulated(self._h) != 0:
+            raise DeviceError("hg_reset_accumulated failed")
 
     def count(self, accumulate: bool = False, per_segment: bool = False, stream: int = 0) -> CountStats:
         """Counts per report id (hg_count_records) of the last scan's records (hits(), or the surviving records of a scan with

@@ -396,6 +396,47 @@ def count_values(file: str, patterns: list[str], flags: list[int] = (), ids: lis
     return rows, outcome[0]
 
 
+def count_values_top(file: str, patterns: list[str], top: int, flags: list[int] = (), ids: list[int] = (), by_pattern: bool = False, buffer_size: int = 262140,
+                     totals: list | None = None) -> tuple[list, int]:
+    """count_values() cut to the `top` most frequent values, with the whole file's values accumulated on the GPU
+    (hg_hyperscan_values_top; grep -o | sort | uniq -c | sort -rn | head): (rows, return code).  A value store on the device
+    takes every chunk's parts behind its scan and is ranked once at the end, so only the kept rows come back, however many
+    chunks the file has.  The rows are shaped and sorted as count_values() gives them; the cut is count_values_files()': the
+    most frequent values, a tie at the cut going to the value that occurs first in the file, so that
+    count_values_top(f, p, N) == count_values_files([f], p, top=N)[0].  top=0 keeps every value.  totals: a list that
+    receives (distinct values, parts), both before the cut."""
+    if top < 0:
+        raise ValueError("top must not be negative")
+    c_patterns, c_flags, c_ids = prepare_patterns(patterns, flags=flags, ids=ids)
+    params = ValuesParams(flags=1 if by_pattern else 0)
+    rows: list = []
+
+    def on_values(_context, data, off, counts, pattern, n_values) -> None:
+        blob = ctypes.string_at(data, off[n_values]) if n_values else b""
+        for j in range(n_values):
+            value = blob[off[j]:off[j + 1]]
+            rows.append((value, pattern[j], counts[j]) if by_pattern else (value, counts[j]))
+
+    callback = _VALUES_EVENT(on_values)
+    engine = _get_hyperscanner_lib()
+    engine.hg_hyperscan_values_top.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint),
+                                               ctypes.POINTER(ctypes.POINTER(ExprExt)), ctypes.c_uint, ctypes.c_int, ctypes.POINTER(ValuesParams), ctypes.c_uint64, _VALUES_EVENT,
+                                               ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    outcome = [0]
+    n_distinct, n_parts = ctypes.c_uint64(), ctypes.c_uint64()
+
+    def native_call() -> None:
+        outcome[0] = engine.hg_hyperscan_values_top(os.fspath(file).encode(), c_patterns, c_flags, c_ids, None, len(c_patterns), buffer_size, ctypes.byref(params), top, callback, None,
+                                                    ctypes.byref(n_distinct), ctypes.byref(n_parts))
+
+    if not _run_native(native_call):
+        return [], _RC_INTERRUPTED
+    if totals is not None:
+        totals[:] = [(n_distinct.value, n_parts.value)]
+    rows.sort(key=(lambda r: (-r[2], r[0], r[1])) if by_pattern else (lambda r: (-r[1], r[0])))
+    return rows, outcome[0]
+
+
 class RankParams(ctypes.Structure):
     """hg_rank_params_t (include/hypergrep_amd.h)."""
 

@@ -923,8 +923,8 @@ int hg_copy_part_lines_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_b
  * than 256 bytes), an insert pass into an open-addressing table of 64-bit slots claimed by compare-and-swap, with integer
  * atomics for count and first, a compaction and a sort by first, and the gathers' copy pass divided by output bytes.  Text is
  * read inside the parts only (whole aligned dwords: never past nbytes rounded up to 4).
- * Not offered: case folding, accumulation across scans on the device, and anything for the databases the parts stage
- * refuses.  Values per file, an order by count and a cut to the most frequent are hg_rank_values' (below). */
+ * Not offered: case folding, and anything for the databases the parts stage refuses.  Values per file, an order by count and
+ * a cut to the most frequent are hg_rank_values' (below); accumulation across scans is hg_accumulate_values' (further below). */
 #define HG_VALUES_BY_PATTERN 1u /* the expression index is part of the key */
 typedef struct hg_values_params { /* sizeof 16 */
     uint32_t flags;               /* HG_VALUES_* */
@@ -1002,7 +1002,8 @@ int hg_hyperscan_values(char *file_name, const char *const *patterns, const unsi
  * The stage runs on the GPU: the values stage's hash, insert and compaction passes with the segment as a third key component
  * (hypergrep_amd/csrc/hg_values.hip), two stable radix sorts, and the kernels of hypergrep_amd/csrc/hg_rank.hip (a lane per
  * group or per segment; no atomics, no text reads), then the gathers' copy pass over the kept rows.
- * Not offered: case folding, accumulation across scans on the device, a tie-break by value bytes, ranking across GPUs. */
+ * Not offered: case folding, a tie-break by value bytes, ranking across GPUs.  Accumulation across scans is
+ * hg_accumulate_values' (below). */
 #define HG_RANK_BY_PATTERN 1u  /* the expression index is part of the key */
 #define HG_RANK_PER_SEGMENT 2u /* the segment is part of the key; order and cut are per segment */
 typedef struct hg_rank_params { /* sizeof 24 */
@@ -1057,6 +1058,92 @@ int hg_hyperscan_files_values(const char *const *file_names, unsigned int n_file
                               const unsigned int *pattern_flags, const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext,
                               const unsigned int elements, const int buffer_size, const hg_rank_params_t *params,
                               hg_file_values_event on_file, void *context, hg_file_summary_t *summaries);
+
+/* Matched values accumulated across scans, with a cut to the most frequent (grep -o | sort | uniq -c | sort -rn | head over a
+ * text that arrives in many buffers): a value store on the scanner, a device-resident table of distinct values that survives
+ * scans.  hg_accumulate_values adds the parts of the last scan with parts (hg_scan_device_parts or
+ * hg_scan_device_segments_parts); hg_rank_accumulated orders the store and cuts it, so that only the kept rows go to the host.
+ * Definition.  Let the accumulated calls since the last reset be 1 .. k and P their scans' parts, one list after the other; a
+ * part's ordinal is the number of parts of the earlier calls plus its index in its own call.  The store's groups are the groups
+ * hg_count_values defines over P, by its Value and Key rules: a part whose piece has no record is not counted, the segment is
+ * never in the key, the expression index is with HG_ACC_BY_PATTERN.  Per group: count, the number of parts in it; first, the
+ * smallest ordinal in it; pattern and line_number those of part `first` (the caller chains line_base across buffers, as for
+ * counts).  A scan that is accumulated twice counts twice.  Every output is a function of the inputs alone.
+ * Cut identity.  A text cut at piece boundaries into buffers that are scanned in order with chained line_base and accumulated one
+ * by one leaves the store the whole text accumulated once leaves: every array of every ranking is equal, first included.
+ * Rank.  hg_rank_accumulated orders the groups by descending count, then ascending first (with HG_ACC_ORDER_FIRST by ascending
+ * first only) and keeps the first `top` (0: all).  Only the kept rows' bytes are gathered: row j is d_bytes[d_off[j],
+ * d_off[j + 1]).  n_distinct is the number of groups before the cut, n_parts the parts of all accumulated calls (counted or
+ * not), n_bytes the kept rows' bytes.  The result stays valid until the next hg_accumulate_values, hg_rank_accumulated or
+ * hg_reset_accumulated on the scanner; scans do not disturb it, and it changes nothing in the store.
+ * params (NULL: all defaults).  hash_bits and table_log2 mean what they mean in hg_values_params_t and govern the call's own
+ * grouping.  store_log2 == 0 lets the store's table grow on its own: the smallest power of two that is at least twice the
+ * distinct values and at least 2^10, never smaller than before.  An explicit store_log2 fixes the table size (for tests); if it
+ * does not hold the values with one slot to spare the call returns HG_ERR_NOMEM.  HG_ACC_BY_PATTERN and hash_bits are fixed
+ * when a store begins: a call that differs from them without HG_ACC_RESET is refused.  HG_ACC_RESET empties the store first.
+ * HG_ERR_ARG, with nothing launched and the reason in hg_scanner_error: everything hg_count_values refuses; unknown flag bits;
+ * an explicit store_log2 above 40; a changed HG_ACC_BY_PATTERN or hash_bits without HG_ACC_RESET; a rank or copy call with no
+ * accumulation since the last reset (for the copies also: no ranking since the last accumulation).
+ * Atomicity.  A refused call and a call that runs out of memory leave the store exactly as it was, HG_ACC_RESET or not.  A
+ * HIP error (HG_ERR_HIP) behind that point leaves it empty, as after hg_reset_accumulated, and says so.
+ * Isolation.  The store has buffers of its own, a values stage of its own among them: the scan's results and an earlier
+ * hg_count_values, hg_rank_values, gather or count stay as they are.
+ * The stage runs on the GPU (hypergrep_amd/csrc/hg_valstore.hip): hg_count_values' grouping of the call's parts, a read-only
+ * lookup of every group in the store's table (a lane per group, a wavefront per value longer than 256 bytes; the text against
+ * the store's byte arena by whole aligned dwords of both), two scans that size the new values, a rehash when the table grows,
+ * an apply pass (a found group adds its count, a new one claims a slot by compare-and-swap) and the gathers' copy pass from
+ * the text to the arena; a ranking is one stable radix sort, a place pass and the copy pass over the kept rows.  acc_us and
+ * rank_us: the calls in microseconds (HIP events; their host synchronisations included).
+ * Not offered: per-segment keys in the store, case folding, ranking across GPUs. */
+#define HG_ACC_BY_PATTERN 1u   /* the expression index is part of the key */
+#define HG_ACC_RESET 2u        /* empty the store first */
+#define HG_ACC_ORDER_FIRST 1u  /* hg_rank_accumulated: keep the store's order, which is first occurrence */
+typedef struct hg_acc_params { /* sizeof 16 */
+    uint32_t flags;            /* HG_ACC_BY_PATTERN, HG_ACC_RESET */
+    uint32_t hash_bits;        /* 0: 64 */
+    uint32_t table_log2;       /* 0: from the call's parts */
+    uint32_t store_log2;       /* 0: from the store's distinct values */
+} hg_acc_params_t;
+typedef struct hg_acc_result { /* sizeof 56 */
+    uint64_t n_distinct;       /* the store's distinct values after the call */
+    uint64_t n_added;          /* of them new with this call */
+    uint64_t n_groups;         /* this call's groups */
+    uint64_t n_parts;          /* this call's parts */
+    uint64_t n_parts_total;    /* the parts accumulated so far */
+    uint64_t n_bytes;          /* the bytes of the store's values */
+    uint32_t store_log2, acc_us; /* the table the store has now */
+} hg_acc_result_t;
+typedef struct hg_acc_rank_result { /* sizeof 88 */
+    uint64_t n_values, n_distinct, n_parts, n_bytes;
+    const uint8_t *d_bytes;        /* DEVICE, valid until the next accumulate, rank or reset on this scanner */
+    const uint64_t *d_off;         /* n_values + 1 */
+    const uint64_t *d_count;       /* parts per row */
+    const uint64_t *d_first;       /* the smallest ordinal per row */
+    const uint32_t *d_pattern;     /* expression index of part `first` */
+    const uint64_t *d_line_number; /* line_number of part `first` */
+    uint32_t store_log2, rank_us;
+} hg_acc_rank_result_t;
+int hg_accumulate_values(hg_scanner_t *scanner, const void *d_text, uint64_t nbytes, const hg_acc_params_t *params, void *stream,
+                         hg_acc_result_t *result);
+int hg_rank_accumulated(hg_scanner_t *scanner, uint64_t top, uint32_t flags, void *stream, hg_acc_rank_result_t *result);
+/* Copy the last ranking's first max_bytes bytes and the per-row arrays of its first max_values rows to host memory (any pointer
+ * may be NULL; off receives min(n_values, max_values) + 1 values). */
+int hg_copy_accumulated(hg_scanner_t *scanner, uint8_t *bytes, uint64_t max_bytes, uint64_t *off, uint64_t *count, uint64_t *first,
+                        uint32_t *pattern, uint64_t *line_number, uint64_t max_values);
+/* The bytes (the first max_bytes of them) into a DEVICE buffer, asynchronously on `stream`. */
+int hg_copy_accumulated_device(hg_scanner_t *scanner, void *d_dst, uint64_t max_bytes, void *stream);
+/* Empty the store (its buffers stay with the scanner).  HG_ERR_ARG for scanner == NULL only. */
+int hg_reset_accumulated(hg_scanner_t *scanner);
+/* hg_hyperscan_values with the store behind every chunk's scan and one ranking at the end: its arguments, reader, chunking,
+ * decompression and database cache, plus `top` (0: all).  Every chunk's parts are accumulated where they lie; on success
+ * on_values is called once, with the kept rows by (count descending, first occurrence in the file).  *n_distinct and *n_parts
+ * (either may be NULL) receive the file's distinct values and its parts, both before the cut (two out-pointers, so that the
+ * callback keeps hg_values_event's signature).  No part record, no line and no
+ * per-chunk value list leaves the GPU.  Return codes and early refusals are hg_hyperscan_values'. */
+int hg_hyperscan_values_top(char *file_name, const char *const *patterns, const unsigned int *pattern_flags,
+                            const unsigned int *pattern_ids, const hs_expr_ext_t *const *ext, const unsigned int elements,
+                            const int buffer_size, const hg_values_params_t *params, uint64_t top, hg_values_event on_values,
+                            void *context, uint64_t *n_distinct, uint64_t *n_parts);
 
 /* Counts per report id (hg_count_records): which expressions fired, and on how many lines, without moving the record list.
  * Bins.  A bin is a distinct report id of the database, in ascending id order (hg_db_report_ids; n_bins <= n_patterns).

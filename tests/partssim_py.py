@@ -38,6 +38,11 @@ def lib() -> ctypes.CDLL:
         _lib.partssim_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
         _lib.partssim_piece.restype = ctypes.c_long
         _lib.partssim_piece.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]
+        p32 = ctypes.POINTER(ctypes.c_uint32)
+        _lib.partssim_pattern_info.restype = ctypes.c_uint32
+        _lib.partssim_pattern_info.argtypes = [ctypes.c_void_p, ctypes.c_uint32, p32]
+        _lib.partssim_piece_grouped.restype = ctypes.c_long
+        _lib.partssim_piece_grouped.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, p32, ctypes.c_size_t, p32, ctypes.c_size_t, p32]
     return _lib
 
 
@@ -73,6 +78,31 @@ class Db:
         n = lib().partssim_piece(self.h, data, len(data), out, cap)
         assert n >= 0
         return [tuple(out[3 * i:3 * i + 3]) for i in range(n)]
+
+    def pattern_info(self, index: int) -> dict:
+        """{"nw", "simple", "nnodes"} of expression `index`."""
+        assert self.h, self.error
+        out = (ctypes.c_uint32 * 3)()
+        n = lib().partssim_pattern_info(self.h, index, out)
+        assert index < n, (index, n)
+        return {"nw": out[0], "simple": out[1], "nnodes": out[2]}
+
+    def n_patterns(self) -> int:
+        assert self.h, self.error
+        return lib().partssim_pattern_info(self.h, 0xFFFFFFFF, (ctypes.c_uint32 * 3)())
+
+    def piece_grouped(self, data: bytes):
+        """The replay of the kernels' decomposition (groups of 64 starts, first-byte rule, ballot / cursor / base loop) of one
+        trimmed piece: ([(from, to, pattern)], ties, trace).  ties[i]: an expression of another bitmap word reaches part i's
+        end too; trace: [(base, ballot rounds, outrun starts)] per group."""
+        cap = len(data) + 1
+        out = (ctypes.c_uint32 * (4 * cap))()
+        trace = (ctypes.c_uint32 * (3 * cap))()
+        groups = ctypes.c_uint32()
+        n = lib().partssim_piece_grouped(self.h, data, len(data), out, cap, trace, cap, ctypes.byref(groups))
+        assert n >= 0, n
+        return ([tuple(out[4 * i:4 * i + 3]) for i in range(n)], [out[4 * i + 3] for i in range(n)],
+                [tuple(trace[3 * i:3 * i + 3]) for i in range(groups.value)])
 
     def text(self, data: bytes, buffer_size: int = 1 << 20, line_base: int = 0):
         """[(line_number, from, to, pattern)] over every piece of a text that has a part."""

@@ -19,7 +19,7 @@ _lib = None
 
 
 def build() -> None:
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("hg_compile.cpp", "hg_compile.h", "hg_core.h", "hg_db.h", "hg_som.h")]
+    deps = [SRC, os.path.join(REPO, "include", "hypergrep_amd.h")] + [os.path.join(CSRC, f) for f in ("hg_compile.cpp", "hg_compile.h", "hg_core.h", "hg_db.h", "hg_som.h")]
     if os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in deps):
         return
     tmp = f"{LIB}.{os.getpid()}.tmp"  # built aside and renamed into place (parallel test workers)
@@ -40,16 +40,35 @@ def lib() -> ctypes.CDLL:
         _lib.somsim_piece.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t]
         _lib.somsim_start.restype = ctypes.c_uint32
         _lib.somsim_start.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32]
+        _lib.somsim_compile_ext.restype = ctypes.c_void_p
+        _lib.somsim_pattern.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+        _lib.somsim_nfa_som.restype = ctypes.c_uint32
+        _lib.somsim_nfa_som.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32]
+        _lib.somsim_nfa_minlen.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
+        _lib.somsim_walk.restype = None
+        _lib.somsim_walk.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                     ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]
     return _lib
 
 
+NONE32 = 0xFFFFFFFF
+EXITS = ("died", "lo", "start", "early")  # how somsim_walk ended: state died, q == lo, piece start, early exit
+
+
 class Db:
-    def __init__(self, patterns, flags, ids=None):
-        """ids default to 0, 1, 2 ...: one report id per expression"""
+    def __init__(self, patterns, flags, ids=None, exts=None):
+        """ids default to 0, 1, 2 ...: one report id per expression; exts: one extsim_py.ExprExt or None per expression"""
         n = len(patterns)
+        self.n = n
         enc = [p.encode() if isinstance(p, str) else p for p in patterns]
         err = ctypes.create_string_buffer(512)
-        self.h = lib().somsim_compile((ctypes.c_char_p * n)(*enc), (ctypes.c_uint * n)(*flags), (ctypes.c_uint * n)(*(ids if ids is not None else range(n))), n, err, 512)
+        pa, fa, ia = (ctypes.c_char_p * n)(*enc), (ctypes.c_uint * n)(*flags), (ctypes.c_uint * n)(*(ids if ids is not None else range(n)))
+        if exts is None:
+            self.h = lib().somsim_compile(pa, fa, ia, n, err, 512)
+        else:
+            self._exts = [e if e is None else ctypes.pointer(e) for e in exts]
+            ea = (ctypes.c_void_p * n)(*[None if e is None else ctypes.cast(e, ctypes.c_void_p) for e in self._exts])
+            self.h = lib().somsim_compile_ext(pa, fa, ia, ea, n, err, 512)
         self.error = None if self.h else err.value.decode()
 
     def ok(self) -> bool:
@@ -71,6 +90,26 @@ class Db:
 
     def start(self, pattern: int, data: bytes, to: int) -> int:
         return lib().somsim_start(self.h, pattern, data, len(data), to)
+
+    def pattern(self, i: int) -> dict:
+        """The compiler's read-out of expression i."""
+        out = (ctypes.c_uint32 * 8)()
+        lib().somsim_pattern(self.h, i, out)
+        return dict(zip(("nw", "max_len", "literal_only", "som_next", "flags", "min_length", "tier", "reverse_tables"), out))
+
+    def nfa_som(self, pattern: int, data: bytes, to: int) -> int:
+        """hg_nfa_som: the scalar loop (NONE32 when no match of the expression ends at `to`)."""
+        return lib().somsim_nfa_som(self.h, pattern, data, len(data), to)
+
+    def nfa_minlen(self, pattern: int, data: bytes, to: int, min_len: int) -> bool:
+        return bool(lib().somsim_nfa_minlen(self.h, pattern, data, len(data), to, min_len))
+
+    def walk(self, pattern: int, text: bytes, a: int, length: int, to: int, early: bool = False, limit: int = 0) -> dict:
+        """somsim_walk, the restatement of the kernel's chunked walk, on the piece text[a, a + length): result, exit (EXITS),
+        the lowest and highest text offset loaded, the 64-byte rounds."""
+        out = (ctypes.c_uint64 * 5)()
+        lib().somsim_walk(self.h, pattern, text, len(text), a, length, to, int(early), limit, out)
+        return {"result": out[0], "exit": EXITS[out[1]], "lowest": out[2], "highest": out[3], "rounds": out[4]}
 
     def __del__(self):
         if getattr(self, "h", None):

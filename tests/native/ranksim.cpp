@@ -47,7 +47,11 @@ struct CheckedText {
 
 struct HostTable {
   unsigned long long *slot;
-  uint64_t load(uint64_t i) const { return slot[i]; }
+  uint64_t *probes;  // read-out: slots loaded so far
+  uint64_t load(uint64_t i) const {
+    ++*probes;
+    return slot[i];
+  }
   uint64_t claim(uint64_t i, uint64_t word) const {
     const uint64_t old = slot[i];
     if (old == HG_VALUES_EMPTY) slot[i] = word;
@@ -94,6 +98,21 @@ uint64_t insert_one(const HgValuesArgs &a, const CheckedText &view, const HostTa
   return hg_values_is_long(a.len[q]) ? wave_insert<SEG>(a, view, t, q) : hg_values_insert<SEG>(a, view, t, q);
 }
 
+// Read-outs of one run (ranksim_trace): what a cell of tests/value_cells.py claims to reach is proved from these.
+struct Trace {
+  uint64_t *part;   // RANKSIM_PART_COLS per part: tier (0 none, 1 lane, 2 wave), home, final slot, slots probed, wrapped past the last
+                    // slot, claimed (1) or joined (0), the key word (0 without HG_RANK_PER_SEGMENT)
+  uint64_t *seg;    // RANKSIM_SEG_COLS per segment (one without HG_RANK_PER_SEGMENT): first_group, seg_distinct, seg_parts, kept
+  uint64_t *group;  // per group of the final order: placed (1) or cut (0)
+  uint64_t *call;   // RANKSIM_CALL_COLS: groups, the count sort's key width, the segment sort's, slots of the table
+};
+constexpr uint32_t RANKSIM_PART_COLS = 7, RANKSIM_SEG_COLS = 4, RANKSIM_CALL_COLS = 4;
+
+long run_all(const uint8_t *text, uint64_t nbytes, uint64_t base, const uint64_t *recs, uint64_t n_recs, const uint64_t *parts, uint64_t n_parts, int segments,
+             const uint64_t *seg_start, uint32_t n_seg_in, uint32_t flags, uint64_t top, uint32_t hash_bits, uint32_t table_log2, uint64_t order_seed, uint64_t tile,
+             uint8_t *out_bytes, uint64_t cap_bytes, uint64_t *off, uint64_t *count, uint64_t *first, uint32_t *pattern, uint64_t *line_number, uint32_t *segment,
+             uint64_t *first_value, uint64_t *seg_distinct, uint64_t *seg_parts, uint64_t *totals, const Trace *tr);
+
 }  // namespace
 
 extern "C" {
@@ -110,6 +129,30 @@ long ranksim_run(const uint8_t *text, uint64_t nbytes, uint64_t base, const uint
                  const uint64_t *seg_start, uint32_t n_seg_in, uint32_t flags, uint64_t top, uint32_t hash_bits, uint32_t table_log2, uint64_t order_seed, uint64_t tile,
                  uint8_t *out_bytes, uint64_t cap_bytes, uint64_t *off, uint64_t *count, uint64_t *first, uint32_t *pattern, uint64_t *line_number, uint32_t *segment,
                  uint64_t *first_value, uint64_t *seg_distinct, uint64_t *seg_parts, uint64_t *totals) {
+  return run_all(text, nbytes, base, recs, n_recs, parts, n_parts, segments, seg_start, n_seg_in, flags, top, hash_bits, table_log2, order_seed, tile, out_bytes, cap_bytes, off, count,
+                 first, pattern, line_number, segment, first_value, seg_distinct, seg_parts, totals, nullptr);
+}
+
+// The same run with its read-outs (Trace above): part RANKSIM_PART_COLS * n_parts, seg RANKSIM_SEG_COLS * max(n_seg, 1), group
+// n_parts, call RANKSIM_CALL_COLS values.  Home, tier, key and everything per segment and per group do not depend on the
+// insertion order; final slot, probes, wrapped and claimed are those of the order the seed gives.
+long ranksim_trace(const uint8_t *text, uint64_t nbytes, uint64_t base, const uint64_t *recs, uint64_t n_recs, const uint64_t *parts, uint64_t n_parts, int segments,
+                   const uint64_t *seg_start, uint32_t n_seg_in, uint32_t flags, uint64_t top, uint32_t hash_bits, uint32_t table_log2, uint64_t order_seed, uint64_t tile,
+                   uint8_t *out_bytes, uint64_t cap_bytes, uint64_t *off, uint64_t *count, uint64_t *first, uint32_t *pattern, uint64_t *line_number, uint32_t *segment,
+                   uint64_t *first_value, uint64_t *seg_distinct, uint64_t *seg_parts, uint64_t *totals, uint64_t *tr_part, uint64_t *tr_seg, uint64_t *tr_group, uint64_t *tr_call) {
+  const Trace tr{tr_part, tr_seg, tr_group, tr_call};
+  return run_all(text, nbytes, base, recs, n_recs, parts, n_parts, segments, seg_start, n_seg_in, flags, top, hash_bits, table_log2, order_seed, tile, out_bytes, cap_bytes, off, count,
+                 first, pattern, line_number, segment, first_value, seg_distinct, seg_parts, totals, &tr);
+}
+
+}  // extern "C"
+
+namespace {
+
+long run_all(const uint8_t *text, uint64_t nbytes, uint64_t base, const uint64_t *recs, uint64_t n_recs, const uint64_t *parts, uint64_t n_parts, int segments,
+             const uint64_t *seg_start, uint32_t n_seg_in, uint32_t flags, uint64_t top, uint32_t hash_bits, uint32_t table_log2, uint64_t order_seed, uint64_t tile,
+             uint8_t *out_bytes, uint64_t cap_bytes, uint64_t *off, uint64_t *count, uint64_t *first, uint32_t *pattern, uint64_t *line_number, uint32_t *segment,
+             uint64_t *first_value, uint64_t *seg_distinct, uint64_t *seg_parts, uint64_t *totals, const Trace *tr) {
   if (!hash_bits) hash_bits = 64;
   if (!table_log2) table_log2 = hg_values_default_log2(n_parts);
   const bool per_seg = (flags & HG_RANK_F_PER_SEGMENT) != 0;
@@ -175,10 +218,14 @@ long ranksim_run(const uint8_t *text, uint64_t nbytes, uint64_t base, const uint
     state = state * 6364136223846793005ull + 1442695040888963407ull;
     std::swap(order[q - 1], order[(state >> 33) % q]);
   }
-  const HostTable t{slot.data()};
+  uint64_t probes = 0;
+  const HostTable t{slot.data(), &probes};
+  if (tr) std::fill(tr->part, tr->part + RANKSIM_PART_COLS * n_parts, 0);
   for (uint64_t i = 0; i < n_parts && !rc; i++) {
     const uint64_t q = order[i];
+    if (tr) tr->part[RANKSIM_PART_COLS * q + 6] = per_seg ? key[q] : 0;
     if (!len[q]) continue;
+    const uint64_t before = probes;
     const uint64_t s = per_seg ? insert_one<true>(a, view, t, q) : insert_one<false>(a, view, t, q);
     if (s == HG_VALUES_NO_SLOT) {
       rc = -4;
@@ -186,6 +233,15 @@ long ranksim_run(const uint8_t *text, uint64_t nbytes, uint64_t base, const uint
     }
     slot_count[s]++;
     slot_first[s] = std::min<unsigned long long>(slot_first[s], q);
+    if (tr) {
+      uint64_t *row = tr->part + RANKSIM_PART_COLS * q;
+      row[0] = hg_values_is_long(len[q]) ? 2 : 1;
+      row[1] = hg_values_home(hash[q], table_log2);
+      row[2] = s;
+      row[3] = probes - before;
+      row[4] = s < row[1];
+      row[5] = (slot[s] & HG_VALUES_REP_MASK) == q;
+    }
   }
   // mark, scan, compact, the sort by first
   uint64_t ng = 0;
@@ -251,6 +307,21 @@ long ranksim_run(const uint8_t *text, uint64_t nbytes, uint64_t base, const uint
   }
   const uint64_t n_values = fvalue[n_seg];
   if (!rc && n_values > ng) rc = -5;
+  if (tr && !rc) {
+    for (uint64_t s = 0; s < n_seg; s++) {
+      const uint64_t row[RANKSIM_SEG_COLS] = {first_group[s], distinct[s], sparts[s], kept[s]};
+      memcpy(tr->seg + RANKSIM_SEG_COLS * s, row, sizeof row);
+    }
+    for (uint64_t j = 0; j < ng; j++) {  // (hg_rank_place's rule, read from what the bounds pass left)
+      const uint64_t s = r.s_seg ? r.s_seg[j] : 0;
+      tr->group[j] = s < n_seg && j >= first_group[s] && j - first_group[s] < kept[s];
+    }
+    uint32_t bits = 1, seg_bits = 1;
+    while (bits < 64 && (n_parts >> bits)) bits++;            // (HgRank::run: count <= n_parts)
+    while (seg_bits < 32 && (n_seg >> seg_bits)) seg_bits++;  // (segment < n_seg)
+    const uint64_t call[RANKSIM_CALL_COLS] = {ng, bits, seg_bits, cap};
+    memcpy(tr->call, call, sizeof call);
+  }
   for (uint64_t j = 0; j <= ng; j++) offs[j + 1] = offs[j] + size[j];
   for (uint64_t j = 0; j < n_values && !rc; j++)
     if (out_first[j] == ~uint64_t{0} || !size[j]) rc = -5;  // every kept row was written
@@ -308,6 +379,10 @@ long ranksim_run(const uint8_t *text, uint64_t nbytes, uint64_t base, const uint
   free(block);
   return rc;
 }
+
+}  // namespace
+
+extern "C" {
 
 // {sizeof params, sizeof result, offsets of the params' fields, offsets of the result's fields, the two flags, sizeof
 // hg_values_params_t and hg_values_result_t}
@@ -398,6 +473,19 @@ int main() {
                              : totals[0] == 1 && count[0] == 3 && first[0] == 0);
       if (!ok) printf("long, flags %u: rc %ld\n", flags, rc);
       bad |= !ok;
+      cases++;
+      // the same with a cut of one row a file, through the read-outs: three wave parts; with the segment in the key the key
+      // words are (1 << 32) and (2 << 32), file 0 has one group, file 1 one; without it one segment owns the one group
+      uint64_t tr_part[3 * 7], tr_seg[2 * 4], tr_group[3], tr_call[4];
+      const long rc2 = ranksim_trace(reinterpret_cast<const uint8_t *>(text.data()), text.size(), base, recs, 3, parts, 3, 1, seg_start, 2, flags, 1, 2, 2, 0, 64, out.data(), out.size(),
+                                     off, count, first, pattern, line, segment, fv, sd, sp, totals, tr_part, tr_seg, tr_group, tr_call);
+      const bool ok2 = rc2 == 0 && tr_part[0] == 2 && tr_part[7] == 2 && tr_part[14] == 2 && tr_part[1] < 4 && tr_part[5] == 1 && tr_call[1] == 2 && tr_call[2] == (flags ? 2u : 1u) &&
+                       tr_call[3] == 4 &&
+                       (flags ? tr_part[6] == (uint64_t{1} << 32) && tr_part[13] == (uint64_t{2} << 32) && tr_call[0] == 2 && tr_seg[0] == 0 && tr_seg[1] == 1 && tr_seg[2] == 1 &&
+                                    tr_seg[3] == 1 && tr_seg[4] == 1 && tr_seg[6] == 2 && tr_group[0] == 1 && tr_group[1] == 1
+                              : tr_part[6] == 0 && tr_call[0] == 1 && tr_seg[1] == 1 && tr_seg[2] == 3 && tr_seg[3] == 1 && tr_group[0] == 1);
+      if (!ok2) printf("long, read-outs, flags %u: rc %ld\n", flags, rc2);
+      bad |= !ok2;
       cases++;
     }
   }

@@ -134,7 +134,13 @@ struct Store {
   std::vector<uint64_t> v_off, v_count, v_first, v_line, v_hash;
   std::vector<uint32_t> v_len, v_pattern;
   std::vector<uint8_t> arena;
+  // read-outs of the last call that ended with 0 (valstoresim_trace)
+  std::vector<uint64_t> tr_group;  // VALSTORESIM_GROUP_COLS per group: tier (1 lane, 2 wave), found (1) or new (0), slots probed, probed past the last slot
+  std::vector<uint64_t> tr_value;  // VALSTORESIM_VALUE_COLS per stored value behind the call: its home in the table before the call (NONE: no table yet) and behind it
+  uint64_t tr_call[8] = {};        // log2 before, log2 behind, a rehash ran, the arena's tail before the call, the same rounded up to 16 (where the new
+                                   // bytes begin), the new bytes, the count sort's key width behind the call, long groups
 };
+constexpr uint32_t VALSTORESIM_GROUP_COLS = 4, VALSTORESIM_VALUE_COLS = 2, VALSTORESIM_CALL_COLS = 8;
 
 }  // namespace
 
@@ -237,9 +243,18 @@ long valstoresim_add(void *handle, const uint8_t *text, uint64_t nbytes, uint64_
   // lookup (read-only): both forms where the lane's is allowed, the wave's alone for long values
   const HostTable t{st.slot.data(), &st.probes};
   bool overflow = false;
+  std::vector<uint64_t> tr_group(VALSTORESIM_GROUP_COLS * ng, 0);
+  uint64_t n_long = 0;
   for (uint64_t j = 0; j < ng; j++) {
+    const uint64_t before = st.probes;
     const uint64_t by_wave = wave_lookup(a, view, arena, t, j, &overflow);
     match[j] = by_wave;
+    const bool is_long = hg_values_is_long(len[g_first[j]]);
+    n_long += is_long;
+    tr_group[VALSTORESIM_GROUP_COLS * j] = is_long ? 2 : 1;
+    tr_group[VALSTORESIM_GROUP_COLS * j + 1] = by_wave != HG_VALSTORE_NONE;
+    tr_group[VALSTORESIM_GROUP_COLS * j + 2] = st.probes - before;
+    tr_group[VALSTORESIM_GROUP_COLS * j + 3] = st.log2 && hg_values_home(hash[g_first[j]], st.log2) + (st.probes - before) > (uint64_t{1} << st.log2);
     if (!hg_values_is_long(len[g_first[j]]) && hg_valstore_lookup(a, view, arena, t, j, &overflow) != by_wave) rc = -3;
   }
   if (overflow) rc = rc ? rc : -4;
@@ -257,6 +272,8 @@ long valstoresim_add(void *handle, const uint8_t *text, uint64_t nbytes, uint64_
   if (log2_new > 30 || (uint64_t{1} << log2_new) <= n_after) return -5;
   // grow, keeping the contents; rehash into a table of the new size
   const uint64_t cap_new = uint64_t{1} << log2_new, padded = (new_bytes + 15) & ~uint64_t{15};
+  const uint32_t log2_old = st.log2;
+  const uint64_t tail_old = st.tail;
   if (log2_new != st.log2) {
     std::vector<unsigned long long> fresh(cap_new, HG_VALUES_EMPTY);
     a.slot_new = fresh.data();
@@ -307,7 +324,29 @@ long valstoresim_add(void *handle, const uint8_t *text, uint64_t nbytes, uint64_
   totals[3] = log2_new;
   totals[4] = st.rehashes;
   totals[5] = st.probes;
+  if (!rc) {
+    st.tr_group.swap(tr_group);
+    st.tr_value.assign(VALSTORESIM_VALUE_COLS * n_after, 0);
+    for (uint64_t i = 0; i < n_after; i++) {
+      st.tr_value[VALSTORESIM_VALUE_COLS * i] = log2_old ? hg_values_home(st.v_hash[i], log2_old) : HG_VALSTORE_NONE;
+      st.tr_value[VALSTORESIM_VALUE_COLS * i + 1] = hg_values_home(st.v_hash[i], log2_new);
+    }
+    uint32_t bits = 1;
+    while (bits < 64 && (st.n_parts >> bits)) bits++;  // (HgValueStore::rank: count <= the accumulated parts)
+    const uint64_t call[VALSTORESIM_CALL_COLS] = {log2_old, log2_new, log2_new != log2_old && n_old, tail_old, a.arena_tail, new_bytes, bits, n_long};
+    memcpy(st.tr_call, call, sizeof call);
+  }
   return rc;
+}
+
+// The read-outs of the last call that returned 0: groups and values are filled up to their caps; counts: {groups, values}.
+void valstoresim_trace(void *handle, uint64_t *groups, uint64_t cap_groups, uint64_t *values, uint64_t cap_values, uint64_t *call, uint64_t *counts) {
+  const Store &st = *static_cast<const Store *>(handle);
+  counts[0] = st.tr_group.size() / VALSTORESIM_GROUP_COLS;
+  counts[1] = st.tr_value.size() / VALSTORESIM_VALUE_COLS;
+  for (uint64_t k = 0; k < st.tr_group.size() && k < VALSTORESIM_GROUP_COLS * cap_groups; k++) groups[k] = st.tr_group[k];
+  for (uint64_t k = 0; k < st.tr_value.size() && k < VALSTORESIM_VALUE_COLS * cap_values; k++) values[k] = st.tr_value[k];
+  memcpy(call, st.tr_call, sizeof st.tr_call);
 }
 
 // A ranking.  out_bytes: room for cap_bytes; off: rows + 1; count, first, pattern, line_number: rows each, rows = min(top,
@@ -480,6 +519,16 @@ int main() {
                     memcmp(out.data() + 1027, other.data(), 1027) == 0;
     if (!ok) printf("long: rc %ld\n", rc);
     bad |= !ok;
+    cases++;
+    // the read-outs of the second call: two wave groups, `other` new and `one` found; the first call left 1027 bytes, so the
+    // new bytes begin at 1040; both values keep their home (no table before the first call, 2^10 slots since)
+    uint64_t groups[2 * 4], values[2 * 2], call[8], counts[2];
+    valstoresim_trace(st, groups, 2, values, 2, call, counts);
+    const bool ok2 = counts[0] == 2 && counts[1] == 2 && groups[0] == 2 && groups[1] == 0 && groups[4] == 2 && groups[5] == 1 && groups[6] >= 1 && values[0] == values[1] &&
+                     values[2] == values[3] && values[0] < 4 && call[0] == 10 && call[1] == 10 && call[2] == 0 && call[3] == 1027 && call[4] == 1040 && call[5] == 1027 && call[6] == 2 &&
+                     call[7] == 2;
+    if (!ok2) printf("long, read-outs: %llu %llu\n", (unsigned long long)counts[0], (unsigned long long)counts[1]);
+    bad |= !ok2;
     cases++;
     valstoresim_free(st);
   }

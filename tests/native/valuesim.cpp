@@ -46,8 +46,10 @@ struct CheckedText {
 struct HostTable {
   unsigned long long *slot;
   uint64_t *probes;
+  std::vector<uint64_t> *seen;  // read-out: the slot words the current probe loaded, in order (nullptr: not kept)
   uint64_t load(uint64_t i) const {
     ++*probes;
+    if (seen) seen->push_back(slot[i]);
     return slot[i];
   }
   uint64_t claim(uint64_t i, uint64_t word) const {
@@ -83,6 +85,21 @@ uint64_t wave_insert(const HgValuesArgs &a, const CheckedText &view, const HostT
   return HG_VALUES_NO_SLOT;
 }
 
+// Read-outs of one run (valuesim_trace): what a cell of tests/value_cells.py claims to reach is proved from these.
+struct Trace {
+  uint64_t *part;  // VALUESIM_PART_COLS per part: tier (0 none, 1 lane, 2 wave), home, final slot, slots probed, wrapped past the
+                   // last slot, claimed (1) or joined (0), occupied slots passed with the part's tag, with another tag
+  uint64_t *wave;  // VALUESIM_WAVE_COLS per wave of 64 parts of the insert pass: path (0 no counted lane, 1 one add by the leader,
+                   // 2 lane by lane), leader lane, active mask
+  uint64_t *call;  // VALUESIM_CALL_COLS: n_long, iterations of the busiest long-kernel wave, last slot occupied, n_values, the
+                   // sort's key width, slots of the table, waves of the long kernel's grid, parts without a value
+};
+constexpr uint32_t VALUESIM_PART_COLS = 8, VALUESIM_WAVE_COLS = 3, VALUESIM_CALL_COLS = 8;
+
+long run_all(const uint8_t *text, uint64_t nbytes, uint64_t base, const uint64_t *recs, uint64_t n_recs, const uint64_t *parts, uint64_t n_parts, int segments,
+             const uint64_t *seg_start, uint32_t flags, uint32_t hash_bits, uint32_t table_log2, uint64_t order_seed, uint64_t tile, uint8_t *out_bytes, uint64_t cap_bytes,
+             uint64_t *off, uint64_t *count, uint64_t *first, uint32_t *pattern, uint64_t *line_number, uint32_t *segment, uint64_t *totals, const Trace *tr);
+
 }  // namespace
 
 extern "C" {
@@ -96,6 +113,29 @@ extern "C" {
 long valuesim_run(const uint8_t *text, uint64_t nbytes, uint64_t base, const uint64_t *recs, uint64_t n_recs, const uint64_t *parts, uint64_t n_parts, int segments,
                   const uint64_t *seg_start, uint32_t flags, uint32_t hash_bits, uint32_t table_log2, uint64_t order_seed, uint64_t tile, uint8_t *out_bytes, uint64_t cap_bytes,
                   uint64_t *off, uint64_t *count, uint64_t *first, uint32_t *pattern, uint64_t *line_number, uint32_t *segment, uint64_t *totals) {
+  return run_all(text, nbytes, base, recs, n_recs, parts, n_parts, segments, seg_start, flags, hash_bits, table_log2, order_seed, tile, out_bytes, cap_bytes, off, count, first, pattern,
+                 line_number, segment, totals, nullptr);
+}
+
+// The same run with its read-outs (Trace above): part VALUESIM_PART_COLS * n_parts, wave VALUESIM_WAVE_COLS * ceil(n_parts / 64),
+// call VALUESIM_CALL_COLS values.  The parts are inserted in their own order when order_seed is 0: home, tier, the wave's path and
+// the set of occupied slots do not depend on the order; final slot, probes, wrapped and claimed are those of that order.
+long valuesim_trace(const uint8_t *text, uint64_t nbytes, uint64_t base, const uint64_t *recs, uint64_t n_recs, const uint64_t *parts, uint64_t n_parts, int segments,
+                    const uint64_t *seg_start, uint32_t flags, uint32_t hash_bits, uint32_t table_log2, uint64_t order_seed, uint64_t tile, uint8_t *out_bytes, uint64_t cap_bytes,
+                    uint64_t *off, uint64_t *count, uint64_t *first, uint32_t *pattern, uint64_t *line_number, uint32_t *segment, uint64_t *totals, uint64_t *tr_part, uint64_t *tr_wave,
+                    uint64_t *tr_call) {
+  const Trace tr{tr_part, tr_wave, tr_call};
+  return run_all(text, nbytes, base, recs, n_recs, parts, n_parts, segments, seg_start, flags, hash_bits, table_log2, order_seed, tile, out_bytes, cap_bytes, off, count, first, pattern,
+                 line_number, segment, totals, &tr);
+}
+
+}  // extern "C"
+
+namespace {
+
+long run_all(const uint8_t *text, uint64_t nbytes, uint64_t base, const uint64_t *recs, uint64_t n_recs, const uint64_t *parts, uint64_t n_parts, int segments,
+             const uint64_t *seg_start, uint32_t flags, uint32_t hash_bits, uint32_t table_log2, uint64_t order_seed, uint64_t tile, uint8_t *out_bytes, uint64_t cap_bytes,
+             uint64_t *off, uint64_t *count, uint64_t *first, uint32_t *pattern, uint64_t *line_number, uint32_t *segment, uint64_t *totals, const Trace *tr) {
   if (!hash_bits) hash_bits = 64;
   if (!table_log2) table_log2 = hg_values_default_log2(n_parts);
   if (table_log2 > 30 || (uint64_t{1} << table_log2) <= n_parts) return -1;
@@ -166,10 +206,14 @@ long valuesim_run(const uint8_t *text, uint64_t nbytes, uint64_t base, const uin
     state = state * 6364136223846793005ull + 1442695040888963407ull;
     std::swap(order[q - 1], order[(state >> 33) % q]);
   }
-  const HostTable t{slot.data(), &probes};
+  std::vector<uint64_t> seen, slot_of(n_parts + 1, HG_VALUES_NO_SLOT);
+  const HostTable t{slot.data(), &probes, tr ? &seen : nullptr};
+  if (tr) std::fill(tr->part, tr->part + VALUESIM_PART_COLS * n_parts, 0);
   for (uint64_t i = 0; i < n_parts && !rc; i++) {
     const uint64_t q = order[i];
     if (!len[q]) continue;
+    seen.clear();
+    const uint64_t before = probes;
     const uint64_t s = hg_values_is_long(len[q]) ? wave_insert(a, view, t, q) : hg_values_insert(a, view, t, q);
     if (s == HG_VALUES_NO_SLOT) {
       rc = -4;
@@ -177,6 +221,36 @@ long valuesim_run(const uint8_t *text, uint64_t nbytes, uint64_t base, const uin
     }
     slot_count[s]++;
     slot_first[s] = std::min<unsigned long long>(slot_first[s], q);
+    slot_of[q] = s;
+    if (tr) {
+      uint64_t *row = tr->part + VALUESIM_PART_COLS * q;
+      row[0] = hg_values_is_long(len[q]) ? 2 : 1;
+      row[1] = hg_values_home(hash[q], table_log2);
+      row[2] = s;
+      row[3] = probes - before;
+      row[4] = s < row[1];
+      row[5] = (slot[s] & HG_VALUES_REP_MASK) == q;
+      for (size_t k = 0; k + 1 < seen.size(); k++)  // (the last word seen is the empty slot it claimed or its group's)
+        row[(seen[k] >> HG_VALUES_REP_BITS) == hg_values_tag(hash[q]) ? 6 : 7]++;
+    }
+  }
+  if (tr) {  // the insert kernel's waves (insert_body): a lane per part, the short parts with a slot counted
+    for (uint64_t w = 0; w * HG_VALUES_WAVE < n_parts; w++) {
+      uint64_t act = 0, s0 = HG_VALUES_NO_SLOT;
+      bool uniform = true;
+      int leader = -1;
+      for (uint32_t lane = 0; lane < HG_VALUES_WAVE && w * HG_VALUES_WAVE + lane < n_parts; lane++) {
+        const uint64_t q = w * HG_VALUES_WAVE + lane;
+        if (!len[q] || hg_values_is_long(len[q]) || slot_of[q] == HG_VALUES_NO_SLOT) continue;
+        act |= uint64_t{1} << lane;
+        if (leader < 0) leader = static_cast<int>(lane), s0 = slot_of[q];
+        uniform = uniform && slot_of[q] == s0;
+      }
+      uint64_t *row = tr->wave + VALUESIM_WAVE_COLS * w;
+      row[0] = !act ? 0 : uniform ? 1 : 2;
+      row[1] = leader < 0 ? 0 : static_cast<uint64_t>(leader);
+      row[2] = act;
+    }
   }
   // mark, scan, compact, sort
   uint64_t n_values = 0;
@@ -201,6 +275,23 @@ long valuesim_run(const uint8_t *text, uint64_t nbytes, uint64_t base, const uin
   totals[1] = offs[n_values];
   totals[2] = probes;
   totals[3] = n_long;
+  if (tr) {
+    // the long kernel's grid (hg_values_launch): min((n_parts + 3) / 4, HG_VALUES_LONG_BLOCKS) workgroups of 4 waves, wave i takes
+    // the list entries i, i + n_waves, ...
+    const uint64_t n_waves = std::min<uint64_t>((n_parts + 3) / 4, HG_VALUES_LONG_BLOCKS) * (HG_VALUES_THREADS / HG_VALUES_WAVE);
+    uint32_t bits = 1;
+    while (bits < 64 && (n_parts >> bits)) bits++;  // (HgValues::group: first < n_parts)
+    uint64_t none = 0;
+    for (uint64_t q = 0; q < n_parts; q++) none += !len[q];
+    tr->call[0] = n_long;
+    tr->call[1] = n_waves ? (n_long + n_waves - 1) / n_waves : 0;
+    tr->call[2] = slot[cap - 1] != HG_VALUES_EMPTY;
+    tr->call[3] = n_values;
+    tr->call[4] = bits;
+    tr->call[5] = cap;
+    tr->call[6] = n_waves;
+    tr->call[7] = none;
+  }
   // copy pass: the line gather's, over entries with nothing but a body
   HgGatherArgs g{};
   g.entries = entries.data();
@@ -238,6 +329,10 @@ long valuesim_run(const uint8_t *text, uint64_t nbytes, uint64_t base, const uin
   free(block);
   return rc;
 }
+
+}  // namespace
+
+extern "C" {
 
 // The hash of text[s, s + len) by the byte-wise definition (which 0), a lane's dword path (1) and a wave's shares (2); *bad is
 // set if a read left [0, nbytes rounded up to 4).
@@ -332,6 +427,37 @@ int main() {
     const bool ok = rc == 0 && totals[0] == 2 && totals[1] == 2000 && totals[3] == 3 && count[0] == 2 && count[1] == 1 && first[1] == 2 && memcmp(out.data(), one.data(), 1000) == 0 &&
                     memcmp(out.data() + 1000, other.data(), 1000) == 0;
     if (!ok) printf("long: rc %ld\n", rc);
+    bad |= !ok;
+    cases++;
+    // the same through the read-outs: three wave parts, no counted lane in the insert pass's only wave, one iteration a wave,
+    // two slots of four taken; in a table of 4 with 2 hash bits every home is a slot of its own or a shared one
+    uint64_t tr_part[3 * 8], tr_wave[3], tr_call[8];
+    const long rc2 = valuesim_trace(reinterpret_cast<const uint8_t *>(text.data()), text.size(), base, recs, 3, parts, 3, 0, nullptr, 0, 2, 2, 0, 64, out.data(), out.size(), off, count,
+                                    first, pattern, line, nullptr, totals, tr_part, tr_wave, tr_call);
+    const bool ok2 = rc2 == 0 && totals[0] == 2 && tr_part[0] == 2 && tr_part[8] == 2 && tr_part[16] == 2 && tr_part[5] == 1 && tr_part[8 + 5] == 0 && tr_part[16 + 5] == 1 &&
+                     tr_part[2] == tr_part[8 + 2] && tr_part[2] != tr_part[16 + 2] && tr_wave[0] == 0 && tr_call[0] == 3 && tr_call[1] == 1 && tr_call[3] == 2 && tr_call[4] == 2 &&
+                     tr_call[5] == 4 && tr_call[6] == 4 && tr_call[7] == 0;
+    if (!ok2) printf("long, read-outs: rc %ld\n", rc2);
+    bad |= !ok2;
+    cases++;
+  }
+  {  // read-outs of the insert pass: 70 parts, `ab` in lanes 1 .. 63 of wave 0 behind an `abc`, then wave 1 with two values
+    std::string text;
+    std::vector<uint64_t> recs, parts;
+    for (uint64_t q = 0; q < 70; q++) {
+      const std::string v = q == 0 || q == 66 ? "abc" : "ab";
+      recs.insert(recs.end(), {q, base + text.size(), v.size() + 1, 0});
+      parts.insert(parts.end(), {q, 0, v.size(), 0, 0});
+      text += v + "\n";
+    }
+    uint8_t out[64];
+    uint64_t off[71], count[71], first[71], line[71], totals[4], tr_part[70 * 8], tr_wave[2 * 3], tr_call[8];
+    uint32_t pattern[71];
+    const long rc = valuesim_trace(reinterpret_cast<const uint8_t *>(text.data()), text.size(), base, recs.data(), 70, parts.data(), 70, 0, nullptr, 0, 1, 7, 0, 16, out, sizeof out, off, count,
+                                   first, pattern, line, nullptr, totals, tr_part, tr_wave, tr_call);
+    const bool ok = rc == 0 && totals[0] == 2 && count[0] == 2 && count[1] == 68 && first[1] == 1 && tr_wave[0] == 2 && tr_wave[1] == 0 && tr_wave[2] == ~uint64_t{0} &&
+                    tr_wave[3] == 2 && tr_wave[5] == 63 && tr_part[0] == 1 && tr_part[1] < 2 && tr_call[0] == 0 && tr_call[1] == 0 && tr_call[4] == 7 && tr_call[5] == 128;
+    if (!ok) printf("insert pass, read-outs: rc %ld\n", rc);
     bad |= !ok;
     cases++;
   }

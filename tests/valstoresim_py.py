@@ -37,6 +37,7 @@ def lib() -> ctypes.CDLL:
         _lib.valstoresim_add.argtypes = [vp, p8, u64, u64, p64, u64, p64, u64, u64, u64, p64]
         _lib.valstoresim_rank.restype = ctypes.c_long
         _lib.valstoresim_rank.argtypes = [vp, u64, ctypes.c_int, u64, ctypes.POINTER(ctypes.c_uint8), u64, u64, p64, p64, p64, p32, p64, p64]
+        _lib.valstoresim_trace.argtypes = [vp, p64, u64, p64, u64, p64, p64]
         _lib.valstoresim_equal.argtypes = [p8, u64, u64, p8, u64, u64, u32, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         _lib.valstoresim_sizes.argtypes = [p32]
     return _lib
@@ -89,6 +90,21 @@ class Store:
         assert rc == 0, f"valstoresim_add returned {rc}"
         self.info = {"n_distinct": totals[0], "n_added": totals[1], "n_groups": totals[2], "store_log2": totals[3], "rehashes": totals[4], "probes": totals[5]}
         return 0
+
+    GROUP_COLS = ("tier", "found", "probes", "wrapped")  # tier: 1 lane, 2 wave
+    VALUE_COLS = ("home_old", "home_new")               # home_old NONE (2^64 - 1) while the store had no table
+    CALL_COLS = ("log2_old", "log2_new", "rehashed", "arena_tail", "tail16", "new_bytes", "sort_bits", "n_long")
+
+    def trace(self, max_groups: int = 1 << 16, max_values: int = 1 << 16):
+        """The read-outs of the last add() that returned 0 (valstoresim.cpp, Store::tr_*): {"groups": a dict of GROUP_COLS per
+        group of the call, in the order of first, "values": one of VALUE_COLS per stored value, "call": one of CALL_COLS}."""
+        g, v = (ctypes.c_uint64 * (len(self.GROUP_COLS) * max_groups))(), (ctypes.c_uint64 * (len(self.VALUE_COLS) * max_values))()
+        call, counts = (ctypes.c_uint64 * len(self.CALL_COLS))(), (ctypes.c_uint64 * 2)()
+        lib().valstoresim_trace(self._h, g, max_groups, v, max_values, call, counts)
+        assert counts[0] <= max_groups and counts[1] <= max_values
+        ng, nv, gc, vc = counts[0], counts[1], len(self.GROUP_COLS), len(self.VALUE_COLS)
+        return {"groups": [dict(zip(self.GROUP_COLS, g[gc * j:gc * (j + 1)])) for j in range(ng)], "values": [dict(zip(self.VALUE_COLS, v[vc * i:vc * (i + 1)])) for i in range(nv)],
+                "call": dict(zip(self.CALL_COLS, call))}
 
     def rank(self, top: int = 0, order_first: bool = False, max_rows: int = 1 << 16, max_bytes: int = 1 << 22):
         out = (ctypes.c_uint8 * max_bytes)()

@@ -32,6 +32,8 @@ def lib() -> ctypes.CDLL:
         _lib.valuesim_run.restype = ctypes.c_long
         _lib.valuesim_run.argtypes = [p8, u64, u64, p64, u64, p64, u64, ctypes.c_int, p64, u32, u32, u32, u64, u64, ctypes.POINTER(ctypes.c_uint8), u64, p64, p64, p64, p32, p64,
                                       p32, p64]
+        _lib.valuesim_trace.restype = ctypes.c_long
+        _lib.valuesim_trace.argtypes = _lib.valuesim_run.argtypes + [p64, p64, p64]
         _lib.valuesim_hash.restype = u64
         _lib.valuesim_hash.argtypes = [p8, u64, u64, u32, u32, u32, u32, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         _lib.valuesim_sizes.argtypes = [p32]
@@ -57,10 +59,17 @@ def hash_of(text: bytes, s: int, length: int, which: int, by_pattern: bool = Fal
     return h
 
 
-def replay(text: bytes, records, parts, by_pattern: bool = False, seg_start=None, hash_bits: int = 0, table_log2: int = 0, order_seed: int = 0, tile: int = 16384, base: int = 0):
+PART_COLS = ("tier", "home", "slot", "probes", "wrapped", "claimed", "same_tag", "other_tag")  # tier: 0 none, 1 lane, 2 wave
+WAVE_COLS = ("path", "leader", "mask")  # path: 0 no counted lane, 1 one add by the leader, 2 lane by lane
+CALL_COLS = ("n_long", "long_iterations", "last_slot_occupied", "n_values", "sort_bits", "slots", "long_waves", "no_value")
+
+
+def replay(text: bytes, records, parts, by_pattern: bool = False, seg_start=None, hash_bits: int = 0, table_log2: int = 0, order_seed: int = 0, tile: int = 16384, base: int = 0,
+           trace: bool = False):
     """The stage over `parts`, (line, from, to, pattern, segment) rows, and `records`, (line, start, len, segment) rows, both in the
     scan's order.  seg_start: the files' offsets (the scan had segments).  Returns (arrays as values_ref.arrays gives them,
-    {"probes", "n_long"})."""
+    {"probes", "n_long"}); with trace also {"parts": a dict of PART_COLS per part, "waves": one of WAVE_COLS per wave of the
+    insert pass, "call": one of CALL_COLS} (valuesim.cpp, Trace)."""
     n, nr = len(parts), len(records)
     segments = seg_start is not None
     c_recs = (ctypes.c_uint64 * max(4 * nr, 1))(*[v for r in records for v in (r[0], r[1] + (0 if segments else base), r[2], r[3])])
@@ -71,9 +80,20 @@ def replay(text: bytes, records, parts, by_pattern: bool = False, seg_start=None
     off, count, first, line = ((ctypes.c_uint64 * (n + 1))() for _ in range(4))
     pattern, segment = ((ctypes.c_uint32 * (n + 1))() for _ in range(2))
     totals = (ctypes.c_uint64 * 4)()
-    rc = lib().valuesim_run(text, len(text), base, c_recs, nr, c_parts, n, 1 if segments else 0, c_seg, 1 if by_pattern else 0, hash_bits, table_log2, order_seed, tile, out, cap,
-                            off, count, first, pattern, line, segment, totals)
+    args = (text, len(text), base, c_recs, nr, c_parts, n, 1 if segments else 0, c_seg, 1 if by_pattern else 0, hash_bits, table_log2, order_seed, tile, out, cap, off, count, first,
+            pattern, line, segment, totals)
+    n_waves = (n + 63) // 64
+    if trace:
+        t_part, t_wave, t_call = (ctypes.c_uint64 * max(len(PART_COLS) * n, 1))(), (ctypes.c_uint64 * max(len(WAVE_COLS) * n_waves, 1))(), (ctypes.c_uint64 * len(CALL_COLS))()
+        rc = lib().valuesim_trace(*args, t_part, t_wave, t_call)
+    else:
+        rc = lib().valuesim_run(*args)
     assert rc == 0, f"valuesim_run returned {rc}"
     nv, nb = totals[0], totals[1]
+    info = {"probes": totals[2], "n_long": totals[3]}
+    if trace:
+        info["parts"] = [dict(zip(PART_COLS, t_part[len(PART_COLS) * q:len(PART_COLS) * (q + 1)])) for q in range(n)]
+        info["waves"] = [dict(zip(WAVE_COLS, t_wave[len(WAVE_COLS) * w:len(WAVE_COLS) * (w + 1)])) for w in range(n_waves)]
+        info["call"] = dict(zip(CALL_COLS, t_call))
     return ({"bytes": bytes(out[:nb]), "off": list(off[:nv + 1]), "count": list(count[:nv]), "first": list(first[:nv]), "pattern": list(pattern[:nv]),
-             "line_number": list(line[:nv]), "segment": list(segment[:nv]) if segments else None}, {"probes": totals[2], "n_long": totals[3]})
+             "line_number": list(line[:nv]), "segment": list(segment[:nv]) if segments else None}, info)

@@ -31,7 +31,7 @@ if os.environ.get("HG_BUILD_OUT"):
 
 HIP_SOURCES = ["hg_stream.hip", "hg_kernels.hip", "hg_always_on.hip", "hg_huge.hip", "hg_som.hip", "hg_comb.hip", "hg_invert.hip", "hg_context.hip", "hg_parts.hip", "hg_segments.hip", "hg_segctx.hip", "hg_segparts.hip", "hg_gather.hip", "hg_partlines.hip", "hg_values.hip", "hg_rank.hip", "hg_valstore.hip", "hg_counts.hip", "hg_flows.hip", "hg_batch.hip", "hg_engine.hip", "hg_capi.hip", "hg_shim.hip", "hg_hsface.hip"]
 CXX_SOURCES = ["hg_compile.cpp"]
-HEADERS = ["hg_mem.h", "hg_db.h", "hg_core.h", "hg_post.h", "hg_engine.h", "hg_compile.h", "hg_synth.h", "hg_confirm_dev.h", "hg_sink_dev.h", "hg_tables_dev.h", "hg_som.h", "hg_comb.h", "hg_invert.h", "hg_context.h", "hg_parts.h", "hg_parts_dev.h", "hg_segments.h", "hg_segctx.h", "hg_segparts.h", "hg_gather.h", "hg_partlines.h", "hg_values.h", "hg_values_dev.h", "hg_rank.h", "hg_valstore.h", "hg_counts.h", "hg_wave_dev.h", "hg_flows.h", "hg_flow_rules.h", "hg_batch.h", "hg_batch_launch.h"]
+HEADERS = ["hg_mem.h", "hg_db.h", "hg_core.h", "hg_post.h", "hg_engine.h", "hg_compile.h", "hg_synth.h", "hg_confirm_dev.h", "hg_sink_dev.h", "hg_tables_dev.h", "hg_som.h", "hg_comb.h", "hg_invert.h", "hg_context.h", "hg_parts.h", "hg_parts_dev.h", "hg_segments.h", "hg_segctx.h", "hg_segparts.h", "hg_gather.h", "hg_partlines.h", "hg_values.h", "hg_values_dev.h", "hg_rank.h", "hg_valstore.h", "hg_counts.h", "hg_wave_dev.h", "hg_flows.h", "hg_flow_rules.h", "hg_batch.h", "hg_batch_launch.h", "hg_deliver.h", "hg_reader.h"]
 
 
 def _hipcc() -> str:

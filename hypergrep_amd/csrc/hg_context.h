@@ -39,6 +39,14 @@ HG_HD HgContextWin hg_context_win(uint64_t line_base, uint64_t n_pieces, uint32_
   return w;
 }
 
+// What a call asks of the stage (hg_context_t of the C ABI).
+struct HgContextParams {
+  uint32_t before, after;
+  uint64_t carry_after;  // after-context the previous buffer still owes, in pieces
+  bool tail;             // also deliver the last `before` pieces that are neither match nor context, as tail records
+  bool any() const { return before || after || carry_after || tail; }
+};
+
 // After-context still owed past the buffer's end.  last_line: the line of the last hit (n_hits != 0).
 HG_HD uint64_t hg_context_owed(uint64_t n_hits, uint64_t last_line, uint64_t line_base, uint64_t n_pieces, uint32_t after, uint64_t carry_after) {
   if (!n_hits) return hg_sat_sub(carry_after, n_pieces);

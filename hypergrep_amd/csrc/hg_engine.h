@@ -190,13 +190,7 @@ hipError_t hg_invert_launch(const HgInvertArgs &a, bool write, uint32_t num_cus,
 
 // The context stage (hg_context.hip), launched like the invert stage.
 hipError_t hg_context_launch(const HgContextArgs &a, bool write, uint32_t num_cus, hipStream_t stream);
-// What a call asks of it (hg_context_t of the C ABI) and what it leaves (hg_context_result_t).
-struct HgContextParams {
-  uint32_t before, after;
-  uint64_t carry_after;  // after-context the previous buffer still owes, in pieces
-  bool tail;             // also deliver the last `before` pieces that are neither match nor context, as tail records
-  bool any() const { return before || after || carry_after || tail; }
-};
+// What a call asks of it is HgContextParams (hg_context.h); what it leaves (hg_context_result_t of the C ABI):
 struct HgContextOutput {
   uint64_t n_context;  // context and tail records, ordered by line
   uint64_t n_tail;     // the tail records among them
